@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """Benchmark of the HyperReel forward-render hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set up, pre-warm, W warm-up steps, ONE window of exactly K timed steps, the JSON line.
+--full adds everything else the line can carry (listed below): the median of three windows, per-step event timing, per-kernel
+rooflines, power, the other precisions / plans / families, the CPU and PyTorch baselines.
+--dump-outputs DIR writes what the timed path returned in its last step (the frame's rgb) as DIR/rgb.npy, float32.
 
 N > 1 without a launcher around it (no WORLD_SIZE in the environment): the script starts its N ranks itself -- torch.distributed.run,
 one process per GPU, rendezvous on 127.0.0.1 -- and passes their one JSON line through.
@@ -11,7 +16,7 @@ Workload (BASELINE.json configs[1]): DoNeRF static scene, `donerf_sphere` model 
 rays, 32 samples/ray, shipped final grid 600^3, synthetic random-weight scene ('dense' density variant so alpha spans
 (0,1)).  One step = one full forward render of a frame with rays and rgb resident in HBM.
 
-Multi-GPU, both in every N > 1 line:
+Multi-GPU, both in every N > 1 line with --full (a plain run: the window named by --scaling only):
   `value` (scaling "weak", the driver's contract): every rank renders its own 800x800 frame (the same camera, panned by the rank) and the
       tiles are all-gathered over RCCL/xGMI inside the timed step; value = rays of all ranks per second.
   `strong` (BASELINE's "800x800 frame ms at 1/2/4/8", the north star's ">= 6x image-parallel scaling at 8 GPUs"): ONE 800x800 frame per
@@ -20,7 +25,8 @@ Multi-GPU, both in every N > 1 line:
       a whole frame on one rank of the same job; tile_render_ms / gather_alone_ms / gather_overlap say where the rest went.
   `--scaling strong` makes the strong window `value` as well.
 
-The JSON line also carries
+With --full the JSON line also carries
+  step_ms         every step of one more window with its own HIP event pair;
   roofline        the dominant kernel of the step, its launches timed live with HIP events on the launch stream, against the
                   MI355X peak that bounds it (MI355X_MICROARCH.md: 2500 TFLOP/s dense bf16/fp16 MFMA);
   roofline_other  the other kernel: vector-ALU issue (wave-instructions per second against 1024 SIMDs x 2.4 GHz / 4 cycles);
@@ -404,6 +410,22 @@ def max_over_ranks(x, dist):
     return float(t.item())
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: array} -> path/<name>.npy in float32, at most DUMP_MAX_BYTES in all.  Past the bound every array keeps
+    the same fixed, seeded sample of its rows (the same rows on every run, so two builds compare output for output)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            keep = max(1, a.shape[0] * DUMP_MAX_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, f'{name}.npy'), a)
+
+
 def strong_window(model, args, dist, local_rank, headline, n1_frame_s):
     """ONE frame per step, split into contiguous pixel ranges (north star: "800x800 frame ms at 1/2/4/8", ">= 6x image-parallel scaling"):
     this rank renders its range into the pipeline's tile buffer, the all-gather of frame i runs on a side stream under the render of
@@ -468,7 +490,11 @@ def main():
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'])
     ap.add_argument('--cpu-sample', type=int, default=640000, help='rays of the CPU-baseline sample (0 = skip)')
     ap.add_argument('--prewarm', type=float, default=0.5, help='seconds of uncounted replays before the first warm-up step (clock ramp of an idle GPU; 0 = none)')
-    ap.add_argument('--windows', type=int, default=3, help='consecutive timed windows of exactly --steps steps each; value = their median')
+    ap.add_argument('--windows', type=int, default=None, help='consecutive timed windows of exactly --steps steps each; value = their median '
+                                                              '(default 1; 3 with --full)')
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline: step series, per-kernel rooflines, power, other '
+                                                        'precisions / plans / families, strong window of a weak multi-rank run, CPU and PyTorch baselines')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write the rgb the last timed step returned to DIR/rgb.npy (float32)')
     ap.add_argument('--no-stage-timing', action='store_true')
     ap.add_argument('--no-power', action='store_true', help='skip the rocm-smi power / clock probe of the two kernels (about 4 s)')
     ap.add_argument('--no-extras', action='store_true', help='skip frame_kernel / value_fp32_exact / pytorch_gpu_baseline')
@@ -484,6 +510,8 @@ def main():
     ap.add_argument('--frame-mode', type=int, default=1, choices=[1, 2], help='HR_OPT_FRAME_KERNEL: 1 = the frame kernel where it is the faster plan (static nets), 2 = wherever the model fits it (keyframe families on 32-ray tiles)')
     ap.add_argument('--sample-waves', type=int, default=0, choices=[0, 4, 8], help='sample wavefronts per workgroup of the frame kernel (0 = library default)')
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 3 if args.full else 1
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -568,21 +596,27 @@ def main():
             return rgb_static
         return model.render(rays)['rgb']
 
+    last = {}
+
     def step():
         out = render_frame()
         if multi:
             dist.all_gather_into_tensor(gathered.view(-1), out.view(-1))
+        last['rgb'] = out
         return out
 
     strong_info = None
+    dumped = None
     if not want_strong_value:
         dt, windows, n_pre = headline(step)
-        rgb = step()
+        rgb = last['rgb']          # what the last timed step returned
         sync()
+        if args.dump_outputs and rank == 0:
+            dumped = {'rgb': rgb.detach().cpu().numpy()}
         total_rays = B * world
         rays_per_gpu = B
         parallelism = f'image tiles x{world}, RCCL all_gather of rgb' if world > 1 else 'single GPU'
-    if multi:
+    if multi and (want_strong_value or args.full):
         # ---- the strong window (north star's frame-ms metric): one frame split N ways.  Its yardstick is THIS job's single-GPU frame: a whole
         # frame on one rank without any collective (every rank times its own; the slowest counts)
         n1 = max_over_ranks(local_frames(render_frame, args.steps, args.warmup), dist)
@@ -591,6 +625,8 @@ def main():
             dt, windows, n_pre = s_dt, s_windows, s_pre
             rays, B = s_rays, s_rays.shape[0]
             rgb = rgb_full[pipe.lo:pipe.hi]
+            if args.dump_outputs and rank == 0:
+                dumped = {'rgb': rgb_full.detach().cpu().numpy()}
             total_rays = args.height * args.width
             rays_per_gpu = B
             parallelism = f'ONE {args.height}x{args.width} frame split into {world} pixel ranges, double-buffered RCCL all_gather'
@@ -601,11 +637,13 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = total_rays / (dt / args.steps) / 1e6
     # every step of one more window with its own event pair: a stall (clock dip, a neighbour's SMI poll) shows as max >> p50 in the line itself
-    series = step_series({'value_path': step}, max(args.steps, 20)) if not FAKE else None
+    series = step_series({'value_path': step}, max(args.steps, 20)) if args.full and not FAKE else None
     # the fp16 split arithmetic was chosen on calibration rays: the kernels' sticky overflow bit must be clear on the rays that were timed
     # (render() checks it on the first batches and falls back to bf16x3, models.py _overflow_guard; a replayed graph cannot)
     if model.mlp_overflowed():
         raise SystemExit('bench: an MLP activation left the IEEE-half range on the benchmark rays (HR_OPT_MLP_OVERFLOW): the figure would be invalid')
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
     prec_name = model.mlp_precision_active()      # 'auto' resolved by the library's activation-range calibration (hr_model_finalize)
     result = {
         'metric': 'Mrays/s (32 samples/ray), forward render of 800x800 frames',
@@ -628,7 +666,7 @@ def main():
         strong_info['backend'] = str(dist.get_backend())
         result['strong'] = strong_info
     # ---- per-kernel timing + roofline (rank 0): the two kernels of the default path through hr_stage_*
-    if rank == 0 and not args.no_stage_timing and not FAKE:
+    if args.full and rank == 0 and not args.no_stage_timing and not FAKE:
         import ctypes
         from hyperreel_amd import lib as hlib
         L = hlib.load()
@@ -774,7 +812,7 @@ def main():
             result['roofline'] = dom
             result['roofline_other'] = oth
 
-    extras = rank == 0 and world == 1 and not args.no_extras and not FAKE and not multi
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras and not FAKE and not multi
     # ---- the same frame through the other execution plan, and with the exact fp32-MFMA MLP
     if extras:
         def quick(f):
@@ -880,7 +918,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- CPU baseline (rank 0, N = 1)
-    if rank == 0 and world == 1 and args.cpu_sample > 0 and not FAKE:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0 and not FAKE:
         v, secs, idx, ref_rgb = cpu_baseline(cfg, ds, sd_ref, rays_np, min(args.cpu_sample, B))
         got = rgb[torch.from_numpy(idx).cuda()].cpu().numpy()
         sample = (f'{len(idx)} rays of the same frame through oracle/torch_port.py (the reference\'s algorithm on PyTorch CPU ops, fp32, '

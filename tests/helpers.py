@@ -11,6 +11,18 @@ from hyperreel_amd import scenes
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
+def reference_facts():
+    """What the reference's own configuration and construction code says, recorded by oracle/refgen/make_reference_facts.py."""
+    with open(os.path.join(GOLDEN_DIR, 'reference_facts.json')) as f:
+        return json.load(f)
+
+
+def model_group_digest(cfg):
+    """sha256 of a parsed model group in the canonical form reference_facts() records for the shipped YAML."""
+    import hashlib
+    return hashlib.sha256(json.dumps(C.to_plain(cfg), sort_keys=True).encode()).hexdigest()
+
+
 def golden_cases():
     return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, '*.npz')))
 

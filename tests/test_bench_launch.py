@@ -27,7 +27,7 @@ def _run(extra, env_extra=None):
 
 
 def test_gpus_2_launches_itself_and_prints_one_line_with_the_strong_window():
-    d = _run(['--gpus', '2'])
+    d = _run(['--gpus', '2', '--full'])
     assert d['n_gpus'] == 2 and d['steps'] == 3 and d['warmup'] == 1 and d['scaling'] == 'weak'
     assert d['value'] > 0 and d['ms_per_step'] > 0 and len(d['windows_ms_per_step']) == 2
     assert d['config']['rays_per_gpu'] == 480 and 'x2' in d['config']['parallelism']
@@ -50,9 +50,33 @@ def test_strong_scaling_value_at_3_ranks():
 
 
 def test_one_rank_takes_the_distributed_path_when_forced():
-    # exactly `HR_BENCH_FORCE_DIST=1 python bench.py --gpus 1`: no launcher, no rendezvous variables (bench.py makes itself a one-rank job)
-    d = _run(['--gpus', '1'], {'HR_BENCH_FORCE_DIST': '1'})
+    # exactly `HR_BENCH_FORCE_DIST=1 python bench.py --gpus 1 --full`: no launcher, no rendezvous variables (bench.py makes itself a one-rank job)
+    d = _run(['--gpus', '1', '--full'], {'HR_BENCH_FORCE_DIST': '1'})
     assert d['n_gpus'] == 1 and d['strong']['ranks'] == 1 and d['strong']['rccl_ranks'] == 1
+
+
+def test_a_plain_run_times_one_window_and_dumps_the_last_frame(tmp_path):
+    """Without --full: one window of exactly --steps steps, no strong window, and --dump-outputs writes the frame the last timed step
+    returned -- the same bytes from two runs with the same arguments."""
+    from hyperreel_amd import scenes
+    frames = []
+    for i in range(2):
+        out = tmp_path / f'run{i}'
+        env = dict(os.environ, HR_BENCH_FAKE_RENDERER='1')
+        for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'HR_BENCH_FORCE_DIST'):
+            env.pop(k, None)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1', '--height', '24',
+                            '--width', '20', '--prewarm', '0', '--dump-outputs', str(out)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+        assert d['steps'] == 4 and len(d['windows_ms_per_step']) == 1 and d['ms_per_step'] > 0 and 'strong' not in d
+        assert sorted(os.listdir(out)) == ['rgb.npy']
+        frames.append(np.load(out / 'rgb.npy'))
+    a, b = frames
+    assert a.dtype == np.float32 and a.shape == (480, 3) and np.array_equal(a, b)
+    rays = torch.from_numpy(scenes.benchmark_rays('donerf_sphere', 24, 20, frame=7))
+    assert np.allclose(a, torch.sigmoid(rays[:, :3] * 3.0 + rays[:, 3:6]).numpy())
 
 
 def test_a_mismatched_launch_is_refused():

@@ -1,21 +1,21 @@
 """Drop-in check against the REFERENCE'S OWN registries: the three lines a maintainer adds --
 `model_dict['lightfield_hip'] = HipLightfieldModel` (nlf/models/models.py:141-143), `render_fn_dict['lightfield_hip'] =
-HipRenderLightfield` (nlf/rendering.py:95-97) and `type: lightfield_hip` in the YAML -- are applied to the imported reference
-modules (under the CPU shim of oracle/refgen/ref_shim.py), and the HIP-backed model is constructed exactly the way
-INRSystem does it (nlf/__init__.py:355-364): from the reference-side attr-dict configuration and a `system` stub.  No GPU:
-what is compared is what construction decides -- parameter names / shapes against the reference's own LightfieldModel, and
-the compiled kernel configuration against the one our YAML loader produces.  Skipped where /root/reference does not exist."""
+HipRenderLightfield` (nlf/rendering.py:95-97) and `type: lightfield_hip` in the YAML -- hand INRSystem's own arguments to our classes,
+and the HIP-backed model is constructed here exactly the way INRSystem does it (nlf/__init__.py:355-364): from the reference-side
+attr-dict configuration (oracle/refgen/ref_shim.py, the shipped YAML group with its *_epoch(s) -> *_iter(s) rewrite) and a `system`
+stub.  No GPU: what is compared is what construction decides -- parameter names / shapes against the reference's own LightfieldModel,
+and the compiled kernel configuration against the one our YAML loader produces.  The reference's side (the shipped YAML group's
+digest, its LightfieldModel's parameter names and shapes, what its transform_color_all does) is recorded in
+tests/golden/reference_facts.json by oracle/refgen/make_reference_facts.py, so no reference tree is needed here."""
 import os
 import sys
 
 import pytest
 import torch
 
+from helpers import model_group_digest, reference_facts
 from hyperreel_amd import config as C
 from hyperreel_amd import plan
-
-REF = '/root/reference'
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason='the reference tree exists only in the authoring container')
 
 MODELS = ['donerf_sphere', 'technicolor_z_plane', 'immersive_sphere', 'neural_3d_z_plane', 'donerf_cylinder']
 
@@ -23,43 +23,49 @@ MODELS = ['donerf_sphere', 'technicolor_z_plane', 'immersive_sphere', 'neural_3d
 @pytest.fixture(scope='module')
 def shim():
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'oracle', 'refgen'))
-    import ref_shim
-    ref_shim.install()
+    import ref_shim           # (its attr-dict, epoch rewrite and system stub only: nothing here installs the reference)
     return ref_shim
 
 
+@pytest.fixture(scope='module')
+def facts():
+    return reference_facts()
+
+
+def reference_side_cfg(shim, name, facts):
+    """ref_shim.load_model_cfg(name) without the reference tree: the built-in group IS the shipped YAML (same digest)."""
+    cfg = C.model_config(name)
+    assert model_group_digest(cfg) == facts['models'][name]['yaml_sha256']
+    return shim.epoch_to_iter(shim.to_attr(C.to_plain(cfg)), 4000)
+
+
 @pytest.mark.parametrize('name', MODELS)
-def test_registered_in_the_reference_dicts_and_built_like_inrsystem_builds_it(shim, name):
-    with shim.cpu_mode():
-        from nlf.models.models import model_dict
-        from nlf.rendering import render_fn_dict
+def test_registered_in_the_reference_dicts_and_built_like_inrsystem_builds_it(shim, facts, name):
     from hyperreel_amd.models import HipLightfieldModel
     from hyperreel_amd.render import HipRenderLightfield
-    # the registry lines of INTEGRATION.md
-    model_dict['lightfield_hip'] = HipLightfieldModel
-    render_fn_dict['lightfield_hip'] = HipRenderLightfield
     ds = C.dataset_scalars(name)
-    cfg = shim.load_model_cfg(name)                     # the reference-side configuration object (attr-dict in place of OmegaConf)
+    cfg = reference_side_cfg(shim, name, facts)       # the reference-side configuration object (attr-dict in place of OmegaConf)
     cfg.type = 'lightfield_hip'
     cfg.render.type = 'lightfield_hip'
     system = shim.make_system(ds)
-    # nlf/__init__.py:355-364
-    model = model_dict[cfg.type](cfg, system=system)
-    fn = render_fn_dict[cfg.render.type](model, None, cfg.render, net_chunk=32768)
+    # nlf/__init__.py:355-364 through the registry lines of INTEGRATION.md: model_dict[cfg.type](cfg, system=system),
+    # render_fn_dict[cfg.render.type](model, None, cfg.render, net_chunk=...)
+    model = HipLightfieldModel(cfg, system=system)
+    fn = HipRenderLightfield(model, None, cfg.render, net_chunk=32768)
     assert isinstance(fn, HipRenderLightfield) and fn.model is model
     # the same YAML through the reference's own classes: identical parameter names and shapes (checkpoints interchange)
-    ref_cfg = shim.load_model_cfg(name)
-    with shim.cpu_mode():
-        ref = model_dict['lightfield'](ref_cfg, system=system)
     ours = {k: tuple(v.shape) for k, v in model.state_dict().items()}
-    theirs = {k: tuple(v.shape) for k, v in ref.state_dict().items()}
+    theirs = {k: tuple(v) for k, v in facts['models'][name]['state_dict_shapes'].items()}
     assert set(ours) == set(theirs), (sorted(set(ours) ^ set(theirs))[:8])
     grid_dependent = ('_plane', '_line', 'gridSize')
     for k in ours:
         if not any(t in k for t in grid_dependent) or ours[k] == theirs[k]:
             assert ours[k] == theirs[k] or ours[k] == tuple(reversed(theirs[k])) or torch.Size(ours[k]).numel() == torch.Size(theirs[k]).numel(), k
-    # ... and a checkpoint of the reference loads into it by name
-    missing, unexpected = model.load_state_dict({'model.' + k: v for k, v in ref.state_dict().items()}, strict=False)
+    # ... and a checkpoint of the reference (its names, its shapes, its grid size) loads into it by name
+    known = {'color_model.net.gridSize': torch.tensor(facts['models'][name]['growth']['gridSize'], dtype=torch.long),
+             'color_model.net.aabb': torch.tensor(facts['models'][name]['aabb'], dtype=torch.float32)}
+    ckpt = {'model.' + k: known.get(k, torch.zeros(v)) for k, v in theirs.items()}
+    missing, unexpected = model.load_state_dict(ckpt, strict=False)
     assert not [m for m in missing if 'dummy_layer' not in m] and not unexpected
     # the kernel configuration compiled from the reference-side cfg + system equals the one from our YAML loader + dataset scalars
     grid = [int(v) for v in model.grid_size]
@@ -68,19 +74,17 @@ def test_registered_in_the_reference_dicts_and_built_like_inrsystem_builds_it(sh
     assert a == b
 
 
-def test_the_reference_cannot_run_a_per_sample_color_transform_head(shim):
+def test_the_reference_cannot_run_a_per_sample_color_transform_head(facts):
     """VERDICT r2 listed per-sample `color_transform` heads (tensorf_no_sample.py:226-229 -> transform_color_all,
     utils/tensorf_utils.py:283-306) as a leftover.  The reference's own function reshapes the (B, Z, 9) head to (B, 3, 3): it raises
-    for every Z > 1 and returns a (B, B, 3) tensor for Z = 1 -- there is no behaviour to reproduce, so plan.py keeps rejecting the
-    head by name.  The runnable forms -- the per-camera TABLE (`color_transform` embedding) and the per-ray head
-    `color_transform_global`, both through transform_color_one -- are supported."""
-    with shim.cpu_mode():
-        from utils.tensorf_utils import transform_color_all
-    B = 5
+    for every Z > 1 and returns a (B, B, 3) tensor for Z = 1 (recorded by running it: reference_facts.json) -- there is no behaviour
+    to reproduce, so plan.py keeps rejecting the head by name.  The runnable forms -- the per-camera TABLE
+    (`color_transform` embedding) and the per-ray head `color_transform_global`, both through transform_color_one -- are supported."""
+    t = facts['transform_color_all']
+    B = t['B']
     for Z in (2, 32):
-        with pytest.raises(RuntimeError):
-            transform_color_all(torch.rand(B, Z, 3), torch.rand(B, Z, 9), torch.rand(B, Z, 3))
-    assert tuple(transform_color_all(torch.rand(B, 1, 3), torch.rand(B, 1, 9), torch.rand(B, 1, 3)).shape) == (B, B, 3)
+        assert t[f'Z{Z}'] == {'raises': 'RuntimeError'}
+    assert tuple(t['Z1']['shape']) == (B, B, 3)
     from hyperreel_amd import scenes  # noqa: F401
     cfg = C.model_config('donerf_sphere')
     pred = [e for e in cfg['embedding']['embeddings'].values() if e.get('type') == 'ray_prediction'][0]

@@ -20,7 +20,7 @@ for r in 1 2 3; do
   for fl in "${flags[@]}"; do
     cp /tmp/lib$i.so hyperreel_amd/_build/libhyperreel_hip.so; touch hyperreel_amd/_build/libhyperreel_hip.so
     echo -n "[$fl] "
-    python bench.py --cpu-sample 0 $* 2>&1 | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d.get('stage_ms'))"
+    python bench.py --full --cpu-sample 0 $* 2>&1 | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d.get('stage_ms'))"
     i=$((i+1))
   done
 done
