@@ -39,8 +39,6 @@ if os.environ.get('HR_FAST_EXP', '1') != '0':
     FLAGS.append('-DHR_FAST_EXP')
 if os.environ.get('HR_FAST_POST', '1') != '0':       # rcp / sqrt / tanh approximations strictly after the near/far mask
     FLAGS.append('-DHR_FAST_POST')
-if os.environ.get('HR_FAST_MATH', '0') == '1':       # measurements only: all three approximation groups
-    FLAGS.append('-DHR_FAST_MATH')
 
 
 def csrc_hash():

@@ -1141,10 +1141,6 @@ static HrGridPlane render_plane(const hr_model* m, int j)
     return g;
 }
 
-#ifdef HR_DEBUG_HSUM
-static unsigned* g_dbg_hsum = nullptr;
-extern "C" void hr_debug_set_hsum(void* p) { g_dbg_hsum = (unsigned*)p; }
-#endif
 static void fill_sample_args(const hr_model* m, HrSampleArgs& a, const float* rays, int64_t n, float* rgb)
 {
     a.cfg_dev = m->kcfg_dev;
@@ -1167,7 +1163,6 @@ static void fill_sample_args(const hr_model* m, HrSampleArgs& a, const float* ra
         auto it = m->raw.find("color_embedding");
         if (it != m->raw.end()) a.color_table = it->second.p;
     }
-    a.dbg_mode = 0;
     a.ray0 = 0;
     a.ray_index = nullptr;
     a.n_rays_dev = nullptr;
@@ -1178,9 +1173,6 @@ static void fill_sample_args(const hr_model* m, HrSampleArgs& a, const float* ra
     a.redo_cap = 0;
     a.redo_band = a.redo_band_q = a.redo_band_off = a.redo_amp_cut = 0.0f;
     a.flags = m->flags;
-#ifdef HR_DEBUG_HSUM
-    a.dbg_hsum = g_dbg_hsum;
-#endif
     a.occ = m->occ;
     a.occ_cells = m->occ_cells;
     a.occ_w = m->occ_n[0]; a.occ_h = m->occ_n[1]; a.occ_d = m->occ_n[2];

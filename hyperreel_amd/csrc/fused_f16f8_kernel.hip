@@ -10,6 +10,4 @@
 // arithmetic's own head error, and a third of the prologue's instructions (K1's phase trace: the prologue is 9 % of a tile).  The exact
 // arithmetics (f16x3, bf16x3, fp32) keep sincosf
 #define HR_FAST_SINCOS 1
-#define HR_TUNING_SET hr_tuning_set_f16f8
-#define HR_TUNING_PHASES hr_tuning_phases_f16f8
 #include "fused_impl.inc"

@@ -43,19 +43,7 @@ struct HrFusedArgs {
     int n_tiles;            // tiles (32 x MT rays) of the launch
     int HS;                 // floats per head row in LDS
     int m_copies;           // decode matrices per sample wavefront in LDS: 1 (RGB shading: basis_mat itself) or rays per pass (SH: per ray)
-#ifdef HR_TUNING            // measurement builds only (tools/frame_stats.py)
-    unsigned long long* stats;   // [grid][8] cycle counters: MLP total / wait first / wait done / barriers, sample total / wait ready
-    int mode;                    // 1: sample wavefronts skip their work, 2: MLP wavefronts skip theirs
-#endif
 };
-
-#ifdef HR_TUNING
-#define HR_T0() const unsigned long long t0__ = __builtin_readcyclecounter()
-#define HR_T1(acc) acc += __builtin_readcyclecounter() - t0__
-#else
-#define HR_T0() do {} while (0)
-#define HR_T1(acc) do {} while (0)
-#endif
 
 __device__ __forceinline__ unsigned hr_lds_peek(const unsigned* p)
 {
@@ -65,15 +53,7 @@ __device__ __forceinline__ unsigned hr_lds_peek(const unsigned* p)
 // wait until the counter has reached `target` (wrap-safe), then acquire
 __device__ __forceinline__ void hr_wait_ge(const unsigned* p, unsigned target)
 {
-#ifdef HR_TUNING     // measurement builds: a protocol bug is a trap (the launch fails with an error), not a hung GPU -- ~0.5 s of spinning
-    unsigned spins = 0;
-    while ((int)(hr_lds_peek(p) - target) < 0) {
-        __builtin_amdgcn_s_sleep(2);
-        if (++spins > (1u << 23)) __builtin_trap();
-    }
-#else
     while ((int)(hr_lds_peek(p) - target) < 0) __builtin_amdgcn_s_sleep(2);
-#endif
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
@@ -90,20 +70,15 @@ struct HrSyncGroup {                       // the NW MLP wavefronts of the workg
     unsigned target;                       // arrivals after which the next barrier opens (per-wavefront copy)
     const unsigned* first;                 // what the input-tile store waits for: `first` (one head buffer) or `done` (two)
     unsigned need_first;
-    unsigned long long t_bar, t_first, t_done;      // HR_TUNING only
     __device__ __forceinline__ void barrier()
     {
-        HR_T0();
         target += NW;
         hr_arrive(bar);
         hr_wait_ge(bar, target);
-        HR_T1(t_bar);
     }
     // the input tile overlays head rows the sample wavefronts read first: wait until they have
-    __device__ __forceinline__ void before_input_store() { HR_T0(); hr_wait_ge(first, need_first); HR_T1(t_first); }
+    __device__ __forceinline__ void before_input_store() { hr_wait_ge(first, need_first); }
     __device__ __forceinline__ bool any(bool pred) { return pred; }        // (the frame kernel keeps no ray lists: every wavefront speaks for itself)
-    __device__ __forceinline__ void gemm_begin() {}
-    __device__ __forceinline__ void gemm_end() {}
 };
 
 template <int NW, bool HOLD_>
@@ -116,7 +91,7 @@ struct HrSinkLds {
     HrSyncGroup<NW>* sync;
     static constexpr bool HOLD = HOLD_;    // true: every output tile of a wavefront is accumulated before begin() (mlp_split_core.inc)
     static constexpr bool TAPS = false;
-    __device__ __forceinline__ void begin() { HR_T0(); hr_wait_ge(done, need_done); HR_T1(sync->t_done); }   // the previous tile's head has been consumed
+    __device__ __forceinline__ void begin() { hr_wait_ge(done, need_done); }   // the previous tile's head has been consumed
     __device__ __forceinline__ void store(int r, int64_t, int n0, const float4 v) { *reinterpret_cast<float4*>(H + r * HS + n0) = v; }
     __device__ __forceinline__ void end()
     {
@@ -176,10 +151,7 @@ __global__ __launch_bounds__(64 * (4 + NS)) void HR_FUSED_KERNEL(const hr_config
     if (wave < NW) {
         // =============================================================== MLP wavefronts
         __builtin_amdgcn_s_setprio(HR_MFMA_PRIO_LO);
-        HrSyncGroup<NW> sync{&sy[0], 0u, (NBUF == 2) ? &sy[3] : &sy[2], 0u, 0ull, 0ull, 0ull};
-#ifdef HR_TUNING
-        const unsigned long long t_start = __builtin_readcyclecounter();
-#endif
+        HrSyncGroup<NW> sync{&sy[0], 0u, (NBUF == 2) ? &sy[3] : &sy[2], 0u};
         HrSinkLds<NW, MT == 2> sink{H0, HS, &sy[3], 0u, &sy[1], &sync};
         HrMlpTrace trace{nullptr, 0};
         unsigned it = 0;
@@ -195,23 +167,8 @@ __global__ __launch_bounds__(64 * (4 + NS)) void HR_FUSED_KERNEL(const hr_config
                 sync.need_first = (unsigned)NS * it;      // tile it-1: every sample wavefront is past its first group
                 sink.need_done = (unsigned)NS * it;       // tile it-1: consumed
             }
-#ifdef HR_TUNING
-            if (fa.mode == 2) {                           // protocol only
-                sync.barrier();
-                sync.before_input_store();
-                sink.begin();
-                sink.end();
-                continue;
-            }
-#endif
             hr_mlp_tile<W, MT, NW, RING>(cfg, fa.m, (int64_t)tile * TM, fa.m.n_rays, Xih, Xil, Xh, Xl, sync, sink, trace);
         }
-#ifdef HR_TUNING
-        if (fa.stats && tid == 0) {
-            unsigned long long* st = fa.stats + (size_t)blockIdx.x * 8;
-            st[0] = __builtin_readcyclecounter() - t_start; st[1] = sync.t_first; st[2] = sync.t_done; st[3] = sync.t_bar; st[6] = it;
-        }
-#endif
     } else {
         // =============================================================== sample wavefronts
         const int sw = wave - NW;
@@ -225,41 +182,18 @@ __global__ __launch_bounds__(64 * (4 + NS)) void HR_FUSED_KERNEL(const hr_config
             if (rig == 0) hr_fill_decode<ZP>(cfg, fa.s, hr_load_ray(cfg, fa.s, 0, false), k, M);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
-#ifdef HR_TUNING
-        const unsigned long long t_start = __builtin_readcyclecounter();
-        unsigned long long t_ready = 0;
-        unsigned long long sph__[12] = {};
-#endif
         unsigned it = 0;
         for (int tile = t_lo + idx; tile < t_hi; tile += wx, ++it) {
-            {
-                HR_T0();
-                hr_wait_ge(&sy[1], it + 1u);     // the tile's head is in H
-                HR_T1(t_ready);
-            }
-#ifdef HR_TUNING
-            if (fa.mode == 1) {
-                hr_arrive(&sy[2]);
-                hr_arrive(&sy[3]);
-                continue;
-            }
-#endif
+            hr_wait_ge(&sy[1], it + 1u);         // the tile's head is in H
             // ray groups sw, sw + NS, ... of the tile
 #pragma unroll 1
             for (int j = 0; j < GPW; ++j) {
                 const int g = sw + NS * j;
-#ifdef HR_TUNING
-                unsigned long long tph__ = __builtin_readcyclecounter();
-#endif
                 const int row = g * RPW + rig;
                 const int64_t ray = (int64_t)tile * TM + row;
                 const bool ray_ok = ray < fa.s.n_rays;
                 HrRayLane L = hr_load_ray(cfg, fa.s, ray, ray_ok);
                 hr_ray_constants(cfg, L);
-#ifdef HR_TUNING
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                HR_SPH(9);
-#endif
                 if (per_ray_M) {
                     hr_fill_decode<ZP>(cfg, fa.s, L, k, M);
                     // the ray's lanes share M; they are one wavefront, whose LDS operations execute in order
@@ -267,42 +201,20 @@ __global__ __launch_bounds__(64 * (4 + NS)) void HR_FUSED_KERNEL(const hr_config
                 }
                 HR_SPH(10);
                 const float* H = H0 + (it & (NBUF - 1)) * (TM * HS);
-                hr_sample_body<ZP, HALF, (NS > 4) ? 1 : 2, NB, PC>(cfg, fa.s, L, ray, ray_ok, k, H + row * HS, HS, M, s_ones, nullptr HR_SPH_ARG);
+                hr_sample_body<ZP, HALF, (NS > 4) ? 1 : 2, NB, PC>(cfg, fa.s, L, ray, ray_ok, k, H + row * HS, HS, M, s_ones, nullptr);
                 if (NBUF == 1 && g < NS) hr_arrive(&sy[2]);   // rows under the MLP's next input tile are free
                 else if (per_ray_M) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // M is rewritten by the next group
             }
             hr_arrive(&sy[3]);
         }
-#ifdef HR_TUNING
-        if (fa.stats && tid == 64 * NW) {
-            unsigned long long* st = fa.stats + (size_t)blockIdx.x * 8;
-            st[4] = __builtin_readcyclecounter() - t_start; st[5] = t_ready;
-        }
-        if (lane == 0)
-            for (int i = 0; i < 12; ++i) atomicAdd(&hr_sample_phase[i], sph__[i]);
-#endif
     }
 }
-
-#ifdef HR_TUNING
-static unsigned long long* g_frame_stats = nullptr;
-static int g_frame_mode = 0;
-extern "C" void HR_TUNING_SET(int mode, void* stats) { g_frame_mode = mode; g_frame_stats = (unsigned long long*)stats; }
-extern "C" void HR_TUNING_PHASES(unsigned long long* out16, int reset)
-{
-    if (reset) { unsigned long long z[16] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(hr_sample_phase), z, sizeof(z)); }
-    else (void)hipMemcpyFromSymbol(out16, HIP_SYMBOL(hr_sample_phase), 16 * sizeof(unsigned long long));
-}
-#endif
 
 // ---------------------------------------------------------------- launcher
 static int hr_fused_head_stride(int nq)
 {
     int hs = nq * 4;
     while ((hs & 7) != 4) hs += 4;               // 16-byte row stride = 4 mod 8 words: the 8 lanes of a ds_write_b128 group hit 8 bank quads
-#ifdef HR_DEBUG_HS_PAD                          // measurement builds: move every head row in LDS
-    hs += HR_DEBUG_HS_PAD;
-#endif
     return hs;
 }
 
@@ -335,10 +247,6 @@ bool HR_FUSED_LAUNCH(const hr_config& cfg, const HrMlpArgs& ma, const HrSampleAr
     fa.m = ma;
     fa.s = sa;
     fa.HS = hr_fused_head_stride(ma.nq);
-#ifdef HR_TUNING
-    fa.stats = g_frame_stats;
-    fa.mode = g_frame_mode;
-#endif
     const bool per_ray_M = (cfg.shading == HR_SHADING_SH);      // RGB shading keeps ONE decode matrix per sample wavefront (basis_mat itself)
     const size_t LDS_MAX = 160 * 1024;
     auto lds_for = [&](int tm, int nbuf, int ns, int rpw) {

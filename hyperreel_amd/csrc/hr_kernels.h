@@ -130,7 +130,6 @@ struct HrSampleArgs {
                                  //   inside a cell of a 0/1 volume the trilinear sample is > 0 exactly when that bit is set; NULL: volume not binary
     int occ_w, occ_h, occ_d;
     float occ_lo[3], occ_inv[3];   // g = (p - lo) * inv - 1
-    int dbg_mode;           // measurement builds only (-DHR_TUNING, HR_SAMPLE_DBG): 1 = skip the feature gather
     // verified fast path.  First pass: redo_list != NULL -- a ray with a comparison within redo_band of flipping is appended as
     // ray0 + (its index in this launch): ray0 = where the launch's `rays` / `rgb` start in the caller's buffers (hr_render walks them in chunks).
     // Second pass: `rays` / `rgb` are the caller's whole buffers and ray_index != NULL -- position i of the launch (head row i) is the caller's
@@ -148,9 +147,6 @@ struct HrSampleArgs {
     float redo_band_off;    // HrRisk::band_off: margin of the point-offset / flow heads
     float redo_amp_cut;     // HrRisk::amp_cut: a live sample conditioned worse than the calibration's rays lists its ray
     unsigned* flags;        // the model's sticky status word (bit 2: the redo list overflowed)
-#ifdef HR_DEBUG_HSUM        // measurement builds (tools/hsum_bisect.py): per ray, the XOR of the bits of every head value the sample stage read, and of its sorted distances
-    unsigned* dbg_hsum;     // [n_rays][2]
-#endif
 };
 
 // training forward (mlp_split_impl.inc, HR_SPLIT_TRAIN_KERNEL): where the output of hidden Linear l (after its LeakyReLU) goes besides LDS --

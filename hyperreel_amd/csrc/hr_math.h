@@ -31,12 +31,6 @@
 //   HR_FAST_SINCOS  v_sin_f32 / v_cos_f32 in the windowed positional encoding
 // Measured on the 800x800 frames: HR_FAST_DIV flipped a `dist <= near` decision on 1 ray in 20 000 of the cylinder scene
 // (RGB error 5e-2 on that ray) for 2 % of the sample kernel's time, so it is off in the shipped build (hyperreel_amd/build.py).
-#if defined(HR_FAST_MATH)
-#define HR_FAST_EXP 1
-#define HR_FAST_DIV 1
-#define HR_FAST_POST 1
-#define HR_FAST_SINCOS 1
-#endif
 #if defined(__HIPCC__) && defined(HR_FAST_DIV)
 #define HR_DIV(a, b) ((a) * __builtin_amdgcn_rcpf(b))
 #define HR_SQRT(x) __builtin_amdgcn_sqrtf(x)
@@ -297,9 +291,6 @@ struct HrRisk {
     bool hit;
     // out: this sample's zc, dlen and amp (0 where the intersection misses) -- what the margins were built from, and what the band probe reads
     float zc, dlen, amp;
-#ifdef HR_DEBUG_HSUM
-    float dbg[8];   // measurement builds: intermediates of the sphere intersection (tools/hsum_bisect.py)
-#endif
 };
 #define HR_RISK_INIT(zc_, q_, off_, cut_) HrRisk{(zc_), (q_), (off_), (cut_), false, 0.0f, 1.0f, 0.0f}
 #define HR_RISK_ABS(risk, x, y) do { if (risk) (risk)->hit = (risk)->hit || (fabsf((x) - (y)) <= (risk)->band_zc * (risk)->dlen); } while (0)
@@ -318,16 +309,10 @@ HR_FN float hr_quadratic_t(float oo, float dd, float od, float radius, HrRisk* r
         band_r = risk->band_zc * risk->dlen;
         risk->hit = risk->hit || (fabsf(disc) <= 8.0f * a * fabsf(radius) * band_r) || (fabsf(radius) <= band_r);
     }
-#if defined(HR_DEBUG_HSUM) && HR_DEBUG_HSUM != 2
-    if (risk) risk->dbg[4] = disc;
-#endif
     disc = (disc < 0.0f) ? 0.0f : disc;
     float sq = HR_SQRT(disc + 1e-8f);
     float t1 = HR_DIV(-b + sq, 2.0f * a);
     float t2 = HR_DIV(-b - sq, 2.0f * a);
-#if defined(HR_DEBUG_HSUM) && HR_DEBUG_HSUM != 2
-    if (risk) { risk->dbg[5] = sq; risk->dbg[6] = t1; risk->dbg[7] = t2; }
-#endif
     if (risk) {
         // d t / d r = +- 2 r / sq for both roots (a cancels); ... and the sign of the near root (which root is returned)
         risk->amp = (disc <= 0.0f) ? 0.0f : 2.0f * fabsf(radius) * HR_RCP_BAND(sq);
@@ -492,17 +477,9 @@ HR_FN float hr_sample_distance(const hr_config& c, const float* hk, int k, const
             sz = hr_zval(c, hk, 2, one_m) * c.origin_scale + c.origin_initial[2];
         }
         float radius = hr_process_z(c, hr_zval(c, hk, 3, one_m), c.z_scale, c.samples[k], risk);
-#if defined(HR_DEBUG_HSUM) && HR_DEBUG_HSUM != 2
-        if (risk) { risk->dbg[0] = hr_zval(c, hk, 3, one_m); risk->dbg[1] = radius; }
-#endif
         float q_[3];
         if (quad && c.origin_scale == 0.0f) { q_[0] = quad[0]; q_[1] = quad[1]; q_[2] = quad[2]; }
         else hr_quadratic_ray_terms(c, ro, rd, sx, sy, sz, q_);
-#if defined(HR_DEBUG_HSUM) && HR_DEBUG_HSUM != 2
-        if (risk) { risk->dbg[2] = q_[0]; risk->dbg[3] = q_[2]; }
-#elif defined(HR_DEBUG_HSUM)
-        if (risk) { risk->dbg[6] = q_[0]; risk->dbg[7] = q_[2]; }
-#endif
         dist = hr_quadratic_t(q_[0], q_[1], q_[2], radius, risk);
     } else if (c.isect_type == HR_ISECT_SPHERE_NEW || c.isect_type == HR_ISECT_CYLINDER_NEW) {
         dist = hr_isect_new(c, hk, k, one_m, ro, rd, risk);

@@ -242,9 +242,6 @@ __device__ __forceinline__ void hr_load_w8(bf16x8 (&h)[NT], hr_v8i (&q)[NT], int
 #ifdef HR_W_LOAD_AUX
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16x8*>(wp), 0, 0x7FFFFFFF, 0x00020000);
 #endif
-#ifdef HR_K1_UBENCH_WFIXED     // measurement builds (tools/k1_operand_ubench.py): every weight load of a layer reads the layer's FIRST k-step -- the same
-    wkt = 0;                   // addresses over and over: served by the vector L1, nothing crosses from the L2
-#endif
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         hr_v4i qq;
@@ -318,25 +315,9 @@ __device__ __forceinline__ void hr_accumulate_f8(floatx16 (&acc)[NT][MT], const 
         const int ws = s + AHEAD;                                  // weights of k-step s + AHEAD: pair P = ws / 2, whose slot pair P - NPQ read at step 2 (P - NPQ) + 1
         const bool w_early = (2 * (ws >> 1) <= s + 2 * NPQ - 2);
         const bool xq_early = (2 * ((s + 1) >> 1) <= s);           // (the rays' single fp8 slot: pair P - 1 read it at step 2 P - 1)
-#ifndef HR_K1_UBENCH_NOWLOAD     // measurement builds: the k-steps after the prologue re-use the weights already in registers
         if (ws < NKT && w_early) hr_load_w8<NT>(wh[ws % R], wq[(ws >> 1) % NPQ], ws & 1, wp, kt0 + ws, tiles_total, tile, lane);
-#endif
-#ifndef HR_K1_UBENCH_NOXLOAD     // ... the rays' operands likewise (no LDS reads in the loop)
         if (s + 1 < NKT) hr_load_x8<MT>(xv[(s + 1) & 1], xq, (s + 1) & 1, xh, xl, stride, s + 1, lane, true, xq_early);
-#endif
         __builtin_amdgcn_s_setprio(HR_MFMA_PRIO_HI);
-#ifdef HR_K1_UBENCH_NOMFMA      // measurement builds: the operands arrive (loads and waits as in the product), no matrix instruction is issued
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) asm volatile("" :: "v"(wh[s % R][nt]));
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) asm volatile("" :: "v"(xv[s & 1][mt]));
-        if (s & 1) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) asm volatile("" :: "v"(wq[(s >> 1) % NPQ][nt]));
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) asm volatile("" :: "v"(xq[mt]));
-        }
-#else
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -349,14 +330,9 @@ __device__ __forceinline__ void hr_accumulate_f8(floatx16 (&acc)[NT][MT], const 
                 for (int mt = 0; mt < MT; ++mt)
                     acc[nt][mt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wq[(s >> 1) % NPQ][nt], xq[mt], acc[nt][mt], 0, 0, 0, sw, 0, sx);
         }
-#endif
         __builtin_amdgcn_s_setprio(HR_MFMA_PRIO_LO);
-#ifndef HR_K1_UBENCH_NOWLOAD
         if (ws < NKT && !w_early) hr_load_w8<NT>(wh[ws % R], wq[(ws >> 1) % NPQ], ws & 1, wp, kt0 + ws, tiles_total, tile, lane);
-#endif
-#ifndef HR_K1_UBENCH_NOXLOAD
         if (s + 1 < NKT && !xq_early) hr_load_x8<MT>(xv[(s + 1) & 1], xq, (s + 1) & 1, xh, xl, stride, s + 1, lane, false, true);
-#endif
     }
 }
 #endif
@@ -426,15 +402,8 @@ __device__ __forceinline__ void hr_split_store8(HR_SPLIT_E* xh, HR_SPLIT_E* xl, 
     const u2 ha2 = __builtin_bit_cast(u2, ha), hb2 = __builtin_bit_cast(u2, hb), la2 = __builtin_bit_cast(u2, la), lb2 = __builtin_bit_cast(u2, lb);
     // permlane32_swap(x, y) -> {[x_low | y_low], [x_high | y_high]}: first result = (lower lanes: own quad g; upper lanes: the
     // partner's quad g + 1), second = (lower: the partner's quad g; upper: own quad g + 1) -- ascending feature order in both halves
-#ifdef HR_NO_PERMLANE_SWAP      // measurement builds: the same exchange through ds_bpermute (is v_permlane32_swap what disturbs the sample wavefronts' upper lanes?)
-    struct P2 { unsigned v[2]; __device__ unsigned operator[](int i) const { return v[i]; } };
-    const bool up = ((int)threadIdx.x & 32) != 0;
-    auto swap = [&](unsigned x, unsigned y) { const unsigned px = __shfl_xor(x, 32, 64), py = __shfl_xor(y, 32, 64); return P2{{up ? py : x, up ? y : px}}; };
-    const P2 h0 = swap(ha2.x, hb2.x), h1 = swap(ha2.y, hb2.y), l0 = swap(la2.x, lb2.x), l1 = swap(la2.y, lb2.y);
-#else
     const auto h0 = __builtin_amdgcn_permlane32_swap(ha2.x, hb2.x, false, false), h1 = __builtin_amdgcn_permlane32_swap(ha2.y, hb2.y, false, false);
     const auto l0 = __builtin_amdgcn_permlane32_swap(la2.x, lb2.x, false, false), l1 = __builtin_amdgcn_permlane32_swap(la2.y, lb2.y, false, false);
-#endif
     *reinterpret_cast<u4*>(xh + idx) = u4{h0[0], h1[0], h0[1], h1[1]};
     *reinterpret_cast<u4*>(xl + idx) = u4{l0[0], l1[0], l0[1], l1[1]};
 }
@@ -585,11 +554,7 @@ __device__ __forceinline__ void hr_mlp_tile(const hr_config& cfg, const HrMlpArg
 #define HR_F8_AHEAD_BIG 3          // weight look-ahead (k-steps) of the stand-alone kernel; 5 and 7 measured level (DESIGN 10)
 #endif
     constexpr int F8A = (RING >= 4 ? HR_F8_AHEAD_BIG : HR_F8_AHEAD_SMALL);
-#ifdef HR_K1_NO_PREN          // measurement builds
-    constexpr bool PREN = false;
-#else
     constexpr bool PREN = (RING >= 4);       // (not in the frame kernel's 168-register plan: the ring would have to live through its epilogues)
-#endif
     HrF8Ring<NT, F8A> ring8;
 #endif
     // ---- hidden layers: wave w owns output features [w*W/NW, (w+1)*W/NW)
@@ -619,7 +584,6 @@ __device__ __forceinline__ void hr_mlp_tile(const hr_config& cfg, const HrMlpArg
         for (int nt = 0; nt < NT; ++nt) tile[nt] = wave * NT + nt;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) hr_acc_init_bias<MT>(acc[nt], bias, tile[nt], lane);
-        sync.gemm_begin();
         int kt0 = 0;
         if (l == 0 || skip) {
             hr_accumulate3<NT, MT>(acc, Xih, Xil, XSI, k0p / 16, wp, 0, tiles_total, tile, lane);
@@ -637,7 +601,6 @@ __device__ __forceinline__ void hr_mlp_tile(const hr_config& cfg, const HrMlpArg
 #endif
         HR_STAMP();                          // 2+3l: GEMM of layer l issued
         sync.barrier();                      // all waves have finished reading Xh/Xl
-        sync.gemm_end();
         HR_STAMP();                          // 3+3l: barrier passed
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
@@ -651,9 +614,6 @@ __device__ __forceinline__ void hr_mlp_tile(const hr_config& cfg, const HrMlpArg
             // the 8-byte stores of one quad collided two ways (34 % of the kernel's LDS cycles were bank conflicts)
 #pragma unroll
             for (int gp = 0; gp < 4; gp += 2) {
-#ifdef HR_TRACE_FINE
-                if (nt == 0 && gp == 0) HR_STAMP();    // (measurement builds: the stamp that used to follow the epilogue's first bias loads)
-#endif
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
                     float v[8];
@@ -683,10 +643,6 @@ __device__ __forceinline__ void hr_mlp_tile(const hr_config& cfg, const HrMlpArg
 #ifdef HR_SPLIT_F8LO
         over8 = over8 || !(amax < 448.0f * x8s);             // an activation whose fp8 image saturated (or a NaN)
         amax = fmaxf(amax, amax_before);
-#endif
-#ifdef HR_TRACE_FINE
-        __builtin_amdgcn_s_waitcnt(0);           // measurement builds: the wavefront's own epilogue (its stores drained) apart from the wait at the barrier
-        HR_STAMP();
 #endif
         sync.barrier();
         HR_STAMP();                              // 4+3l: epilogue + barrier done

@@ -5,44 +5,10 @@
 // mlp_f16f8_kernel.hip (fp16 leading product + fp8 corrections: what HR_MLP_AUTO resolves to, verified -- DESIGN 3c).
 #include "mlp_split_core.inc"
 
-#ifdef HR_K1_CU_TURNS
-// Measurement builds: the two workgroups that share a compute unit take TURNS at the matrix pipe.  Left alone they run in phase -- both in a
-// layer's GEMM (the pipe is the bound: 8.2 k cycles for the two), then both in its epilogue (the pipe idles 4 k cycles) -- K1's phase trace.  A
-// word per compute unit in global memory (index from HW_ID / XCC_ID) is taken before a GEMM and given back after it; a workgroup that finds it
-// taken spends the wait where it would otherwise have contended.  A HINT, not a lock anything depends on: the wait is bounded.
-__device__ unsigned hr_cu_turn[1 << 12];
-__device__ __forceinline__ unsigned hr_cu_index()
-{
-    const unsigned hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));            // HW_REG_HW_ID, all 32 bits: cu_id [11:8], sh_id [12], se_id [15:13]
-    const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));           // HW_REG_XCC_ID [3:0]
-    return ((xcc & 15u) << 8) | (((hw >> 13) & 7u) << 5) | (((hw >> 12) & 1u) << 4) | ((hw >> 8) & 15u);
-}
-#endif
-
 struct HrSyncBlock {                       // the whole block is the MLP group
     __device__ __forceinline__ void barrier() { __syncthreads(); }
     __device__ __forceinline__ bool any(bool pred) { return __syncthreads_or(pred ? 1 : 0) != 0; }     // a barrier that ORs a predicate over the group
     __device__ __forceinline__ void before_input_store() {}
-#ifdef HR_K1_CU_TURNS
-    __device__ __forceinline__ void gemm_begin()
-    {
-        if (threadIdx.x == 0) {
-            unsigned* w = hr_cu_turn + hr_cu_index();
-            for (int i = 0; i < 4000; ++i) {
-                if (atomicCAS(w, 0u, 1u) == 0u) break;
-                __builtin_amdgcn_s_sleep(2);
-            }
-        }
-        __syncthreads();
-    }
-    __device__ __forceinline__ void gemm_end()      // (called behind the barrier that ends the GEMM)
-    {
-        if (threadIdx.x == 0) atomicExch(hr_cu_turn + hr_cu_index(), 0u);
-    }
-#else
-    __device__ __forceinline__ void gemm_begin() {}
-    __device__ __forceinline__ void gemm_end() {}
-#endif
 };
 
 struct HrSinkWorkspace {                   // HQ layout: the 32 lanes of a half-wave write 512 contiguous bytes.  (Plain stores
@@ -79,13 +45,6 @@ __global__ __launch_bounds__(64 * NW, (MT == 2) ? 2 : 1) void HR_SPLIT_KERNEL(co
     if (trace.tr && (threadIdx.x & 63) == 0) trace.tr[0] = __builtin_readcyclecounter();    // 0: start
     trace.tri = 1;
     HrSyncBlock sync;
-#ifdef HR_K1_STAGGER           // measurement builds: the second workgroup of each compute unit (blocks 256 .. 511 of the first round) starts late, so that the two
-    // co-resident workgroups run their GEMM and epilogue phases out of step (K1's phase trace: left alone they run in phase)
-    if ((blockIdx.x >> 8) & 1) {
-#pragma unroll 1
-        for (int i = 0; i < HR_K1_STAGGER; ++i) __builtin_amdgcn_s_sleep(64);
-    }
-#endif
     // second pass of the verified fast path: the launch is sized for the list's capacity, *n_rays_dev rays are there (block-uniform exit,
     // before any barrier)
     int64_t n_rays = a.n_rays;
@@ -178,12 +137,6 @@ void HR_SPLIT_LAUNCH(const hr_config& cfg, const HrMlpArgs& args, hipStream_t st
     // 64 rays per workgroup, 4 wavefronts: two workgroups per CU hide each other's epilogues (1.50 ms per 640k rays;
     // 128 rays / one workgroup per CU: half the L1 weight traffic but nothing to overlap with, 1.83 ms; 8 wavefronts
     // per workgroup: no gain).  Other hidden widths are rejected by hr_model_create.
-#ifdef HR_K1_MT4        // measurement builds: 128-ray tiles (one workgroup per CU), -DHR_K1_MT4=4 or 8 wavefronts
-    if (cfg.mlp_hidden == 256 && !args.ray_index) { hr_launch_mlp_split_t<256, 4, HR_K1_MT4>(cfg, args, stream); return; }
-#endif
-#ifdef HR_K1_NW8        // measurement builds: eight wavefronts per workgroup (a wavefront owns 32 hidden features), four per SIMD at two workgroups per CU
-    if (cfg.mlp_hidden == 256) hr_launch_mlp_split_t<256, 2, 8>(cfg, args, stream);
-#else
 #ifdef HR_SPLIT_LIST_NW8
     // the verified fast path's second pass: a handful of tiles, each alone on its CU -- what counts is the latency of ONE tile through the six
     // layers.  Eight wavefronts (32 hidden features each) halve every wavefront's share; same arithmetic, same bits (a whole frame this way is
@@ -191,5 +144,4 @@ void HR_SPLIT_LAUNCH(const hr_config& cfg, const HrMlpArgs& args, hipStream_t st
     if (cfg.mlp_hidden == 256 && args.ray_index) { hr_launch_mlp_split_t<256, 2, 8>(cfg, args, stream); return; }
 #endif
     if (cfg.mlp_hidden == 256) hr_launch_mlp_split_t<256, 2, 4>(cfg, args, stream);
-#endif
 }

@@ -43,22 +43,13 @@ __device__ __forceinline__ float hr_block_exchange(float v, int src_tid, float* 
     return s_x[src_tid];
 }
 
-// Measurement builds (-DHR_DPP_GUARD, tools/build_variant.py): four idle issue slots in front of every cross-lane read, tied to the value
-// it reads -- if an image ever depended on the distance between a register's write and its DPP / permlane read, this build would differ
-#ifdef HR_DPP_GUARD
-#define HR_DPP_PRE(v) asm volatile("s_nop 3" : "+v"(v))
-#else
-#define HR_DPP_PRE(v) do {} while (0)
-#endif
-
 template <int CTRL>
 __device__ __forceinline__ float hr_dpp_f(float v)
 {
-    HR_DPP_PRE(v);
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
 }
 template <int CTRL>
-__device__ __forceinline__ int hr_dpp_i(int v) { HR_DPP_PRE(v); return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+__device__ __forceinline__ int hr_dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
 
 // Cross-lane moves of the per-ray sort / scan / sum as pure VALU operations (DPP, v_permlane16_swap): the generic
 // __shfl_* forms go through the LDS crossbar (ds_bpermute_b32: ~100 cycles of latency each, 42 of them per sample slot).
@@ -67,7 +58,6 @@ __device__ __forceinline__ int hr_dpp_i(int v) { HR_DPP_PRE(v); return __builtin
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ float hr_dpp_old(float old, float v)       // lanes without a source (or masked rows) keep `old`
 {
-    HR_DPP_PRE(v);
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
 }
 
@@ -83,14 +73,12 @@ __device__ __forceinline__ float hr_lane_xor(float v)
         const float up = hr_dpp_f<0x12C>(v), dn = hr_dpp_f<0x124>(v);      // row_ror:12 reads lane l + 4, row_ror:4 lane l - 4 (mod 16)
         return ((int)threadIdx.x & 4) ? dn : up;
     } else if constexpr (D == 16) {
-        HR_DPP_PRE(v);
         // v_permlane16_swap_b32: odd rows of the first operand <-> even rows of the second; with v in both, the first result
         // holds row r-1 in the odd rows, the second row r+1 in the even rows
         const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, v), __builtin_bit_cast(unsigned, v), false, false);
         return __builtin_bit_cast(float, ((int)threadIdx.x & 16) ? r[0] : r[1]);
     } else {
         // v_permlane32_swap_b32: the upper half of the first operand <-> the lower half of the second
-        HR_DPP_PRE(v);
         const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, v), __builtin_bit_cast(unsigned, v), false, false);
         return __builtin_bit_cast(float, ((int)threadIdx.x & 32) ? r[0] : r[1]);
     }
@@ -219,15 +207,11 @@ template <int J> struct HrPlaneAxes {
 //   neural_3d Z=64 keyframe         4.55 (L1 hit rate 61 %)   3.95                   2.93
 template <int ZP, bool HALF>
 struct HrGatherTune {
-#ifdef HR_SAMPLE_MIN_BLOCKS_FP32
-    static constexpr int MIN_BLOCKS = HR_SAMPLE_MIN_BLOCKS_FP32;
-#else
     static constexpr int MIN_BLOCKS = 4;     // generic gather: 110-120 VGPRs, 5 workgroups/CU (96) spills in both texel formats.  The class
                                              // gathers take 64-78 (two line taps) / 86-88 (keyframe blend) registers and run 6 / 5 per CU as they are.
                                              // Round 6, DoNeRF (78): capped at 72 (3 spills) 0.70 ms, at 64 (21 spills) 1.12 against 0.68; held to
                                              // 5 / 4 per CU by LDS 0.745 / 0.883 (profiles/r06_k2_occupancy_ab*.txt); the keyframe form capped at 80:
                                              // 7-9 spills, slower in round 5 (0.78 vs 0.76 ms)
-#endif
 };
 
 // acc[j] (+)= w * texel[q0 + j] for the first min(nb, G) channel groups of one tap; `off` is the
@@ -819,10 +803,6 @@ __device__ __forceinline__ void hr_gather_844(const HrGridPlane* pl, const HrAxi
 template <int HI>
 __device__ __forceinline__ float hr_fma_mix(unsigned word, float w, float c)
 {
-#ifdef HR_NO_MIX_ASM       // measurement builds: the same operation left to the compiler
-    typedef _Float16 hr_h2 __attribute__((ext_vector_type(2)));
-    return __builtin_fmaf((float)__builtin_bit_cast(hr_h2, word)[HI], w, c);
-#endif
     float d;
     if constexpr (HI) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(word), "v"(w), "v"(c));
     else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(word), "v"(w), "v"(c));
@@ -831,10 +811,6 @@ __device__ __forceinline__ float hr_fma_mix(unsigned word, float w, float c)
 template <int HI>
 __device__ __forceinline__ float hr_mul_mix(unsigned word, float w)           // fma(x, w, +0): the product (only a zero's sign can differ)
 {
-#ifdef HR_NO_MIX_ASM
-    typedef _Float16 hr_h2 __attribute__((ext_vector_type(2)));
-    return __builtin_fmaf((float)__builtin_bit_cast(hr_h2, word)[HI], w, 0.0f);
-#endif
     float d;
     if constexpr (HI) asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(word), "v"(w));
     else asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(word), "v"(w));
@@ -982,23 +958,10 @@ __device__ __forceinline__ void hr_gather_844h(const HrGridPlane* pl, const HrAx
     sig_feat = valid ? out[0] : 0.0f; pre0 = valid ? out[1] : 0.0f; pre1 = valid ? out[2] : 0.0f; pre2 = valid ? out[3] : 0.0f;
 }
 
-#ifdef HR_TUNING
-// per-phase cycle accounting of the sample body (tools/frame_stats.py): wave-uniform accumulators owned by the caller
-__device__ unsigned long long hr_sample_phase[16];
-#define HR_SPH(i) do { const unsigned long long t__ = __builtin_readcyclecounter(); sph__[i] += t__ - tph__; tph__ = t__; } while (0)
-#define HR_SPH_BEGIN() unsigned long long tph__ = __builtin_readcyclecounter()
-#define HR_SPH_PARAM , unsigned long long (&sph__)[12]
-#define HR_SPH_ARG , sph__
-#elif defined(HR_PHASE_MARK)     // tools/phase_table: comments in the assembly that delimit the phases
+#ifdef HR_PHASE_MARK     // tools/phase_table: comments in the assembly that delimit the phases
 #define HR_SPH(i) do { __builtin_amdgcn_sched_barrier(0); asm volatile("; HRPHASE " #i ::: "memory"); } while (0)
-#define HR_SPH_BEGIN() do {} while (0)
-#define HR_SPH_PARAM
-#define HR_SPH_ARG
 #else
 #define HR_SPH(i) do {} while (0)
-#define HR_SPH_BEGIN() do {} while (0)
-#define HR_SPH_PARAM
-#define HR_SPH_ARG
 #endif
 
 // AlphaGridMask.sample_alpha(p) > 0 (utils/tensorf_utils.py:459-484; the test the reference carries at tensorf_no_sample.py:171-177)
@@ -1180,7 +1143,7 @@ __device__ __forceinline__ void hr_fill_decode(const hr_config& cfg, const HrSam
 // scratch of the block for rays that span several wavefronts (ZP > 64, stand-alone kernel only).
 template <int ZP, bool HALF, int PIPE, int NB, int PC>
 __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSampleArgs& a, const HrRayLane& L, int64_t ray, bool ray_ok, int k,
-                                               const float* hrow, int HS, const float* M, const float* ones, float* s_x HR_SPH_PARAM)
+                                               const float* hrow, int HS, const float* M, const float* ones, float* s_x)
 {
     const int tid = threadIdx.x;
     const int Z = cfg.z_channels;
@@ -1201,43 +1164,14 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
         hk = hrow + (kk / Mz) * HS + (kk % Mz) * P;
     }
 
-    HR_SPH_BEGIN();
     // ---- distances: intersect + mask, then sort along the ray (base.py:152-210)
     float dist = __builtin_inff();
-#ifdef HR_TUNING
-    if (a.dbg_mode & 16) dist = 0.5f + 0.01f * (float)k + hk[0] * 1e-9f; else
-#endif
     // verified fast path (a.redo_list, DESIGN 3i): which of this sample's comparisons are within the band of flipping
     // (always evaluated -- ~25 vector instructions per sample; a pointer that may be NULL at run time would put the struct into scratch memory)
     HrRisk risk_ = HR_RISK_INIT(a.redo_band, a.redo_band_q, a.redo_band_off, a.redo_amp_cut);
     HrRisk* const risk = &risk_;
-#ifdef HR_DEBUG_HSUM
-    unsigned dbg_early = 0u;                      // the head values as they are read HERE, before the distance is computed from them
-    if (lane_ok) for (int i = 0; i < P; ++i) dbg_early ^= __builtin_bit_cast(unsigned, hk[i]) * (unsigned)(2 * (k * P + i) + 1);
-    asm volatile("" : "+v"(dbg_early));
-    unsigned dbg_mism = 0u;                       // the same words read twice, back to back, through a volatile pointer: do two reads of LDS ever disagree?
-    if (lane_ok) {
-        const volatile float* vh = hk;
-        for (int i = 0; i < P; ++i) {
-            const float r1 = vh[i];
-            const float r2 = vh[i];
-            if (__builtin_bit_cast(unsigned, r1) != __builtin_bit_cast(unsigned, r2)) dbg_mism += 1u;
-        }
-    }
-    const unsigned dbg_ray = (__builtin_bit_cast(unsigned, ro[0]) * 3u) ^ (__builtin_bit_cast(unsigned, ro[1]) * 5u) ^ (__builtin_bit_cast(unsigned, ro[2]) * 7u) ^
-                             (__builtin_bit_cast(unsigned, rd[0]) * 11u) ^ (__builtin_bit_cast(unsigned, rd[1]) * 13u) ^ (__builtin_bit_cast(unsigned, rd[2]) * 17u) ^
-                             (__builtin_bit_cast(unsigned, cfg.samples[kk]) * (unsigned)(2 * k + 1));
-#endif
     if (lane_ok) dist = hr_sample_distance(cfg, hk, k, ro, rd, risk, L.quad);
-#ifdef HR_DEBUG_HSUM
-    float dbg_mid[8];
-    for (int i = 0; i < 8; ++i) dbg_mid[i] = risk_.dbg[i];
-    const unsigned dbg_pre = lane_ok ? __builtin_bit_cast(unsigned, dist) * (unsigned)(2 * k + 1) : 0u;       // the distance before the sort
-#endif
     HR_SPH(0);
-#ifdef HR_TUNING
-    if (!(a.dbg_mode & 8))
-#endif
     // verified fast path: the points' margin grows with the largest |d distance / d length| among the ray's live samples (the sort below
     // moves distances between lanes; the margin does not follow them)
     float band_p = 0.0f;
@@ -1258,9 +1192,6 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
         }
     }
     if (cfg.sort) dist = hr_sort_ray<ZP>(dist, k, s_x);
-#ifdef HR_DEBUG_HSUM
-    const unsigned dbg_sorted = lane_ok ? __builtin_bit_cast(unsigned, dist) * (unsigned)(2 * k + 1) : 0u;    // ... after it
-#endif
     HR_SPH(1);
 
     // ---- points, contraction, advect, offset
@@ -1268,9 +1199,6 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
     const float base_t = L.base_t, time_off = L.time_off;
     float p[3] = {0.f, 0.f, 0.f};
     float dist_c = 0.0f;
-#ifdef HR_TUNING
-    if (a.dbg_mode & 32) { p[0] = dist * 0.3f; p[1] = dist * 0.2f; p[2] = dist * 0.1f; dist_c = dist; } else
-#endif
     if (lane_ok) hr_sample_point(cfg, hk, dist, ro, rd, oc, time_off, p, &dist_c);
 
     // deltas (tensorf_no_sample.py:137-144)
@@ -1281,17 +1209,10 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
     HR_SPH(2);
 
     // ---- feature gather
-#ifdef HR_TUNING      // measurement builds only: HR_SAMPLE_DBG=1 skips the feature gather
-    bool valid = lane_ok && hr_sample_valid(cfg, p, dist_c) && !(a.dbg_mode & 1) && (a.rows_out == nullptr);
-#else
     bool valid = lane_ok && hr_sample_valid(cfg, p, dist_c, risk, band_p) && (a.rows_out == nullptr);
-#endif
     if (a.occ && valid) valid = hr_occupancy_test(a, p);     // opt-in occupancy early-reject: empty space is neither gathered nor composited (sigma = 0)
     float sig_feat = 0.0f;
     float pre0 = 0.0f, pre1 = 0.0f, pre2 = 0.0f;
-#ifdef HR_TUNING
-    if (!(a.dbg_mode & 2))
-#endif
     if constexpr (PC != 0) {               // plane classes [8, 4, 4] / [8, 0, 0] (hr_gather_844 / hr_gather_844h)
         float pn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (valid) {
@@ -1391,9 +1312,6 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
                 r0 = HR_RCP(1.0f + HR_EXP(-pre0)); r1 = HR_RCP(1.0f + HR_EXP(-pre1)); r2 = HR_RCP(1.0f + HR_EXP(-pre2));
             }
         }
-#ifdef HR_TUNING
-        if (!(a.dbg_mode & 64))
-#endif
         if (cfg.f_color_scale.offset >= 0) {       // scale_shift_color_all, tensorf_utils.py:267-273
             const hr_head_field& fs = cfg.f_color_scale;
             const hr_head_field& fh = cfg.f_color_shift;
@@ -1461,31 +1379,6 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
         }
     }
 
-#ifdef HR_DEBUG_HSUM
-    if (a.dbg_hsum) {
-        unsigned hx = 0u;
-        if (lane_ok) for (int i = 0; i < P; ++i) hx ^= __builtin_bit_cast(unsigned, hk[i]) * (unsigned)(2 * (k * P + i) + 1);
-        unsigned dx = lane_ok ? __builtin_bit_cast(unsigned, dist_c) * (unsigned)(2 * k + 1) : 0u;
-        unsigned px = dbg_pre, sx = dbg_sorted, ex = dbg_early, rx = lane_ok ? dbg_ray : 0u;
-        for (int d = 1; d < ZW; d <<= 1) { hx ^= __shfl_xor(hx, d, 64); dx ^= __shfl_xor(dx, d, 64); px ^= __shfl_xor(px, d, 64); sx ^= __shfl_xor(sx, d, 64);
-                                           ex ^= __shfl_xor(ex, d, 64); rx ^= __shfl_xor(rx, d, 64); }
-        unsigned mx = dbg_mism;
-        for (int d = 1; d < ZW; d <<= 1) mx += __shfl_xor(mx, d, 64);
-#if HR_DEBUG_HSUM >= 2          // 2: the six products + two sums per lane (hr_math.h); 3: the eight intermediates of the default debug level, per lane
-        constexpr int DBG_STRIDE = 16 + 8 * 32 + 8;          // per ray: 16 checksums, 8 raw words per lane (up to 32 lanes), the ray's 6 floats + 2 spare
-        if (lane_ok && k < 32) for (int i = 0; i < 8; ++i) a.dbg_hsum[(size_t)DBG_STRIDE * ray + 16 + 8 * k + i] = __builtin_bit_cast(unsigned, dbg_mid[i]);
-        if (ray_ok && k == 0) for (int i = 0; i < 3; ++i) { a.dbg_hsum[(size_t)DBG_STRIDE * ray + 272 + i] = __builtin_bit_cast(unsigned, ro[i]); a.dbg_hsum[(size_t)DBG_STRIDE * ray + 275 + i] = __builtin_bit_cast(unsigned, rd[i]); }
-#else
-        constexpr int DBG_STRIDE = 16;
-#endif
-        if (ray_ok && k == 0) { unsigned* o = a.dbg_hsum + (size_t)DBG_STRIDE * ray; o[0] = hx; o[1] = dx; o[2] = px; o[3] = sx; o[4] = ex; o[5] = rx; o[6] = mx; }
-        for (int i = 0; i < 8; ++i) {            // the intermediates of the sphere intersection, in evaluation order: the first that differs names the operation
-            unsigned c = lane_ok ? __builtin_bit_cast(unsigned, dbg_mid[i]) * (unsigned)(2 * k + 1) : 0u;
-            for (int d = 1; d < ZW; d <<= 1) c ^= __shfl_xor(c, d, 64);
-            if (ray_ok && k == 0) a.dbg_hsum[(size_t)DBG_STRIDE * ray + 8 + i] = c;
-        }
-    }
-#endif
     // ---- optional diagnostics
     if (lane_ok) {
         const int64_t s = ray * Z + k;

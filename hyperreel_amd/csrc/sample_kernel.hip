@@ -83,9 +83,6 @@ __global__ __launch_bounds__(256, (HrGatherTune<ZP, HALF>::MIN_BLOCKS)) void hr_
     }
     const bool per_ray_M = (cfg.shading == HR_SHADING_SH);
     float* M = s_M + (per_ray_M ? rib * 3 * CA : 0);
-#ifdef HR_TUNING
-    if (!(a.dbg_mode & 4))
-#endif
     if (per_ray_M) {                               // SH: folded with the ray's view direction, which its lanes read themselves (the record is not published yet)
         HrRayLane V = hr_load_ray(cfg, a, 0, false);
         if (ray_ok) {
@@ -101,19 +98,13 @@ __global__ __launch_bounds__(256, (HrGatherTune<ZP, HALF>::MIN_BLOCKS)) void hr_
     __syncthreads();
     const HrRayLane L = hr_read_ray_record(s_ray + rib * HR_RAY_RECORD);
 
-#ifdef HR_TUNING
-    unsigned long long sph__[12] = {};
-#endif
-    hr_sample_body<ZP, HALF, 1, NB, PC>(cfg, a, L, ray, ray_ok, k, s_head + rib * RPR * HS, HS, M, s_ones, s_x HR_SPH_ARG);
+    hr_sample_body<ZP, HALF, 1, NB, PC>(cfg, a, L, ray, ray_ok, k, s_head + rib * RPR * HS, HS, M, s_ones, s_x);
 }
 
 static size_t hr_sample_lds_bytes(int nq, int ca_total, int ZP, int rows_per_ray)
 {
     const int RPB = 256 / ZP;
     size_t bytes = ((size_t)RPB * rows_per_ray * (nq * 4 + 4) + (size_t)RPB * 3 * ca_total + (ZP > 64 ? 256 : 0)) * sizeof(float);
-#ifdef HR_SAMPLE_LDS_FLOOR     // measurement builds: fewer workgroups per CU than the registers allow (profiles/r06_k2_occupancy_ab.txt)
-    if (bytes < HR_SAMPLE_LDS_FLOOR) bytes = HR_SAMPLE_LDS_FLOOR;
-#endif
     return bytes;
 }
 
@@ -126,11 +117,6 @@ void hr_launch_samples(const hr_config& cfg, const HrSampleArgs& args, hipStream
     const int RPB = 256 / ZP;
     const unsigned blocks = (unsigned)((args.n_rays + RPB - 1) / RPB);
     const size_t lds = hr_sample_lds_bytes(args.nq, args.ca_total, ZP, args.rows_per_ray);
-    HrSampleArgs args2 = args;
-#ifdef HR_TUNING       // measurement builds only (tools/): HR_SAMPLE_DBG=1 skips the feature gather
-    static const int dbg = [] { const char* e = getenv("HR_SAMPLE_DBG"); return e ? atoi(e) : 0; }();
-    args2.dbg_mode = dbg;
-#endif
     // few samples x many head columns can exceed the 64 KiB a kernel gets by default (e.g. 32 rays x 8 x 64 floats)
     const bool big_lds = lds > 64 * 1024;
     // the shipped [8, 4, 4] / [8, 0, 0] decompositions get the class-specialised gather of their texel format (sample_core.inc); ZP >= 8
@@ -143,7 +129,7 @@ void hr_launch_samples(const hr_config& cfg, const HrSampleArgs& args, hipStream
 #define HR_LAUNCH_SAMPLES_N(Z_, H_, P_, N_) \
     do { \
         if (big_lds) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&hr_sample_kernel<Z_, H_, P_, N_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((hr_sample_kernel<Z_, H_, P_, N_>), dim3(blocks), dim3(256), lds, stream, args2.cfg_dev, args2); \
+        hipLaunchKernelGGL((hr_sample_kernel<Z_, H_, P_, N_>), dim3(blocks), dim3(256), lds, stream, args.cfg_dev, args); \
     } while (0)
 #define HR_LAUNCH_SAMPLES_T(Z_, H_, P_) \
     do { \

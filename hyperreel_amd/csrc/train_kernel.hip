@@ -725,7 +725,7 @@ static bool hr_lines_opt_in(int pc, size_t lds)
 template <int ZP>
 static bool hr_launch_gather_bwd_lines(const hr_config& cfg, const HrTrainArgs& args, hipStream_t stream)
 {
-#if defined(HR_TRAIN_NO_WINDOWS) || defined(HR_TRAIN_DET)      // measurement builds / the deterministic build: the global-atomics kernel for everything
+#ifdef HR_TRAIN_DET      // the deterministic build: the global-atomics kernel for everything
     (void)cfg; (void)args; (void)stream;
     return false;
 #else

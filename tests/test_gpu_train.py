@@ -104,7 +104,7 @@ def test_a_batch_spread_over_every_keyframe_matches_autograd(model, grid):
     large grid -- takes the two-pass split.  Tolerances: on the 900 x 700 plane a texel is 1e-3 of the box, so the fp32 rounding of a
     coordinate moves the random features 70x more than on the 40^3 fixtures: forward 2e-4, and single samples that the two
     implementations weigh differently show in individual gradient entries (the same 3.2e-3 of a_b0's largest entry with the
-    global-atomics kernel, HR_TRAIN_NO_WINDOWS builds) -- entries at 5e-3 of the tensor's largest, and what a lost or doubled
+    global-atomics kernel in place of the windowed one) -- entries at 5e-3 of the tensor's largest, and what a lost or doubled
     group of rays would move, the whole tensor, at ||difference|| <= 2e-3 ||gradient||; the MLP gradients, sums over 12 288 rays
     through the split-bf16 training GEMMs, at 3e-3."""
     from types import SimpleNamespace

@@ -1,7 +1,7 @@
 """Shader clock and socket power while K1 runs back to back (rocm-smi polled from a thread), for the product and for measurement builds of it:
 is K1's time an ENERGY figure?  (Every schedule change of round 6 -- prefetches, look-ahead 3 / 5 / 7, 4 or 8 wavefronts, staggered or
 turn-taking workgroups -- ran level, while removing WORK (instructions, L2 traffic, MFMAs) always paid, additively.)
-python tools/k1_power_probe.py [product k1_nomfma ...]"""
+python tools/k1_power_probe.py [product NAME ...]   (NAME: tools/_bin/libhr_NAME.so)"""
 import json, os, subprocess, sys, threading, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
