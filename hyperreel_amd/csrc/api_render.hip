@@ -1,0 +1,400 @@
+// C ABI, rendering: kernel arguments from the model, the launch plans of hr_render (chunked two-kernel, frame kernel, cascade front,
+// verified fast path) and the single-stage entry points.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "hr_model.h"
+
+// tier: 0 = the model's primary arithmetic; the verified fast path's later passes: 1 = its f16x3 tiles, 2 = its bf16x3 tiles (fill_mlp_args(..., tier))
+void launch_mlp(const hr_model* m, const hr_config& c, const HrMlpArgs& a, hipStream_t st, int tier)
+{
+    if (c.mlp_layers == 0) return;               // ZeroMLP: the workspace already holds the (all-zero) head
+    const int prec = tier == 1 ? HR_MLP_F16X3 : (tier == 2 ? HR_MLP_BF16X3 : m->active_precision);
+    if (prec == HR_MLP_BF16X3) hr_launch_mlp_bf16x3(c, a, st);
+    else if (prec == HR_MLP_F16X3) hr_launch_mlp_f16x3(c, a, st);
+    else if (prec == HR_MLP_F16X2) hr_launch_mlp_f16x2(c, a, st);
+    else if (prec == HR_MLP_F16F8) hr_launch_mlp_f16f8(c, a, st);
+    else hr_launch_mlp(c, a, st);
+}
+
+void fill_mlp_args(const hr_model* m, HrMlpArgs& a, const float* rays, int64_t n, int tier)
+{
+    const HrMlpTiles& t = m->tiles[tier];
+    a.rays = rays;
+    a.n_rays = n;
+    a.head = m->head;
+    for (int l = 0; l < HR_MAX_LAYERS; ++l) {
+        a.wpack[l] = t.wpack[l];
+        a.wsplit[l] = t.wsplit[l];
+        a.bias[l] = t.bias[l];
+        a.winv[l] = t.winv[l];
+        a.xexp[l] = tier > 0 ? 0 : m->xexp[l];
+        a.n_tiles[l] = t.n_tiles[l];
+    }
+    a.ray0 = 0;
+    a.ray_index = nullptr;
+    a.n_rays_dev = nullptr;
+    a.list_off = 0;
+    a.n_rays_copy = nullptr;
+    a.redo_list = nullptr;
+    a.redo_count = nullptr;
+    a.redo_cap = 0;
+    a.n_out = m->n_out;
+    a.nq = (m->n_out + 3) / 4;
+    a.k0p = m->k0p;
+    a.trace = nullptr;
+    a.flags = m->flags;
+}
+
+// Plane pair j as the render kernels get it.  Inside hr_render_frame on a keyframe net all rays of the call share one time, and that time
+// sits on a keyframe row (advect_points quantises it, utils/flow_utils.py:10-35): the time plane is then handed over as the LINE that
+// row is -- the gather's line form, 2 taps instead of 4 (the other row's weight is the 1e-7 left by rounding, see hr_render_frame).
+static HrGridPlane render_plane(const hr_model* m, int j)
+{
+    HrGridPlane g = m->planes[j];
+    if (m->frame_row >= 0 && m->frame_line[j]) {
+        g.b = m->frame_line[j];
+        g.bh = g.bw;
+        g.bw = 1;
+    }
+    return g;
+}
+
+void fill_sample_args(const hr_model* m, HrSampleArgs& a, const float* rays, int64_t n, float* rgb)
+{
+    a.cfg_dev = m->kcfg_dev;
+    a.rays = rays;
+    a.head = m->head;
+    a.nq = (m->n_out + 3) / 4;
+    a.n_rays = n;
+    a.rgb = rgb;
+    a.fields = hr_fields();
+    for (int j = 0; j < 3; ++j) a.planes[j] = render_plane(m, j);
+    a.basis = m->basis;
+    a.basis_t = m->basis_t;
+    a.slot_col = m->slot_col;
+    a.basis_ld = m->basis_ld;
+    a.n_basis_cols = m->n_basis_cols;
+    a.ca_total = m->ca_total;
+    // the table is read in place from the uploaded copy (12 floats per camera, no re-layout)
+    a.color_table = nullptr;
+    if (m->cfg.color_table_views > 0) {
+        auto it = m->raw.find("color_embedding");
+        if (it != m->raw.end()) a.color_table = it->second.p;
+    }
+    a.ray0 = 0;
+    a.ray_index = nullptr;
+    a.n_rays_dev = nullptr;
+    a.list_off = 0;
+    a.zero_word = nullptr;
+    a.redo_list = nullptr;
+    a.redo_count = nullptr;
+    a.redo_cap = 0;
+    a.redo_band = a.redo_band_q = a.redo_band_off = a.redo_amp_cut = 0.0f;
+    a.flags = m->flags;
+    a.occ = m->occ;
+    a.occ_cells = m->occ_cells;
+    a.occ_w = m->occ_n[0]; a.occ_h = m->occ_n[1]; a.occ_d = m->occ_n[2];
+    for (int i = 0; i < 3; ++i) { a.occ_lo[i] = m->occ_lo[i]; a.occ_inv[i] = m->occ_inv[i]; }
+    a.rows_per_ray = rows_per_ray(m->cfg);
+    a.rows_out = nullptr;
+    a.row_dim = a.n_row_inputs = 0;
+    for (int i = 0; i < 4; ++i) a.row_kind[i] = a.row_len[i] = 0;
+}
+
+// Cascade, everything before the final sample kernel: coarse MLP -> coarse intersect (emits the point MLP's input
+// rows, one per coarse sample) -> point MLP over n * casc_in_z rows.  Leaves the fine head in m->head.
+static void launch_cascade_front(hr_model* m, const float* rays, int64_t n, hipStream_t st)
+{
+    hr_model* c0 = m->coarse.get();
+    HrMlpArgs ma;
+    fill_mlp_args(c0, ma, rays, n);
+    launch_mlp(c0, c0->kcfg, ma, st);
+    HrSampleArgs sa;
+    fill_sample_args(c0, sa, rays, n, nullptr);
+    sa.rows_out = m->rows;
+    sa.row_dim = m->cfg.casc_row_dim;
+    sa.n_row_inputs = m->cfg.casc_n_inputs;
+    for (int i = 0; i < 4; ++i) { sa.row_kind[i] = m->cfg.casc_input_kind[i]; sa.row_len[i] = m->cfg.casc_input_dim[i]; }
+    hr_launch_samples(c0->kcfg, sa, st);
+    hr_config kc = m->kcfg;
+    kc.ray_dim = m->cfg.casc_row_dim;            // the point MLP's "rays" are the rows
+    HrMlpArgs mb;
+    fill_mlp_args(m, mb, m->rows, n * m->cfg.casc_in_z);
+    launch_mlp(m, kc, mb, st);
+}
+
+// redo0 >= 0: first pass of the verified fast path -- tiles that raise a range bit list their rays (indices start at redo0);
+// safe: the whole launch with the f16x3 tiles (hr_render_fields with diagnostics: one arithmetic for every output)
+void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int64_t redo0, int tier)
+{
+    if (m->coarse) {
+        launch_cascade_front(m, rays, n, st);
+        return;
+    }
+    HrMlpArgs ma;
+    fill_mlp_args(m, ma, rays, n, tier);
+    if (redo0 >= 0) {
+        ma.ray0 = redo0;
+        ma.redo_list = m->redo_list;
+        ma.redo_count = m->redo_count;
+        ma.redo_cap = m->redo_cap;
+    }
+    launch_mlp(m, m->kcfg, ma, st, tier);
+}
+
+// The frame kernel (fused_impl.inc) for the whole ray list; false: the model does not fit it (nothing launched)
+bool launch_frame(hr_model* m, const float* rays, int64_t n, float* rgb, bool probe, hipStream_t st)
+{
+    if (!m->opt_frame_kernel || m->coarse || m->is_coarse || m->cfg.mlp_layers == 0) return false;
+    if (m->verified) return false;               // the verified fast path is a two-pass plan over the HBM workspace
+    if (n > ((int64_t)1 << 36)) return false;
+    HrMlpArgs ma;
+    fill_mlp_args(m, ma, rays, n);
+    ma.head = nullptr;
+    HrSampleArgs sa;
+    fill_sample_args(m, sa, rays, n, rgb);
+    sa.head = nullptr;
+    switch (m->active_precision) {
+        case HR_MLP_BF16X3: return hr_launch_frame_bf16x3(m->kcfg, ma, sa, m->opt_sample_waves, m->opt_frame_kernel, m->n_cus, probe, st);
+        case HR_MLP_F16X3: return hr_launch_frame_f16x3(m->kcfg, ma, sa, m->opt_sample_waves, m->opt_frame_kernel, m->n_cus, probe, st);
+        case HR_MLP_F16X2: return hr_launch_frame_f16x2(m->kcfg, ma, sa, m->opt_sample_waves, m->opt_frame_kernel, m->n_cus, probe, st);
+        case HR_MLP_F16F8: return hr_launch_frame_f16f8(m->kcfg, ma, sa, m->opt_sample_waves, m->opt_frame_kernel, m->n_cus, probe, st);
+        default: return false;          // the exact-fp32 MLP (v_mfma_f32_16x16x4_f32) keeps its own kernel
+    }
+}
+
+static int check_render(const hr_model* m, const float* rays, int64_t n, const float* rgb)
+{
+    if (!m) return fail(HR_E_INVALID, "null model");
+    if (!m->finalized) return fail(HR_E_STATE, "hr_model_finalize has not been called");
+    if (n < 0) return fail(HR_E_INVALID, "negative ray count");
+    if (n > 0 && (!rays || !rgb)) return fail(HR_E_INVALID, "null ray / rgb buffer");
+    return HR_OK;
+}
+
+// rays per launch of a call of n rays: as many launches as the workspace demands, of equal size (a short last launch leaves the chip half empty
+// for a whole kernel)
+static int64_t even_chunk(const hr_model* m, int64_t n)
+{
+    if (n <= m->chunk) return m->chunk;
+    const int64_t k = (n + m->chunk - 1) / m->chunk;
+    const int64_t per = (((n + k - 1) / k) + 63) & ~(int64_t)63;
+    return per < m->chunk ? per : m->chunk;
+}
+
+// The verified fast path over one call's rays: first pass in f16f8 with the rays at risk listed on the device, then the list
+// again with the f16x3 tiles (in slices of the chunk's head workspace), then whatever left the half range there with the bf16x3 tiles.
+// list_cap: entries of the list this call may use.
+void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st)
+{
+    const hr_config& c = m->cfg;
+    const int64_t per = even_chunk(m, n_rays);
+    for (int64_t r0 = 0; r0 < n_rays; r0 += per) {
+        const int64_t n = (n_rays - r0 < per) ? (n_rays - r0) : per;
+        const float* rays = rays_dev + r0 * c.ray_dim;
+        HrMlpArgs ma;
+        fill_mlp_args(m, ma, rays, n, 0);
+        ma.ray0 = r0;                                  // tiles that raise a range bit list their rays (indices start at r0)
+        ma.redo_list = m->redo_list;
+        ma.redo_count = m->redo_count;
+        ma.redo_cap = list_cap;
+        launch_mlp(m, m->kcfg, ma, st, 0);
+        HrSampleArgs sa;
+        fill_sample_args(m, sa, rays, n, rgb_dev + r0 * 3);
+        sa.ray0 = r0;
+        sa.redo_list = m->redo_list;
+        sa.redo_count = m->redo_count;
+        sa.redo_cap = list_cap;
+        sa.redo_band = m->redo_band;
+        sa.redo_band_q = m->redo_band_q;
+        sa.redo_band_off = m->redo_band_off;
+        sa.redo_amp_cut = HR_VERIFY_AMP_CUT;
+        hr_launch_samples(m->kcfg, sa, st);
+    }
+    // second pass: the listed rays (count on the device: the launches are sized for the capacity, blocks past the count leave at once) through
+    // the f16x3 tiles, gathered from / scattered to the caller's buffers by index.  The head workspace is free again; a list longer than it is
+    // walked in slices.  The counter is cleared for the next call by the FIRST slice's sample kernel, which like every later launch of the
+    // pass reads the copy the first slice's MLP kernel made (a memset node between calls does not survive hipGraph replay)
+    for (int64_t off = 0; off < list_cap; off += m->chunk) {
+        const int64_t cap = (list_cap - off < m->chunk) ? (list_cap - off) : m->chunk;
+        HrMlpArgs ma;
+        fill_mlp_args(m, ma, rays_dev, cap, 1);
+        ma.ray_index = m->redo_list + off;
+        ma.list_off = off;
+        ma.n_rays_dev = off == 0 ? m->redo_count : m->redo_count + 1;
+        ma.n_rays_copy = off == 0 ? m->redo_count + 1 : nullptr;
+        ma.redo_list = m->wide_list;                   // a tile of THIS pass in which an activation leaves the half range goes on to the third
+        ma.redo_count = m->redo_count + 2;
+        ma.redo_cap = m->wide_cap;
+        launch_mlp(m, m->kcfg, ma, st, 1);
+        HrSampleArgs sa;
+        fill_sample_args(m, sa, rays_dev, cap, rgb_dev);
+        sa.ray_index = m->redo_list + off;
+        sa.list_off = off;
+        sa.n_rays_dev = m->redo_count + 1;
+        sa.zero_word = off == 0 ? m->redo_count : nullptr;
+        hr_launch_samples(m->kcfg, sa, st);
+    }
+    // third pass: those tiles' rays with the bf16x3 tiles -- halves with the fp32 exponent range, nothing to overflow.  What a captured
+    // viewer loop gets where the host's guard (models.py: a sticky bit read between calls) cannot reach
+    HrMlpArgs ma;
+    fill_mlp_args(m, ma, rays_dev, m->wide_cap, 2);
+    ma.ray_index = m->wide_list;
+    ma.n_rays_dev = m->redo_count + 2;
+    ma.n_rays_copy = m->redo_count + 3;
+    launch_mlp(m, m->kcfg, ma, st, 2);
+    HrSampleArgs sa;
+    fill_sample_args(m, sa, rays_dev, m->wide_cap, rgb_dev);
+    sa.ray_index = m->wide_list;
+    sa.n_rays_dev = m->redo_count + 3;
+    sa.zero_word = m->redo_count + 2;
+    hr_launch_samples(m->kcfg, sa, st);
+}
+
+// entries of the ray list one hr_render call may fill: a sixteenth of its rays, at least 32 768 (never more than the rays there are, or the buffer).
+// The second pass's launches are sized for it -- ~1.7 ns per workgroup that finds nothing to do -- and the calibration gives the fast path up
+// above a twentieth (HR_VERIFY_LISTED_LIMIT)
+int redo_list_cap(const hr_model* m, int64_t n_rays)
+{
+    int64_t cap = n_rays / 16 > 32768 ? n_rays / 16 : 32768;
+    cap = (cap + 63) & ~(int64_t)63;
+    if (cap > n_rays) cap = (n_rays + 63) & ~(int64_t)63;
+    return (int)(cap < m->redo_cap ? cap : m->redo_cap);
+}
+
+int hr_render_fields(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, const hr_fields* fields, void* stream)
+{
+    int rc = check_render(m, rays_dev, n_rays, rgb_dev);
+    if (rc != HR_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const hr_config& c = m->cfg;
+    const int Z = c.z_channels;
+    if (!fields && launch_frame(m, rays_dev, n_rays, rgb_dev, false, st)) {
+        HR_HIP(hipGetLastError());
+        return HR_OK;
+    }
+    // (Running the sample stage of chunk i on a second stream under the MLP of chunk i+1 was
+    //  measured twice -- plain, and with the MLP limited to one workgroup per CU so that sample
+    //  blocks could co-reside -- and is slower than back-to-back launches: 3.0-3.9 vs 2.79 ms per
+    //  800x800 frame; the two kernels do not interleave on the CUs.)
+    // verified fast path.  With diagnostics requested every output comes from ONE arithmetic: the f16x3 tiles throughout.
+    // So does a model with an occupancy volume (hr_occupancy_test decides per cell from a head-dependent point; the band does not cover it),
+    // and a render inside a stream capture whose band is out of date (hr_model_update_config since the last measurement: measuring synchronises).
+    bool verify = m->verified && !fields && !m->occ && n_rays < ((int64_t)1 << 31);
+    if (verify && m->band_stale) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+        if (cs == hipStreamCaptureStatusNone) {
+            rc = calibrate_band(m, st);
+            if (rc != HR_OK) return rc;
+            verify = verify && m->verified;            // HR_MLP_AUTO may just have given the fast path up
+        } else {
+            verify = false;
+        }
+    }
+    if (verify && n_rays > 0) {
+        render_verified(m, rays_dev, n_rays, rgb_dev, redo_list_cap(m, n_rays), st);
+        HR_HIP(hipGetLastError());
+        return HR_OK;
+    }
+    const bool safe_all = m->verified != 0;
+    const int64_t per = even_chunk(m, n_rays);
+    for (int64_t r0 = 0; r0 < n_rays; r0 += per) {
+        const int64_t n = (n_rays - r0 < per) ? (n_rays - r0) : per;
+        const float* rays = rays_dev + r0 * c.ray_dim;
+        launch_front(m, rays, n, st, -1, safe_all ? 1 : 0);
+        HrSampleArgs sa;
+        fill_sample_args(m, sa, rays, n, rgb_dev + r0 * 3);
+        if (fields) {
+            if (fields->distances_dev) sa.fields.distances_dev = fields->distances_dev + r0 * Z;
+            if (fields->points_dev) sa.fields.points_dev = fields->points_dev + r0 * Z * 3;
+            if (fields->sigma_dev) sa.fields.sigma_dev = fields->sigma_dev + r0 * Z;
+            if (fields->weights_dev) sa.fields.weights_dev = fields->weights_dev + r0 * Z;
+            if (fields->head_dev)
+                hr_launch_head_export(m->head, fields->head_dev + r0 * (int64_t)Z * c.preds_per_z, n, Z, c.preds_per_z, m->p_live,
+                                      (m->n_out + 3) / 4, rows_per_ray(c), m->col_map, st);
+        }
+        hr_launch_samples(m->kcfg, sa, st);
+    }
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}
+
+int hr_render(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, void* stream)
+{
+    return hr_render_fields(m, rays_dev, n_rays, rgb_dev, nullptr, stream);
+}
+
+int hr_render_frame(hr_model* m, const float* rays_dev, int64_t n_rays, float time, float* rgb_dev, void* stream)
+{
+    if (!m) return fail(HR_E_INVALID, "null model");
+    const hr_config& c = m->cfg;
+    hipStream_t st = (hipStream_t)stream;
+    m->frame_row = -1;
+    if (c.video && c.num_keyframes >= 2 && !m->coarse && !m->is_coarse && c.grid_dtype != HR_GRID_FP16 && m->finalized) {
+        // the time tap of every ray of the frame, as hr_sample_body computes it from the ray's last column (host restatement of
+        // hr_base_time, hr_normalize_time and hr_make_tap, csrc/hr_math.h; float32 throughout)
+        float base_t = 0.0f;
+        if (c.advect) {
+            float tt = time * c.flow_fac;
+            tt = fminf(fmaxf(tt, 0.0f), c.flow_kmax);
+            base_t = rintf(tt - 1e-5f) * c.flow_inv_fac;
+        }
+        const float g = (base_t * c.time_scale + c.time_offset) * 2.0f - 1.0f;
+        const int n = c.num_keyframes;
+        const float ix = ((g + 1.0f) / 2.0f) * (float)(n - 1);
+        const float f0 = floorf(ix), f1 = f0 + 1.0f;
+        const int i0 = (int)f0, i1 = i0 + 1;
+        const bool ok0 = i0 >= 0 && i0 < n, ok1 = i1 >= 0 && i1 < n;
+        const float w0 = ok0 ? f1 - ix : 0.0f, w1 = ok1 ? ix - f0 : 0.0f;
+        for (int j = 0; j < 3; ++j) {
+            const HrGridPlane& p = m->planes[j];
+            if (p.bw <= 1 || p.cd4 + p.ca4 == 0) continue;
+            const int row_floats = p.bw * p.tex;
+            if (!m->frame_line[j]) continue;
+            hr_launch_blend_rows(reinterpret_cast<const float*>(p.b), m->frame_line[j], row_floats, ok0 ? i0 : 0, ok1 ? i1 : 0, w0, w1, st);
+            m->frame_row = 0;
+        }
+    }
+    const int rc = hr_render_fields(m, rays_dev, n_rays, rgb_dev, nullptr, stream);
+    m->frame_row = -1;
+    return rc;
+}
+
+int hr_stage_mlp(hr_model* m, const float* rays_dev, int64_t n_rays, void* stream)
+{
+    int rc = check_render(m, rays_dev, n_rays, rays_dev);
+    if (rc != HR_OK) return rc;
+    if (n_rays > m->chunk) return fail(HR_E_INVALID, "n_rays exceeds the reserved chunk (%lld)", (long long)m->chunk);
+    launch_front(m, rays_dev, n_rays, (hipStream_t)stream);   // cascades: everything up to the fine head
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}
+
+int hr_stage_samples(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, void* stream)
+{
+    int rc = check_render(m, rays_dev, n_rays, rgb_dev);
+    if (rc != HR_OK) return rc;
+    if (n_rays > m->chunk) return fail(HR_E_INVALID, "n_rays exceeds the reserved chunk (%lld)", (long long)m->chunk);
+    HrSampleArgs sa;
+    fill_sample_args(m, sa, rays_dev, n_rays, rgb_dev);
+    hr_launch_samples(m->kcfg, sa, (hipStream_t)stream);
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}
+
+int hr_debug_trace_mlp(hr_model* m, const float* rays_dev, int64_t n_rays, unsigned long long* trace_dev, void* stream)
+{
+    int rc = check_render(m, rays_dev, n_rays, rays_dev);
+    if (rc != HR_OK) return rc;
+    if (n_rays > m->chunk) return fail(HR_E_INVALID, "n_rays exceeds the reserved chunk (%lld)", (long long)m->chunk);
+    if (m->coarse) return fail(HR_E_INVALID, "hr_debug_trace_mlp does not support cascades");
+    HrMlpArgs ma;
+    fill_mlp_args(m, ma, rays_dev, n_rays);
+    ma.trace = trace_dev;
+    launch_mlp(m, m->kcfg, ma, (hipStream_t)stream);
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}

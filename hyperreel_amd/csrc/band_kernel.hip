@@ -1,6 +1,6 @@
 // Band probe of the verified fast path: how far the cheap MLP arithmetic (f16f8) moves the quantities the per-sample stage
 // COMPARES -- primitive lengths (plane depth / radius), distances, points -- measured per model on its calibration rays against the
-// reference-grade arithmetic (f16x3), in the normalisation the sample stage's per-sample margins use (hr_math.h, HrRisk).  hr_model_finalize / hr_model_calibrate set the model's "at risk" band from it (api.hip,
+// reference-grade arithmetic (f16x3), in the normalisation the sample stage's per-sample margins use (hr_math.h, HrRisk).  hr_model_finalize / hr_model_calibrate set the model's "at risk" band from it (api_mlp.hip,
 // calibrate_band): a comparison further than the band from flipping falls the same way under both arithmetics.
 // The reference has no counterpart: its BaseMLP is fp32 (nlf/nets/mlp.py:159-172) and its decisions are exact comparisons
 // (nlf/intersect/base.py:194, utils/intersect_utils.py:45-150).

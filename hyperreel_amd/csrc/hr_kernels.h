@@ -1,4 +1,4 @@
-// Internal interface between the C-ABI layer (api.hip) and the kernels.
+// Internal interface between the C-ABI layer (api*.hip) and the kernels.
 #ifndef HR_KERNELS_H
 #define HR_KERNELS_H
 

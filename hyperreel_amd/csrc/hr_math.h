@@ -272,7 +272,7 @@ HR_FN void hr_contract_point(const hr_config& c, float px, float py, float pz, f
 // change a pixel by 1e-2.  With a non-NULL HrRisk the functions below also report whether any comparison they made was inside its margin;
 // the sample kernel collects the rays that have such a sample and hr_render renders them again with the reference-grade arithmetic.
 //
-// The margins are derived per SAMPLE from one number the model is calibrated for (api.hip: calibrate_band; band_kernel.hip):
+// The margins are derived per SAMPLE from one number the model is calibrated for (api_mlp.hip: calibrate_band; band_kernel.hip):
 //   band_zc  how far the two arithmetics' values of  z * scale + anchor  (process_z_vals before the inverse contraction: a smooth, bounded-
 //            slope function of one head column) may differ -- 4 x the largest difference measured on the calibration rays;
 // pushed through the derivatives of what follows it:
@@ -367,7 +367,7 @@ HR_FN float hr_zval(const hr_config& c, const float* hk, int ch, float one_m)
 HR_FN float hr_inverse_contract_slope(const hr_config& c, float zc, float r)
 {
     if (c.contract_type == HR_CONTRACT_AFFINE) return fabsf(c.c_aff_fac);
-    if (c.contract_type == HR_CONTRACT_DONERF) return 1.0f;       // (not derived: such models are not verified, api.hip can_verify)
+    if (c.contract_type == HR_CONTRACT_DONERF) return 1.0f;       // (not derived: such models are not verified, api_mlp.hip can_verify)
     if (fabsf(zc) < 1.0f) return fabsf(c.c_d0);
     const float ru = r * HR_RCP_BAND(c.c_d0);                      // 1 / inv
     return fabsf(c.c_d0 * ru * ru * HR_RCP_BAND(c.c_d_scale));

@@ -1,0 +1,197 @@
+// Private to the C-ABI layer (api*.hip): the model behind an hr_model handle, its device memory, and the helpers the
+// api files share.  Not part of the public interface (include/hyperreel_hip.h), whose declarations give the hr_* entry points
+// that the api files define their C linkage.
+#ifndef HR_MODEL_H
+#define HR_MODEL_H
+
+#include <hip/hip_runtime.h>
+
+#include <map>
+#include <memory>
+#include <string>
+
+#include "hr_kernels.h"
+#include "hr_train.h"
+
+// functions and types shared between the api files: the library exports none of them
+#define HR_HIDDEN __attribute__((visibility("hidden")))
+
+// sample wavefronts per workgroup of the frame kernel when the caller does not say (measured: DESIGN.md section 3)
+#ifndef HR_DEFAULT_SAMPLE_WAVES
+#define HR_DEFAULT_SAMPLE_WAVES 0      // the plan's own choice (8)
+#endif
+
+// the error message of the calling thread (hr_last_error); returns `code`
+HR_HIDDEN int fail(int code, const char* fmt, ...);
+
+#define HR_HIP(call)                                                                                   \
+    do {                                                                                               \
+        hipError_t e__ = (call);                                                                       \
+        if (e__ != hipSuccess) return fail(HR_E_HIP, "%s failed: %s", #call, hipGetErrorString(e__));  \
+    } while (0)
+
+// One device allocation, freed when its owner goes (move-only)
+template <typename T>
+class HR_HIDDEN DevMem {
+public:
+    DevMem() = default;
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    DevMem(DevMem&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevMem& operator=(DevMem&& o) noexcept
+    {
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    ~DevMem() { reset(); }
+    hipError_t alloc(size_t bytes) { reset(); return hipMalloc((void**)&p_, bytes); }   // (frees what it held first)
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+    }
+    operator T*() const { return p_; }
+    T* operator->() const { return p_; }
+
+private:
+    T* p_ = nullptr;
+};
+
+struct HR_HIDDEN DevBuf {
+    DevMem<float> p;
+    size_t bytes = 0;
+};
+
+// One packing of the MLP: MFMA B-operand tiles per Linear (layout documented in hr_kernels.h)
+struct HR_HIDDEN HrMlpTiles {
+    DevMem<float4> wpack[HR_MAX_LAYERS];     // HR_MLP_FP32: fp32 tiles
+    DevMem<uint16_t> wsplit[HR_MAX_LAYERS];  // the split arithmetics: hi / lo tiles
+    DevMem<float> bias[HR_MAX_LAYERS];
+    float winv[HR_MAX_LAYERS] = {};          // 2^-s of the packed split weights (HrMlpArgs::winv)
+    int n_tiles[HR_MAX_LAYERS] = {};
+    int64_t bytes = 0;
+};
+
+struct HR_HIDDEN hr_model {
+    hr_config cfg;        // as handed over by the caller
+    hr_config kcfg;       // what the kernels see: dead head columns removed (preds_per_z, field offsets)
+    HrColMap col_map;     // user column -> live column (-1: never read by the path, not computed)
+    int p_live = 0;
+    bool finalized = false;
+    std::map<std::string, DevBuf> raw;     // uploaded tensors, reference layout, device memory
+    std::map<std::string, size_t> expect;  // name -> expected byte size
+    // packed MLP, by tier: 0 = the active arithmetic.  Verified fast path: the MLP runs f16f8, rays with a comparison at risk
+    // (or a range bit) are listed on the device and rendered again by a second, list-driven pass at the end of hr_render with tier 1, the
+    // f16x3 tiles; tier 2: bf16x3 tiles (fp32 exponent range) for the third pass -- the tiles of the second pass in which an activation left
+    // the IEEE-half range (what the reference's fp32 BaseMLP, nlf/nets/mlp.py:159-172, cannot do)
+    HrMlpTiles tiles[3];
+    int xexp[HR_MAX_LAYERS] = {};         // f16 + fp8 split: exponent of the fp8 images of hidden Linear l's output (HrMlpArgs::xexp), from act_max
+    int k0p = 0;
+    int n_out = 0;
+    int active_precision = HR_MLP_FP32;   // the arithmetic the MLP kernels run: cfg.mlp_precision, with HR_MLP_AUTO resolved (resolve_precision)
+    float act_max[HR_MAX_LAYERS] = {};    // calibration: max |input feature|, max |pre-activation| of hidden Linear l - 1
+    int calibrated = 0;                   // 0: not calibrated (cascade rows / unsupported width), 1: synthetic rays (finalize), 2: the caller's rays
+    DevMem<unsigned> flags;               // sticky device status word (HrMlpArgs::flags)
+    int verified = 0;                     // the verified fast path is on (tiles[1], tiles[2])
+    DevMem<int> redo_list;                // the second pass's rays
+    DevMem<int> wide_list;                // the third pass's rays
+    DevMem<unsigned> redo_count;          // [0] second-pass counter, [1] its copy, [2] third-pass counter, [3] its copy
+    int redo_cap = 0;                    // entries the list holds (hr_model_reserve); a call uses max(32 768, n_rays / 16) of them
+    int wide_cap = 0;
+    float redo_band = 0.0f;              // the margins of THIS model (calibrate_band; hr_math.h HrRisk): of zc,
+    float redo_band_q = 0.0f;            //   of a point coordinate per unit of amplification,
+    float redo_band_off = 0.0f;          //   of the point-offset / flow heads
+    hr_verify_info vinfo = {};
+    DevMem<float> calib_rays;            // the rays the arithmetic was decided on (synthetic, or a strided sample of the caller's): kept for the band
+    int64_t calib_n = 0;
+    bool band_stale = false;             // hr_model_update_config changed the activations' constants: the band is measured again before the next render
+    int64_t mlp_bytes = 0;
+    // packed grids
+    DevMem<float> grid_a[3];   // texel storage (floats, or halfs when cfg.grid_dtype == HR_GRID_FP16)
+    DevMem<float> grid_b[3];
+    HrGridPlane planes[3] = {};
+    DevMem<float> basis;
+    DevMem<float> basis_t;               // column-major copy for the decode-matrix fold (HrSampleArgs::basis_t)
+    DevMem<int> slot_col;
+    int basis_ld = 0;
+    int n_basis_cols = 0;
+    int ca_total = 0;
+    // workspace
+    DevMem<float> head;
+    int64_t chunk = 0;
+    int64_t packed_bytes = 0;
+    // point_prediction cascade (hr_model_create_cascade): `this` is the fine level (point MLP, second intersect,
+    // colour); `coarse` holds the ray MLP and the first intersect and owns no grids
+    DevMem<hr_config> kcfg_dev;          // device copy of kcfg for the sample kernel (the MLP kernels take it by value)
+    std::unique_ptr<hr_model> coarse;
+    bool is_coarse = false;
+    DevMem<float> rows;      // input rows of the point MLP for one chunk: (chunk * casc_in_z, casc_row_dim)
+    // training path (hr_train_*): the caller's configuration on the device and packed gradient accumulators
+    DevMem<hr_config> ucfg_dev;
+    float* grad_a[3] = {};               // training: packed texel-gradient accumulators of the plane pairs -- slices of grad_pool
+    float* grad_b[3] = {};
+    DevMem<char> grad_pool;              // ONE allocation (cleared by one memset per step)
+    size_t grad_pool_bytes = 0;
+    HrMlpTiles train_tiles;              // training forward (hr_mlp_train_forward): bf16 split tiles of the CURRENT parameter values, re-packed on the device every step
+    DevMem<long long> grad_fx;           // deterministic training (HR_OPT_TRAIN_DETERMINISTIC): ONE 64-bit fixed-point buffer for every accumulator of a step
+    size_t grad_fx_elems = 0;
+    DevMem<HrFxUnit> fx_unit;            // ... and THIS model's fixed-point unit of the step (hr_train.h)
+    int opt_train_det = 0;
+    DevMem<float> tape;                  // per-sample values between the backward's phases: 8 words x tape_samples
+    int64_t tape_samples = 0;
+    // occupancy early-reject (hr_model_set_occupancy)
+    DevMem<float> occ;
+    DevMem<unsigned> occ_cells;           // one bit per lattice cell, built from a 0/1 volume (HrSampleArgs::occ_cells)
+    int occ_n[3] = {};
+    float occ_lo[3] = {}, occ_inv[3] = {};
+    // execution plan of hr_render (hr_model_set_option)
+    int frame_row = -1;                  // hr_render_frame: >= 0 while a call renders from frame_line[] (-1: general path)
+    DevMem<float> frame_line[3];         // the frame's blended keyframe rows, one line per time plane (float32 texels)
+    int opt_frame_kernel = 0;              // two kernels per chunk: level with the frame kernel since K1 took buffer loads (1.96 vs 1.99 ms per DoNeRF frame, interleaved
+                                           // events, profiles/r05_headline_diag_*.json) and with the tighter tail (hardware block dispatch instead of a static tile deal)
+    int opt_sample_waves = HR_DEFAULT_SAMPLE_WAVES;
+    int n_cus = 0;
+};
+
+static inline int layer_in(const hr_config& c, int l)
+{
+    if (l == 0) return c.mlp_in;
+    return c.mlp_hidden + (((c.mlp_skip_mask >> l) & 1) ? c.mlp_in : 0);
+}
+
+// samples whose head values one MLP row produces: all Z of a ray, or Z / casc_in_z per coarse point
+static inline int samples_per_row(const hr_config& c) { return c.casc_in_z > 0 ? c.z_channels / c.casc_in_z : c.z_channels; }
+static inline int rows_per_ray(const hr_config& c) { return c.casc_in_z > 0 ? c.casc_in_z : 1; }
+
+static inline int layer_out(const hr_config& c, int l) { return (l == c.mlp_layers - 1) ? samples_per_row(c) * c.preds_per_z : c.mlp_hidden; }
+
+// a ray with a live sample beyond it (60 degrees off a plane's normal; a sphere nearly tangent) is not what the margins of the verified fast
+// path are measured on -- its errors are the geometry's, the MLP's two-plane / Pluecker inputs included -- and is always listed
+constexpr float HR_VERIFY_AMP_CUT = 2.0f;
+
+// ---- api_mlp.hip
+// Linear l as the kernels compute it, in output tiles of tile_n features; with the model's k0p / n_out and live head columns
+struct HR_HIDDEN HrMlpLayer {
+    int N_user, Kt;          // the torch matrix
+    int N, Kp, nt;           // rows the kernels compute, padded K, output tiles
+    bool first, skip, last;
+    int k0p;                 // mlp_in padded to a multiple of 16
+    int n_out;               // head columns of one MLP row
+    int P_user, P_live;
+    int live_cols[64];       // live column c' of a sample -> the user's column
+};
+HR_HIDDEN HrMlpLayer mlp_layer(const hr_model* m, int l, int tile_n);
+HR_HIDDEN int resolve_precision(hr_model* m, const float* rays_dev, int64_t n, hipStream_t st);
+HR_HIDDEN int pack_mlp(hr_model* m);
+HR_HIDDEN int calibrate_band(hr_model* m, hipStream_t st);
+
+// ---- api_render.hip (tier: 0 = the model's primary arithmetic; the verified fast path's later passes: 1 = its f16x3 tiles, 2 = its bf16x3 tiles)
+HR_HIDDEN void launch_mlp(const hr_model* m, const hr_config& c, const HrMlpArgs& a, hipStream_t st, int tier = 0);
+HR_HIDDEN void fill_mlp_args(const hr_model* m, HrMlpArgs& a, const float* rays, int64_t n, int tier = 0);
+HR_HIDDEN void fill_sample_args(const hr_model* m, HrSampleArgs& a, const float* rays, int64_t n, float* rgb);
+HR_HIDDEN void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int64_t redo0 = -1, int tier = 0);
+HR_HIDDEN bool launch_frame(hr_model* m, const float* rays, int64_t n, float* rgb, bool probe, hipStream_t st);
+HR_HIDDEN void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st);
+HR_HIDDEN int redo_list_cap(const hr_model* m, int64_t n_rays);
+
+#endif  // HR_MODEL_H

@@ -363,7 +363,7 @@ void hr_launch_fixed_to_float(const long long* src, float* dst, int64_t n, const
 
 
 // ---------------------------------------------------------------- device-side weight packing for the training step's fused MLP forward
-// Same layout and roundings as pack_mlp (api.hip) for the bf16 split: wsplit[(((kt * nt + t) * 2 + part) * 64 + lane) * 8 + j] =
+// Same layout and roundings as pack_mlp (api_mlp.hip) for the bf16 split: wsplit[(((kt * nt + t) * 2 + part) * 64 + lane) * 8 + j] =
 // W[n = 32 t + (lane & 31)][k = 16 kt + 8 (lane >> 5) + j], part 0 = bf16(w), part 1 = bf16(w - hi); K order: layer 0 the input features
 // padded to k0p, skip layers [input padded to k0p | hidden]; last layer: kernel row n = k * P_live + c' is the user's row
 // k * P_user + live_cols[c'] (BaseMLP's weights, nlf/nets/mlp.py:127-172, as torch stores them: (out, in)).

@@ -840,7 +840,7 @@ def compile_model(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp3
 
 
 def live_head_columns(hc):
-    """Per-sample head columns the path reads (mirror of analyse_live_columns in csrc/api.hip).
+    """Per-sample head columns the path reads (mirror of analyse_live_columns in csrc/api_model.hip).
     The library drops the others from the last Linear; `hr_render_fields` reports them as 0."""
     live = [False] * hc.preds_per_z
 

@@ -193,7 +193,7 @@ def test_row_features_equal_the_kernel_encoding(hm):
         _, fine = plan.compile_model(g.cfg, g.dataset, g.grid)
         rows = np.random.default_rng(0).standard_normal((64, fine.casc_row_dim)).astype(np.float32)
         kc = plan.hr_config.from_buffer_copy(fine)
-        kc.ray_dim = fine.casc_row_dim                     # the point MLP's "rays" are the rows (api.hip launch_cascade_front)
+        kc.ray_dim = fine.casc_row_dim                     # the point MLP's "rays" are the rows (api_render.hip launch_cascade_front)
         want = np.zeros((64, fine.mlp_in), np.float32)
         hm.hm_features(C.byref(kc), fp(rows), 64, fp(want))
         assert np.abs(row_features(fine, torch.from_numpy(rows)).numpy() - want).max() <= 2e-7, case

@@ -39,7 +39,7 @@ def ht():
 
 
 def pack_grids(port, video):
-    """Texel layout of hr_model_finalize (api.hip): [H][W][4*cd4 density | 4*ca4 appearance] per plane pair."""
+    """Texel layout of hr_model_finalize (api_model.hip): [H][W][4*cd4 density | 4*ca4 appearance] per plane pair."""
     planes, packed, app_off, real_off = (GridPlane * 3)(), [], 0, 0
     for j in range(3):
         da, db, aa, ab = [t.detach().numpy()[0] for t in (port.d_a[j], port.d_b[j], port.a_a[j], port.a_b[j])]
