@@ -184,10 +184,26 @@ static int64_t even_chunk(const hr_model* m, int64_t n)
     return per < m->chunk ? per : m->chunk;
 }
 
+// The sample stage of one launch: the plain kernel, or with `maps` (hr_render_maps: non-NULL, some pointer set) the kernel that also
+// writes the per-ray maps.  r0: the launch's first ray in the caller's buffers, as args.rgb is offset (0 for the list-driven passes,
+// whose rays are indices into the whole call)
+static void launch_samples(const hr_model* m, const HrSampleArgs& sa, const hr_maps* maps, int64_t r0, hipStream_t st)
+{
+    if (!maps) {
+        hr_launch_samples(m->kcfg, sa, st);
+        return;
+    }
+    hr_maps mp = *maps;
+    if (mp.distances_dev) mp.distances_dev += r0;
+    if (mp.points_dev) mp.points_dev += r0 * 3;
+    if (mp.acc_dev) mp.acc_dev += r0;
+    hr_launch_samples_maps(m->kcfg, sa, mp, st);
+}
+
 // The verified fast path over one call's rays: first pass in f16f8 with the rays at risk listed on the device, then the list
 // again with the f16x3 tiles (in slices of the chunk's head workspace), then whatever left the half range there with the bf16x3 tiles.
-// list_cap: entries of the list this call may use.
-void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st)
+// list_cap: entries of the list this call may use.  maps: every pass writes the maps of the rays it writes pixels of (launch_samples)
+void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st, const hr_maps* maps)
 {
     const hr_config& c = m->cfg;
     const int64_t per = even_chunk(m, n_rays);
@@ -211,7 +227,7 @@ void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* 
         sa.redo_band_q = m->redo_band_q;
         sa.redo_band_off = m->redo_band_off;
         sa.redo_amp_cut = HR_VERIFY_AMP_CUT;
-        hr_launch_samples(m->kcfg, sa, st);
+        launch_samples(m, sa, maps, r0, st);
     }
     // second pass: the listed rays (count on the device: the launches are sized for the capacity, blocks past the count leave at once) through
     // the f16x3 tiles, gathered from / scattered to the caller's buffers by index.  The head workspace is free again; a list longer than it is
@@ -235,7 +251,7 @@ void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* 
         sa.list_off = off;
         sa.n_rays_dev = m->redo_count + 1;
         sa.zero_word = off == 0 ? m->redo_count : nullptr;
-        hr_launch_samples(m->kcfg, sa, st);
+        launch_samples(m, sa, maps, 0, st);
     }
     // third pass: those tiles' rays with the bf16x3 tiles -- halves with the fp32 exponent range, nothing to overflow.  What a captured
     // viewer loop gets where the host's guard (models.py: a sticky bit read between calls) cannot reach
@@ -250,7 +266,7 @@ void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* 
     sa.ray_index = m->wide_list;
     sa.n_rays_dev = m->redo_count + 3;
     sa.zero_word = m->redo_count + 2;
-    hr_launch_samples(m->kcfg, sa, st);
+    launch_samples(m, sa, maps, 0, st);
 }
 
 // entries of the ray list one hr_render call may fill: a sixteenth of its rays, at least 32 768 (never more than the rays there are, or the buffer).
@@ -264,14 +280,17 @@ int redo_list_cap(const hr_model* m, int64_t n_rays)
     return (int)(cap < m->redo_cap ? cap : m->redo_cap);
 }
 
-int hr_render_fields(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, const hr_fields* fields, void* stream)
+// hr_render, hr_render_fields and hr_render_maps (and their hr_render_frame forms) in one: `fields` non-NULL = diagnostics (one arithmetic,
+// the f16x3 tiles throughout, for every output), `maps` non-NULL = the per-ray maps on the plan hr_render takes, except the frame kernel
+static int render_impl(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, const hr_fields* fields, const hr_maps* maps,
+                       hipStream_t st)
 {
     int rc = check_render(m, rays_dev, n_rays, rgb_dev);
     if (rc != HR_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
+    if (maps && !maps->distances_dev && !maps->points_dev && !maps->acc_dev) maps = nullptr;
     const hr_config& c = m->cfg;
     const int Z = c.z_channels;
-    if (!fields && launch_frame(m, rays_dev, n_rays, rgb_dev, false, st)) {
+    if (!fields && !maps && launch_frame(m, rays_dev, n_rays, rgb_dev, false, st)) {
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
@@ -295,7 +314,7 @@ int hr_render_fields(hr_model* m, const float* rays_dev, int64_t n_rays, float* 
         }
     }
     if (verify && n_rays > 0) {
-        render_verified(m, rays_dev, n_rays, rgb_dev, redo_list_cap(m, n_rays), st);
+        render_verified(m, rays_dev, n_rays, rgb_dev, redo_list_cap(m, n_rays), st, maps);
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
@@ -316,18 +335,28 @@ int hr_render_fields(hr_model* m, const float* rays_dev, int64_t n_rays, float* 
                 hr_launch_head_export(m->head, fields->head_dev + r0 * (int64_t)Z * c.preds_per_z, n, Z, c.preds_per_z, m->p_live,
                                       (m->n_out + 3) / 4, rows_per_ray(c), m->col_map, st);
         }
-        hr_launch_samples(m->kcfg, sa, st);
+        launch_samples(m, sa, maps, r0, st);
     }
     HR_HIP(hipGetLastError());
     return HR_OK;
 }
 
-int hr_render(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, void* stream)
+int hr_render_fields(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, const hr_fields* fields, void* stream)
 {
-    return hr_render_fields(m, rays_dev, n_rays, rgb_dev, nullptr, stream);
+    return render_impl(m, rays_dev, n_rays, rgb_dev, fields, nullptr, (hipStream_t)stream);
 }
 
-int hr_render_frame(hr_model* m, const float* rays_dev, int64_t n_rays, float time, float* rgb_dev, void* stream)
+int hr_render_maps(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, const hr_maps* maps, void* stream)
+{
+    return render_impl(m, rays_dev, n_rays, rgb_dev, nullptr, maps, (hipStream_t)stream);
+}
+
+int hr_render(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, void* stream)
+{
+    return render_impl(m, rays_dev, n_rays, rgb_dev, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int hr_render_frame_maps(hr_model* m, const float* rays_dev, int64_t n_rays, float time, float* rgb_dev, const hr_maps* maps, void* stream)
 {
     if (!m) return fail(HR_E_INVALID, "null model");
     const hr_config& c = m->cfg;
@@ -358,9 +387,14 @@ int hr_render_frame(hr_model* m, const float* rays_dev, int64_t n_rays, float ti
             m->frame_row = 0;
         }
     }
-    const int rc = hr_render_fields(m, rays_dev, n_rays, rgb_dev, nullptr, stream);
+    const int rc = render_impl(m, rays_dev, n_rays, rgb_dev, nullptr, maps, st);
     m->frame_row = -1;
     return rc;
+}
+
+int hr_render_frame(hr_model* m, const float* rays_dev, int64_t n_rays, float time, float* rgb_dev, void* stream)
+{
+    return hr_render_frame_maps(m, rays_dev, n_rays, time, rgb_dev, nullptr, stream);
 }
 
 int hr_stage_mlp(hr_model* m, const float* rays_dev, int64_t n_rays, void* stream)

@@ -180,6 +180,8 @@ void hr_launch_mlp_f16x3(const hr_config& cfg, const HrMlpArgs& args, hipStream_
 void hr_launch_mlp_f16x2(const hr_config& cfg, const HrMlpArgs& args, hipStream_t stream);   // fp16, weights unsplit
 void hr_launch_mlp_f16f8(const hr_config& cfg, const HrMlpArgs& args, hipStream_t stream);   // fp16 leading product, the two correction products as one fp8 K=64 MFMA
 void hr_launch_samples(const hr_config& cfg, const HrSampleArgs& args, hipStream_t stream);
+// hr_launch_samples that also writes the per-ray maps (sample_maps_kernel.hip; maps: ray-indexed like args.rgb)
+void hr_launch_samples_maps(const hr_config& cfg, const HrSampleArgs& args, const hr_maps& maps, hipStream_t stream);
 // fused frame kernel (fused_impl.inc): MLP + sample stage of all rays in one persistent launch, head tile in LDS.
 // Returns false when the model does not fit it (nothing launched); probe: only answer.
 bool hr_launch_frame_bf16x3(const hr_config& cfg, const HrMlpArgs& ma, const HrSampleArgs& sa, int sample_waves, int frame_mode, int n_cus, bool probe,

@@ -191,7 +191,8 @@ HR_HIDDEN void fill_mlp_args(const hr_model* m, HrMlpArgs& a, const float* rays,
 HR_HIDDEN void fill_sample_args(const hr_model* m, HrSampleArgs& a, const float* rays, int64_t n, float* rgb);
 HR_HIDDEN void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int64_t redo0 = -1, int tier = 0);
 HR_HIDDEN bool launch_frame(hr_model* m, const float* rays, int64_t n, float* rgb, bool probe, hipStream_t st);
-HR_HIDDEN void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st);
+HR_HIDDEN void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st,
+                               const hr_maps* maps = nullptr);
 HR_HIDDEN int redo_list_cap(const hr_model* m, int64_t n_rays);
 
 #endif  // HR_MODEL_H

@@ -1141,9 +1141,12 @@ __device__ __forceinline__ void hr_fill_decode(const hr_config& cfg, const HrSam
 // Everything from the head values of sample k to the ray's colour.  PIPE: depth of the gather's load pipeline, NB: 2 = compiled for static nets only, 4 = static or keyframe, PC: plane class (hr_plane_class: 1 = [8, 4, 4], 2 = [8, 0, 0], 0 = generic).  `hrow`: this ray's head row(s) in LDS (row stride
 // HS floats; RPR rows when the head comes from a point MLP); `M`: the ray's decode matrix in LDS; `ones`: hr_gather_ones_init's block; `s_x`: 256-float
 // scratch of the block for rays that span several wavefronts (ZP > 64, stand-alone kernel only).
-template <int ZP, bool HALF, int PIPE, int NB, int PC>
+// MAPS (hr_sample_maps_kernel only): also the ray's weighted sums of distance and point and its sum of weights -- the reference's
+// fields=['distances', 'points'] and acc_map (tensorf_no_sample.py:232, 254-278) -- into `*maps`, which no other instantiation reads.
+template <int ZP, bool HALF, int PIPE, int NB, int PC, bool MAPS = false>
 __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSampleArgs& a, const HrRayLane& L, int64_t ray, bool ray_ok, int k,
-                                               const float* hrow, int HS, const float* M, const float* ones, float* s_x)
+                                               const float* hrow, int HS, const float* M, const float* ones, float* s_x,
+                                               const hr_maps* maps = nullptr)
 {
     const int tid = threadIdx.x;
     const int Z = cfg.z_channels;
@@ -1352,6 +1355,47 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
     }
     // the lane that holds the ray's sums writes the pixel: the last one after the row sums, the first one after a butterfly
     if (ray_ok && k == (ROWS ? ZP - 1 : 0) && a.rows_out == nullptr) hr_write_pixel(cfg, a, ray, hrow, c0, c1, c2, acc_w);
+    if constexpr (MAPS) {                          // the maps: weight * distance, weight * point, summed as the colour is; acc_w is the sum of the weights
+        float md = 0.0f, mp0 = 0.0f, mp1 = 0.0f, mp2 = 0.0f;
+        if (lane_ok) { md = weight * dist_c; mp0 = weight * p[0]; mp1 = weight * p[1]; mp2 = weight * p[2]; }
+        if constexpr (ROWS) {
+#define HR_ROW_SUM(x) do { x += hr_dpp_f<0x111>(x); x += hr_dpp_f<0x112>(x); x += hr_dpp_f<0x114>(x); x += hr_dpp_f<0x118>(x); \
+                           if (ZP >= 32) x += hr_dpp_old<0x142, 0xA>(0.0f, x); \
+                           if (ZP == 64) x += hr_dpp_old<0x143, 0xC>(0.0f, x); } while (0)
+            HR_ROW_SUM(md); HR_ROW_SUM(mp0); HR_ROW_SUM(mp1); HR_ROW_SUM(mp2);
+#undef HR_ROW_SUM
+        } else {
+#pragma unroll
+            for (int d = ZW >> 1; d > 0; d >>= 1) {
+                md += __shfl_xor(md, d, 64);
+                mp0 += __shfl_xor(mp0, d, 64);
+                mp1 += __shfl_xor(mp1, d, 64);
+                mp2 += __shfl_xor(mp2, d, 64);
+            }
+        }
+        if constexpr (ZP > 64) {                   // the ray's wavefronts in order, through s_x[16 ..] (the colour's 4 x 4 floats stay untouched)
+            float* q = s_x + 16;
+            if ((tid & 63) == 0) {
+                float* o = q + 4 * (tid >> 6);
+                o[0] = md; o[1] = mp0; o[2] = mp1; o[3] = mp2;
+            }
+            __syncthreads();
+            const int w0 = ((tid >> 6) / WPR) * WPR;
+            md = q[4 * w0 + 0]; mp0 = q[4 * w0 + 1]; mp1 = q[4 * w0 + 2]; mp2 = q[4 * w0 + 3];
+            for (int i = 1; i < WPR; ++i) {
+                md += q[4 * (w0 + i) + 0]; mp0 += q[4 * (w0 + i) + 1]; mp1 += q[4 * (w0 + i) + 2]; mp2 += q[4 * (w0 + i) + 3];
+            }
+        }
+        if (ray_ok && k == (ROWS ? ZP - 1 : 0) && a.rows_out == nullptr) {
+            if (maps->distances_dev) maps->distances_dev[ray] = md;
+            if (maps->acc_dev) maps->acc_dev[ray] = acc_w;
+            if (maps->points_dev) {
+                maps->points_dev[ray * 3 + 0] = mp0;
+                maps->points_dev[ray * 3 + 1] = mp1;
+                maps->points_dev[ray * 3 + 2] = mp2;
+            }
+        }
+    }
     if constexpr (ZP <= 64) {
         if (a.redo_list) {                         // one list entry per ray with a sample at risk, written by the lane that wrote the pixel
             const unsigned long long bal = __builtin_amdgcn_ballot_w64(risk_.hit && lane_ok);

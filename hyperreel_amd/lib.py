@@ -6,12 +6,12 @@ raises.  The product never routes through PyTorch ops or the CPU oracle.
 import ctypes as C
 import os
 
-from .plan import hr_camera, hr_config, hr_fields
+from .plan import hr_camera, hr_config, hr_fields, hr_maps
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, '_build', 'libhyperreel_hip.so')
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 
 
@@ -55,6 +55,8 @@ SYMBOLS = [
     ('hr_render', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ('hr_render_frame', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     ('hr_render_fields', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(hr_fields), C.c_void_p]),
+    ('hr_render_maps', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(hr_maps), C.c_void_p]),
+    ('hr_render_frame_maps', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.POINTER(hr_maps), C.c_void_p]),
     ('hr_allgather_tiles', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ('hr_shard_range', C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ('hr_generate_rays', C.c_int, [C.POINTER(hr_camera), C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -15,7 +15,7 @@ from torch import nn
 
 from . import lib as _lib
 from .config import n_to_reso, to_plain
-from .plan import compile_model, hr_fields, upload_names
+from .plan import compile_model, hr_fields, hr_maps, upload_names
 
 MAT_MODE = [[0, 1], [0, 2], [1, 2]]
 VEC_MODE = [2, 1, 0]
@@ -374,6 +374,9 @@ class HipLightfieldModel(nn.Module):
         self.sample_waves = kwargs.get('sample_waves')
         self.train_deterministic = bool(kwargs.get('train_deterministic', False))
         self.train_fused_mlp = bool(kwargs.get('train_fused_mlp', False))
+        # opt-in: an eval-mode forward whose requested fields are only 'distances' / 'points' (weighted sums) is served by render(maps=...):
+        # O(B) memory on hr_render's plan, instead of the per-sample diagnostics path (_forward_fields)
+        self.fast_fields = bool(kwargs.get('fast_fields', False))
         net = cfg['color']['net']
         if 'grid_size' in kwargs and kwargs['grid_size'] is not None:
             grid = list(kwargs['grid_size'])
@@ -722,12 +725,18 @@ class HipLightfieldModel(nn.Module):
         # the C ABI takes no row stride: extra columns are cut (6-column nets ignore camera id / time, rendering.py)
         return rays[:, :hc.ray_dim].contiguous().float()
 
-    def render(self, rays, want=(), out=None, frame_time=None):
+    MAP_COLUMNS = {'distances': 1, 'points': 3, 'acc': 1}
+
+    def render(self, rays, want=(), out=None, frame_time=None, maps=(), maps_out=None):
         """rays (B, 6|8) on the HIP device -> dict with 'rgb' (B,3) and any of
         'distances' (B,Z), 'points' (B,Z,3), 'sigma' (B,Z), 'render_weights' (B,Z),
         'head' (B,Z*P) listed in `want`.  out: an existing (B,3) float32 device tensor to render into.
         frame_time: the caller's statement that every ray carries this time (one frame of a keyframe net): hr_render_frame, which reads
-        one row of each time plane instead of blending two (images agree with the general path to ~1e-6, not bit for bit)."""
+        one row of each time plane instead of blending two (images agree with the general path to ~1e-6, not bit for bit).
+        maps: per-ray maps from the same launches as the image (hr_render_maps; 'rgb' is bit for bit the one without them):
+        'distances' (B,1) = sum_k w_k d_k (depth), 'points' (B,3) = sum_k w_k p_k (expected point), 'acc' (B,1) = sum_k w_k (opacity) --
+        the reference's fields=['distances', 'points'] and acc_map.  maps_out: {name: existing contiguous float32 device tensor} to
+        render those maps into (a captured graph's fixed buffers).  `want` and `maps` are exclusive."""
         import ctypes as C
         h = self.native()
         self._sync_occupancy()
@@ -736,16 +745,43 @@ class HipLightfieldModel(nn.Module):
         B = rays.shape[0]
         hc = self._hc
         Z = hc.z_channels
+        maps = tuple(maps)
+        if want and maps:
+            raise ValueError('render(): `want` (per-sample diagnostics) and `maps` (per-ray maps) cannot be combined')
+        unknown = [k for k in maps if k not in self.MAP_COLUMNS]
+        if unknown:
+            raise ValueError(f'render(): unknown maps {unknown}; available: {sorted(self.MAP_COLUMNS)}')
+        if maps_out and set(maps_out) - set(maps):
+            raise ValueError('render(): maps_out holds buffers for maps that were not requested')
         if out is not None and (out.shape != (B, 3) or out.dtype != torch.float32 or out.device != rays.device or not out.is_contiguous()):
             raise ValueError('out must be a contiguous (B, 3) float32 tensor on the rays\' device')
         out = {'rgb': out if out is not None else torch.empty((B, 3), dtype=torch.float32, device=rays.device)}
+        mp = None
+        if maps:
+            mp = hr_maps()
+            slots = {'distances': 'distances_dev', 'points': 'points_dev', 'acc': 'acc_dev'}
+            for k in maps:
+                t = (maps_out or {}).get(k)
+                shape = (B, self.MAP_COLUMNS[k])
+                if t is None:
+                    t = torch.empty(shape, dtype=torch.float32, device=rays.device)
+                elif t.shape != shape or t.dtype != torch.float32 or t.device != rays.device or not t.is_contiguous():
+                    raise ValueError(f'maps_out[{k!r}] must be a contiguous {shape} float32 tensor on the rays\' device')
+                out[k] = t
+                setattr(mp, slots[k], t.data_ptr())
         stream = C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream)
         with torch.cuda.device(rays.device):
             if not want:
                 for attempt in (0, 1):
-                    if frame_time is not None:
+                    if frame_time is not None and mp is not None:
+                        _lib.check(L.hr_render_frame_maps(h, C.c_void_p(rays.data_ptr()), B, float(frame_time), C.c_void_p(out['rgb'].data_ptr()),
+                                                          C.byref(mp), stream), 'hr_render_frame_maps')
+                    elif frame_time is not None:
                         _lib.check(L.hr_render_frame(h, C.c_void_p(rays.data_ptr()), B, float(frame_time), C.c_void_p(out['rgb'].data_ptr()), stream),
                                    'hr_render_frame')
+                    elif mp is not None:
+                        _lib.check(L.hr_render_maps(h, C.c_void_p(rays.data_ptr()), B, C.c_void_p(out['rgb'].data_ptr()), C.byref(mp), stream),
+                                   'hr_render_maps')
                     else:
                         _lib.check(L.hr_render(h, C.c_void_p(rays.data_ptr()), B, C.c_void_p(out['rgb'].data_ptr()), stream), 'hr_render')
                     if attempt == 1 or not self._overflow_guard(rays):
@@ -938,6 +974,11 @@ class HipLightfieldModel(nn.Module):
             return {'rgb': self.forward_train(rays)}
         if not fields:
             return {'rgb': self.render(rays)['rgb']}
+        if self.fast_fields and not self.training:
+            maps = self._fast_field_maps(fields, render_kwargs)
+            if maps is not None:
+                r = self.render(rays, maps=maps)
+                return {k: r[k] for k in ['rgb', *maps]}
         if self.training and torch.is_grad_enabled() and self._hc.z_channels <= 64:
             # INRSystem.training_step passes the regularizers' field list on the main forward (nlf/__init__.py:658-690): the colour
             # stays differentiable (training arithmetic: no eval-mode clamp, the per-step background draw) and the requested fields are
@@ -1013,6 +1054,28 @@ class HipLightfieldModel(nn.Module):
             x['time_offset'] = (t - base).expand(B, Z).contiguous()
             x['times'] = t.expand(B, Z).contiguous()
         return x
+
+    def _field_names(self):
+        """The keys _forward_fields can produce for this model (others are skipped, as the reference's loop over x skips them)."""
+        hc = getattr(self, '_hc', None)
+        if hc is None:                                  # no native model yet: the configuration it will be built from
+            hc = self._compile(self.grid_size)[1]
+        names = {'render_weights', 'points', 'distances', 'viewdirs', 'weights'}
+        names |= {n for n, f in (('color_scale', hc.f_color_scale), ('color_shift', hc.f_color_shift)) if f.offset >= 0}
+        if hc.advect:
+            names |= {'base_times', 'time_offset', 'times'}
+        return names
+
+    def _fast_field_maps(self, fields, render_kwargs):
+        """fast_fields: the maps that serve `fields` when every producible requested key is a weighted sum of 'distances' / 'points'
+        (none of them in no_over_fields); None: the request needs the per-sample path."""
+        if render_kwargs.get('pred_weights_fields'):
+            return None
+        no_over = set(render_kwargs.get('no_over_fields', []))
+        keys = [k for k in dict.fromkeys(fields) if k in self._field_names()]
+        if any(k not in ('distances', 'points') or k in no_over for k in keys):
+            return None
+        return tuple(keys)
 
     def _forward_fields(self, rays, render_kwargs, r=None):
         """render_kwargs `fields` / `no_over_fields` (tensorf_no_sample.py:254-278).  r: per-sample values already at hand (the training

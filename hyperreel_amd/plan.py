@@ -99,6 +99,11 @@ class hr_fields(C.Structure):
                 ('weights_dev', C.c_void_p), ('head_dev', C.c_void_p)]
 
 
+class hr_maps(C.Structure):
+    """Per-ray maps of hr_render_maps (include/hyperreel_hip.h): depth (n), expected point (n, 3), opacity (n)."""
+    _fields_ = [('distances_dev', C.c_void_p), ('points_dev', C.c_void_p), ('acc_dev', C.c_void_p)]
+
+
 # --------------------------------------------------------------------------- small helpers
 # Training iteration the schedules are evaluated at while compile_config runs (None: converged, every weight 1)
 _ITERATION = None

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define HR_ABI_VERSION 26
+#define HR_ABI_VERSION 27
 
 #define HR_MAX_Z 256         /* samples per ray (z_channels) supported by the sample kernel */
 #define HR_MAX_P 64          /* per-sample head columns (preds_per_z) */
@@ -239,6 +239,16 @@ typedef struct hr_fields {
     float* head_dev;            /* (n, Z*P)  raw MLP output */
 } hr_fields;
 
+/* Per-ray maps of hr_render_maps / hr_render_frame_maps (device pointers, any may be NULL): the ray's weighted sums over its
+ * samples, sum_k w_k x[key]_k, which the reference returns for render_kwargs fields=['distances', 'points']
+ * (tensorf_no_sample.py:254-278), and its acc_map sum_k w_k (tensorf_no_sample.py:232).  w_k are the compositing weights
+ * ('render_weights'); distances and points are hr_fields' per-sample values. */
+typedef struct hr_maps {
+    float* distances_dev;       /* (n)    sum_k w_k x['distances'][k]: the depth map */
+    float* points_dev;          /* (n, 3) sum_k w_k x['points'][k]: the expected point */
+    float* acc_dev;             /* (n)    sum_k w_k: the opacity (acc_map; before the white background) */
+} hr_maps;
+
 /* Pinhole camera of the viewer / offline-render path: what get_coords_from_camera
  * (datasets/base.py:485-518) consumes -- a 3x4 camera-to-world pose and intrinsics K. */
 typedef struct hr_camera {
@@ -308,8 +318,9 @@ int hr_model_reserve(hr_model* m, int64_t rays_per_chunk);
  *                         MLP wavefronts hand the (B, Z*P) head that the reference materialises between RayPredictionEmbedding and
  *                         Intersect (nlf/embedding/ray.py:332-337 -> nlf/intersect/base.py:142-259) to sample wavefronts of the
  *                         same workgroup through LDS -- no workspace traffic (static nets, 64-ray tiles).  Models that do not
- *                         fit (wider heads, cascades, the exact-fp32 MLP, other plane decompositions), and every hr_render_fields
- *                         call with a non-NULL `fields`, take the two-kernel path.
+ *                         fit (wider heads, cascades, the exact-fp32 MLP, other plane decompositions), every hr_render_fields
+ *                         call with a non-NULL `fields` and every hr_render_maps / hr_render_frame_maps call with a map requested
+ *                         take the two-kernel path (same images).
  *                         2: additionally the keyframe families (480-column heads, 960 at 64 samples per ray;
  *                         nlf/nets/tensorf_dynamic.py:645-839) on 32-ray tiles, two head buffers where they fit: same images, no
  *                         head workspace traffic, measured as fast as or slower than two kernels (hence not part of 1).
@@ -401,6 +412,14 @@ int hr_render(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev
 int hr_render_frame(hr_model* m, const float* rays_dev, int64_t n_rays, float time, float* rgb_dev, void* stream);
 int hr_render_fields(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev,
                      const hr_fields* fields, void* stream);
+/* hr_render / hr_render_frame that also write the per-ray maps of `maps` (hr_maps) in the same launches: rgb_dev is bit for bit
+ * hr_render's / hr_render_frame's, on the same plan -- the verified fast path included (its later passes rewrite the listed rays'
+ * maps with the pixels), no safe tier as hr_render_fields' diagnostics force -- except that HR_OPT_FRAME_KERNEL does not apply: a
+ * maps call takes the two-kernel path.  O(n) memory, no allocation, no synchronisation (capturable).  maps == NULL, or all three
+ * pointers NULL: exactly hr_render / hr_render_frame. */
+int hr_render_maps(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, const hr_maps* maps, void* stream);
+int hr_render_frame_maps(hr_model* m, const float* rays_dev, int64_t n_rays, float time, float* rgb_dev, const hr_maps* maps,
+                         void* stream);
 
 /* Image-parallel frames: every rank renders a contiguous pixel range of the frame into `tile_dev` and the tiles are
  * assembled on every rank by ONE all-gather over RCCL / xGMI: full_dev[r * floats_per_rank ..] = rank r's tile_dev[0 .. floats_per_rank).
