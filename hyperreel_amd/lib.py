@@ -28,6 +28,11 @@ class hr_train_tensors(C.Structure):
                 ('basis', C.c_void_p), ('color_table', C.c_void_p)]
 
 
+class hr_image_scores(C.Structure):
+    """Result of hr_image_metrics, written on the device (include/hyperreel_hip.h)."""
+    _fields_ = [('sse', C.c_double), ('ssim_sum', C.c_double * 3)]
+
+
 class hr_verify_info(C.Structure):
     """What the verified fast path rests on for one model (include/hyperreel_hip.h)."""
     _fields_ = [('verified', C.c_int32), ('fallback', C.c_int32), ('band', C.c_float), ('band_q', C.c_float), ('band_off', C.c_float),
@@ -73,6 +78,8 @@ SYMBOLS = [
     ('hr_dense_alpha', C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                  C.c_void_p, C.c_void_p]),
     ('hr_pack_display', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    ('hr_image_metrics_workspace', C.c_size_t, [C.c_int32, C.c_int32]),
+    ('hr_image_metrics', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('hr_plane_reg_forward', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     ('hr_plane_reg_backward', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('hr_adam_step', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -892,6 +892,14 @@ class HipLightfieldModel(nn.Module):
         its host round trips: pose -> rays -> rgb, all on the device and on the current stream."""
         return self.render(self.generate_rays(pose, K, width, height, time, cam_id, pixel_range), frame_time=time)['rgb']
 
+    def evaluate(self, rays, gt, h, w, frame_time=None, ssim=True):
+        """Render a frame and score it against its ground truth without leaving the device until the four sums are read: what
+        validation_image does on the host (nlf/__init__.py:976-980, metrics.py:25-35).  rays: the frame's h*w rays; gt: (h*w, 3)
+        on the HIP device.  Returns (rgb, {'mse', 'psnr', 'ssim'}); rgb is the unchanged render() call's, bit for bit."""
+        from . import metrics
+        rgb = self.render(rays, frame_time=frame_time)['rgb']
+        return rgb, metrics.scores_to_metrics(metrics.image_scores(rgb, gt, h, w, ssim=ssim), h, w)
+
     def pack_display(self, rgb, height, width, transpose=False, flip=False, rgba8=True):
         """The viewer's hand-over (utils/gui_utils.py:174-205) on the device: rgb (H*W, 3) as rendered -> the displayed
         buffer, transposed / flipped as NeRFGUI does on the host, as 8-bit RGBA (to8b, utils/__init__.py:47) or fp32 RGB."""

@@ -30,6 +30,8 @@
 extern "C" {
 #endif
 
+/* Bumped when an existing struct, enum value or signature changes.  Purely additive entry points (new functions and the structs only
+ * they use, such as the image scores below) do not bump it: every binding of version 27 keeps working against a library that has them. */
 #define HR_ABI_VERSION 27
 
 #define HR_MAX_Z 256         /* samples per ray (z_channels) supported by the sample kernel */
@@ -545,6 +547,30 @@ int hr_dense_alpha(hr_model* m, const int32_t n[3], float length, int32_t num_fr
  * rgba8 != 0: 4 bytes per pixel, to8b(x) = (uint8)(255 * clip(x, 0, 1)) (utils/__init__.py:47) and alpha 255;
  * rgba8 == 0: 3 floats per pixel, values unchanged. */
 int hr_pack_display(const float* rgb_dev, int32_t h, int32_t w, int32_t transpose, int32_t flip, int32_t rgba8, void* out_dev, void* stream);
+
+/* Image scores: what the reference computes on the host for every validation image (nlf/__init__.py:976-980:
+ * val/psnr and val/ssim from metrics.py:25-35, scikit-image's peak_signal_noise_ratio(data_range=1.0) and
+ * structural_similarity(win_size=11, gaussian_weights=True, multichannel=True, data_range=1.0), after results['rgb'].cpu().numpy())
+ * and, as psnr_gpu (metrics.py:37-45), for every training step (nlf/__init__.py:668).  Written on the device as SUMS: the
+ * divisions and the logarithm are host arithmetic on four doubles (mse = sse / (3 h w), psnr = -10 log10(mse),
+ * ssim = (ssim_sum[0] + ssim_sum[1] + ssim_sum[2]) / (3 (h - 10) (w - 10))), and the sums of the tiles of image-parallel ranks add. */
+typedef struct hr_image_scores {
+    double sse;                 /* sum over all 3*h*w values of (pred - gt)^2: fp32 differences and squares, added in double */
+    double ssim_sum[3];         /* per channel: sum of the SSIM map S over the (h-10)*(w-10) pixels at least 5 away from every border
+                                 * (the crop scikit-image applies); S from the 11-tap Gaussian window (sigma 1.5), population
+                                 * covariances, C1 = 0.01^2, C2 = 0.03^2 */
+} hr_image_scores;
+
+/* bytes of workspace_dev that a call on an h x w frame needs (either value of want_ssim); 0 for h < 1 or w < 1 */
+size_t hr_image_metrics_workspace(int32_t h, int32_t w);
+
+/* pred_dev, gt_dev: (h * w, 3) float32, as hr_render writes a frame -> *out_dev (device memory).  One read of each image serves both
+ * scores.  want_ssim == 0 (the per-step train/psnr, metrics.py:37-45): the squared-error sum alone, any h, w >= 1, ssim_sum left at 0;
+ * otherwise h, w >= 11 (HR_E_INVALID below that: the window does not fit).  The sums are added in a fixed order without atomics:
+ * calls on the same inputs give the same bits.  Every byte of *out_dev and of the workspace that is read is written first by the same
+ * call (nothing to clear between calls); no allocation, no synchronisation, capturable in a hipGraph.  No model is involved. */
+int hr_image_metrics(const float* pred_dev, const float* gt_dev, int32_t h, int32_t w, int32_t want_ssim, hr_image_scores* out_dev,
+                     void* workspace_dev, void* stream);
 
 /* TensoRF regularisers of one (1, C, H, W) float32 plane (TVLoss, nlf/regularizers/tensorf.py:14-34; density_L1,
  * nlf/nets/tensorf_base.py:1024-1035), no model involved.  Forward ADDS to sums_dev[3] =
