@@ -1,0 +1,136 @@
+// Camera arithmetic shared by the ray kernels (pack_kernels.hip: hr_generate_rays; rays_kernel.hip: hr_generate_rays_ndc,
+// hr_rayset_batch) and, compiled by the host compiler, by the CPU suite (tests/host_math/hr_camera_host.cpp):
+//   hr_pixel_ray        pixel + camera -> the ray the reference's dataset stores (pinhole, optionally NDC)
+//   hr_subsample_*      the k-th pixel of the checkerboard rule (x + y + offset) % every == 0, in closed form
+//   hr_perm             a keyed bijection of [0, n): the epoch's order
+// IEEE division and square root throughout: these values feed the intersections, whose comparisons must fall as the reference's.
+// The library is built with -ffp-contract=off, the host restatement too: no multiply is fused with an add.
+#ifndef HR_CAMERA_H
+#define HR_CAMERA_H
+
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/hyperreel_hip.h"
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define HR_CAM_FN __host__ __device__ __forceinline__
+#else
+#define HR_CAM_FN static inline
+#endif
+
+// Camera -> ray (utils/ray_utils.py:98-135, datasets/base.py:485-518): pixel centres +0.5, directions (x, -y, -1) / focal,
+// rotated by the pose, normalised; origin = pose translation.  With `ndc`: get_ndc_rays_fx_fy (utils/ray_utils.py:137-164) in
+// its operation order, with the DATASET's W, H, fx, fy, near (datasets/technicolor.py:355-358), which need not be the frame's.
+// The two scalar factors -1 / (W / (2 fx)) are Python floats in the reference (double arithmetic, rounded once when they meet
+// the float32 tensor), so they are formed in double here.
+HR_CAM_FN void hr_pixel_ray(const hr_camera& cam, const hr_ndc* ndc, int x, int y, float* out)
+{
+    const float i = (float)x, j = (float)y;
+    const float dx = (i - cam.cx + 0.5f) / cam.fx;
+    const float dy = -(j - cam.cy + 0.5f) / cam.fy;
+    const float dz = -1.0f;
+    float wx = dx * cam.c2w[0] + dy * cam.c2w[1] + dz * cam.c2w[2];
+    float wy = dx * cam.c2w[4] + dy * cam.c2w[5] + dz * cam.c2w[6];
+    float wz = dx * cam.c2w[8] + dy * cam.c2w[9] + dz * cam.c2w[10];
+    const float nrm = fmaxf(sqrtf(wx * wx + wy * wy + wz * wz), 1e-12f);   // F.normalize(p=2, eps=1e-12)
+    wx = wx / nrm; wy = wy / nrm; wz = wz / nrm;
+    out[0] = cam.c2w[3]; out[1] = cam.c2w[7]; out[2] = cam.c2w[11];
+    out[3] = wx; out[4] = wy; out[5] = wz;
+    if (!ndc) return;
+    const float sx = (float)(-1.0 / ((double)ndc->width / (2.0 * (double)ndc->fx)));
+    const float sy = (float)(-1.0 / ((double)ndc->height / (2.0 * (double)ndc->fy)));
+    const float t = -(ndc->near + out[2]) / wz;               // shift the origin to the near plane
+    const float ox = out[0] + t * wx, oy = out[1] + t * wy, oz = out[2] + t * wz;
+    const float ox_oz = ox / oz, oy_oz = oy / oz;
+    const float o2 = 1.0f + (2.0f * ndc->near) / oz;
+    out[0] = sx * ox_oz;
+    out[1] = sy * oy_oz;
+    out[2] = o2;
+    out[3] = sx * (wx / wz - ox_oz);
+    out[4] = sy * (wy / wz - oy_oz);
+    out[5] = 1.0f - o2;
+}
+
+// ---- checkerboard subsampling (datasets/technicolor.py:211-236, datasets/neural_3d.py:168-185): pixel (x, y) is kept when
+// (x + y + offset) % every == 0.  For a fixed x exactly one of `every` consecutive rows keeps it, so every block of `every` rows
+// holds exactly w kept pixels.  Within a block that starts at a row whose first kept column is c = (-(y0 + offset)) mod every, row r
+// keeps the columns (c - r) mod every, + every, ...: w / every of them, one more when (c - r) mod every < w % every.
+
+// kept pixels in rows [0, r) of such a block, r <= every
+HR_CAM_FN int64_t hr_subsample_block_rows(int w, int every, int c, int r)
+{
+    const int q = w / every, rem = w % every;
+    const int lo = c - rem + 1 > 0 ? c - rem + 1 : 0;               // rows 0 .. c: first column c - s, below rem from s = c - rem + 1 on
+    const int hi = r < c + 1 ? r : c + 1;
+    const int a = hi > lo ? hi - lo : 0;
+    const int b = r - (every + c - rem + 1);                        // rows c + 1 .. : first column every + c - s
+    return (int64_t)r * q + a + (b > 0 ? b : 0);
+}
+
+HR_CAM_FN int hr_subsample_first_col(int y, int every, int offset)
+{
+    return (every - (int)(((int64_t)y + offset) % every)) % every;
+}
+
+HR_CAM_FN int64_t hr_subsample_count(int w, int h, int every, int offset)
+{
+    const int full = h / every, y0 = full * every;
+    return (int64_t)full * w + hr_subsample_block_rows(w, every, hr_subsample_first_col(y0, every, offset), h - y0);
+}
+
+// the k-th kept pixel in row-major order, k < hr_subsample_count
+HR_CAM_FN void hr_subsample_pixel(int w, int h, int every, int offset, int64_t k, int* x, int* y)
+{
+    (void)h;
+    const int64_t blk = k / w;
+    const int64_t kk = k - blk * w;
+    const int y0 = (int)blk * every;
+    const int c = hr_subsample_first_col(y0, every, offset);
+    int lo = 0, hi = every - 1;                                      // the last row r of the block with block_rows(r) <= kk
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (hr_subsample_block_rows(w, every, c, mid) <= kk) lo = mid; else hi = mid - 1;
+    }
+    *y = y0 + lo;
+    *x = (c - lo + every) % every + (int)(kk - hr_subsample_block_rows(w, every, c, lo)) * every;
+}
+
+// ---- the epoch's order: a keyed bijection of [0, n), n < 2^63.  A 4-round Feistel network over the next even number of bits
+// (a bijection of [0, 2^2b) whatever the round function is), cycle-walked into [0, n): 2^2b < 4 n, so a walk takes fewer than
+// four steps on average.  It replaces np.random.permutation(len(self)) per epoch (datasets/base.py:202-227); it does not
+// reproduce numpy's stream -- the contract is "every element exactly once per epoch, order set by (seed, epoch)".
+HR_CAM_FN uint64_t hr_mix64(uint64_t z)
+{
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+HR_CAM_FN uint64_t hr_perm_key(uint64_t seed, uint64_t epoch)
+{
+    return hr_mix64(hr_mix64(seed + 0x9e3779b97f4a7c15ull) ^ (epoch + 0x7f4a7c159e3779b9ull));
+}
+
+HR_CAM_FN uint64_t hr_perm(uint64_t n, uint64_t key, uint64_t i)
+{
+    if (n <= 1) return 0;
+    const int bits = 64 - __builtin_clzll(n - 1);
+    const int hb = (bits + 1) >> 1;                                   // bits of one half, 1 .. 32
+    const uint64_t mask = (1ull << hb) - 1;
+    uint64_t x = i;
+    do {
+        uint64_t l = x >> hb, r = x & mask;
+        for (int round = 0; round < 4; ++round) {
+            const uint64_t f = hr_mix64(r + key * (uint64_t)(2 * round + 1) + (uint64_t)round) >> 32;
+            const uint64_t t = l ^ (f & mask);
+            l = r;
+            r = t;
+        }
+        x = (l << hb) | r;
+    } while (x >= n);
+    return x;
+}
+
+#endif  // HR_CAMERA_H

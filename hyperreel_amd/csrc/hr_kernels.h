@@ -233,6 +233,32 @@ void hr_launch_band_probe(const HrBandArgs& a, int z_channels, hipStream_t strea
 
 void hr_launch_generate_rays(const hr_camera& cam, int ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays, hipStream_t stream);
 
+// camera rays with NDC and the training feed (rays_kernel.hip; arithmetic: hr_camera.h)
+void hr_launch_generate_rays_ndc(const hr_camera& cam, const hr_ndc* ndc, int ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays,
+                                 hipStream_t stream);
+// one image of a device-resident training set: its camera and its subsample rule (x + y + offset) % every == 0
+struct HrRayImage {
+    hr_camera cam;
+    int32_t every, offset;
+};
+struct HrRaySetArgs {
+    const HrRayImage* images;    // [n_images]
+    const int64_t* prefix;       // [n_images + 1]: kept pixels of the images before i; prefix[n_images] = size
+    const uint8_t* pixels;       // [n_images][h][w][3], 8-bit RGB
+    int n_images, width, height, ray_dim;
+    int has_ndc;
+    hr_ndc ndc;
+    int64_t size;
+    int64_t first, n;            // rows [first, first + n) of the epoch's order
+    uint64_t key;                // hr_perm_key(seed, epoch)
+    const int64_t* indices;      // [n] set elements of the call's rows instead of the epoch's order, or NULL
+    float* coords;               // (n, ray_dim); any output may be NULL
+    float* rgb;                  // (n, 3)
+    float* weight;               // (n, 1)
+    int64_t* elements;           // (n): the set element of each row
+};
+void hr_launch_rayset_batch(const HrRaySetArgs& a, hipStream_t stream);
+
 // layout kernels (pack_kernels.hip)
 // dst[y][x][c_off + c] = src[c][y][x] for c < C  (dst texel stride = tex floats)
 // Per-sample head columns the path actually reads (hr_model_finalize drops the others from the

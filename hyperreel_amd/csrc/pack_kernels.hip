@@ -1,4 +1,5 @@
 // One-time layout transforms run by hr_model_finalize (not on the render path).
+#include "hr_camera.h"
 #include "hr_kernels.h"
 #include "hr_math.h"
 
@@ -57,24 +58,13 @@ void hr_launch_head_export(const float* head, float* out, int64_t n_rays, int Z,
                        rows_per_ray, map);
 }
 
-// Camera -> rays (utils/ray_utils.py:98-135, datasets/base.py:485-518): pixel centres +0.5,
-// directions (x, -y, -1) / focal, rotated by the pose, normalised; origin = pose translation.
+// Camera -> rays: hr_pixel_ray (hr_camera.h) per pixel of the row-major image [+ cam_id, time].
 __global__ void hr_generate_rays_kernel(const hr_camera cam, int ray_dim, int64_t first_pixel, int64_t n_pixels, float* __restrict__ rays)
 {
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_pixels; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t p = first_pixel + t;
-        const float i = (float)(p % cam.width), j = (float)(p / cam.width);
-        const float dx = (i - cam.cx + 0.5f) / cam.fx;
-        const float dy = -(j - cam.cy + 0.5f) / cam.fy;
-        const float dz = -1.0f;
-        float wx = dx * cam.c2w[0] + dy * cam.c2w[1] + dz * cam.c2w[2];
-        float wy = dx * cam.c2w[4] + dy * cam.c2w[5] + dz * cam.c2w[6];
-        float wz = dx * cam.c2w[8] + dy * cam.c2w[9] + dz * cam.c2w[10];
-        const float nrm = fmaxf(sqrtf(wx * wx + wy * wy + wz * wz), 1e-12f);   // F.normalize(p=2, eps=1e-12)
-        wx = wx / nrm; wy = wy / nrm; wz = wz / nrm;
         float* r = rays + t * ray_dim;
-        r[0] = cam.c2w[3]; r[1] = cam.c2w[7]; r[2] = cam.c2w[11];
-        r[3] = wx; r[4] = wy; r[5] = wz;
+        hr_pixel_ray(cam, nullptr, (int)(p % cam.width), (int)(p / cam.width), r);
         if (ray_dim == 8) { r[6] = cam.cam_id; r[7] = cam.time; }
     }
 }

@@ -1,0 +1,105 @@
+// Camera rays with NDC (hr_generate_rays_ndc) and the training feed (hr_rayset_batch / hr_rayset_order).  One lane per ray; the
+// arithmetic is hr_camera.h's, which the CPU suite compiles for the host.  Launch-bound at a training batch (16 384 rays: 64
+// workgroups); nothing to tune beyond the stores: a lane owns a whole output row and writes it in 16- or 8-byte pieces when the
+// buffer is aligned for that, so a wavefront's stores cover a contiguous 64 * row bytes.
+#include "hr_camera.h"
+#include "hr_kernels.h"
+
+namespace {
+
+// VEC: rows start on 8-byte (6 columns) / 16-byte (8 columns) boundaries
+template <bool VEC>
+__device__ __forceinline__ void store_ray(float* __restrict__ r, const float* v, int ray_dim)
+{
+    if (VEC && ray_dim == 8) {
+        reinterpret_cast<float4*>(r)[0] = make_float4(v[0], v[1], v[2], v[3]);
+        reinterpret_cast<float4*>(r)[1] = make_float4(v[4], v[5], v[6], v[7]);
+    } else if (VEC) {
+        reinterpret_cast<float2*>(r)[0] = make_float2(v[0], v[1]);
+        reinterpret_cast<float2*>(r)[1] = make_float2(v[2], v[3]);
+        reinterpret_cast<float2*>(r)[2] = make_float2(v[4], v[5]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 8; ++c)                    // (fixed trip count: v stays in registers)
+            if (c < ray_dim) r[c] = v[c];
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void hr_generate_rays_ndc_kernel(const hr_camera cam, const hr_ndc ndc, int has_ndc, int ray_dim,
+                                                                   int64_t first_pixel, int64_t n_pixels, float* __restrict__ rays)
+{
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n_pixels; t += (int64_t)gridDim.x * 256) {
+        const int64_t p = first_pixel + t;
+        float v[8];
+        hr_pixel_ray(cam, has_ndc ? &ndc : nullptr, (int)(p % cam.width), (int)(p / cam.width), v);
+        v[6] = cam.cam_id; v[7] = cam.time;
+        store_ray<VEC>(rays + t * ray_dim, v, ray_dim);
+    }
+}
+
+// row -> set element -> image (binary search in the prefix sums) -> pixel (closed form) -> ray, colour, weight
+template <bool VEC>
+__global__ __launch_bounds__(256) void hr_rayset_batch_kernel(const HrRaySetArgs a)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.n) return;
+    const int64_t e = a.indices ? a.indices[t] : (int64_t)hr_perm((uint64_t)a.size, a.key, (uint64_t)(a.first + t));
+    if (a.elements) a.elements[t] = e;
+    if (!a.coords && !a.rgb && !a.weight) return;
+    const bool inside = e >= 0 && e < a.size;           // only a caller's own index can be outside
+    float v[8], c[3], wgt = 0.0f;
+    if (inside) {
+        int lo = 0, hi = a.n_images - 1;                 // the image with prefix[i] <= e < prefix[i + 1]
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (a.prefix[mid + 1] > e) hi = mid; else lo = mid + 1;
+        }
+        const HrRayImage& im = a.images[lo];
+        int x, y;
+        hr_subsample_pixel(a.width, a.height, im.every, im.offset, e - a.prefix[lo], &x, &y);
+        hr_pixel_ray(im.cam, a.has_ndc ? &a.ndc : nullptr, x, y, v);
+        v[6] = im.cam.cam_id; v[7] = im.cam.time;
+        if (a.rgb) {
+            const uint8_t* px = a.pixels + (((int64_t)lo * a.height + y) * a.width + x) * 3;
+            c[0] = (float)px[0] / 255.0f; c[1] = (float)px[1] / 255.0f; c[2] = (float)px[2] / 255.0f;   // ToTensor
+        }
+        wgt = 1.0f;
+    } else {
+        for (int k = 0; k < 8; ++k) v[k] = __builtin_nanf("");
+        c[0] = c[1] = c[2] = __builtin_nanf("");
+    }
+    if (a.coords) store_ray<VEC>(a.coords + t * a.ray_dim, v, a.ray_dim);
+    if (a.rgb) { float* o = a.rgb + t * 3; o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; }
+    if (a.weight) a.weight[t] = wgt;
+}
+
+bool rows_aligned(const float* p, int ray_dim)
+{
+    return p && (reinterpret_cast<uintptr_t>(p) & (ray_dim == 8 ? 15 : 7)) == 0;
+}
+
+}  // namespace
+
+void hr_launch_generate_rays_ndc(const hr_camera& cam, const hr_ndc* ndc, int ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays,
+                                 hipStream_t stream)
+{
+    if (n_pixels <= 0) return;
+    int64_t blocks = (n_pixels + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    const hr_ndc nd = ndc ? *ndc : hr_ndc();
+    if (rows_aligned(rays, ray_dim))
+        hipLaunchKernelGGL(hr_generate_rays_ndc_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, cam, nd, ndc ? 1 : 0, ray_dim,
+                           first_pixel, n_pixels, rays);
+    else
+        hipLaunchKernelGGL(hr_generate_rays_ndc_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, cam, nd, ndc ? 1 : 0, ray_dim,
+                           first_pixel, n_pixels, rays);
+}
+
+void hr_launch_rayset_batch(const HrRaySetArgs& a, hipStream_t stream)
+{
+    if (a.n <= 0) return;
+    const dim3 grid((unsigned)((a.n + 255) / 256));
+    if (!a.coords || rows_aligned(a.coords, a.ray_dim)) hipLaunchKernelGGL(hr_rayset_batch_kernel<true>, grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(hr_rayset_batch_kernel<false>, grid, dim3(256), 0, stream, a);
+}

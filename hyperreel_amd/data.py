@@ -1,0 +1,165 @@
+"""The training feed on the device (include/hyperreel_hip.h: hr_rayset_*).
+
+The reference's datasets build `all_inputs`, a host float tensor of ray_dim + 4 floats per training ray
+(datasets/base.py:130-143, datasets/technicolor.py:238-282), shuffle it on the host every epoch (base.py:202-227) and
+slice batches out of it (format_batch, base.py:278-284).  A DeviceRaySet keeps the 8-bit images in device memory with
+one camera and one subsample rule per image, and computes a batch's rays when they are drawn.  Nothing here reads
+files: decoding images stays with the caller.  No CPU path: a missing library or a failing call raises."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import lib as _lib
+from .plan import hr_camera, hr_ndc
+
+# subsample rules of the reference's datasets that are not the checkerboard: named so that the refusal can say which
+UNSUPPORTED_RULES = {
+    'random_subsample': 'datasets/neural_3d.py:152-166 draws np.random.permutation per image',
+    'importance_subsample': 'datasets/neural_3d.py:191-204 thresholds the difference to the previous frame',
+    'test_subsample': 'datasets/neural_3d.py:187-189 masks on a ray coordinate',
+    'fisheye': "datasets/immersive.py:43-48,514-523 undistorts through cv2's fisheye model",
+}
+
+
+def make_ndc(ndc):
+    """None | hr_ndc | dict(fx, fy, near, width, height) -> hr_ndc or None."""
+    if ndc is None or isinstance(ndc, hr_ndc):
+        return ndc
+    missing = [k for k in ('fx', 'fy', 'near', 'width', 'height') if k not in ndc]
+    if missing or len(ndc) != 5:
+        raise ValueError(f'ndc needs exactly fx, fy, near, width, height; got {sorted(ndc)}')
+    out = hr_ndc()
+    out.fx, out.fy, out.near = float(ndc['fx']), float(ndc['fy']), float(ndc['near'])
+    out.width, out.height = int(ndc['width']), int(ndc['height'])
+    return out
+
+
+def make_camera(pose, K, width, height, cam_id=0.0, time=0.0):
+    """3x4 camera-to-world `pose`, 3x3 intrinsics `K` -> hr_camera."""
+    cam = hr_camera()
+    p = np.asarray(pose, np.float32)[:3, :4].reshape(-1)
+    for i in range(12):
+        cam.c2w[i] = float(p[i])
+    Km = np.asarray(K, np.float32)
+    cam.fx, cam.fy, cam.cx, cam.cy = float(Km[0, 0]), float(Km[1, 1]), float(Km[0, 2]), float(Km[1, 2])
+    cam.width, cam.height = int(width), int(height)
+    cam.cam_id, cam.time = float(cam_id), float(time)
+    return cam
+
+
+class DeviceRaySet:
+    """images_u8: (n, H, W, 3) uint8 (numpy, or a torch tensor on the host or the device), RGB as Image.convert("RGB") holds
+    them; poses (n, 3, 4); intrinsics (n, 3, 3) or one (3, 3); times, cam_ids: (n) or None (6-column rays); img_wh = (W, H);
+    ndc: None | dict(fx, fy, near, width, height) | hr_ndc; subsample: None (every pixel) or one (every, offset) per image
+    (DeviceRaySet.video_rule builds the reference's).  Element e of the set is row e of the reference's all_inputs."""
+
+    def __init__(self, images_u8, poses, intrinsics, times, cam_ids, img_wh, ndc=None, subsample=None, device=None):
+        if isinstance(subsample, str):
+            why = UNSUPPORTED_RULES.get(subsample)
+            raise NotImplementedError(f'subsample rule {subsample!r} is not supported' + (f' ({why})' if why else '')
+                                      + ': only the checkerboard rule (x + y + offset) % every == 0 is')
+        L = _lib.load()
+        W, H = int(img_wh[0]), int(img_wh[1])
+        poses = np.asarray(poses, np.float32)
+        n = poses.shape[0]
+        Ks = np.asarray(intrinsics, np.float32)
+        Ks = np.broadcast_to(Ks, (n, 3, 3)) if Ks.ndim == 2 else Ks
+        video = times is not None
+        self.ray_dim = 8 if video else 6
+        times = np.zeros(n) if times is None else np.asarray(times, np.float64)
+        cam_ids = np.zeros(n) if cam_ids is None else np.asarray(cam_ids, np.float64)
+        rules = [(1, 0)] * n if subsample is None else [(int(e), int(o)) for e, o in subsample]
+        if not (len(images_u8) == len(Ks) == len(times) == len(cam_ids) == len(rules) == n):
+            raise ValueError('images, poses, intrinsics, times, cam_ids and subsample must describe the same number of images')
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.width, self.height, self.n_images = W, H, n
+        self._ndc = make_ndc(ndc)
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(L.hr_rayset_create(n, W, H, self.ray_dim, C.byref(self._ndc) if self._ndc is not None else None, C.byref(self._h)),
+                       'hr_rayset_create')
+            for i in range(n):
+                img = images_u8[i]
+                img = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
+                if img.dtype != torch.uint8 or tuple(img.shape) != (H, W, 3):
+                    raise ValueError(f'image {i}: expected uint8 ({H}, {W}, 3), got {img.dtype} {tuple(img.shape)}')
+                img = img.contiguous()
+                cam = make_camera(poses[i], Ks[i], W, H, cam_ids[i], times[i])
+                _lib.check(L.hr_rayset_set_image(self._h, i, C.byref(cam), rules[i][0], rules[i][1], C.c_void_p(img.data_ptr())),
+                           'hr_rayset_set_image')
+        self._size = int(L.hr_rayset_size(self._h))
+
+    def __len__(self):
+        return self._size
+
+    def close(self):
+        if getattr(self, '_h', None):
+            _lib.load().hr_rayset_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def batch(self, batch_idx, batch_size, epoch=0, seed=0, indices=None, out=None):
+        """Rows [batch_idx * batch_size, + batch_size) of the epoch's order (the last batch of an epoch is short), or the set
+        elements `indices` (int64 tensor on the device).  Returns {'coords', 'rgb', 'weight'} -- the keys format_batch yields
+        (datasets/base.py:278-284) -- as fresh float32 tensors, or written into `out`'s tensors (fixed buffers for a captured graph)."""
+        if indices is not None:
+            if indices.dtype != torch.int64 or indices.device != self.device or not indices.is_contiguous():
+                raise ValueError('indices must be a contiguous int64 tensor on the set\'s device')
+            first, n = 0, indices.numel()
+        else:
+            first = int(batch_idx) * int(batch_size)
+            n = min(int(batch_size), self._size - first)
+            if n <= 0:
+                raise IndexError(f'batch {batch_idx} of {batch_size} starts beyond the set\'s {self._size} rays')
+        if out is None:
+            out = {'coords': torch.empty((n, self.ray_dim), dtype=torch.float32, device=self.device),
+                   'rgb': torch.empty((n, 3), dtype=torch.float32, device=self.device),
+                   'weight': torch.empty((n, 1), dtype=torch.float32, device=self.device)}
+        else:
+            for k, cols in (('coords', self.ray_dim), ('rgb', 3), ('weight', 1)):
+                t = out[k]
+                if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n, cols):
+                    raise ValueError(f"out['{k}'] must be a contiguous float32 ({n}, {cols}) tensor on the set's device")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().hr_rayset_batch(self._h, first, n, int(seed), int(epoch),
+                                                   C.c_void_p(indices.data_ptr()) if indices is not None else None,
+                                                   C.c_void_p(out['coords'].data_ptr()), C.c_void_p(out['rgb'].data_ptr()),
+                                                   C.c_void_p(out['weight'].data_ptr()), self._stream()), 'hr_rayset_batch')
+        return out
+
+    def order(self, first, n, epoch=0, seed=0):
+        """The set elements of rows [first, first + n) of the epoch's order: (n) int64 on the device."""
+        out = torch.empty((int(n),), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().hr_rayset_order(self._h, int(first), int(n), int(seed), int(epoch), C.c_void_p(out.data_ptr()), self._stream()),
+                       'hr_rayset_order')
+        return out
+
+    @staticmethod
+    def video_rule(frame, load_full_step=1, subsample_keyframe_step=1, subsample_keyframe_frac=1.0, subsample_frac=1.0,
+                   keyframe_offset=0, frame_offset=0, rule='regular_subsample'):
+        """The reference's checkerboard rule over images in load order (datasets/technicolor.py:211-236,
+        datasets/neural_3d.py:168-185): `frame` holds each image's frame number; a frame divisible by load_full_step keeps every
+        pixel, one divisible by subsample_keyframe_step keeps every round(1 / subsample_keyframe_frac)-th with the running
+        keyframe_offset, any other every round(1 / subsample_frac)-th with the running frame_offset.  The counters start at the
+        given values (Neural 3D resets both to the video's index per video, neural_3d.py:225-226).  Returns [(every, offset)]."""
+        if rule != 'regular_subsample':
+            why = UNSUPPORTED_RULES.get(rule)
+            raise NotImplementedError(f'subsample rule {rule!r} is not supported' + (f' ({why})' if why else ''))
+        frames = [int(frame)] if np.isscalar(frame) else [int(f) for f in frame]
+        out = []
+        for f in frames:
+            if f % load_full_step == 0:
+                out.append((1, 0))
+            elif f % subsample_keyframe_step == 0:
+                out.append((int(np.round(1.0 / subsample_keyframe_frac)), keyframe_offset))
+                keyframe_offset += 1
+            else:
+                out.append((int(np.round(1.0 / subsample_frac)), frame_offset))
+                frame_offset += 1
+        return out

@@ -861,10 +861,12 @@ class HipLightfieldModel(nn.Module):
             return True
         return False
 
-    def generate_rays(self, pose, K, width, height, time=None, cam_id=0.0, pixel_range=None, device=None):
+    def generate_rays(self, pose, K, width, height, time=None, cam_id=0.0, pixel_range=None, device=None, ndc=None):
         """get_coords_from_camera (datasets/base.py:485-518) on the device: 3x4 camera-to-world
         `pose`, 3x3 intrinsics `K` -> rays (n, 6|8) for pixels [lo, hi) of the row-major image
-        (whole image by default).  80 bytes cross the PCIe bus instead of the ray list."""
+        (whole image by default).  80 bytes cross the PCIe bus instead of the ray list.
+        ndc: dict(fx, fy, near, width, height) or an hr_ndc -- the DATASET's to_ndc arguments (datasets/technicolor.py:355-358),
+        for nets trained on use_ndc datasets: the rays then pass through get_ndc_rays_fx_fy (hr_generate_rays_ndc)."""
         import ctypes as C
         import numpy as np
         from .plan import hr_camera
@@ -883,14 +885,20 @@ class HipLightfieldModel(nn.Module):
         rd = self._hc.ray_dim
         rays = torch.empty((hi - lo, rd), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.hr_generate_rays(C.byref(cam), rd, lo, hi - lo, C.c_void_p(rays.data_ptr()),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_generate_rays')
+            if ndc is None:
+                _lib.check(L.hr_generate_rays(C.byref(cam), rd, lo, hi - lo, C.c_void_p(rays.data_ptr()),
+                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_generate_rays')
+            else:
+                from .data import make_ndc
+                nd = make_ndc(ndc)
+                _lib.check(L.hr_generate_rays_ndc(C.byref(cam), C.byref(nd), rd, lo, hi - lo, C.c_void_p(rays.data_ptr()),
+                                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_generate_rays_ndc')
         return rays
 
-    def render_camera(self, pose, K, width, height, time=None, cam_id=0.0, pixel_range=None):
+    def render_camera(self, pose, K, width, height, time=None, cam_id=0.0, pixel_range=None, ndc=None):
         """The viewer's frame path (utils/gui_utils.py:139-212, nlf/__init__.py:754-807) without
         its host round trips: pose -> rays -> rgb, all on the device and on the current stream."""
-        return self.render(self.generate_rays(pose, K, width, height, time, cam_id, pixel_range), frame_time=time)['rgb']
+        return self.render(self.generate_rays(pose, K, width, height, time, cam_id, pixel_range, ndc=ndc), frame_time=time)['rgb']
 
     def evaluate(self, rays, gt, h, w, frame_time=None, ssim=True):
         """Render a frame and score it against its ground truth without leaving the device until the four sums are read: what

@@ -94,6 +94,11 @@ class hr_camera(C.Structure):
                 ('width', C.c_int32), ('height', C.c_int32), ('cam_id', C.c_float), ('time', C.c_float)]
 
 
+class hr_ndc(C.Structure):
+    """The arguments of get_ndc_rays_fx_fy as the dataset's to_ndc passes them (include/hyperreel_hip.h)."""
+    _fields_ = [('fx', C.c_float), ('fy', C.c_float), ('near', C.c_float), ('width', C.c_int32), ('height', C.c_int32)]
+
+
 class hr_fields(C.Structure):
     _fields_ = [('distances_dev', C.c_void_p), ('points_dev', C.c_void_p), ('sigma_dev', C.c_void_p),
                 ('weights_dev', C.c_void_p), ('head_dev', C.c_void_p)]

@@ -260,6 +260,17 @@ typedef struct hr_camera {
     float cam_id, time;         /* columns 6 and 7 of 8-column rays (datasets/base.py:511-515) */
 } hr_camera;
 
+/* Normalised device coordinates of the forward-facing datasets (use_ndc: True in conf/experiment/dataset/{technicolor,neural_3d,
+ * llff}.yaml): the arguments of get_ndc_rays_fx_fy (utils/ray_utils.py:137-164) as the dataset's to_ndc passes them
+ * (datasets/technicolor.py:355-358: self.img_wh, self.K, self.near) -- the DATASET's size and focal lengths, which stay the same
+ * when a frame is generated at another size with a scaled K (utils/gui_utils.py:151-158). */
+typedef struct hr_ndc {
+    float fx, fy, near;
+    int32_t width, height;
+} hr_ndc;
+
+typedef struct hr_rayset hr_rayset;
+
 typedef struct hr_model hr_model;
 
 int hr_abi_version(void);
@@ -441,6 +452,42 @@ int hr_shard_range(int64_t n_pixels, int32_t rank, int32_t world, int64_t* first
  * device from 80 bytes of camera replaces the 15-20 MB host->device copy of a frame's ray list;
  * with image-parallel rendering every rank generates only its own pixel range. */
 int hr_generate_rays(const hr_camera* cam, int32_t ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays_dev, void* stream);
+/* hr_generate_rays followed by get_ndc_rays_fx_fy (utils/ray_utils.py:137-164) on every ray, as get_coords / get_coords_from_camera
+ * do for use_ndc datasets (datasets/base.py:507-509, datasets/technicolor.py:384-385, datasets/neural_3d.py:383,400): origin shifted
+ * to the near plane and projected, direction = projected difference, d_z = 1 - o_z; IEEE divisions in the reference's order.
+ * ndc == NULL: exactly hr_generate_rays (the same bits). */
+int hr_generate_rays_ndc(const hr_camera* cam, const hr_ndc* ndc, int32_t ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays_dev,
+                         void* stream);
+
+/* ---- training feed --------------------------------------------------------------------------------
+ * A device-resident training set.  The reference keeps `all_inputs`, a host float tensor of ray_dim + 4 floats per training ray
+ * (prepare_train_data / update_all_data, datasets/base.py:130-143, datasets/technicolor.py:238-282), shuffles it on the host every
+ * epoch (base.py:202-227) and slices batches out of it (format_batch, base.py:278-284).  Here the 8-bit images live in device memory
+ * (3 bytes per pixel) with one camera and one subsample rule per image, and a batch's rays are computed when they are drawn.
+ * The set element e (0 <= e < hr_rayset_size) is the e-th row of the reference's all_inputs: images in index order, within an image
+ * the pixels with (x + y + offset) % every == 0 in row-major order (subsample, technicolor.py:211-236; every == 1: all of them).
+ *
+ * hr_rayset_create: n_images images of width x height on the current device, ray_dim 6 or 8, ndc as for hr_generate_rays_ndc (copied;
+ * NULL: world-space rays).  The library owns the pixel store (n_images * height * width * 3 bytes) and the per-image table. */
+int hr_rayset_create(int32_t n_images, int32_t width, int32_t height, int32_t ray_dim, const hr_ndc* ndc, hr_rayset** out);
+void hr_rayset_destroy(hr_rayset* set);
+/* Image i: pose, intrinsics, cam_id and time in `cam` (its width / height must be the set's), the subsample rule (every >= 1,
+ * offset >= 0) and height * width * 3 bytes of RGB, row-major, host or device memory -- what Image.convert("RGB") holds before ToTensor
+ * (get_rgb, technicolor.py:398-417).  Synchronous (set-up, not the training loop).  Images not yet set hold no rays. */
+int hr_rayset_set_image(hr_rayset* set, int32_t i, const hr_camera* cam, int32_t every, int32_t offset, const uint8_t* rgb_host_or_dev);
+/* rays in the set after subsampling: the reference's len(all_coords); negative on a null set */
+int64_t hr_rayset_size(const hr_rayset* set);
+/* Rows [first, first + n) of the order of epoch `epoch`: row r is set element perm(r), a bijection of [0, size) keyed by
+ * (seed, epoch) -- every ray exactly once per epoch, replacing np.random.permutation (base.py:202-227), not reproducing its stream.
+ * With indices_dev (n int64, device memory) output row j is element indices_dev[j] instead: the caller's own sampler; an element
+ * outside [0, size) yields a row of NaN with weight 0.  coords_dev (n, ray_dim): the ray of the element's pixel as
+ * hr_generate_rays_ndc computes it [+ cam_id, time]; rgb_dev (n, 3) = (float)u8 / 255.0f (ToTensor: exact); weight_dev (n, 1) = 1
+ * (get_weights, base.py:191-194).  Outputs may be NULL.  first + n > size is HR_E_INVALID, not a wrap.  One kernel on `stream`: no
+ * allocation, no synchronisation, no memset, every output element written; capturable in a hipGraph. */
+int hr_rayset_batch(const hr_rayset* set, int64_t first, int64_t n, uint64_t seed, uint64_t epoch, const int64_t* indices_dev,
+                    float* coords_dev, float* rgb_dev, float* weight_dev, void* stream);
+/* elements_dev[j] (n int64) = the set element of row first + j of that order: which ray each row of hr_rayset_batch is. */
+int hr_rayset_order(const hr_rayset* set, int64_t first, int64_t n, uint64_t seed, uint64_t epoch, int64_t* elements_dev, void* stream);
 
 /* Grid management: F.interpolate(plane, size=(h2, w2), mode='bilinear', align_corners=True) of one
  * (1, C, H, W) float32 plane or line, as TensorVMSplit.up_sampling_VM / TensorVMKeyframeTime.up_sampling_VM apply it
