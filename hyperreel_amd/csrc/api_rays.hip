@@ -1,16 +1,20 @@
-// C ABI, camera rays and the training feed: hr_generate_rays_ndc, hr_rayset_* (kernels: rays_kernel.hip; arithmetic: hr_camera.h).
+// C ABI, camera rays, light-field rays and the training feed: hr_generate_rays_ndc, hr_generate_rays_lightfield, hr_generate_rays_epi,
+// hr_rayset_* (kernels: rays_kernel.hip; arithmetic: hr_camera.h, hr_lightfield.h).
 // No model handle.  The set owns its device memory; hr_rayset_batch / hr_rayset_order enqueue one kernel and nothing else.
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
 #include "hr_camera.h"
+#include "hr_lightfield.h"
 #include "hr_model.h"
 
 struct HR_HIDDEN hr_rayset {
     int n_images = 0, width = 0, height = 0, ray_dim = 0;
     bool has_ndc = false;
     hr_ndc ndc = {};
+    bool lightfield = false;              // made by hr_rayset_create_lightfield: the images are views of `lf`
+    hr_lightfield lf = {};
     std::vector<HrRayImage> images;       // every == 0: not set yet (no rays)
     std::vector<int64_t> prefix;          // [n_images + 1]
     DevMem<HrRayImage> images_dev;
@@ -25,6 +29,32 @@ int check_ndc(const hr_ndc* ndc, const char* who)
     if (ndc && (ndc->width < 1 || ndc->height < 1 || ndc->fx == 0.0f || ndc->fy == 0.0f))
         return fail(HR_E_INVALID, "%s: bad hr_ndc (width %d, height %d, fx %g, fy %g)", who, (int)ndc->width, (int)ndc->height, (double)ndc->fx,
                     (double)ndc->fy);
+    return HR_OK;
+}
+
+int check_lightfield(const hr_lightfield* lf, float a, float b, const char* who)
+{
+    if (!lf) return fail(HR_E_INVALID, "%s: null hr_lightfield", who);
+    if (lf->width < 1 || lf->height < 1 || lf->aspect == 0.0f)
+        return fail(HR_E_INVALID, "%s: bad hr_lightfield (width %d, height %d, aspect %g)", who, (int)lf->width, (int)lf->height, (double)lf->aspect);
+    if (!isfinite(lf->aspect) || !isfinite(lf->st_scale) || !isfinite(lf->uv_scale) || !isfinite(lf->near) || !isfinite(lf->far) || !isfinite(a) ||
+        !isfinite(b))
+        return fail(HR_E_INVALID, "%s: non-finite scalar (aspect %g, st_scale %g, uv_scale %g, near %g, far %g; position %g, %g)", who,
+                    (double)lf->aspect, (double)lf->st_scale, (double)lf->uv_scale, (double)lf->near, (double)lf->far, (double)a, (double)b);
+    return HR_OK;
+}
+
+int generate_lightfield(const hr_lightfield* lf, bool epi, float a, float b, int64_t first, int64_t n, float* rays_dev, void* stream, const char* who)
+{
+    if (int rc = check_lightfield(lf, a, b, who)) return rc;
+    const int64_t size = (int64_t)lf->width * lf->height;
+    if (first < 0 || n < 0 || first > size || n > size - first)
+        return fail(HR_E_INVALID, "%s: rows [%lld, %lld + %lld) outside the list's %lld rays", who, (long long)first, (long long)first, (long long)n,
+                    (long long)size);
+    if (n > 0 && !rays_dev) return fail(HR_E_INVALID, "%s: null output", who);
+    if (n == 0) return HR_OK;              // an empty range: nothing to launch
+    hr_launch_generate_rays_lightfield(*lf, epi, a, b, first, n, rays_dev, (hipStream_t)stream);
+    HR_HIP(hipGetLastError());
     return HR_OK;
 }
 
@@ -48,6 +78,8 @@ HrRaySetArgs set_args(const hr_rayset* s, int64_t first, int64_t n, uint64_t see
     a.n_images = s->n_images; a.width = s->width; a.height = s->height; a.ray_dim = s->ray_dim;
     a.has_ndc = s->has_ndc ? 1 : 0;
     a.ndc = s->ndc;
+    a.lightfield = s->lightfield ? 1 : 0;
+    a.lf = s->lf;
     a.size = s->prefix[s->n_images];
     a.first = first; a.n = n;
     a.key = hr_perm_key(seed, epoch);
@@ -55,6 +87,16 @@ HrRaySetArgs set_args(const hr_rayset* s, int64_t first, int64_t n, uint64_t see
 }
 
 }  // namespace
+
+int hr_generate_rays_lightfield(const hr_lightfield* lf, float s, float t, int64_t first_pixel, int64_t n_pixels, float* rays_dev, void* stream)
+{
+    return generate_lightfield(lf, false, s, t, first_pixel, n_pixels, rays_dev, stream, "hr_generate_rays_lightfield");
+}
+
+int hr_generate_rays_epi(const hr_lightfield* lf, float v, float t, int64_t first, int64_t n, float* rays_dev, void* stream)
+{
+    return generate_lightfield(lf, true, v, t, first, n, rays_dev, stream, "hr_generate_rays_epi");
+}
 
 int hr_generate_rays_ndc(const hr_camera* cam, const hr_ndc* ndc, int32_t ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays_dev,
                          void* stream)
@@ -71,6 +113,25 @@ int hr_generate_rays_ndc(const hr_camera* cam, const hr_ndc* ndc, int32_t ray_di
     return HR_OK;
 }
 
+// the set's tables and pixel store; `s` is deleted on failure
+static int rayset_alloc(hr_rayset* s, hr_rayset** out, const char* who)
+{
+    const int n_images = s->n_images, width = s->width, height = s->height;
+    s->images.assign((size_t)n_images, HrRayImage());
+    s->prefix.assign((size_t)n_images + 1, 0);
+    hipError_t e = s->images_dev.alloc(sizeof(HrRayImage) * (size_t)n_images);
+    if (e == hipSuccess) e = s->prefix_dev.alloc(sizeof(int64_t) * ((size_t)n_images + 1));
+    if (e == hipSuccess) e = s->pixels.alloc((size_t)n_images * height * width * 3);
+    if (e == hipSuccess) e = hipMemcpy(s->images_dev, s->images.data(), sizeof(HrRayImage) * (size_t)n_images, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(s->prefix_dev, s->prefix.data(), sizeof(int64_t) * ((size_t)n_images + 1), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        delete s;
+        return fail(HR_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    *out = s;
+    return HR_OK;
+}
+
 int hr_rayset_create(int32_t n_images, int32_t width, int32_t height, int32_t ray_dim, const hr_ndc* ndc, hr_rayset** out)
 {
     if (!out) return fail(HR_E_INVALID, "hr_rayset_create: null argument");
@@ -82,36 +143,30 @@ int hr_rayset_create(int32_t n_images, int32_t width, int32_t height, int32_t ra
     s->n_images = n_images; s->width = width; s->height = height; s->ray_dim = ray_dim;
     s->has_ndc = ndc != nullptr;
     if (ndc) s->ndc = *ndc;
-    s->images.assign((size_t)n_images, HrRayImage());
-    s->prefix.assign((size_t)n_images + 1, 0);
-    hipError_t e = s->images_dev.alloc(sizeof(HrRayImage) * (size_t)n_images);
-    if (e == hipSuccess) e = s->prefix_dev.alloc(sizeof(int64_t) * ((size_t)n_images + 1));
-    if (e == hipSuccess) e = s->pixels.alloc((size_t)n_images * height * width * 3);
-    if (e == hipSuccess) e = hipMemcpy(s->images_dev, s->images.data(), sizeof(HrRayImage) * (size_t)n_images, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(s->prefix_dev, s->prefix.data(), sizeof(int64_t) * ((size_t)n_images + 1), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        delete s;
-        return fail(HR_E_HIP, "hr_rayset_create: %s", hipGetErrorString(e));
-    }
-    *out = s;
-    return HR_OK;
+    return rayset_alloc(s, out, "hr_rayset_create");
+}
+
+int hr_rayset_create_lightfield(int32_t n_views, const hr_lightfield* lf, hr_rayset** out)
+{
+    if (!out) return fail(HR_E_INVALID, "hr_rayset_create_lightfield: null argument");
+    *out = nullptr;
+    if (int rc = check_lightfield(lf, 0.0f, 0.0f, "hr_rayset_create_lightfield")) return rc;
+    if (n_views < 1) return fail(HR_E_INVALID, "hr_rayset_create_lightfield: %d views", (int)n_views);
+    hr_rayset* s = new hr_rayset();
+    s->n_images = n_views; s->width = lf->width; s->height = lf->height; s->ray_dim = 6;
+    s->lightfield = true;
+    s->lf = *lf;
+    return rayset_alloc(s, out, "hr_rayset_create_lightfield");
 }
 
 void hr_rayset_destroy(hr_rayset* set) { delete set; }
 
-int hr_rayset_set_image(hr_rayset* set, int32_t i, const hr_camera* cam, int32_t every, int32_t offset, const uint8_t* rgb_host_or_dev)
+// pixels and table entry of image i, then the prefix sums from i on
+static int rayset_commit(hr_rayset* set, int i, const HrRayImage& image, const uint8_t* rgb_host_or_dev)
 {
-    if (!set || !cam || !rgb_host_or_dev) return fail(HR_E_INVALID, "hr_rayset_set_image: null argument");
-    if (i < 0 || i >= set->n_images) return fail(HR_E_INVALID, "hr_rayset_set_image: image %d of %d", (int)i, set->n_images);
-    if (every < 1 || offset < 0) return fail(HR_E_INVALID, "hr_rayset_set_image: subsample rule every %d, offset %d (every >= 1, offset >= 0)", (int)every, (int)offset);
-    if (cam->width != set->width || cam->height != set->height || cam->fx == 0.0f || cam->fy == 0.0f)
-        return fail(HR_E_INVALID, "hr_rayset_set_image: bad camera (%d x %d in a set of %d x %d, fx %g, fy %g)", (int)cam->width, (int)cam->height,
-                    set->width, set->height, (double)cam->fx, (double)cam->fy);
     const size_t bytes = (size_t)set->height * set->width * 3;
     HR_HIP(hipMemcpy(set->pixels + (size_t)i * bytes, rgb_host_or_dev, bytes, hipMemcpyDefault));
-    set->images[i].cam = *cam;
-    set->images[i].every = every;
-    set->images[i].offset = offset;
+    set->images[i] = image;
     for (int j = i; j < set->n_images; ++j) {
         const HrRayImage& im = set->images[j];
         set->prefix[j + 1] = set->prefix[j] + (im.every > 0 ? hr_subsample_count(set->width, set->height, im.every, im.offset) : 0);
@@ -119,6 +174,34 @@ int hr_rayset_set_image(hr_rayset* set, int32_t i, const hr_camera* cam, int32_t
     HR_HIP(hipMemcpy(set->images_dev + i, &set->images[i], sizeof(HrRayImage), hipMemcpyHostToDevice));
     HR_HIP(hipMemcpy(set->prefix_dev + i, &set->prefix[i], sizeof(int64_t) * (size_t)(set->n_images + 1 - i), hipMemcpyHostToDevice));
     return HR_OK;
+}
+
+int hr_rayset_set_image(hr_rayset* set, int32_t i, const hr_camera* cam, int32_t every, int32_t offset, const uint8_t* rgb_host_or_dev)
+{
+    if (!set || !cam || !rgb_host_or_dev) return fail(HR_E_INVALID, "hr_rayset_set_image: null argument");
+    if (set->lightfield) return fail(HR_E_INVALID, "hr_rayset_set_image: the set holds light-field views (hr_rayset_create_lightfield): use hr_rayset_set_view");
+    if (i < 0 || i >= set->n_images) return fail(HR_E_INVALID, "hr_rayset_set_image: image %d of %d", (int)i, set->n_images);
+    if (every < 1 || offset < 0) return fail(HR_E_INVALID, "hr_rayset_set_image: subsample rule every %d, offset %d (every >= 1, offset >= 0)", (int)every, (int)offset);
+    if (cam->width != set->width || cam->height != set->height || cam->fx == 0.0f || cam->fy == 0.0f)
+        return fail(HR_E_INVALID, "hr_rayset_set_image: bad camera (%d x %d in a set of %d x %d, fx %g, fy %g)", (int)cam->width, (int)cam->height,
+                    set->width, set->height, (double)cam->fx, (double)cam->fy);
+    HrRayImage im = HrRayImage();
+    im.cam = *cam;
+    im.every = every; im.offset = offset;
+    return rayset_commit(set, i, im, rgb_host_or_dev);
+}
+
+int hr_rayset_set_view(hr_rayset* set, int32_t i, float s, float t, int32_t every, int32_t offset, const uint8_t* rgb_host_or_dev)
+{
+    if (!set || !rgb_host_or_dev) return fail(HR_E_INVALID, "hr_rayset_set_view: null argument");
+    if (!set->lightfield) return fail(HR_E_INVALID, "hr_rayset_set_view: the set holds posed images (hr_rayset_create): use hr_rayset_set_image");
+    if (i < 0 || i >= set->n_images) return fail(HR_E_INVALID, "hr_rayset_set_view: view %d of %d", (int)i, set->n_images);
+    if (every < 1 || offset < 0) return fail(HR_E_INVALID, "hr_rayset_set_view: subsample rule every %d, offset %d (every >= 1, offset >= 0)", (int)every, (int)offset);
+    if (!isfinite(s) || !isfinite(t)) return fail(HR_E_INVALID, "hr_rayset_set_view: non-finite position (%g, %g)", (double)s, (double)t);
+    HrRayImage im = HrRayImage();
+    im.every = every; im.offset = offset;
+    im.s = s; im.t = t;
+    return rayset_commit(set, i, im, rgb_host_or_dev);
 }
 
 int64_t hr_rayset_size(const hr_rayset* set)

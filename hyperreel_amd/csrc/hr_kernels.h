@@ -236,10 +236,14 @@ void hr_launch_generate_rays(const hr_camera& cam, int ray_dim, int64_t first_pi
 // camera rays with NDC and the training feed (rays_kernel.hip; arithmetic: hr_camera.h)
 void hr_launch_generate_rays_ndc(const hr_camera& cam, const hr_ndc* ndc, int ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays,
                                  hipStream_t stream);
-// one image of a device-resident training set: its camera and its subsample rule (x + y + offset) % every == 0
+// two-plane light-field rays (rays_kernel.hip; arithmetic: hr_lightfield.h).  epi: (a, b) = (v, t) of get_epi_rays, else (s, t) of the view
+void hr_launch_generate_rays_lightfield(const hr_lightfield& lf, bool epi, float a, float b, int64_t first, int64_t n, float* rays, hipStream_t stream);
+// one image of a device-resident training set: its camera -- or, in a light-field set, its position (s, t) on the camera plane -- and
+// its subsample rule (x + y + offset) % every == 0
 struct HrRayImage {
     hr_camera cam;
     int32_t every, offset;
+    float s, t;
 };
 struct HrRaySetArgs {
     const HrRayImage* images;    // [n_images]
@@ -248,6 +252,8 @@ struct HrRaySetArgs {
     int n_images, width, height, ray_dim;
     int has_ndc;
     hr_ndc ndc;
+    int lightfield;              // the images are views of `lf` (ray_dim 6, no camera, no NDC)
+    hr_lightfield lf;
     int64_t size;
     int64_t first, n;            // rows [first, first + n) of the epoch's order
     uint64_t key;                // hr_perm_key(seed, epoch)

@@ -1,8 +1,10 @@
-// Camera rays with NDC (hr_generate_rays_ndc) and the training feed (hr_rayset_batch / hr_rayset_order).  One lane per ray; the
-// arithmetic is hr_camera.h's, which the CPU suite compiles for the host.  Launch-bound at a training batch (16 384 rays: 64
+// Camera rays with NDC (hr_generate_rays_ndc), two-plane light-field rays (hr_generate_rays_lightfield, hr_generate_rays_epi) and the
+// training feed (hr_rayset_batch / hr_rayset_order).  One lane per ray; the arithmetic is hr_camera.h's and hr_lightfield.h's, which
+// the CPU suite compiles for the host.  Launch-bound at a training batch (16 384 rays: 64
 // workgroups); nothing to tune beyond the stores: a lane owns a whole output row and writes it in 16- or 8-byte pieces when the
 // buffer is aligned for that, so a wavefront's stores cover a contiguous 64 * row bytes.
 #include "hr_camera.h"
+#include "hr_lightfield.h"
 #include "hr_kernels.h"
 
 namespace {
@@ -38,8 +40,22 @@ __global__ __launch_bounds__(256) void hr_generate_rays_ndc_kernel(const hr_came
     }
 }
 
+// a view at (a, b) = (s, t), or with EPI the slice at (a, b) = (v, t): row p = y * width + x of the list
+template <bool VEC, bool EPI>
+__global__ __launch_bounds__(256) void hr_generate_rays_lightfield_kernel(const hr_lightfield lf, float a, float b, int64_t first, int64_t n,
+                                                                          float* __restrict__ rays)
+{
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
+        const int64_t p = first + t;
+        float v[8];
+        if (EPI) hr_epi_ray(lf, a, b, (int)(p % lf.width), (int)(p / lf.width), v);
+        else hr_lightfield_ray(lf, a, b, (int)(p % lf.width), (int)(p / lf.width), v);
+        store_ray<VEC>(rays + t * 6, v, 6);
+    }
+}
+
 // row -> set element -> image (binary search in the prefix sums) -> pixel (closed form) -> ray, colour, weight
-template <bool VEC>
+template <bool VEC, bool LF>
 __global__ __launch_bounds__(256) void hr_rayset_batch_kernel(const HrRaySetArgs a)
 {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -58,8 +74,12 @@ __global__ __launch_bounds__(256) void hr_rayset_batch_kernel(const HrRaySetArgs
         const HrRayImage& im = a.images[lo];
         int x, y;
         hr_subsample_pixel(a.width, a.height, im.every, im.offset, e - a.prefix[lo], &x, &y);
-        hr_pixel_ray(im.cam, a.has_ndc ? &a.ndc : nullptr, x, y, v);
-        v[6] = im.cam.cam_id; v[7] = im.cam.time;
+        if (LF) {
+            hr_lightfield_ray(a.lf, im.s, im.t, x, y, v);
+        } else {
+            hr_pixel_ray(im.cam, a.has_ndc ? &a.ndc : nullptr, x, y, v);
+            v[6] = im.cam.cam_id; v[7] = im.cam.time;
+        }
         if (a.rgb) {
             const uint8_t* px = a.pixels + (((int64_t)lo * a.height + y) * a.width + x) * 3;
             c[0] = (float)px[0] / 255.0f; c[1] = (float)px[1] / 255.0f; c[2] = (float)px[2] / 255.0f;   // ToTensor
@@ -96,10 +116,34 @@ void hr_launch_generate_rays_ndc(const hr_camera& cam, const hr_ndc* ndc, int ra
                            first_pixel, n_pixels, rays);
 }
 
+template <bool EPI>
+static void launch_lightfield(const hr_lightfield& lf, float a, float b, int64_t first, int64_t n, float* rays, hipStream_t stream)
+{
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (rows_aligned(rays, 6))
+        hipLaunchKernelGGL((hr_generate_rays_lightfield_kernel<true, EPI>), dim3((unsigned)blocks), dim3(256), 0, stream, lf, a, b, first, n, rays);
+    else
+        hipLaunchKernelGGL((hr_generate_rays_lightfield_kernel<false, EPI>), dim3((unsigned)blocks), dim3(256), 0, stream, lf, a, b, first, n, rays);
+}
+
+void hr_launch_generate_rays_lightfield(const hr_lightfield& lf, bool epi, float a, float b, int64_t first, int64_t n, float* rays, hipStream_t stream)
+{
+    if (n <= 0) return;
+    if (epi) launch_lightfield<true>(lf, a, b, first, n, rays, stream);
+    else launch_lightfield<false>(lf, a, b, first, n, rays, stream);
+}
+
 void hr_launch_rayset_batch(const HrRaySetArgs& a, hipStream_t stream)
 {
     if (a.n <= 0) return;
     const dim3 grid((unsigned)((a.n + 255) / 256));
-    if (!a.coords || rows_aligned(a.coords, a.ray_dim)) hipLaunchKernelGGL(hr_rayset_batch_kernel<true>, grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(hr_rayset_batch_kernel<false>, grid, dim3(256), 0, stream, a);
+    const bool vec = !a.coords || rows_aligned(a.coords, a.ray_dim);
+    if (a.lightfield) {
+        if (vec) hipLaunchKernelGGL((hr_rayset_batch_kernel<true, true>), grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((hr_rayset_batch_kernel<false, true>), grid, dim3(256), 0, stream, a);
+    } else {
+        if (vec) hipLaunchKernelGGL((hr_rayset_batch_kernel<true, false>), grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((hr_rayset_batch_kernel<false, false>), grid, dim3(256), 0, stream, a);
+    }
 }

@@ -4,14 +4,17 @@ The reference's datasets build `all_inputs`, a host float tensor of ray_dim + 4 
 (datasets/base.py:130-143, datasets/technicolor.py:238-282), shuffle it on the host every epoch (base.py:202-227) and
 slice batches out of it (format_batch, base.py:278-284).  A DeviceRaySet keeps the 8-bit images in device memory with
 one camera and one subsample rule per image, and computes a batch's rays when they are drawn.  Nothing here reads
-files: decoding images stays with the caller.  No CPU path: a missing library or a failing call raises."""
+files: decoding images stays with the caller.  No CPU path: a missing library or a failing call raises.
+
+DeviceRaySet.from_lightfield does the same for the two-plane light-field datasets (datasets/lightfield.py,
+datasets/stanford.py): a position (s, t) on the camera plane per view instead of a camera."""
 import ctypes as C
 
 import numpy as np
 import torch
 
 from . import lib as _lib
-from .plan import hr_camera, hr_ndc
+from .plan import hr_camera, hr_lightfield, hr_ndc
 
 # subsample rules of the reference's datasets that are not the checkerboard: named so that the refusal can say which
 UNSUPPORTED_RULES = {
@@ -48,6 +51,44 @@ def make_camera(pose, K, width, height, cam_id=0.0, time=0.0):
     return cam
 
 
+def make_lightfield(width, height, aspect=None, st_scale=1.0, uv_scale=1.0, near=-1.0, far=0.0):
+    """The arguments of get_lightfield_rays / get_epi_rays (utils/ray_utils.py:14-78) besides the position -> hr_lightfield.
+    width x height: U x V of a view, U x S of an epipolar slice.  aspect: W / H of the images by default (datasets/stanford.py:66);
+    near, far: the planes' z (datasets/lightfield.py:56-57)."""
+    lf = hr_lightfield()
+    lf.width, lf.height = int(width), int(height)
+    lf.aspect = float(width) / float(height) if aspect is None else float(aspect)
+    lf.st_scale, lf.uv_scale, lf.near, lf.far = float(st_scale), float(uv_scale), float(near), float(far)
+    return lf
+
+
+def lightfield_coord(s_idx, t_idx, rows, cols):
+    """LightfieldDataset.get_coord (datasets/lightfield.py:185-191): grid indices (fractional ones too) -> (s, t) in [-1, 1], t
+    pointing up; a grid of one column / row sits at 0."""
+    s = (s_idx / (cols - 1)) * 2 - 1 if cols > 1 else 0
+    t = -(((t_idx / (rows - 1)) * 2 - 1) if rows > 1 else 0)
+    return (s, t)
+
+
+def stanford_normalize_coord(coord, camera_coords):
+    """StanfordLightfieldDataset.normalize_coord (datasets/stanford.py:82-106): a camera position (x, y) read from a file name ->
+    (s, t), x over the rig's x range to [-1, 1], y likewise and divided by the rig's aspect.  camera_coords: every camera's (x, y)."""
+    xs = [c[0] for c in camera_coords]
+    ys = [c[1] for c in camera_coords]
+    x_range, y_range = (np.min(xs), np.max(xs)), (np.min(ys), np.max(ys))
+    aspect = (x_range[1] - x_range[0]) / (y_range[1] - y_range[0])
+    norm_x = ((coord[0] - x_range[0]) / (x_range[1] - x_range[0])) * 2 - 1
+    norm_y = (((coord[1] - y_range[0]) / (y_range[1] - y_range[0])) * 2 - 1) / aspect
+    return (norm_x, norm_y)
+
+
+def _as_u8_image(img, i, H, W):
+    img = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
+    if img.dtype != torch.uint8 or tuple(img.shape) != (H, W, 3):
+        raise ValueError(f'image {i}: expected uint8 ({H}, {W}, 3), got {img.dtype} {tuple(img.shape)}')
+    return img.contiguous()
+
+
 class DeviceRaySet:
     """images_u8: (n, H, W, 3) uint8 (numpy, or a torch tensor on the host or the device), RGB as Image.convert("RGB") holds
     them; poses (n, 3, 4); intrinsics (n, 3, 3) or one (3, 3); times, cam_ids: (n) or None (6-column rays); img_wh = (W, H);
@@ -80,15 +121,46 @@ class DeviceRaySet:
             _lib.check(L.hr_rayset_create(n, W, H, self.ray_dim, C.byref(self._ndc) if self._ndc is not None else None, C.byref(self._h)),
                        'hr_rayset_create')
             for i in range(n):
-                img = images_u8[i]
-                img = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
-                if img.dtype != torch.uint8 or tuple(img.shape) != (H, W, 3):
-                    raise ValueError(f'image {i}: expected uint8 ({H}, {W}, 3), got {img.dtype} {tuple(img.shape)}')
-                img = img.contiguous()
+                img = _as_u8_image(images_u8[i], i, H, W)
                 cam = make_camera(poses[i], Ks[i], W, H, cam_ids[i], times[i])
                 _lib.check(L.hr_rayset_set_image(self._h, i, C.byref(cam), rules[i][0], rules[i][1], C.c_void_p(img.data_ptr())),
                            'hr_rayset_set_image')
         self._size = int(L.hr_rayset_size(self._h))
+
+    @classmethod
+    def from_lightfield(cls, images_u8, st, lightfield, subsample=None, device=None):
+        """A set of two-plane light-field views (hr_rayset_create_lightfield): images_u8 (n, V, U, 3) uint8 as for the constructor,
+        st: (n, 2) the views' (s, t) -- lightfield_coord or stanford_normalize_coord of each -- in the order the reference's
+        prepare_train_data visits them, t outer and s inner (datasets/lightfield.py:106-141); lightfield: make_lightfield(...).
+        Element e is row e of that order's concatenated get_lightfield_rays; rays have 6 columns."""
+        if isinstance(subsample, str):
+            why = UNSUPPORTED_RULES.get(subsample)
+            raise NotImplementedError(f'subsample rule {subsample!r} is not supported' + (f' ({why})' if why else '')
+                                      + ': only the checkerboard rule (x + y + offset) % every == 0 is')
+        if not isinstance(lightfield, hr_lightfield):
+            raise TypeError('lightfield must be an hr_lightfield (data.make_lightfield)')
+        L = _lib.load()
+        st = np.asarray(st, np.float64).reshape(-1, 2)
+        n = st.shape[0]
+        W, H = int(lightfield.width), int(lightfield.height)
+        rules = [(1, 0)] * n if subsample is None else [(int(e), int(o)) for e, o in subsample]
+        if not (len(images_u8) == len(rules) == n):
+            raise ValueError('images, st and subsample must describe the same number of views')
+        self = cls.__new__(cls)
+        self.ray_dim = 6
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.width, self.height, self.n_images = W, H, n
+        self._ndc = None
+        self._lightfield = lightfield
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(L.hr_rayset_create_lightfield(n, C.byref(lightfield), C.byref(self._h)), 'hr_rayset_create_lightfield')
+            for i in range(n):
+                img = _as_u8_image(images_u8[i], i, H, W)
+                _lib.check(L.hr_rayset_set_view(self._h, i, float(st[i, 0]), float(st[i, 1]), rules[i][0], rules[i][1], C.c_void_p(img.data_ptr())),
+                           'hr_rayset_set_view')
+        self._size = int(L.hr_rayset_size(self._h))
+        return self
 
     def __len__(self):
         return self._size

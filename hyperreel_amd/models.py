@@ -900,6 +900,45 @@ class HipLightfieldModel(nn.Module):
         its host round trips: pose -> rays -> rgb, all on the device and on the current stream."""
         return self.render(self.generate_rays(pose, K, width, height, time, cam_id, pixel_range, ndc=ndc), frame_time=time)['rgb']
 
+    def _lightfield_rays(self, epi, a, b, lightfield, pixel_range, device):
+        import ctypes as C
+        from .plan import hr_lightfield
+        if not isinstance(lightfield, hr_lightfield):
+            raise TypeError('lightfield must be an hr_lightfield (data.make_lightfield)')
+        self.native()
+        if self._hc.ray_dim != 6:
+            raise ValueError(f'two-plane light-field rays have 6 columns; this model takes {self._hc.ray_dim}')
+        L = _lib.load()
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        lo, hi = (0, int(lightfield.width) * int(lightfield.height)) if pixel_range is None else (int(pixel_range[0]), int(pixel_range[1]))
+        if hi < lo:
+            raise ValueError(f'pixel_range {pixel_range} is reversed')
+        rays = torch.empty((hi - lo, 6), dtype=torch.float32, device=dev)
+        fn, name = (L.hr_generate_rays_epi, 'hr_generate_rays_epi') if epi else (L.hr_generate_rays_lightfield, 'hr_generate_rays_lightfield')
+        with torch.cuda.device(dev):
+            _lib.check(fn(C.byref(lightfield), float(a), float(b), lo, hi - lo, C.c_void_p(rays.data_ptr()),
+                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), name)
+        return rays
+
+    def generate_lightfield_rays(self, s, t, lightfield, pixel_range=None, device=None):
+        """get_lightfield_rays (utils/ray_utils.py:14-45) on the device: rays (n, 6) for pixels [lo, hi) of the row-major U x V view at
+        camera-plane position (s, t) (whole view by default); lightfield: data.make_lightfield(...).  28 bytes cross the PCIe bus
+        instead of the ray list (datasets/stanford.py:120)."""
+        return self._lightfield_rays(False, s, t, lightfield, pixel_range, device)
+
+    def render_lightfield_view(self, s, t, lightfield, pixel_range=None):
+        """render(generate_lightfield_rays(...))['rgb'], bit for bit; image-parallel ranks pass their own pixel_range."""
+        return self.render(self.generate_lightfield_rays(s, t, lightfield, pixel_range))['rgb']
+
+    def generate_epi_rays(self, v, t, lightfield, pixel_range=None, device=None):
+        """get_epi_rays (utils/ray_utils.py:47-78) on the device: the epipolar slice (u, s) at a fixed (v, t), rays (U * S, 6) with
+        lightfield.width = U and lightfield.height = S (nlf/visualizers/epipolar.py:106)."""
+        return self._lightfield_rays(True, v, t, lightfield, pixel_range, device)
+
+    def render_epi(self, v, t, lightfield, pixel_range=None):
+        """render(generate_epi_rays(...))['rgb'], bit for bit."""
+        return self.render(self.generate_epi_rays(v, t, lightfield, pixel_range))['rgb']
+
     def evaluate(self, rays, gt, h, w, frame_time=None, ssim=True):
         """Render a frame and score it against its ground truth without leaving the device until the four sums are read: what
         validation_image does on the host (nlf/__init__.py:976-980, metrics.py:25-35).  rays: the frame's h*w rays; gt: (h*w, 3)

@@ -99,6 +99,12 @@ class hr_ndc(C.Structure):
     _fields_ = [('fx', C.c_float), ('fy', C.c_float), ('near', C.c_float), ('width', C.c_int32), ('height', C.c_int32)]
 
 
+class hr_lightfield(C.Structure):
+    """Two-plane light field: the arguments of get_lightfield_rays / get_epi_rays besides the position (include/hyperreel_hip.h)."""
+    _fields_ = [('width', C.c_int32), ('height', C.c_int32), ('aspect', C.c_float), ('st_scale', C.c_float), ('uv_scale', C.c_float),
+                ('near', C.c_float), ('far', C.c_float)]
+
+
 class hr_fields(C.Structure):
     _fields_ = [('distances_dev', C.c_void_p), ('points_dev', C.c_void_p), ('sigma_dev', C.c_void_p),
                 ('weights_dev', C.c_void_p), ('head_dev', C.c_void_p)]

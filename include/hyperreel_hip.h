@@ -269,6 +269,17 @@ typedef struct hr_ndc {
     int32_t width, height;
 } hr_ndc;
 
+/* Two-plane light field (the Stanford configs: datasets/lightfield.py, datasets/stanford.py): what get_lightfield_rays and
+ * get_epi_rays (utils/ray_utils.py:14-78) take besides the position on the camera plane.  A ray starts at (s, t) * st_scale on the
+ * plane z = near and passes through (u, v) * uv_scale on the plane z = far.  The reference's use_inf, center_u and center_v are
+ * accepted there and never read; they are not part of this interface. */
+typedef struct hr_lightfield {
+    int32_t width, height;      /* U x V of a view; U x S of an epipolar slice */
+    float aspect;               /* v (and an EPI's s) is divided by it: W / H of the images (datasets/stanford.py:66) */
+    float st_scale, uv_scale;
+    float near, far;            /* z of the camera plane and of the image plane (-1 and 0 by default) */
+} hr_lightfield;
+
 typedef struct hr_rayset hr_rayset;
 
 typedef struct hr_model hr_model;
@@ -459,6 +470,22 @@ int hr_generate_rays(const hr_camera* cam, int32_t ray_dim, int64_t first_pixel,
 int hr_generate_rays_ndc(const hr_camera* cam, const hr_ndc* ndc, int32_t ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays_dev,
                          void* stream);
 
+/* rays_dev[n_pixels, 6] for pixels [first_pixel, first_pixel + n_pixels) of the row-major U x V view at camera-plane position
+ * (s, t): get_lightfield_rays (utils/ray_utils.py:14-45) in its order of float32 operations.  Pixel (x, y):
+ *   u = linspace(-1, 1, U)[x] * uv_scale,  v = linspace(1, -1, V)[y] / aspect * uv_scale  (torch.linspace's float32 elements on the
+ *   CPU: stepped from the start in the first half, from the end in the second; U or V == 1: the start),
+ *   origin = (s * st_scale, t * st_scale, near),  direction = (u - o_x, v - o_y, far - near) / max(|.|, 1e-12).
+ * A range holds the same bits as the same rows of the whole view, so every image-parallel rank generates its own hr_shard_range.
+ * One kernel on `stream`: no allocation, no synchronisation, no memset, every output element written; capturable in a hipGraph.
+ * HR_E_INVALID before any launch: width or height < 1, aspect == 0, a non-finite scalar, a negative range, first_pixel + n_pixels
+ * beyond U * V, rays_dev NULL with n_pixels > 0. */
+int hr_generate_rays_lightfield(const hr_lightfield* lf, float s, float t, int64_t first_pixel, int64_t n_pixels, float* rays_dev,
+                                void* stream);
+/* The epipolar slice (u, s) at a fixed (v, t): get_epi_rays (utils/ray_utils.py:47-78).  lf->width = U, lf->height = S; row
+ * p = j * U + x:  u as above,  s = linspace(-1, 1, S)[j] / aspect * st_scale,  origin = (s, t * st_scale, near),
+ * direction = (u - s, v * uv_scale - t * st_scale, far - near), normalised.  Rows [first, first + n); otherwise as above. */
+int hr_generate_rays_epi(const hr_lightfield* lf, float v, float t, int64_t first, int64_t n, float* rays_dev, void* stream);
+
 /* ---- training feed --------------------------------------------------------------------------------
  * A device-resident training set.  The reference keeps `all_inputs`, a host float tensor of ray_dim + 4 floats per training ray
  * (prepare_train_data / update_all_data, datasets/base.py:130-143, datasets/technicolor.py:238-282), shuffles it on the host every
@@ -475,6 +502,19 @@ void hr_rayset_destroy(hr_rayset* set);
  * offset >= 0) and height * width * 3 bytes of RGB, row-major, host or device memory -- what Image.convert("RGB") holds before ToTensor
  * (get_rgb, technicolor.py:398-417).  Synchronous (set-up, not the training loop).  Images not yet set hold no rays. */
 int hr_rayset_set_image(hr_rayset* set, int32_t i, const hr_camera* cam, int32_t every, int32_t offset, const uint8_t* rgb_host_or_dev);
+/* A set whose images are views of one two-plane light field (datasets/lightfield.py, datasets/stanford.py): n_views images of
+ * lf->width x lf->height, ray_dim 6, *lf copied.  Element e is views in index order, row-major within a view (after the view's
+ * checkerboard rule) -- the order prepare_train_data concatenates in when the caller lists the views as its loops do, t outer and s
+ * inner (datasets/lightfield.py:106-141).  That method holds a leftover debugging exit() at line 120 and cannot run as shipped, so
+ * this contract is defined by the ray function (get_lightfield_rays, as hr_generate_rays_lightfield computes it, bit for bit) and
+ * that loop order, not by a run of the method.  hr_rayset_size / _batch / _order / _destroy work on it unchanged: the same
+ * permutation, colours, weights and NaN rows.  hr_rayset_set_image on such a set, and hr_rayset_set_view on a set made by
+ * hr_rayset_create, are HR_E_INVALID. */
+int hr_rayset_create_lightfield(int32_t n_views, const hr_lightfield* lf, hr_rayset** out);
+/* View i: its position (s, t) on the camera plane (before st_scale: LightfieldDataset.get_coord, lightfield.py:185-191, or
+ * StanfordLightfieldDataset.normalize_coord, stanford.py:95-106), the subsample rule and height * width * 3 bytes of RGB as for
+ * hr_rayset_set_image.  Synchronous. */
+int hr_rayset_set_view(hr_rayset* set, int32_t i, float s, float t, int32_t every, int32_t offset, const uint8_t* rgb_host_or_dev);
 /* rays in the set after subsampling: the reference's len(all_coords); negative on a null set */
 int64_t hr_rayset_size(const hr_rayset* set);
 /* Rows [first, first + n) of the order of epoch `epoch`: row r is set element perm(r), a bijection of [0, size) keyed by
