@@ -33,6 +33,15 @@ class hr_image_scores(C.Structure):
     _fields_ = [('sse', C.c_double), ('ssim_sum', C.c_double * 3)]
 
 
+class hr_loss_out(C.Structure):
+    """Result of hr_image_loss, written on the device (include/hyperreel_hip.h)."""
+    _fields_ = [('loss_sum', C.c_double), ('sse', C.c_double), ('loss', C.c_float), ('pad', C.c_float)]
+
+
+HR_LOSS_MSE, HR_LOSS_WEIGHTED_MSE, HR_LOSS_MAE, HR_LOSS_WEIGHTED_MAE, HR_LOSS_HUBER = 0, 1, 2, 3, 4
+HR_LOSS_PREMULTIPLIED = 0x100
+
+
 class hr_verify_info(C.Structure):
     """What the verified fast path rests on for one model (include/hyperreel_hip.h)."""
     _fields_ = [('verified', C.c_int32), ('fallback', C.c_int32), ('band', C.c_float), ('band_q', C.c_float), ('band_off', C.c_float),
@@ -92,6 +101,9 @@ SYMBOLS = [
     ('hr_pack_display', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     ('hr_image_metrics_workspace', C.c_size_t, [C.c_int32, C.c_int32]),
     ('hr_image_metrics', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('hr_image_loss_workspace', C.c_size_t, [C.c_int64]),
+    ('hr_image_loss', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
     ('hr_plane_reg_forward', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     ('hr_plane_reg_backward', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('hr_adam_step', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

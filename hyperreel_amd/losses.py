@@ -1,0 +1,123 @@
+"""Training image loss on the device (hr_image_loss): the reference's loss module (losses.py: loss_dict) for the types that
+INRSystem.training_step can call (nlf/__init__.py:665: `self.loss(results['rgb'] * weight, rgb * weight, **batch)`), one launch pair
+for the loss, the squared error of train/psnr (:668) and the gradient with respect to the prediction.
+
+    loss_fn = get_loss(cfg.training.loss)                       # INRSystem.__init__: self.loss = hyperreel_amd.losses.get_loss(cfg.training.loss)
+    image_loss = loss_fn(rgb_pred * weight, rgb * weight, **batch)          # the reference's line, unchanged
+    image_loss, sse = loss_fn.step_loss(rgb_pred, rgb, weight)  # the same value with the two multiplies inside the kernel, and psnr's sum
+    image_loss.backward()                                       # d loss / d rgb_pred was written by the forward call
+
+There is no CPU path: tensors that are not contiguous float32 on the HIP device raise.
+"""
+import ctypes as C
+
+import torch
+from torch import nn
+
+from . import lib as _lib
+
+TYPES = {'mse': _lib.HR_LOSS_MSE, 'weighted_mse': _lib.HR_LOSS_WEIGHTED_MSE, 'mae': _lib.HR_LOSS_MAE, 'weighted_mae': _lib.HR_LOSS_WEIGHTED_MAE,
+         'huber': _lib.HR_LOSS_HUBER}
+# in the reference's loss_dict, but their forward(inputs, targets) does not take training_step's **batch: the reference cannot train with them either
+REFUSED = ('tv', 'complex_mse', 'complex_mae', 'mse_top_n', 'mae_top_n')
+OUT_DOUBLES = C.sizeof(_lib.hr_loss_out) // 8           # hr_loss_out as a float64 tensor: [loss_sum, sse, {loss, pad} as two float32]
+
+
+def workspace_doubles(n_rays):
+    """Length of the float64 workspace tensor a call on n_rays rays needs."""
+    return max(int(_lib.load().hr_image_loss_workspace(int(n_rays))) // 8, 1)
+
+
+def _check(name, t, numel, device=None):
+    if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
+        raise RuntimeError(f'{name} must be a tensor on the HIP device; there is no CPU path')
+    if device is not None and t.device != device:
+        raise ValueError(f'{name} is on {t.device}, the prediction on {device}')
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f'{name} must be a contiguous float32 tensor, got {t.dtype}{"" if t.is_contiguous() else ", not contiguous"}')
+    if t.numel() != numel:
+        raise ValueError(f'{name} must hold {numel} values, got {tuple(t.shape)}')
+    return t
+
+
+class ImageLoss(torch.autograd.Function):
+    """(pred, gt, weight | None) -> (loss, sse): one hr_image_loss call.  loss: 0-d float32, the mean; sse: 0-d float64, the unweighted
+    squared-error sum of pred against gt (not differentiable).  d loss / d pred is written by the same call when pred requires a gradient;
+    backward multiplies it by the incoming gradient on the device.  gt and weight are data: they get no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, weight, kind, delta, out, workspace):
+        if not isinstance(pred, torch.Tensor) or pred.dim() < 1 or pred.shape[-1] != 3 or pred.numel() == 0:
+            raise ValueError(f'the prediction must be a non-empty (B, 3) tensor, got {tuple(getattr(pred, "shape", ()))}')
+        n = pred.numel() // 3
+        pred = _check('the prediction', pred, 3 * n)
+        dev = pred.device
+        gt = _check('the target', gt, 3 * n, dev)
+        if weight is not None:
+            weight = _check('weight', weight, n, dev)
+        if out is None:
+            out = torch.empty((OUT_DOUBLES,), dtype=torch.float64, device=dev)
+        elif out.shape != (OUT_DOUBLES,) or out.dtype != torch.float64 or out.device != dev or not out.is_contiguous():
+            raise ValueError(f'out must be a contiguous ({OUT_DOUBLES},) float64 tensor on the prediction\'s device')
+        need = workspace_doubles(n)
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.float64, device=dev)
+        elif workspace.dtype != torch.float64 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
+            raise ValueError(f'workspace must be a contiguous float64 tensor of at least {need} elements on the prediction\'s device')
+        d_pred = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().hr_image_loss(
+                C.c_void_p(pred.data_ptr()), C.c_void_p(gt.data_ptr()), C.c_void_p(weight.data_ptr() if weight is not None else 0), n, int(kind),
+                float(delta), C.c_void_p(0), C.c_void_p(out.data_ptr()), C.c_void_p(d_pred.data_ptr() if d_pred is not None else 0),
+                C.c_void_p(workspace.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_image_loss')
+        ctx.d_pred = d_pred
+        loss, sse = out.view(torch.float32)[4], out[1]
+        ctx.mark_non_differentiable(sse)
+        return loss, sse
+
+    @staticmethod
+    def backward(ctx, d_loss, d_sse):
+        return ctx.d_pred * d_loss, None, None, None, None, None, None
+
+
+class HipImageLoss(nn.Module):
+    """The reference's loss module of one type.  forward(inputs, targets, **kwargs) has its signature and its meaning: inputs and targets
+    as given (training_step passes them multiplied by the weight), kwargs['weight'] read by the weighted types only.  step_loss takes the
+    un-multiplied tensors and the weight."""
+
+    def __init__(self, type, delta=1.0):
+        super().__init__()
+        self.type, self.kind, self.delta = type, TYPES[type], float(delta)
+
+    def forward(self, inputs, targets, out=None, workspace=None, **kwargs):
+        weight = kwargs.get('weight') if self.type.startswith('weighted_') else None
+        if not isinstance(weight, torch.Tensor):
+            weight = None                                   # the reference's `weight = 1.0`
+        return ImageLoss.apply(inputs, targets, weight, self.kind | _lib.HR_LOSS_PREMULTIPLIED, self.delta, out, workspace)[0]
+
+    def step_loss(self, rgb_pred, rgb, weight=None, out=None, workspace=None):
+        """(loss, sse): loss = forward(rgb_pred * weight, rgb * weight, weight=weight); sse = sum (rgb_pred - rgb)^2, float64, from which
+        psnr_gpu's value is -10 log10(sse / (3 B))."""
+        return ImageLoss.apply(rgb_pred, rgb, weight, self.kind, self.delta, out, workspace)
+
+    def extra_repr(self):
+        return f'type={self.type}' + (f', delta={self.delta}' if self.type == 'huber' else '')
+
+
+def get_loss(cfg):
+    """loss_dict[cfg.type](cfg) of the reference (nlf/__init__.py:294) for cfg = cfg.training.loss: a mapping or an object with `type`
+    (and `delta` for huber, 1.0 when absent), or the type's name."""
+    def field(key, default=None):
+        if isinstance(cfg, str):
+            return cfg if key == 'type' else default
+        if hasattr(cfg, 'get'):
+            return cfg.get(key, default)
+        return getattr(cfg, key, default)
+
+    type = field('type')
+    if type in REFUSED:
+        raise NotImplementedError(f"loss type '{type}': its forward(inputs, targets) does not accept training_step's **batch in the reference "
+                                  'either; hr_image_loss implements ' + ' | '.join(sorted(TYPES)))
+    if type not in TYPES:
+        raise KeyError(f"unknown loss type '{type}' (the reference's loss_dict has none of that name)")
+    return HipImageLoss(type, delta=field('delta', 1.0) if type == 'huber' else 1.0)

@@ -659,6 +659,46 @@ size_t hr_image_metrics_workspace(int32_t h, int32_t w);
 int hr_image_metrics(const float* pred_dev, const float* gt_dev, int32_t h, int32_t w, int32_t want_ssim, hr_image_scores* out_dev,
                      void* workspace_dev, void* stream);
 
+/* Training image loss: INRSystem.training_step's
+ *     image_loss = self.loss(results['rgb'] * weight, rgb * weight, **batch)            (nlf/__init__.py:665)
+ * for the modules of losses.py's loss_dict that accept that call, with the squared error train/psnr needs (psnr_gpu, :668) from the
+ * same read.  `type` is one of the five values below, optionally | HR_LOSS_PREMULTIPLIED.  Per element, with prediction p, target g and
+ * the ray's weight w (1 where weight_dev is NULL):
+ *     d = p*w - g*w  (two fp32 products, one fp32 subtraction), dd/dp = w;
+ *     with HR_LOSS_PREMULTIPLIED (p and g already carry the weight, the reference's own call form): d = p - g, dd/dp = 1;
+ *   type                  term                                            d term / d d
+ *   HR_LOSS_MSE           d*d                                             2*d
+ *   HR_LOSS_WEIGHTED_MSE  w*d*d                                           2*w*d
+ *   HR_LOSS_MAE           |d|                                             sign(d), sign(0) = 0
+ *   HR_LOSS_WEIGHTED_MAE  w*|d|                                           w*sign(d)
+ *   HR_LOSS_HUBER         |d| < delta ? d*d/2 : delta*(|d| - delta/2)     |d| < delta ? d : delta*sign(d)       (nn.HuberLoss)
+ * The loss is the mean of the terms over all 3 * n_rays elements. */
+#define HR_LOSS_MSE 0
+#define HR_LOSS_WEIGHTED_MSE 1
+#define HR_LOSS_MAE 2
+#define HR_LOSS_WEIGHTED_MAE 3
+#define HR_LOSS_HUBER 4
+#define HR_LOSS_PREMULTIPLIED 0x100
+
+typedef struct hr_loss_out {
+    double loss_sum;            /* sum of the 3 * n_rays terms: fp32 terms, added in double */
+    double sse;                 /* sum of (pred - gt)^2 over the values as passed, without the weight: hr_image_scores.sse of the batch */
+    float loss;                 /* loss_sum / (3 * n_rays), formed in double and rounded once */
+    float pad;                  /* written as 0 */
+} hr_loss_out;
+
+/* bytes of workspace_dev that a call on n_rays rays needs; 0 for n_rays < 1 */
+size_t hr_image_loss_workspace(int64_t n_rays);
+
+/* pred_dev, gt_dev: (n_rays, 3) float32; weight_dev: (n_rays, 1) float32 or NULL (every weight 1) -> *out_dev (device memory) and, when
+ * d_pred_dev is not NULL, d_pred_dev (n_rays, 3) = d loss / d pred, times *upstream_dev (one float in device memory, read by the
+ * kernel: no host read of an upstream gradient; NULL: 1).  delta is read by HR_LOSS_HUBER only and must be > 0 there.  One pass over the
+ * three inputs.  The sums are added in a fixed order without atomics: calls on the same inputs give the same bits.  Every byte of
+ * *out_dev and of the workspace that is read is written first by the same call (nothing to clear between calls); no allocation, no
+ * synchronisation, capturable in a hipGraph.  n_rays < 1, an unknown type and a NULL pred / gt / out / workspace are HR_E_INVALID. */
+int hr_image_loss(const float* pred_dev, const float* gt_dev, const float* weight_dev, int64_t n_rays, int32_t type, float delta,
+                  const float* upstream_dev, hr_loss_out* out_dev, float* d_pred_dev, void* workspace_dev, void* stream);
+
 /* TensoRF regularisers of one (1, C, H, W) float32 plane (TVLoss, nlf/regularizers/tensorf.py:14-34; density_L1,
  * nlf/nets/tensorf_base.py:1024-1035), no model involved.  Forward ADDS to sums_dev[3] =
  *   { sum (x[:, 1:, :] - x[:, :-1, :])^2,  sum (x[:, :, 1:] - x[:, :, :-1])^2,  sum |x| };

@@ -2,12 +2,13 @@
 MSE image loss, backward, Adam) at the shipped batch size (conf/experiment/training/*.yaml: batch_size 16384) on the
 full-size synthetic scene of bench.py.
 
-    python tools/train_bench.py [--model donerf_sphere] [--batch 16384] [--steps 30] [--torch-gpu]
+    python tools/train_bench.py [--model donerf_sphere] [--batch 16384] [--steps 30] [--torch-gpu] [--hip-loss]
 
 Prints one JSON line: ms per step of the HIP training path (hr_train_features + HipLinear MFMA GEMMs + hr_train_forward /
 hr_train_backward) with the sample stage's forward and backward kernels timed on their own, and with --torch-gpu the
 same step of the PyTorch-ROCm restatement of the reference (oracle/torch_port.py, autograd over grid_sample / sort /
-cumprod) on the same GPU, weights and rays.  The oracle is only the comparator here, never the thing shipped.
+cumprod) on the same GPU, weights and rays.  The oracle is only the comparator here, never the thing shipped.  --hip-loss: the image loss of the
+step through hyperreel_amd.losses (hr_image_loss, weight 1) instead of the torch expression; the default stays the torch expression.
 """
 import argparse
 import json
@@ -45,7 +46,7 @@ def timed(fn, reps, warm=3, rounds=2):
     return best
 
 
-def train_step_figures(model_name='donerf_sphere', batch=16384, steps=30, torch_gpu=False, blas=True):
+def train_step_figures(model_name='donerf_sphere', batch=16384, steps=30, torch_gpu=False, blas=True, hip_loss=False):
     """ms per optimizer step of the HIP training path and of its parts (bench.py quotes this for its `train_step` key)"""
     import types
     args = types.SimpleNamespace(model=model_name, batch=batch, steps=steps, torch_gpu=torch_gpu)
@@ -66,9 +67,16 @@ def train_step_figures(model_name='donerf_sphere', batch=16384, steps=30, torch_
     from hyperreel_amd.optim import HipAdam
     opt = HipAdam(params, lr=1e-3, betas=(0.9, 0.99), eps=1e-8)              # the reference's Adam (utils/__init__.py:61-66) as one launch
 
+    if hip_loss:
+        from hyperreel_amd.losses import get_loss
+        loss_fn, weight = get_loss({'type': 'mse'}), torch.ones((args.batch, 1), device='cuda')
+        image_loss = lambda rgb: loss_fn.step_loss(rgb, target, weight)[0]
+    else:
+        image_loss = lambda rgb: ((rgb - target) ** 2).mean()
+
     def step():
         opt.zero_grad(set_to_none=True)
-        loss = ((model.forward_train(rays, white_bg=False) - target) ** 2).mean()
+        loss = image_loss(model.forward_train(rays, white_bg=False))
         loss.backward()
         opt.step()
 
@@ -80,7 +88,7 @@ def train_step_figures(model_name='donerf_sphere', batch=16384, steps=30, torch_
     def fwd_bwd():
         for p in params:
             p.grad = None
-        ((model.forward_train(rays, white_bg=False) - target) ** 2).mean().backward()
+        image_loss(model.forward_train(rays, white_bg=False)).backward()
 
     ms_fwd_bwd = timed(fwd_bwd, args.steps)
     # the sample stage alone
@@ -169,6 +177,8 @@ def train_step_figures(model_name='donerf_sphere', batch=16384, steps=30, torch_
         out['speedup_vs_torch_rocm_port'] = round(ms_ref / ms_step, 2)
     if not blas:
         out.pop('rocblas_ms_mlp_forward_backward')
+    if hip_loss:
+        out['image_loss'] = 'hr_image_loss'
     return out
 
 
@@ -178,8 +188,9 @@ def main():
     ap.add_argument('--batch', type=int, default=16384)
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--torch-gpu', action='store_true')
+    ap.add_argument('--hip-loss', action='store_true')
     args = ap.parse_args()
-    print(json.dumps(train_step_figures(args.model, args.batch, args.steps, args.torch_gpu)))
+    print(json.dumps(train_step_figures(args.model, args.batch, args.steps, args.torch_gpu, hip_loss=args.hip_loss)))
 
 
 if __name__ == '__main__':
