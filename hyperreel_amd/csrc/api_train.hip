@@ -31,9 +31,11 @@ int hr_linear_backward(const float* x_dev, int64_t ldx, const float* w_dev, cons
     if (rows < 0 || in < 1 || out < 1 || ldx < in || ld_dy < out || (dx_dev && ld_dx < in) || (y_dev && ldy < out))
         return fail(HR_E_INVALID, "bad Linear shape");
     if (rows > 0 && (!x_dev || !w_dev || !dy_dev || !dw_dev || !db_dev || !workspace_dev)) return fail(HR_E_INVALID, "null argument");
-    if (leaky_slope >= 0.0f && !y_dev) return fail(HR_E_INVALID, "an activated layer needs its output for the LeakyReLU mask");
+    // (an empty batch has an empty output: no mask to ask for -- the weight and bias gradients are zero)
+    if (rows > 0 && leaky_slope >= 0.0f && !y_dev) return fail(HR_E_INVALID, "an activated layer needs its output for the LeakyReLU mask");
     if (rows > 0x7fffffff) return fail(HR_E_INVALID, "more than 2^31 rows");
     if (rows == 0) {
+        if (!dw_dev || !db_dev) return fail(HR_E_INVALID, "null argument");
         HR_HIP(hipMemsetAsync(dw_dev, 0, sizeof(float) * (size_t)out * in, (hipStream_t)stream));
         HR_HIP(hipMemsetAsync(db_dev, 0, sizeof(float) * (size_t)out, (hipStream_t)stream));
         return HR_OK;

@@ -38,6 +38,8 @@ class TorchPort:
         self.dev = torch.device(device)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
         self.layers = [(t(w), t(b)) for w, b in o.layers]
+        # a cascade's point MLPs by stage index, kept on the object so that a gradient check can make them leaves
+        self.point_layers = {idx: [(t(w), t(b)) for w, b in pp['layers']] for idx, pp in getattr(o, '_pp', {}).items()}
         self.samples = t(o.samples) if hasattr(o, 'samples') else None      # voxel_grid keeps per-axis anchors instead
         self.aabb = t(o.aabb)
         self.inv_size = t(o.inv_size)
@@ -170,8 +172,7 @@ class TorchPort:
                 if point_head is not None:
                     h = point_head
                 else:
-                    layers = [(torch.from_numpy(w).to(self.dev), torch.from_numpy(b).to(self.dev)) for w, b in pp['layers']]
-                    h = self._run_layers(self._param_pe(inp, pp['cfg']['params']), layers, pp['skips'], pp['D'])
+                    h = self._run_layers(self._param_pe(inp, pp['cfg']['params']), self.point_layers[idx], pp['skips'], pp['D'])
                 h = h.view(B, -1, sum(pp['shapes']))
                 off = 0
                 for name, n, act in zip(pp['names'], pp['shapes'], pp['acts']):

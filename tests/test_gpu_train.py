@@ -31,6 +31,13 @@ def _reference_grads(g, rays, G, white):
     leaves['basis'] = port.basis.requires_grad_(True)
     for i, (w, b) in enumerate(port.layers):
         leaves[f'w{i}'], leaves[f'b{i}'] = w.requires_grad_(True), b.requires_grad_(True)
+    for idx in sorted(port.point_layers):                  # a cascade's point MLP: 'pw<i>' / 'pb<i>'
+        for i, (w, b) in enumerate(port.point_layers[idx]):
+            leaves[f'pw{i}'], leaves[f'pb{i}'] = w.requires_grad_(True), b.requires_grad_(True)
+    table = [k for k in g.state_dict if k.endswith('color_embedding')]
+    if table and port.o.ds.get('val_all', False):          # the per-camera colour table (ColorTransformEmbedding, dataset.val_all): 'table'
+        port.color_table = torch.from_numpy(np.ascontiguousarray(g.state_dict[table[0]], np.float32))
+        leaves['table'] = port.color_table.requires_grad_(True)
     r = torch.from_numpy(rays)
     rgb = port.color(port.embed(r), train=True, white_bg=bool(white))
     (rgb * torch.from_numpy(G)).sum().backward()
