@@ -10,10 +10,6 @@
 
 namespace {
 
-const int MAT_MODE[3][2] = {{0, 1}, {0, 2}, {1, 2}};   // tensorf_base.py:231
-const int VEC_MODE[3] = {2, 1, 0};                     // tensorf_base.py:232
-const int MAT_MODE_TIME0[3] = {2, 1, 0};               // tensorf_dynamic.py:48 (first index of each pair)
-
 // z_vals channels read per sample: z (z_plane, euclidean_distance_unified, voxel_grid), origin xyz + radius
 // (sphere/cylinder), origin xyz + resize xyz + raw offset + radius (sphere_new/cylinder_new)
 int isect_z_channels(int t)
@@ -191,9 +187,7 @@ static int create_level(const hr_config* cfg, bool coarse, hr_model** out)
     }
     const hr_config& c = m->cfg;
     {   // LDS of the sample kernel: 256/ZP rays x head rows x (live head columns + 4) + the decode matrices
-        int ZP = 8;
-        while (ZP < c.z_channels) ZP <<= 1;
-        const size_t rpb = 256 / ZP, nq = ((size_t)samples_per_row(c) * m->p_live + 3) / 4;
+        const size_t rpb = 256 / hr_round_zp(c.z_channels), nq = ((size_t)samples_per_row(c) * m->p_live + 3) / 4;
         size_t ca = 0;
         for (int j = 0; j < 3; ++j) ca += 4 * (size_t)((c.n_app[j] + 3) / 4);
         const size_t lds = 4 * (rpb * rows_per_ray(c) * (nq * 4 + 4) + rpb * 3 * ca + 256);
@@ -214,25 +208,18 @@ static int create_level(const hr_config* cfg, bool coarse, hr_model** out)
         *out = m;
         return HR_OK;
     }
-    int n_app_sum = 0;
+    HrGridPlane pl[3];                     // the extents hr_model_finalize packs by; the uploads carry every channel of the configuration
+    int ca_total = 0, n_app_sum = 0;
+    (void)hr_plane_geometry(c, pl, &ca_total, &n_app_sum);
     for (int j = 0; j < 3; ++j) {
-        const size_t hw = (size_t)c.grid[MAT_MODE[j][1]] * c.grid[MAT_MODE[j][0]];
         const char* kinds[2] = {"density", "app"};
         const int nch[2] = {c.n_den[j], c.n_app[j]};
         for (int t = 0; t < 2; ++t) {
-            if (c.video) {
-                snprintf(name, sizeof(name), "%s_plane_space.%d", kinds[t], j);
-                m->expect[name] = sizeof(float) * nch[t] * hw;
-                snprintf(name, sizeof(name), "%s_plane_time.%d", kinds[t], j);
-                m->expect[name] = sizeof(float) * (size_t)nch[t] * c.num_keyframes * c.grid[MAT_MODE_TIME0[j]];
-            } else {
-                snprintf(name, sizeof(name), "%s_plane.%d", kinds[t], j);
-                m->expect[name] = sizeof(float) * nch[t] * hw;
-                snprintf(name, sizeof(name), "%s_line.%d", kinds[t], j);
-                m->expect[name] = sizeof(float) * (size_t)nch[t] * c.grid[VEC_MODE[j]];
-            }
+            snprintf(name, sizeof(name), c.video ? "%s_plane_space.%d" : "%s_plane.%d", kinds[t], j);
+            m->expect[name] = sizeof(float) * (size_t)nch[t] * pl[j].ah * pl[j].aw;
+            snprintf(name, sizeof(name), c.video ? "%s_plane_time.%d" : "%s_line.%d", kinds[t], j);
+            m->expect[name] = sizeof(float) * (size_t)nch[t] * pl[j].bh * pl[j].bw;
         }
-        n_app_sum += c.n_app[j];
     }
     m->expect["basis_mat.weight"] = sizeof(float) * (size_t)c.app_dim * n_app_sum;
     if (c.color_table_views > 0) m->expect["color_embedding"] = sizeof(float) * (size_t)c.color_table_views * 12;
@@ -327,41 +314,13 @@ int hr_model_finalize(hr_model* m)
     }
 
     // ---- grids: channel-last texels, density | appearance interleaved per plane pair
-    int app_off = 0, real_off = 0;
+    const bool cols_ok = hr_plane_geometry(c, m->planes, &m->ca_total, &m->n_basis_cols);
     for (int j = 0; j < 3; ++j) {
         HrGridPlane& g = m->planes[j];
-        g = HrGridPlane();
         m->grid_a[j].reset();
         m->grid_b[j].reset();
-        int nd = c.n_den[j], na = c.n_app[j];
-        // tensorf_dynamic.py:310-311,355-356: a plane pair whose DENSITY plane has no
-        // components is skipped for density and appearance alike
-        if (c.video && nd == 0) na = 0;
-        g.cd4 = (nd + 3) / 4;
-        g.ca4 = (na + 3) / 4;
-        g.aw = c.grid[MAT_MODE[j][0]];
-        g.ah = c.grid[MAT_MODE[j][1]];
-        g.ax = MAT_MODE[j][0];
-        g.ay = MAT_MODE[j][1];
-        if (c.video) {
-            g.bw = c.grid[MAT_MODE_TIME0[j]];
-            g.bh = c.num_keyframes;
-            g.bx = MAT_MODE_TIME0[j];
-        } else {
-            g.bw = 1;
-            g.bh = c.grid[VEC_MODE[j]];
-            g.bx = VEC_MODE[j];
-        }
-        g.app_off = app_off;
-        g.app_real = na;
-        g.app_real_off = real_off;
-        app_off += 4 * g.ca4;
-        real_off += na;
-        const int half = (c.grid_dtype == HR_GRID_FP16);
-        int tex = 4 * (g.cd4 + g.ca4);
+        const int half = (c.grid_dtype == HR_GRID_FP16), tex = g.tex, nd = c.n_den[j], na = g.app_real;
         if (tex == 0) continue;
-        if (half) tex = (tex + 7) & ~7;               // whole 16-byte loads of 8 halfs
-        g.tex = tex;
         const size_t esz = half ? 2 : sizeof(float);
         const size_t a_bytes = esz * (size_t)g.aw * g.ah * tex;
         const size_t b_bytes = esz * (size_t)g.bw * g.bh * tex;
@@ -386,14 +345,11 @@ int hr_model_finalize(hr_model* m)
         g.b = m->grid_b[j];
         m->packed_bytes += (int64_t)(a_bytes + b_bytes);
     }
-    m->ca_total = app_off;
     // basis_mat columns follow the reference's torch.cat over the sampled planes.  For the
     // video net a skipped plane pair contributes no columns; its n_app must then be 0 too
     // (otherwise the reference itself fails with a shape error in basis_mat).
-    int n_app_sum = 0;
-    for (int j = 0; j < 3; ++j) n_app_sum += c.n_app[j];
-    if (real_off != n_app_sum) return fail(HR_E_INVALID, "video net: n_lamb_sh must be 0 wherever n_lamb_sigma is 0");
-    m->n_basis_cols = n_app_sum;
+    if (!cols_ok) return fail(HR_E_INVALID, "video net: n_lamb_sh must be 0 wherever n_lamb_sigma is 0");
+    const int n_app_sum = m->n_basis_cols;
     m->basis.reset();
     {
         const size_t bytes = m->raw["basis_mat.weight"].bytes;

@@ -232,16 +232,14 @@ static bool hr_launch_fused_t(const hr_config& cfg, const HrFusedArgs& fa, size_
 bool HR_FUSED_LAUNCH(const hr_config& cfg, const HrMlpArgs& ma, const HrSampleArgs& sa, int sample_waves, int frame_mode, int n_cus, bool probe,
                      hipStream_t stream)
 {
-    const int Z = cfg.z_channels;
-    int ZP = 8;
-    while (ZP < Z) ZP <<= 1;
+    const int Z = cfg.z_channels, ZP = hr_round_zp(Z);
     const int L = cfg.mlp_layers;
     if (cfg.mlp_hidden != 256 || L < 2) return false;
     if ((cfg.mlp_skip_mask >> (L - 1)) & 1) return false;                   // the input tile is gone by the last Linear
     if (sa.rows_per_ray != 1 || sa.rows_out) return false;                  // point_prediction cascades
     // the shipped decompositions [8, 4, 4] / [8, 0, 0], in either texel format: the class-specialised gathers (others: two-kernel path)
     const bool half = (cfg.grid_dtype == HR_GRID_FP16);
-    const int cls = hr_plane_class(sa.planes, 0, sa.ca_total);
+    const int cls = hr_plane_class(sa.planes, sa.ca_total, hr_plane_fits_gather);
     if (cls == 0) return false;
     HrFusedArgs fa;
     fa.m = ma;

@@ -99,6 +99,7 @@ struct HrMlpArgs {
 
 // ---------------------------------------------------------------- sample stage (sample_kernel.hip)
 #include "hr_grid.h"
+#include "hr_plan.h"
 
 struct HrSampleArgs {
     const hr_config* cfg_dev;   // device copy of the configuration: the sample kernel indexes it per lane (samples[k] ...), and a

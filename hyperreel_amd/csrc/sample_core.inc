@@ -572,20 +572,6 @@ struct HrPc844 {
     static constexpr int APP_OFF = (J == 0) ? 0 : ((J == 1) ? 8 : 12);   // first decode-matrix slot of this pair's appearance channels
 };
 
-// 1: [8, 4, 4] (all three plane pairs), 2: [8, 0, 0] (plane pair 0 only: the technicolor models), 0: anything else
-__host__ __device__ inline int hr_plane_class(const HrGridPlane* pl, int grid_fp16, int ca_total)
-{
-    (void)grid_fp16;                       // float16 texels have the same group structure (hr_gather_844h)
-    auto ok = [&](int j, int cd4, int off) {
-        return pl[j].cd4 == cd4 && pl[j].ca4 == cd4 && pl[j].tex == 8 * cd4 && pl[j].app_off == off && pl[j].aw >= 2 && pl[j].ah >= 2 &&
-               pl[j].bh >= 2 && (pl[j].bw == 1 || pl[j].bw >= 2);
-    };
-    if (!ok(0, 2, 0)) return 0;
-    if (ok(1, 1, 8) && ok(2, 1, 12) && ca_total == 16) return 1;
-    if (pl[1].cd4 + pl[1].ca4 == 0 && pl[2].cd4 + pl[2].ca4 == 0 && ca_total == 8) return 2;
-    return 0;
-}
-
 struct HrAxisTapsC {
     hr_axis_tap_c ax[3];        // x @ grid[0], y @ grid[1], z @ grid[2]
     hr_axis_tap_c t;            // keyframe axis (video)

@@ -22,10 +22,7 @@ struct HrSamplePlan {
 static HrSamplePlan hr_sample_plan(const hr_config& cfg, const HrSampleArgs& args)
 {
     HrSamplePlan P;
-    const int Z = cfg.z_channels;
-    int ZP = 8;
-    while (ZP < Z) ZP <<= 1;
-    P.zp = ZP;
+    const int ZP = P.zp = hr_round_zp(cfg.z_channels);
     const int RPB = 256 / ZP;
     P.blocks = (unsigned)((args.n_rays + RPB - 1) / RPB);
     P.lds = hr_sample_lds_bytes(args.nq, args.ca_total, ZP, args.rows_per_ray);
@@ -33,7 +30,7 @@ static HrSamplePlan hr_sample_plan(const hr_config& cfg, const HrSampleArgs& arg
     P.big_lds = P.lds > 64 * 1024;
     // the shipped [8, 4, 4] / [8, 0, 0] decompositions get the class-specialised gather of their texel format (sample_core.inc); ZP >= 8
     // keeps a quad inside one ray, video nets additionally need two keyframes
-    P.pclass = (args.rows_out == nullptr && (!cfg.video || cfg.num_keyframes >= 2)) ? hr_plane_class(args.planes, 0, args.ca_total) : 0;
+    P.pclass = (args.rows_out == nullptr && (!cfg.video || cfg.num_keyframes >= 2)) ? hr_plane_class(args.planes, args.ca_total, hr_plane_fits_gather) : 0;
     // every second factor a line (static nets; a keyframe net inside hr_render_frame): the gather compiled for two line taps
     P.all_lines = P.pclass != 0;
     for (int j = 0; j < 3; ++j)

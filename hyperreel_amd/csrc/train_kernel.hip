@@ -22,15 +22,13 @@
 // do not (rows, features, occupancy) are compiled once, in the default build.
 #ifdef HR_TRAIN_DET
 namespace hr_det {
+constexpr bool HR_TRAIN_DETERMINISTIC = true;
+#else
+constexpr bool HR_TRAIN_DETERMINISTIC = false;
 #endif
 #include "hr_train.h"
 
-// Phase A walks a ray serially and is bound by the latency of that walk (every sample's gather waits on its point), not by
-// issue slots: a batch of 16 384 rays in full wavefronts is ONE wavefront per CU with nothing to hide the latency behind.
-// HR_TRAIN_RPW rays per wavefront (the other lanes idle) gives every SIMD several wavefronts instead.
-#ifndef HR_TRAIN_RPW
-#define HR_TRAIN_RPW 16
-#endif
+// Phase A, one thread per ray, HR_TRAIN_RPW rays per wavefront (hr_plan.h)
 template <int ZP>
 __global__ __launch_bounds__(64) void hr_train_kernel(const hr_config* __restrict__ cfgp, const HrTrainArgs a)
 {
@@ -327,22 +325,16 @@ __global__ __launch_bounds__(256) void hr_train_lanes_kernel(const hr_config* __
 }
 
 template <int ZP>
-static void hr_launch_train_lanes(const hr_config& cfg, const HrTrainArgs& args, hipStream_t stream)
+static void hr_launch_train_lanes(const HrTrainPlan& P, const HrTrainArgs& args, hipStream_t stream)
 {
-    constexpr int RPB = 256 / ZP;
-    const unsigned blocks = (unsigned)((args.n_rays + RPB - 1) / RPB);
-    const size_t lds = sizeof(float) * RPB * 3 * args.ca_total;
-    const int pc = hr_plane_class(args.planes, 0, args.ca_total);
-    if (pc == 1 && !cfg.video) hipLaunchKernelGGL((hr_train_lanes_kernel<ZP, 2, 1>), dim3(blocks), dim3(256), lds, stream, args.cfg_dev, args);
-    else if (pc == 1) hipLaunchKernelGGL((hr_train_lanes_kernel<ZP, 4, 1>), dim3(blocks), dim3(256), lds, stream, args.cfg_dev, args);
-    else if (pc == 2) hipLaunchKernelGGL((hr_train_lanes_kernel<ZP, 4, 2>), dim3(blocks), dim3(256), lds, stream, args.cfg_dev, args);
-    else hipLaunchKernelGGL((hr_train_lanes_kernel<ZP, 4, 0>), dim3(blocks), dim3(256), lds, stream, args.cfg_dev, args);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(P.a_blocks), dim3(256), P.a_lds, stream, args.cfg_dev, args); };
+    if (P.a_pc == 1 && P.a_nb == 2) launch(hr_train_lanes_kernel<ZP, 2, 1>);
+    else if (P.a_pc == 1) launch(hr_train_lanes_kernel<ZP, 4, 1>);
+    else if (P.a_pc == 2) launch(hr_train_lanes_kernel<ZP, 4, 2>);
+    else launch(hr_train_lanes_kernel<ZP, 4, 0>);
 }
 
-// Phase B.  HR_TRAIN_LPS = 16 adjacent lanes per sample, one texel channel each (a plane pair has 8 or 16 channels per
-// texel in every shipped model), so that the atomics of one tap are one contiguous run; a workgroup is 16 such groups
-// and walks the samples of RPB whole rays (1 ray when it has 16 samples or more).
-#define HR_TRAIN_LPS 16
+// Phase B, HR_TRAIN_LPS = 16 lanes per sample (hr_plan.h).
 // rows of basis_mat: 3 (RGB) or 27 (SH: 3 colours x 9 basis functions)
 __device__ __forceinline__ int hr_train_basis_rows(const hr_config& c) { return c.shading == HR_SHADING_SH ? 27 : 3; }
 
@@ -400,9 +392,6 @@ __global__ __launch_bounds__(256, 4) void hr_train_gather_bwd_kernel(const hr_co
 }
 
 #ifndef HR_TRAIN_DET       // the class-specialised, LDS-windowed phase B: float accumulators (the deterministic build takes the generic kernel above)
-// rays per trip: four samples per 16-lane group between the barriers (the per-trip staging of the decode matrices, its barriers and
-// the fold into basis_mat's gradient are then a quarter; measured 1 / 2 / 4 / 8 samples: DoNeRF sample-stage backward 0.84 / 0.80 /
-// 0.78 / 0.77 ms, immersive 1.46 / 1.32 / 1.24 / 1.21, neural_3d 2.56 / 2.32 / 2.19 / 2.14 -- profiles/r03_c_train_experiments.txt)
 // ---- phase B of the shipped decompositions ([8, 4, 4]: PC = 1, [8, 0, 0]: PC = 2), taps on the tape.
 // The generic path (hr_sample_train_bwd_taps) walks the three plane pairs one after the other with 16 lanes each -- pairs 1 and 2
 // have 8 channels, so half the lanes idle twice -- and keeps three run-time plane descriptors live: ~200 uniform values against ~100
@@ -515,10 +504,6 @@ __device__ __forceinline__ void hr_bwd_class_sample(const hr_config& c, const Hr
     a.tape.dp[s] = dp[0]; a.tape.dp[NS + s] = dp[1]; a.tape.dp[2 * NS + s] = dp[2];
 }
 
-#ifndef HR_TRAIN_TRIP_MULT
-#define HR_TRAIN_TRIP_MULT 4
-#endif
-#define HR_TRAIN_LINES_RPB(ZP) (HR_TRAIN_TRIP_MULT * (((1024 / HR_TRAIN_LPS) + (ZP) - 1) / (ZP)))
 // Phase B with the contended part of the gradient in LDS.  Static nets (KEYED = false): the three lines, whole -- a few hundred
 // texels that every sample of the batch hits.  Keyframe nets (KEYED = true): the two rows of each time plane that the rays of
 // one keyframe interval blend between -- the batch's rays are walked in the order of tape.perm (grouped by that row,
@@ -678,32 +663,6 @@ __global__ __launch_bounds__(1024) void hr_train_bucket_kernel(const hr_config* 
     for (int64_t r = threadIdx.x; r < n; r += 1024) perm[atomicAdd(&cnt[hr_train_time_row(c, rays + r * c.ray_dim) + 1], 1)] = (int)r;
 }
 
-// LDS bytes of the windows of plane pairs `pairs`; keyed: two rows of each time plane, else the whole lines
-static size_t hr_train_window_bytes(const HrTrainArgs& args, unsigned pairs, bool keyed)
-{
-    size_t n = 0;
-    for (int j = 0; j < 3; ++j) {
-        const HrGridPlane& g = args.planes[j];
-        if (g.cd4 + g.ca4 == 0 || !((pairs >> j) & 1u)) continue;
-        n += sizeof(float) * (size_t)(keyed ? 2 * g.bw : g.bh) * g.tex;
-    }
-    return n;
-}
-
-// 1: the [8, 4, 4] decomposition, 2: [8, 0, 0] (what hr_bwd_class_sample is compiled for), 0: anything else
-static int hr_train_plane_class(const HrTrainArgs& a, const hr_config& cfg)
-{
-    const HrGridPlane* pl = a.planes;
-    auto ok = [&](int j, int cd4, int off) {
-        return pl[j].cd4 == cd4 && pl[j].ca4 == cd4 && pl[j].tex == 8 * cd4 && pl[j].app_off == off &&
-               (int64_t)pl[j].aw * pl[j].ah * pl[j].tex < (1ll << 30) && (int64_t)pl[j].bw * pl[j].bh * pl[j].tex < (1ll << 30);
-    };
-    if (!a.tape.taps || !a.tape.dp || a.n_rays * cfg.z_channels >= (1ll << 30) || !ok(0, 2, 0)) return 0;
-    if (ok(1, 1, 8) && ok(2, 1, 12) && a.ca_total == 16) return 1;
-    if (pl[1].cd4 + pl[1].ca4 == 0 && pl[2].cd4 + pl[2].ca4 == 0 && a.ca_total == 8) return 2;
-    return 0;
-}
-
 template <int ZP, bool KEYED>
 static void hr_launch_lines_kernel(int pc, unsigned blocks, size_t lds, hipStream_t stream, const HrTrainArgs& args, unsigned pairs, int add_dp)
 {
@@ -721,54 +680,25 @@ static bool hr_lines_opt_in(int pc, size_t lds)
     return hr_lds_opt_in(opt[pc], fn, lds);
 }
 
-#endif
+
+// the plan's lines kernel; false (nothing launched) when the runtime refuses its LDS request
 template <int ZP>
-static bool hr_launch_gather_bwd_lines(const hr_config& cfg, const HrTrainArgs& args, hipStream_t stream)
+static bool hr_launch_lines(const HrTrainPlan& P, const HrTrainArgs& args, hipStream_t stream)
 {
-#ifdef HR_TRAIN_DET      // the deterministic build: the global-atomics kernel for everything
-    (void)cfg; (void)args; (void)stream;
-    return false;
-#else
-    constexpr int RPB = HR_TRAIN_LINES_RPB(ZP);
-    const int pc = hr_train_plane_class(args, cfg);
-    bool any = false, keyed = false;
-    for (int j = 0; j < 3; ++j)
-        if (args.planes[j].cd4 + args.planes[j].ca4 > 0) { any = true; keyed = keyed || args.planes[j].bw != 1; }
-    if (!any) return false;
-    const size_t base = sizeof(float) * (2 * RPB * 3 * args.ca_total + 27 * args.n_basis_cols + 4 * RPB);
-    const size_t cap = 150 * 1024;
-    const int64_t iters = (args.n_rays + RPB - 1) / RPB;
-    const int cus = hr_current_device_cus();
-    const unsigned blocks = (unsigned)(iters < cus ? iters : cus);
-    if (!keyed) {
-        const size_t lds = base + hr_train_window_bytes(args, 7u, false);
-        if (lds > cap) return false;
-        if (!hr_lines_opt_in<ZP, false>(pc, lds)) return false;
-        hr_launch_lines_kernel<ZP, false>(pc, blocks, lds, stream, args, 7u, 0);
+    auto run = [&](auto keyed) {
+        constexpr bool KEYED = decltype(keyed)::value;
+        if (!hr_lines_opt_in<ZP, KEYED>(P.b_pc, P.lines_lds)) return false;
+        if (KEYED) hipLaunchKernelGGL(hr_train_bucket_kernel, dim3(1), dim3(1024), P.bucket_lds, stream, args.cfg_dev, args.rays, args.n_rays, args.tape.perm);
+        for (int p = 0; p < P.passes; ++p)
+            hr_launch_lines_kernel<ZP, KEYED>(P.b_pc, P.lines_blocks, P.pass_lds[p], stream, args, P.pass_pairs[p], P.pass_add_dp[p]);
         return true;
-    }
-    // keyframe net: needs the taps on the tape (two passes re-read them) and the grouped order; all pairs in one pass if their
-    // rows fit, else pair 0 (the wide one) and pairs 1 + 2
-    if (!args.tape.taps || !args.tape.dp || !args.tape.perm || args.n_rays > 0x7fffffff || !cfg.video || cfg.num_keyframes < 2 || cfg.num_keyframes > 8192) return false;
-    unsigned passes[2] = {7u, 0u};
-    if (base + hr_train_window_bytes(args, 7u, true) > cap) { passes[0] = 1u; passes[1] = 6u; }
-    size_t lds_max = 0;
-    for (int p = 0; p < 2; ++p) {
-        if (!passes[p]) continue;
-        const size_t lds = base + hr_train_window_bytes(args, passes[p], true);
-        if (lds > cap) return false;
-        lds_max = lds > lds_max ? lds : lds_max;
-    }
-    if (!hr_lines_opt_in<ZP, true>(pc, lds_max)) return false;
-    hipLaunchKernelGGL(hr_train_bucket_kernel, dim3(1), dim3(1024), sizeof(int) * (cfg.num_keyframes + 1), stream, args.cfg_dev, args.rays, args.n_rays, args.tape.perm);
-    for (int p = 0; p < 2; ++p) {
-        if (!passes[p]) continue;
-        const size_t lds = base + hr_train_window_bytes(args, passes[p], true);
-        hr_launch_lines_kernel<ZP, true>(pc, blocks, lds, stream, args, passes[p], p);
-    }
-    return true;
-#endif
+    };
+    return !P.keyed ? run(std::false_type()) : run(std::true_type());
 }
+#else      // the deterministic build has no lines kernel, and its plan never asks for one
+template <int ZP>
+static bool hr_launch_lines(const HrTrainPlan&, const HrTrainArgs&, hipStream_t) { return false; }
+#endif
 
 // Tail of phase B (taps path): one thread per sorted sample
 __global__ __launch_bounds__(256) void hr_train_point_bwd_kernel(const hr_config* __restrict__ cfgp, const HrTrainArgs a)
@@ -790,56 +720,29 @@ __global__ __launch_bounds__(256) void hr_train_dist_bwd_kernel(const hr_config*
     hr_sample_train_dist_bwd(c, a, s / c.z_channels, (int)(s % c.z_channels));
 }
 
-#ifdef HR_TRAIN_DET
+// hr_train_plan (hr_plan.h) decides, this launches.  What only the runtime knows stays here: the device's CU count, and whether it
+// grants the lines kernel's LDS request -- if not, phase B takes the plan's global-atomics kernel
 static void hr_launch_train_impl(const hr_config& cfg, const HrTrainArgs& args_in, hipStream_t stream)
-#else
-void hr_launch_train(const hr_config& cfg, const HrTrainArgs& args_in, hipStream_t stream)
-#endif
 {
     if (args_in.n_rays <= 0) return;
-    int ZP = 8;
-    while (ZP < cfg.z_channels) ZP <<= 1;
     HrTrainArgs args = args_in;
-    if (ZP > 64) { args.tape.taps = nullptr; args.tape.dp = nullptr; }     // the one-thread-per-ray phase A leaves no taps
-    const unsigned blocks = (unsigned)((args.n_rays + HR_TRAIN_RPW - 1) / HR_TRAIN_RPW);
-    switch (ZP) {                                  // phase A: a lane per sample where a ray fits one wavefront
-        case 8: hr_launch_train_lanes<8>(cfg, args, stream); break;
-        case 16: hr_launch_train_lanes<16>(cfg, args, stream); break;
-        case 32: hr_launch_train_lanes<32>(cfg, args, stream); break;
-        case 64: hr_launch_train_lanes<64>(cfg, args, stream); break;
-        case 128: hipLaunchKernelGGL(hr_train_kernel<128>, dim3(blocks), dim3(64), 0, stream, args.cfg_dev, args); break;
-        case 256: hipLaunchKernelGGL(hr_train_kernel<256>, dim3(blocks), dim3(64), 0, stream, args.cfg_dev, args); break;
-        default: break;
-    }
-    if (!args.d_rgb) return;
-    bool done = false;
-    switch (ZP) {
-        case 8: done = hr_launch_gather_bwd_lines<8>(cfg, args, stream); break;
-        case 16: done = hr_launch_gather_bwd_lines<16>(cfg, args, stream); break;
-        case 32: done = hr_launch_gather_bwd_lines<32>(cfg, args, stream); break;
-        case 64: done = hr_launch_gather_bwd_lines<64>(cfg, args, stream); break;
-        case 128: done = hr_launch_gather_bwd_lines<128>(cfg, args, stream); break;
-        case 256: done = hr_launch_gather_bwd_lines<256>(cfg, args, stream); break;
-        default: break;
-    }
-    const int GROUPS = 256 / HR_TRAIN_LPS;
-    const int RPB = (ZP >= GROUPS) ? 1 : GROUPS / ZP;
-    const int64_t nblocks = (args.n_rays + RPB - 1) / RPB;
-    const int64_t resident = 16 * (int64_t)hr_current_device_cus();          // four 256-thread workgroups per CU are resident (128 registers); four rounds of them: the blocks differ in cost
-    const unsigned bblocks = (unsigned)(nblocks < resident ? nblocks : resident);
-    const size_t lds = sizeof(float) * (RPB * 3 * args.ca_total) + sizeof(hr_acc_t) * (RPB * 3 * args.ca_total + 27 * args.n_basis_cols);
-    if (!done) switch (ZP) {
-        case 8: hipLaunchKernelGGL(hr_train_gather_bwd_kernel<8>, dim3(bblocks), dim3(256), lds, stream, args.cfg_dev, args); break;
-        case 16: hipLaunchKernelGGL(hr_train_gather_bwd_kernel<16>, dim3(bblocks), dim3(256), lds, stream, args.cfg_dev, args); break;
-        case 32: hipLaunchKernelGGL(hr_train_gather_bwd_kernel<32>, dim3(bblocks), dim3(256), lds, stream, args.cfg_dev, args); break;
-        case 64: hipLaunchKernelGGL(hr_train_gather_bwd_kernel<64>, dim3(bblocks), dim3(256), lds, stream, args.cfg_dev, args); break;
-        case 128: hipLaunchKernelGGL(hr_train_gather_bwd_kernel<128>, dim3(bblocks), dim3(256), lds, stream, args.cfg_dev, args); break;
-        case 256: hipLaunchKernelGGL(hr_train_gather_bwd_kernel<256>, dim3(bblocks), dim3(256), lds, stream, args.cfg_dev, args); break;
-        default: break;
-    }
-    const int64_t ns = args.n_rays * cfg.z_channels;
-    if (args.tape.taps) hipLaunchKernelGGL(hr_train_point_bwd_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, stream, args.cfg_dev, args);
-    hipLaunchKernelGGL(hr_train_dist_bwd_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, stream, args.cfg_dev, args);
+    const HrTrainPlanIn in = {args.n_rays, args.d_rgb != nullptr, args.tape.taps != nullptr, args.tape.dp != nullptr, args.tape.perm != nullptr,
+                              HR_TRAIN_DETERMINISTIC, sizeof(hr_acc_t), hr_current_device_cus()};
+    const HrTrainPlan P = hr_train_plan(cfg, args.planes, args.ca_total, args.n_basis_cols, in);
+    if (P.thread_per_ray) { args.tape.taps = nullptr; args.tape.dp = nullptr; }     // the one-thread-per-ray phase A leaves no taps
+    hr_with_zp(P.zp, [&](auto zp) {                  // phase A
+        constexpr int ZP = decltype(zp)::value;
+        if constexpr (ZP <= 64) hr_launch_train_lanes<ZP>(P, args, stream);
+        else hipLaunchKernelGGL(hr_train_kernel<ZP>, dim3(P.a_blocks), dim3(64), 0, stream, args.cfg_dev, args);
+    });
+    if (!P.backward) return;
+    bool done = false;                                // phase B
+    if (P.lines) hr_with_zp(P.zp, [&](auto zp) { done = hr_launch_lines<decltype(zp)::value>(P, args, stream); });
+    if (!done) hr_with_zp(P.zp, [&](auto zp) {
+        hipLaunchKernelGGL(hr_train_gather_bwd_kernel<decltype(zp)::value>, dim3(P.atomics_blocks), dim3(256), P.atomics_lds, stream, args.cfg_dev, args);
+    });
+    if (P.taps) hipLaunchKernelGGL(hr_train_point_bwd_kernel, dim3(P.tail_blocks), dim3(256), 0, stream, args.cfg_dev, args);
+    hipLaunchKernelGGL(hr_train_dist_bwd_kernel, dim3(P.tail_blocks), dim3(256), 0, stream, args.cfg_dev, args);
 }
 
 #ifdef HR_TRAIN_DET
@@ -884,6 +787,8 @@ void hr_launch_train_det(const hr_config& cfg, const void* args_flt, size_t args
     hr_det::hr_launch_train_impl(cfg, a, stream);
 }
 #else
+void hr_launch_train(const hr_config& cfg, const HrTrainArgs& args, hipStream_t stream) { hr_launch_train_impl(cfg, args, stream); }
+
 // Coarse level of a point_prediction cascade (hr_ray_rows ... in hr_train.h): rows forward per ray, then per sample the
 // point backward and the intersection backward.  Elementwise work, no gather.
 template <int ZP>
@@ -906,18 +811,10 @@ __global__ __launch_bounds__(256) void hr_rows_bwd_kernel(const hr_config* __res
 void hr_launch_rows(const hr_config& cfg, const HrRowsArgs& args, hipStream_t stream)
 {
     if (args.n_rays <= 0) return;
-    int ZP = 8;
-    while (ZP < cfg.z_channels) ZP <<= 1;
     const unsigned blocks = (unsigned)((args.n_rays + 63) / 64);
-    switch (ZP) {
-        case 8: hipLaunchKernelGGL(hr_rows_kernel<8>, dim3(blocks), dim3(64), 0, stream, args.cfg_dev, args); break;
-        case 16: hipLaunchKernelGGL(hr_rows_kernel<16>, dim3(blocks), dim3(64), 0, stream, args.cfg_dev, args); break;
-        case 32: hipLaunchKernelGGL(hr_rows_kernel<32>, dim3(blocks), dim3(64), 0, stream, args.cfg_dev, args); break;
-        case 64: hipLaunchKernelGGL(hr_rows_kernel<64>, dim3(blocks), dim3(64), 0, stream, args.cfg_dev, args); break;
-        case 128: hipLaunchKernelGGL(hr_rows_kernel<128>, dim3(blocks), dim3(64), 0, stream, args.cfg_dev, args); break;
-        case 256: hipLaunchKernelGGL(hr_rows_kernel<256>, dim3(blocks), dim3(64), 0, stream, args.cfg_dev, args); break;
-        default: break;
-    }
+    hr_with_zp(hr_round_zp(cfg.z_channels), [&](auto zp) {
+        hipLaunchKernelGGL(hr_rows_kernel<decltype(zp)::value>, dim3(blocks), dim3(64), 0, stream, args.cfg_dev, args);
+    });
     if (!args.d_rows) return;
     const int64_t ns = args.n_rays * cfg.z_channels;
     const unsigned sb = (unsigned)((ns + 255) / 256);

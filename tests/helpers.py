@@ -1,4 +1,6 @@
 """Shared test plumbing: golden fixtures -> (cfg, dataset scalars, regenerated weights, rays, expected)."""
+import ctypes
+import functools
 import glob
 import json
 import os
@@ -155,10 +157,50 @@ def port_leaves(port):
     return out
 
 
+class GridPlane(ctypes.Structure):          # mirrors HrGridPlane (hyperreel_amd/csrc/hr_grid.h)
+    _fields_ = [('a', ctypes.c_void_p), ('b', ctypes.c_void_p)] + [(k, ctypes.c_int) for k in
+                ('tex', 'aw', 'ah', 'bw', 'bh', 'cd4', 'ca4', 'ax', 'ay', 'bx', 'app_off', 'app_real', 'app_real_off')]
+
+
+class TrainPlan(ctypes.Structure):          # mirrors HrTrainPlan (hyperreel_amd/csrc/hr_plan.h)
+    _fields_ = [(k, ctypes.c_int) for k in ('zp', 'thread_per_ray', 'rays_per_group', 'a_pc', 'a_nb')] + [('a_blocks', ctypes.c_uint), ('a_lds', ctypes.c_size_t)] + \
+               [(k, ctypes.c_int) for k in ('backward', 'taps', 'lines', 'keyed', 'b_pc', 'passes')] + \
+               [('pass_pairs', ctypes.c_uint * 2), ('pass_add_dp', ctypes.c_int * 2), ('pass_lds', ctypes.c_size_t * 2), ('lines_lds', ctypes.c_size_t),
+                ('lines_blocks', ctypes.c_uint), ('bucket_lds', ctypes.c_size_t), ('atomics_rpb', ctypes.c_int), ('atomics_blocks', ctypes.c_uint),
+                ('atomics_lds', ctypes.c_size_t), ('tail_blocks', ctypes.c_uint)]
+
+
+PLANE_CLASS = ['generic', '8,4,4', '8,0,0']          # hr_plane_class
+
+
+@functools.lru_cache(maxsize=None)
+def plan_lib():
+    """Host build of hyperreel_amd/csrc/hr_plan.h (tests/host_math/hr_plan_host.cpp): the library's own geometry and dispatch decisions."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    src = os.path.join(here, 'host_math', 'hr_plan_host.cpp')
+    deps = [src, os.path.join(here, '..', 'include', 'hyperreel_hip.h')] + [os.path.join(here, '..', 'hyperreel_amd', 'csrc', f) for f in ('hr_plan.h', 'hr_grid.h')]
+    lib = ctypes.CDLL(build_host_lib(os.path.join(here, 'host_math', '_build', 'libhr_plan_host.so'), src, deps))
+    assert lib.hp_sizeof_plane() == ctypes.sizeof(GridPlane) and lib.hp_sizeof_plan() == ctypes.sizeof(TrainPlan)
+    return lib
+
+
+def plane_geometry(hc):
+    """hr_plane_geometry of a compiled config: (HrGridPlane[3] without texel pointers, ca_total, n_basis_cols, consistent)."""
+    planes, ca, nb = (GridPlane * 3)(), ctypes.c_int(), ctypes.c_int()
+    ok = plan_lib().hp_plane_geometry(ctypes.byref(hc), planes, ctypes.byref(ca), ctypes.byref(nb))
+    return planes, ca.value, nb.value, bool(ok)
+
+
+def train_plan(hc, n_rays=96, deterministic=False):
+    """hr_train_plan for a backward step of n_rays rays on a model of `hc` whose tape has taps (what hr_train_backward provides)."""
+    out = TrainPlan()
+    plan_lib().hp_train_plan(ctypes.byref(hc), ctypes.c_longlong(n_rays), int(bool(deterministic)), ctypes.byref(out))
+    return out
+
+
 def train_branch(hc, n_rays=96, deterministic=False):
-    """The kernels hr_launch_train (csrc/train_kernel.hip) picks for a compiled config -- for a cascade, its fine level --, from the
-    quantities it dispatches on: the plane geometry hr_model_finalize derives from hr_config (api_model.hip), hr_plane_class
-    (sample_core.inc), hr_train_plane_class and the LDS budget of hr_launch_gather_bwd_lines.  Returns a dict:
+    """The kernels hr_launch_train (csrc/train_kernel.hip) picks for a compiled config -- for a cascade, its fine level --: what the
+    library's own hr_train_plan (csrc/hr_plan.h, compiled for the host) answers, as a dict:
       zp               z_channels rounded up to a power of two (8 ... 256)
       thread_per_ray   phase A is hr_train_kernel<zp> (zp > 64: no taps on the tape), else hr_train_lanes_kernel<zp, nb, pc>
       rays_per_group   rays of one phase-A workgroup (lanes) or wavefront (thread per ray)
@@ -166,60 +208,14 @@ def train_branch(hc, n_rays=96, deterministic=False):
       nb               the lanes kernel's NB (2: compiled for static nets only)
       video, keyed     keyframe net; phase B keeps two time-plane rows per pair (KEYED) instead of whole lines
       phase_b          'lines' (hr_train_gather_bwd_lines_kernel, window in LDS) | 'atomics' (hr_train_gather_bwd_kernel)
-      phase_b_class    PC of the lines kernel (hr_train_plane_class: 'generic' without taps)
+      phase_b_class    PC of the lines kernel ('generic' without taps)
       passes           lines kernel launches (2: pair 0, then pairs 1 + 2); 0 with 'atomics'
       lds_bytes        the largest dynamic LDS request of the lines kernel considered (cap: 150 KiB)
     The lines path also needs the runtime to grant the LDS request (hr_lds_opt_in), which a gfx950 workgroup's 160 KiB always does."""
-    MAT, VEC = [(0, 1), (0, 2), (1, 2)], [2, 1, 0]
-    zp = 8
-    while zp < hc.z_channels:
-        zp <<= 1
-    video = bool(hc.video)
-    pl, app_off = [], 0
-    for j in range(3):
-        nd, na = int(hc.n_den[j]), int(hc.n_app[j])
-        if video and nd == 0:
-            na = 0
-        cd4, ca4 = (nd + 3) // 4, (na + 3) // 4
-        bw, bh = (int(hc.grid[VEC[j]]), int(hc.num_keyframes)) if video else (1, int(hc.grid[VEC[j]]))
-        pl.append(dict(cd4=cd4, ca4=ca4, tex=4 * (cd4 + ca4), app_off=app_off, aw=int(hc.grid[MAT[j][0]]), ah=int(hc.grid[MAT[j][1]]), bw=bw, bh=bh))
-        app_off += 4 * ca4
-    ca_total, n_basis_cols = app_off, sum(int(v) for v in hc.n_app)
-
-    def plane_class(fits):
-        ok = lambda j, cd4, off: pl[j]['cd4'] == cd4 and pl[j]['ca4'] == cd4 and pl[j]['tex'] == 8 * cd4 and pl[j]['app_off'] == off and fits(pl[j])
-        if not ok(0, 2, 0):
-            return 'generic'
-        if ok(1, 1, 8) and ok(2, 1, 12) and ca_total == 16:
-            return '8,4,4'
-        if pl[1]['tex'] == 0 and pl[2]['tex'] == 0 and ca_total == 8:
-            return '8,0,0'
-        return 'generic'
-    pc_a = plane_class(lambda p: p['aw'] >= 2 and p['ah'] >= 2 and p['bh'] >= 2 and (p['bw'] == 1 or p['bw'] >= 2))
-    taps = zp <= 64
-    pc_b = 'generic'
-    if taps and n_rays * hc.z_channels < (1 << 30):
-        pc_b = plane_class(lambda p: p['aw'] * p['ah'] * p['tex'] < (1 << 30) and p['bw'] * p['bh'] * p['tex'] < (1 << 30))
-    used = [p for p in pl if p['tex'] > 0]
-    keyed = any(p['bw'] != 1 for p in used)
-    rpb = 4 * ((64 + zp - 1) // zp)                                    # HR_TRAIN_LINES_RPB
-    base = 4 * (2 * rpb * 3 * ca_total + 27 * n_basis_cols + 4 * rpb)
-    window = lambda pairs: sum(4 * (2 * p['bw'] if keyed else p['bh']) * p['tex'] for j, p in enumerate(pl) if p['tex'] > 0 and (pairs >> j) & 1)
-    cap = 150 * 1024
-    phase_b, passes, lds = 'atomics', 0, base + window(7)
-    if deterministic or not used:
-        pass
-    elif not keyed:
-        if lds <= cap:
-            phase_b, passes = 'lines', 1
-    elif taps and video and 2 <= hc.num_keyframes <= 8192:
-        split = [7] if lds <= cap else [1, 6]
-        lds = max(base + window(p) for p in split)
-        if lds <= cap:
-            phase_b, passes = 'lines', len(split)
-    return dict(zp=zp, thread_per_ray=zp > 64, rays_per_group=16 if zp > 64 else 256 // zp, plane_class=pc_a,
-                nb=2 if (pc_a == '8,4,4' and not video) else 4, video=video, keyed=keyed, phase_b=phase_b, phase_b_class=pc_b,
-                passes=passes, lds_bytes=lds)
+    p = train_plan(hc, n_rays, deterministic)
+    return dict(zp=p.zp, thread_per_ray=bool(p.thread_per_ray), rays_per_group=p.rays_per_group, plane_class=PLANE_CLASS[p.a_pc], nb=p.a_nb,
+                video=bool(hc.video), keyed=bool(p.keyed), phase_b='lines' if p.lines else 'atomics', phase_b_class=PLANE_CLASS[p.b_pc],
+                passes=p.passes, lds_bytes=p.lines_lds)
 
 
 def build_host_lib(out, src, deps):

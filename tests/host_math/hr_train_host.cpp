@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "../../hyperreel_amd/csrc/hr_mask.h"
+#include "../../hyperreel_amd/csrc/hr_plan.h"
 #include "../../hyperreel_amd/csrc/hr_train.h"
 
 extern "C" {
@@ -31,18 +32,9 @@ int ht_train(const hr_config* c, const float* rays, const float* head, long long
     std::vector<int> src(NS);
     a.tape.ds = ds.data(); a.tape.src = src.data(); a.tape.dfeat = dfeat.data(); a.tape.dpre = dpre.data();
     a.tape.ddc = ddc.data(); a.tape.dts = dts.data();
-    int ZP = 8;
-    while (ZP < c->z_channels) ZP <<= 1;
-    for (long long i = 0; i < n; ++i) {
-        switch (ZP) {
-            case 8: hr_ray_train<8>(*c, a, i); break;
-            case 16: hr_ray_train<16>(*c, a, i); break;
-            case 32: hr_ray_train<32>(*c, a, i); break;
-            case 64: hr_ray_train<64>(*c, a, i); break;
-            case 128: hr_ray_train<128>(*c, a, i); break;
-            default: hr_ray_train<256>(*c, a, i); break;
-        }
-    }
+    hr_with_zp(hr_round_zp(c->z_channels), [&](auto zp) {
+        for (long long i = 0; i < n; ++i) hr_ray_train<decltype(zp)::value>(*c, a, i);
+    });
     if (!d_rgb) return 0;
     for (long long i = 0; i < n; ++i) {                     // phase B, the way a workgroup of the device does it per ray
         const float* r = rays + (size_t)i * c->ray_dim;
@@ -87,18 +79,9 @@ int ht_rows(const hr_config* c, const float* rays, const float* head, long long 
     std::vector<float> ds(NS), dts(NS);
     std::vector<int> src(NS);
     a.tape.ds = ds.data(); a.tape.src = src.data(); a.tape.dts = dts.data();
-    int ZP = 8;
-    while (ZP < c->z_channels) ZP <<= 1;
-    for (long long i = 0; i < n; ++i) {
-        switch (ZP) {
-            case 8: hr_ray_rows<8>(*c, a, i); break;
-            case 16: hr_ray_rows<16>(*c, a, i); break;
-            case 32: hr_ray_rows<32>(*c, a, i); break;
-            case 64: hr_ray_rows<64>(*c, a, i); break;
-            case 128: hr_ray_rows<128>(*c, a, i); break;
-            default: hr_ray_rows<256>(*c, a, i); break;
-        }
-    }
+    hr_with_zp(hr_round_zp(c->z_channels), [&](auto zp) {
+        for (long long i = 0; i < n; ++i) hr_ray_rows<decltype(zp)::value>(*c, a, i);
+    });
     if (!d_rows) return 0;
     for (long long i = 0; i < n; ++i)
         for (int k = 0; k < c->z_channels; ++k) hr_sample_rows_bwd(*c, a, i, k);

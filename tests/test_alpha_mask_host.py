@@ -11,7 +11,8 @@ import torch
 
 from hyperreel_amd import config as cfgmod
 from hyperreel_amd import plan, scenes
-from test_train_host import GridPlane, ht  # noqa: F401  (the host library fixture and the plane descriptor)
+from helpers import plane_geometry
+from test_train_host import ht  # noqa: F401  (the host library fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FP = C.POINTER(C.c_float)
@@ -31,18 +32,17 @@ def load(case):
     return z, r, cfg, ds, sd
 
 
-def pack(sd, video, names=None):
-    """Packed density texels of the three plane pairs (appearance is not read by the mask)."""
+def pack(sd, hc):
+    """Packed texels of the three plane pairs, the descriptors from hr_plane_geometry (csrc/hr_plan.h); the appearance channels stay zero
+    (the mask does not read them)."""
     NET = 'model.color_model.net.'
-    a_name, b_name = ('density_plane_space', 'density_plane_time') if video else ('density_plane', 'density_line')
-    planes, keep = (GridPlane * 3)(), []
+    a_name, b_name = ('density_plane_space', 'density_plane_time') if hc.video else ('density_plane', 'density_line')
+    planes, keep = plane_geometry(hc)[0], []
     for j in range(3):
         da, db = np.asarray(sd[f'{NET}{a_name}.{j}'], np.float32)[0], np.asarray(sd[f'{NET}{b_name}.{j}'], np.float32)[0]
         g = planes[j]
         nd = da.shape[0]
-        g.cd4, g.ca4 = (nd + 3) // 4, 0
-        g.ah, g.aw, g.bh, g.bw = da.shape[1], da.shape[2], db.shape[1], db.shape[2]
-        g.tex = 4 * g.cd4
+        assert (g.ah, g.aw, g.bh, g.bw) == (da.shape[1], da.shape[2], db.shape[1], db.shape[2])
         pa = np.zeros((g.ah, g.aw, max(g.tex, 1)), np.float32)
         pb = np.zeros((g.bh, g.bw, max(g.tex, 1)), np.float32)
         pa[..., :nd], pb[..., :nd] = da.transpose(1, 2, 0), db.transpose(1, 2, 0)
@@ -69,10 +69,9 @@ def dense_alpha(ht, hc, planes, n, num_frames, prev=None, prev_aabb=None):
 def test_dense_alpha_update_and_shrink_match_the_reference(ht, case):
     from hyperreel_amd.models import HipLightfieldModel
     z, r, cfg, ds, sd = load(case)
-    video = cfg.color.net.type == 'tensor_vm_split_time'
     F = int(ds['num_frames'])
     hc = plan.compile_config(cfg, ds, r['grid'])
-    planes, keep = pack(sd, video)
+    planes, keep = pack(sd, hc)
     # 1. getDenseAlpha without a mask
     a1 = dense_alpha(ht, hc, planes, r['n1'], F)
     assert np.abs(a1 - z['alpha1']).max() <= 2e-7 and z['alpha1'].max() > 1e-3
@@ -96,7 +95,7 @@ def test_dense_alpha_update_and_shrink_match_the_reference(ht, case):
     # 3. getDenseAlpha again on the shrunk grid: the mask now rejects points (compute_alpha, tensorf_base.py:491-503)
     sd2 = {'model.color_model.net.' + k: v.numpy() for k, v in own.items()}
     hc2 = m._compile(m.grid_size)[1]
-    planes2, keep2 = pack(sd2, video)
+    planes2, keep2 = pack(sd2, hc2)
     a2 = dense_alpha(ht, hc2, planes2, r['n2'], F, prev=net.alpha_volume.numpy(), prev_aabb=net.alpha_aabb.numpy())
     assert np.abs(a2 - z['alpha2']).max() <= 2e-7
     assert ((a2 > 0) == (z['alpha2'] > 0)).all()

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import Golden, build_host_lib, trainable_sweep_cases
+from helpers import Golden, GridPlane, build_host_lib, plane_geometry, trainable_sweep_cases
 from hyperreel_amd import plan
 from torch_port import TorchPort
 
@@ -20,17 +20,11 @@ OUT = os.path.join(HERE, 'host_math', '_build', 'libhr_train_host.so')
 CSRC = os.path.join(HERE, '..', 'hyperreel_amd', 'csrc')
 
 FP = C.POINTER(C.c_float)
-MAT, VEC = [(0, 1), (0, 2), (1, 2)], [2, 1, 0]
-
-
-class GridPlane(C.Structure):          # mirrors HrGridPlane (hyperreel_amd/csrc/hr_grid.h)
-    _fields_ = [('a', C.c_void_p), ('b', C.c_void_p)] + [(k, C.c_int) for k in
-                ('tex', 'aw', 'ah', 'bw', 'bh', 'cd4', 'ca4', 'ax', 'ay', 'bx', 'app_off', 'app_real', 'app_real_off')]
 
 
 @pytest.fixture(scope='module')
 def ht():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ('hr_train.h', 'hr_mask.h', 'hr_math.h', 'hr_grid.h')] + [os.path.join(HERE, '..', 'include', 'hyperreel_hip.h')]
+    deps = [SRC] + [os.path.join(CSRC, f) for f in ('hr_train.h', 'hr_mask.h', 'hr_math.h', 'hr_grid.h', 'hr_plan.h')] + [os.path.join(HERE, '..', 'include', 'hyperreel_hip.h')]
     build_host_lib(OUT, SRC, deps)
     lib = C.CDLL(OUT)
     lib.ht_unsupported.restype = C.c_char_p
@@ -38,22 +32,17 @@ def ht():
     return lib
 
 
-def pack_grids(port, video):
-    """Texel layout of hr_model_finalize (api_model.hip): [H][W][4*cd4 density | 4*ca4 appearance] per plane pair."""
-    planes, packed, app_off, real_off = (GridPlane * 3)(), [], 0, 0
+def pack_grids(port, hc):
+    """Texel layout of hr_model_finalize (api_model.hip): [H][W][4*cd4 density | 4*ca4 appearance] per plane pair, the descriptors from the
+    library's own hr_plane_geometry (csrc/hr_plan.h)."""
+    planes, ca_total, _, ok = plane_geometry(hc)
+    assert ok
+    packed = []
     for j in range(3):
         da, db, aa, ab = [t.detach().numpy()[0] for t in (port.d_a[j], port.d_b[j], port.a_a[j], port.a_b[j])]
-        nd, na = da.shape[0], aa.shape[0]
-        if video and nd == 0:
-            na = 0
         g = planes[j]
-        g.cd4, g.ca4 = (nd + 3) // 4, (na + 3) // 4
-        g.ah, g.aw = da.shape[1], da.shape[2]
-        g.bh, g.bw = db.shape[1], db.shape[2]
-        g.app_off, g.app_real, g.app_real_off = app_off, na, real_off
-        app_off += 4 * g.ca4
-        real_off += na
-        g.tex = 4 * (g.cd4 + g.ca4)
+        nd, na = da.shape[0], g.app_real
+        assert (g.ah, g.aw, g.bh, g.bw) == (da.shape[1], da.shape[2], db.shape[1], db.shape[2])
         pa = np.zeros((g.ah, g.aw, max(g.tex, 1)), np.float32)
         pb = np.zeros((g.bh, g.bw, max(g.tex, 1)), np.float32)
         pa[..., :nd] = da.transpose(1, 2, 0)
@@ -62,7 +51,7 @@ def pack_grids(port, video):
         pb[..., 4 * g.cd4:4 * g.cd4 + na] = ab[:na].transpose(1, 2, 0)
         g.a, g.b = pa.ctypes.data, pb.ctypes.data
         packed.append((pa, pb, nd, na, 4 * g.cd4))
-    return planes, packed, app_off
+    return planes, packed, ca_total
 
 
 # the five benchmark families, then every shipped model YAML (and variant) the training path accepts: z-plane / sphere /
@@ -131,7 +120,7 @@ def test_backward_matches_autograd(ht, case, white):
         head0, head, rgb_ref, G = reference(rays)
         assert bool(torch.isfinite(head.grad).all())
 
-    planes, packed, ca_total = pack_grids(port, port.o.video)
+    planes, packed, ca_total = pack_grids(port, hc)
     gbuf = [(np.zeros_like(pa), np.zeros_like(pb)) for pa, pb, *_ in packed]
     g_a = (FP * 3)(*[b[0].ctypes.data_as(FP) for b in gbuf])
     g_b = (FP * 3)(*[b[1].ctypes.data_as(FP) for b in gbuf])
@@ -262,7 +251,7 @@ def test_backward_at_other_sample_counts(ht, model, z):
     rgb_ref = port.color(port.embed(rays, head=head), train=True, white_bg=True)
     G = torch.randn(rgb_ref.shape, generator=torch.Generator().manual_seed(1))
     (rgb_ref * G).sum().backward()
-    planes, packed, ca_total = pack_grids(port, port.o.video)
+    planes, packed, ca_total = pack_grids(port, hc)
     gbuf = [(np.zeros_like(pa), np.zeros_like(pb)) for pa, pb, *_ in packed]
     g_a = (FP * 3)(*[b[0].ctypes.data_as(FP) for b in gbuf])
     g_b = (FP * 3)(*[b[1].ctypes.data_as(FP) for b in gbuf])

@@ -8,8 +8,9 @@ compiler fold the branches, and counts the instructions between phase markers (`
 HR_SPH hooks of sample_core.inc under -DHR_PHASE_MARK).  Counts are per wavefront pass = per sample slot."""
 import collections, ctypes, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
 from hyperreel_amd import build as B, config as C, plan
+from helpers import plan_lib, plane_geometry
 
 
 def emit(obj, path, out):
@@ -57,24 +58,12 @@ def main():
     lines = []
     emit(hc, 'c', lines)
     Z = hc.z_channels
-    ZP = 8
-    while ZP < Z: ZP *= 2
-    # plane descriptors as hr_model_finalize builds them
-    MAT = [(0, 1), (0, 2), (1, 2)]; VEC = [2, 1, 0]
-    pl = []
-    app_off = real_off = 0
-    for j in range(3):
-        nd, na = hc.n_den[j], hc.n_app[j]
-        if hc.video and nd == 0: na = 0
-        cd4, ca4 = (nd + 3) // 4, (na + 3) // 4
-        tex = 4 * (cd4 + ca4)
-        if half: tex = (tex + 7) & ~7
-        bw, bh = (hc.grid[VEC[j]] if hc.video else 1), (hc.num_keyframes if hc.video else hc.grid[VEC[j]])
-        pl.append(f'    b.planes[{j}].tex = {tex}; b.planes[{j}].aw = {hc.grid[MAT[j][0]]}; b.planes[{j}].ah = {hc.grid[MAT[j][1]]}; '
-                  f'b.planes[{j}].bw = {bw}; b.planes[{j}].bh = {bh}; b.planes[{j}].cd4 = {cd4}; b.planes[{j}].ca4 = {ca4}; '
-                  f'b.planes[{j}].app_off = {app_off}; b.planes[{j}].app_real = {na}; b.planes[{j}].app_real_off = {real_off}; '
-                  f'b.planes[{j}].a = a.planes[{j}].a; b.planes[{j}].b = a.planes[{j}].b;')
-        app_off += 4 * ca4; real_off += na
+    # sample-count rounding and plane descriptors from the library's own code (csrc/hr_plan.h, host build)
+    ZP = plan_lib().hp_round_zp(Z)
+    planes, app_off, real_off, _ = plane_geometry(hc)
+    fields = ('tex', 'aw', 'ah', 'bw', 'bh', 'cd4', 'ca4', 'app_off', 'app_real', 'app_real_off')
+    pl = ['    ' + ' '.join(f'b.planes[{j}].{k} = {getattr(planes[j], k)};' for k in fields) + f' b.planes[{j}].a = a.planes[{j}].a; b.planes[{j}].b = a.planes[{j}].b;'
+          for j in range(3)]
     nd_, na_ = list(hc.n_den)[:3], list(hc.n_app)[:3]
     pclass = 1 if (nd_ == [8, 4, 4] and na_ == [8, 4, 4]) else (2 if (nd_ == [8, 0, 0] and na_[0] == 8) else 0)
     src = f'''#define HR_PHASE_MARK
