@@ -514,7 +514,7 @@ int calibrate_band(hr_model* m, hipStream_t st)
             HR_HIP(rgb2.alloc(sizeof(float) * nu * 3));
             HR_HIP(hipMemcpyAsync(sel, rays_h.data(), sizeof(float) * nu * c.ray_dim, hipMemcpyHostToDevice, st));
             HR_HIP(hipMemsetAsync(m->redo_count, 0, 4 * sizeof(unsigned), st));
-            render_verified(m, sel, nu, rgb, redo_list_cap(m, nu), st);
+            render_verified(m, sel, nu, rgb, hr_redo_list_cap(nu, m->redo_cap), st);
             unsigned listed = 0;
             HR_HIP(hipMemcpyAsync(&listed, m->redo_count + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
             for (int64_t r0 = 0; r0 < nu; r0 += m->chunk) {

@@ -92,69 +92,11 @@ int validate(const hr_config& c, bool coarse = false)
     return HR_OK;
 }
 
-// Which of the P per-sample head columns does the path read?  Columns that are not read are
-// dropped from the last Linear (fewer MFMAs, smaller head).  Shipped cases: the three sphere /
-// cylinder origin channels when origin_scale_factor == 0 (primitive.py:410-412 multiplies them
-// by zero) and `point_sigma` in models whose point_offset stage reads `sigma` instead.
+// The live head columns of the model's configuration (hr_live_columns, hr_plan.h; HR_PRUNE=0 keeps every column) -> col_map, p_live, kcfg
 void analyse_live_columns(hr_model* m)
 {
-    const hr_config& c = m->cfg;
-    bool live[64] = {};
-    auto mark = [&](const hr_head_field& f, int first, int count) {
-        if (f.offset < 0) return;
-        for (int i = first; i < first + count && f.offset + i < 64; ++i) live[f.offset + i] = true;
-    };
-    int z_anchor = 0;                 // a z_vals channel that is always read
-    if (c.isect_type == HR_ISECT_SPHERE || c.isect_type == HR_ISECT_CYLINDER) {
-        z_anchor = 3;
-        mark(c.f_z_vals, 3, 1);
-        if (c.origin_scale != 0.0f) mark(c.f_z_vals, 0, 3);
-    } else if (c.isect_type == HR_ISECT_DEFORMABLE_VOXEL_GRID) {
-        z_anchor = 3;
-        mark(c.f_z_vals, 3, 1);
-        if (c.dvg_normal_scale != 0.0f) mark(c.f_z_vals, 0, 3);
-    } else if (c.isect_type == HR_ISECT_SPHERE_NEW || c.isect_type == HR_ISECT_CYLINDER_NEW) {
-        z_anchor = 7;
-        mark(c.f_z_vals, 6, 2);
-        // kept contiguous up to the anchor so that offset + channel stays valid after compaction
-        if (c.resize_scale != 0.0f || c.origin_scale != 0.0f) mark(c.f_z_vals, 3, 3);
-        if (c.origin_scale != 0.0f) mark(c.f_z_vals, 0, 3);
-    } else {
-        mark(c.f_z_vals, 0, 1);
-    }
-    mark(c.f_isect_sigma, 0, 1);
-    if (c.point_offset) {
-        mark(c.f_point_offset, 0, 3);
-        mark(c.f_offset_sigma, 0, 1);
-    }
-    mark(c.f_color_scale, 0, 3);
-    mark(c.f_color_shift, 0, 3);
-    mark(c.f_color_scale_global, 0, c.f_color_scale_global.channels == 9 ? 9 : 3);    // 9: the head is a 3x3 `color_transform_global`
-    mark(c.f_color_shift_global, 0, 3);
-    if (c.advect && c.use_spatial_flow) mark(c.f_spatial_flow, 0, 3);
     const char* e = getenv("HR_PRUNE");
-    const bool prune = !(e && e[0] == '0');
-    int n = 0;
-    for (int i = 0; i < 64; ++i) {
-        const bool keep = (i < c.preds_per_z) && (live[i] || !prune);
-        m->col_map.col[i] = keep ? n++ : -1;
-    }
-    m->p_live = n;
-    m->kcfg = c;
-    m->kcfg.preds_per_z = n;
-    auto remap = [&](hr_head_field& f, int anchor) {   // anchor: a channel of the field that is always live
-        if (f.offset < 0) return;
-        f.offset = m->col_map.col[f.offset + anchor] - anchor;
-    };
-    remap(m->kcfg.f_z_vals, z_anchor);   // may become negative: only the live channels are read then
-    remap(m->kcfg.f_isect_sigma, 0);
-    if (c.point_offset) { remap(m->kcfg.f_point_offset, 0); remap(m->kcfg.f_offset_sigma, 0); }
-    else { m->kcfg.f_point_offset.offset = -1; m->kcfg.f_offset_sigma.offset = -1; }
-    remap(m->kcfg.f_color_scale, 0);
-    remap(m->kcfg.f_color_shift, 0);
-    remap(m->kcfg.f_color_scale_global, 0);
-    remap(m->kcfg.f_color_shift_global, 0);
-    if (c.advect && c.use_spatial_flow) remap(m->kcfg.f_spatial_flow, 0); else m->kcfg.f_spatial_flow.offset = -1;
+    hr_live_columns(m->cfg, !(e && e[0] == '0'), m->col_map.col, &m->p_live, &m->kcfg);
 }
 
 }  // namespace
@@ -186,16 +128,11 @@ static int create_level(const hr_config* cfg, bool coarse, hr_model** out)
         (void)hipMemcpy(m->kcfg_dev, &m->kcfg, sizeof(hr_config), hipMemcpyHostToDevice);
     }
     const hr_config& c = m->cfg;
-    {   // LDS of the sample kernel: 256/ZP rays x head rows x (live head columns + 4) + the decode matrices
-        const size_t rpb = 256 / hr_round_zp(c.z_channels), nq = ((size_t)samples_per_row(c) * m->p_live + 3) / 4;
-        size_t ca = 0;
-        for (int j = 0; j < 3; ++j) ca += 4 * (size_t)((c.n_app[j] + 3) / 4);
-        const size_t lds = 4 * (rpb * rows_per_ray(c) * (nq * 4 + 4) + rpb * 3 * ca + 256);
-        if (lds > 160 * 1024 - 4096) {             // (- the static words of the sample kernel: the ray records, hr_gather_ones)
-            const int z = c.z_channels, pl = m->p_live;
-            hr_model_destroy(m);                      // also releases the device configuration
-            return fail(HR_E_INVALID, "z_channels %d x %d head columns need %zu bytes of LDS per workgroup (160 KiB available)", z, pl, lds);
-        }
+    size_t lds = 0;
+    if (hr_sample_lds_refused(c, m->p_live, &lds)) {
+        const int z = c.z_channels, pl = m->p_live;
+        hr_model_destroy(m);                      // also releases the device configuration
+        return fail(HR_E_INVALID, "z_channels %d x %d head columns need %zu bytes of LDS per workgroup (160 KiB available)", z, pl, lds);
     }
     char name[64];
     for (int l = 0; l < c.mlp_layers; ++l) {
@@ -385,17 +322,7 @@ int hr_model_finalize(hr_model* m)
     HR_HIP(hipGetLastError());
     m->finalized = true;
     if (m->chunk == 0) {
-        // 131072 rays per launch measured best among 16k..640k (DoNeRF: a 185 MB head).  The head of a chunk should still be in the
-        // 256 MB Infinity Cache when the sample kernel reads it: wide heads (Neural-3D: 64 samples x 15 columns = 3840 bytes per ray) get
-        // fewer rays per launch -- measured on the 800x800 frames (profiles/r04_z_chunk_sweep.txt): neural_3d 4.44 ms at 131 072 rays
-        // (503 MB), 4.18 at 65 536 (252 MB), 4.24 at 49 152; the 1920-byte heads (technicolor, immersive: 252 MB at 131 072) are best there
-        const int64_t nq = ((int64_t)m->n_out + 3) / 4;
-        int64_t rays = (256ll << 20) / (nq * 16 * rows_per_ray(m->cfg));
-        if (rays >= 16384) rays &= ~(int64_t)16383;
-        // (163 840 = 231 MB of DoNeRF head: the largest that still sits in the cache next to the grids' hot lines -- and with hr_render's even split
-        //  an 800x800 frame is 4 launches of 160 000 rays instead of 4 x 131 072 + 115 712: 1.717 vs 1.729 ms, profiles/r06_chunk_sweep.txt; 213 376: 1.824)
-        rays = rays > 163840 ? 163840 : (rays < 4096 ? 4096 : rays);
-        const int rc = hr_model_reserve(m, rays);
+        const int rc = hr_model_reserve(m, hr_default_chunk(hr_head_quads(m->cfg, m->p_live), rows_per_ray(m->cfg)));
         if (rc != HR_OK) return rc;
     }
     return calibrate_band(m, nullptr);
@@ -442,7 +369,7 @@ int hr_model_reserve(hr_model* m, int64_t rays_per_chunk)
     m->rows.reset();
     m->chunk = 0;
     const size_t n_rows = (size_t)rays_per_chunk * rows_per_ray(m->cfg);      // a multiple of 64
-    const size_t nq = ((size_t)samples_per_row(m->cfg) * m->p_live + 3) / 4;
+    const size_t nq = (size_t)hr_head_quads(m->cfg, m->p_live);
     const size_t bytes = sizeof(float) * n_rows * nq * 4;                        // HQ layout over rows
     HR_HIP(m->head.alloc(bytes));
     if (m->cfg.mlp_layers == 0) HR_HIP(hipMemset(m->head, 0, bytes));   // ZeroMLP: written once, only ever read
@@ -453,12 +380,12 @@ int hr_model_reserve(hr_model* m, int64_t rays_per_chunk)
     }
     m->chunk = rays_per_chunk;
     // verified fast path: the list of rays the second pass renders again.  The buffer holds 4 M entries (16 MB); a call uses
-    // max(32 768, n_rays / 16) of them (measured: 0.01 - 2.5 % of a frame's rays are listed; the calibration gives the fast path up above 5 %)
+    // hr_redo_list_cap of them (max(32 768, n_rays / 16); measured: 0.01 - 2.5 % of a frame's rays are listed; the calibration gives the fast path up above 5 %)
     // and walks them in slices of the chunk's head workspace.  Beyond that the kernels raise bit 2 of the status word (HR_OPT_REDO_OVERFLOW)
     m->redo_list.reset();
     m->wide_list.reset();
     m->redo_cap = 1 << 22;
-    m->wide_cap = (int)(rays_per_chunk < 8192 ? rays_per_chunk : 8192);       // third pass: 128 tiles (rays outside the calibrated range are the exception)
+    m->wide_cap = hr_wide_cap(rays_per_chunk);
     HR_HIP(m->redo_list.alloc(sizeof(int) * (size_t)m->redo_cap));
     HR_HIP(m->wide_list.alloc(sizeof(int) * (size_t)m->wide_cap));
     if (!m->redo_count) {

@@ -2,8 +2,6 @@
 // verified fast path) and the single-stage entry points.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-
 #include "hr_model.h"
 
 // tier: 0 = the model's primary arithmetic; the verified fast path's later passes: 1 = its f16x3 tiles, 2 = its bf16x3 tiles (fill_mlp_args(..., tier))
@@ -144,25 +142,25 @@ void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int
     launch_mlp(m, m->kcfg, ma, st, tier);
 }
 
-// The frame kernel (fused_impl.inc) for the whole ray list; false: the model does not fit it (nothing launched)
+// The frame kernel (fused_impl.inc) for the whole ray list; false: hr_frame_plan says the call does not fit it (nothing launched)
 bool launch_frame(hr_model* m, const float* rays, int64_t n, float* rgb, bool probe, hipStream_t st)
 {
-    if (!m->opt_frame_kernel || m->coarse || m->is_coarse || m->cfg.mlp_layers == 0) return false;
-    if (m->verified) return false;               // the verified fast path is a two-pass plan over the HBM workspace
-    if (n > ((int64_t)1 << 36)) return false;
+    const int prec = m->active_precision, L = m->cfg.mlp_layers;
+    const bool split = prec == HR_MLP_BF16X3 || prec == HR_MLP_F16X3 || prec == HR_MLP_F16X2 || prec == HR_MLP_F16F8;      // their elements: 16 bits (HrMlpTiles::wsplit)
+    const HrFramePlanIn in = {n, m->opt_frame_kernel, m->opt_sample_waves, m->coarse || m->is_coarse, m->verified != 0, split, sizeof(uint16_t),
+                              (m->n_out + 3) / 4, m->k0p, L > 0 ? m->tiles[0].n_tiles[L - 1] : 0, m->n_cus};
+    const HrGridPlane planes[3] = {render_plane(m, 0), render_plane(m, 1), render_plane(m, 2)};
+    const HrFramePlan P = hr_frame_plan(m->kcfg, planes, m->ca_total, in);
+    if (!P.fits) return false;
+    if (probe || n <= 0) return true;
     HrMlpArgs ma;
     fill_mlp_args(m, ma, rays, n);
     ma.head = nullptr;
     HrSampleArgs sa;
     fill_sample_args(m, sa, rays, n, rgb);
     sa.head = nullptr;
-    switch (m->active_precision) {
-        case HR_MLP_BF16X3: return hr_launch_frame_bf16x3(m->kcfg, ma, sa, m->opt_sample_waves, m->opt_frame_kernel, m->n_cus, probe, st);
-        case HR_MLP_F16X3: return hr_launch_frame_f16x3(m->kcfg, ma, sa, m->opt_sample_waves, m->opt_frame_kernel, m->n_cus, probe, st);
-        case HR_MLP_F16X2: return hr_launch_frame_f16x2(m->kcfg, ma, sa, m->opt_sample_waves, m->opt_frame_kernel, m->n_cus, probe, st);
-        case HR_MLP_F16F8: return hr_launch_frame_f16f8(m->kcfg, ma, sa, m->opt_sample_waves, m->opt_frame_kernel, m->n_cus, probe, st);
-        default: return false;          // the exact-fp32 MLP (v_mfma_f32_16x16x4_f32) keeps its own kernel
-    }
+    const auto launch = prec == HR_MLP_BF16X3 ? hr_launch_frame_bf16x3 : prec == HR_MLP_F16X3 ? hr_launch_frame_f16x3 : prec == HR_MLP_F16X2 ? hr_launch_frame_f16x2 : hr_launch_frame_f16f8;
+    return launch(m->kcfg, ma, sa, P, st);
 }
 
 static int check_render(const hr_model* m, const float* rays, int64_t n, const float* rgb)
@@ -172,16 +170,6 @@ static int check_render(const hr_model* m, const float* rays, int64_t n, const f
     if (n < 0) return fail(HR_E_INVALID, "negative ray count");
     if (n > 0 && (!rays || !rgb)) return fail(HR_E_INVALID, "null ray / rgb buffer");
     return HR_OK;
-}
-
-// rays per launch of a call of n rays: as many launches as the workspace demands, of equal size (a short last launch leaves the chip half empty
-// for a whole kernel)
-static int64_t even_chunk(const hr_model* m, int64_t n)
-{
-    if (n <= m->chunk) return m->chunk;
-    const int64_t k = (n + m->chunk - 1) / m->chunk;
-    const int64_t per = (((n + k - 1) / k) + 63) & ~(int64_t)63;
-    return per < m->chunk ? per : m->chunk;
 }
 
 // The sample stage of one launch: the plain kernel, or with `maps` (hr_render_maps: non-NULL, some pointer set) the kernel that also
@@ -206,7 +194,7 @@ static void launch_samples(const hr_model* m, const HrSampleArgs& sa, const hr_m
 void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st, const hr_maps* maps)
 {
     const hr_config& c = m->cfg;
-    const int64_t per = even_chunk(m, n_rays);
+    const int64_t per = hr_even_chunk(m->chunk, n_rays);
     for (int64_t r0 = 0; r0 < n_rays; r0 += per) {
         const int64_t n = (n_rays - r0 < per) ? (n_rays - r0) : per;
         const float* rays = rays_dev + r0 * c.ray_dim;
@@ -269,17 +257,6 @@ void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* 
     launch_samples(m, sa, maps, 0, st);
 }
 
-// entries of the ray list one hr_render call may fill: a sixteenth of its rays, at least 32 768 (never more than the rays there are, or the buffer).
-// The second pass's launches are sized for it -- ~1.7 ns per workgroup that finds nothing to do -- and the calibration gives the fast path up
-// above a twentieth (HR_VERIFY_LISTED_LIMIT)
-int redo_list_cap(const hr_model* m, int64_t n_rays)
-{
-    int64_t cap = n_rays / 16 > 32768 ? n_rays / 16 : 32768;
-    cap = (cap + 63) & ~(int64_t)63;
-    if (cap > n_rays) cap = (n_rays + 63) & ~(int64_t)63;
-    return (int)(cap < m->redo_cap ? cap : m->redo_cap);
-}
-
 // hr_render, hr_render_fields and hr_render_maps (and their hr_render_frame forms) in one: `fields` non-NULL = diagnostics (one arithmetic,
 // the f16x3 tiles throughout, for every output), `maps` non-NULL = the per-ray maps on the plan hr_render takes, except the frame kernel
 static int render_impl(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, const hr_fields* fields, const hr_maps* maps,
@@ -314,12 +291,12 @@ static int render_impl(hr_model* m, const float* rays_dev, int64_t n_rays, float
         }
     }
     if (verify && n_rays > 0) {
-        render_verified(m, rays_dev, n_rays, rgb_dev, redo_list_cap(m, n_rays), st, maps);
+        render_verified(m, rays_dev, n_rays, rgb_dev, hr_redo_list_cap(n_rays, m->redo_cap), st, maps);
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
     const bool safe_all = m->verified != 0;
-    const int64_t per = even_chunk(m, n_rays);
+    const int64_t per = hr_even_chunk(m->chunk, n_rays);
     for (int64_t r0 = 0; r0 < n_rays; r0 += per) {
         const int64_t n = (n_rays - r0 < per) ? (n_rays - r0) : per;
         const float* rays = rays_dev + r0 * c.ray_dim;
@@ -363,27 +340,13 @@ int hr_render_frame_maps(hr_model* m, const float* rays_dev, int64_t n_rays, flo
     hipStream_t st = (hipStream_t)stream;
     m->frame_row = -1;
     if (c.video && c.num_keyframes >= 2 && !m->coarse && !m->is_coarse && c.grid_dtype != HR_GRID_FP16 && m->finalized) {
-        // the time tap of every ray of the frame, as hr_sample_body computes it from the ray's last column (host restatement of
-        // hr_base_time, hr_normalize_time and hr_make_tap, csrc/hr_math.h; float32 throughout)
-        float base_t = 0.0f;
-        if (c.advect) {
-            float tt = time * c.flow_fac;
-            tt = fminf(fmaxf(tt, 0.0f), c.flow_kmax);
-            base_t = rintf(tt - 1e-5f) * c.flow_inv_fac;
-        }
-        const float g = (base_t * c.time_scale + c.time_offset) * 2.0f - 1.0f;
-        const int n = c.num_keyframes;
-        const float ix = ((g + 1.0f) / 2.0f) * (float)(n - 1);
-        const float f0 = floorf(ix), f1 = f0 + 1.0f;
-        const int i0 = (int)f0, i1 = i0 + 1;
-        const bool ok0 = i0 >= 0 && i0 < n, ok1 = i1 >= 0 && i1 < n;
-        const float w0 = ok0 ? f1 - ix : 0.0f, w1 = ok1 ? ix - f0 : 0.0f;
+        const HrTimeTap t = hr_frame_time_tap(c, time);      // the time tap every ray of the frame shares
         for (int j = 0; j < 3; ++j) {
             const HrGridPlane& p = m->planes[j];
             if (p.bw <= 1 || p.cd4 + p.ca4 == 0) continue;
             const int row_floats = p.bw * p.tex;
             if (!m->frame_line[j]) continue;
-            hr_launch_blend_rows(reinterpret_cast<const float*>(p.b), m->frame_line[j], row_floats, ok0 ? i0 : 0, ok1 ? i1 : 0, w0, w1, st);
+            hr_launch_blend_rows(reinterpret_cast<const float*>(p.b), m->frame_line[j], row_floats, t.i0, t.i1, t.w0, t.w1, st);
             m->frame_row = 0;
         }
     }

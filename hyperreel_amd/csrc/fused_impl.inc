@@ -29,7 +29,7 @@
 //   * tiles are dealt XCD-aware: workgroup b runs on XCD b % 8, and each XCD gets one contiguous eighth of the ray list
 //     (neighbouring rays share texels in that XCD's L2).
 //
-// Applies when the head tile fits (hr_fused_plan in the launcher); everything else takes the two-kernel path.
+// Applies when the head tile fits (hr_frame_plan, hr_plan.h); everything else takes the two-kernel path.
 #ifndef HR_MFMA_PRIO_HI
 #define HR_MFMA_PRIO_HI 3
 #define HR_MFMA_PRIO_LO 2
@@ -211,13 +211,6 @@ __global__ __launch_bounds__(64 * (4 + NS)) void HR_FUSED_KERNEL(const hr_config
 }
 
 // ---------------------------------------------------------------- launcher
-static int hr_fused_head_stride(int nq)
-{
-    int hs = nq * 4;
-    while ((hs & 7) != 4) hs += 4;               // 16-byte row stride = 4 mod 8 words: the 8 lanes of a ds_write_b128 group hit 8 bank quads
-    return hs;
-}
-
 template <int ZP, bool HALF, int NS, int PC, int MT, int NB, int NBUF>
 static bool hr_launch_fused_t(const hr_config& cfg, const HrFusedArgs& fa, size_t lds, int grid, hipStream_t stream)
 {
@@ -227,78 +220,31 @@ static bool hr_launch_fused_t(const hr_config& cfg, const HrFusedArgs& fa, size_
     return true;
 }
 
-// Returns false when the model does not fit the fused kernel (the caller then takes the two-kernel path); `probe`: only answer.
-// frame_mode: 1 = where it fits and is expected to be the faster plan, 2 = wherever it fits (HR_OPT_FRAME_KERNEL)
-bool HR_FUSED_LAUNCH(const hr_config& cfg, const HrMlpArgs& ma, const HrSampleArgs& sa, int sample_waves, int frame_mode, int n_cus, bool probe,
-                     hipStream_t stream)
+// Launches the instantiation plan P (hr_frame_plan, hr_plan.h: it fits, and there are rays) names; false: the runtime refused its LDS
+bool HR_FUSED_LAUNCH(const hr_config& cfg, const HrMlpArgs& ma, const HrSampleArgs& sa, const HrFramePlan& P, hipStream_t stream)
 {
-    const int Z = cfg.z_channels, ZP = hr_round_zp(Z);
-    const int L = cfg.mlp_layers;
-    if (cfg.mlp_hidden != 256 || L < 2) return false;
-    if ((cfg.mlp_skip_mask >> (L - 1)) & 1) return false;                   // the input tile is gone by the last Linear
-    if (sa.rows_per_ray != 1 || sa.rows_out) return false;                  // point_prediction cascades
-    // the shipped decompositions [8, 4, 4] / [8, 0, 0], in either texel format: the class-specialised gathers (others: two-kernel path)
+    static_assert(sizeof(HR_SPLIT_E) == sizeof(uint16_t), "launch_frame sizes the plan's tiles for 16-bit split elements");
     const bool half = (cfg.grid_dtype == HR_GRID_FP16);
-    const int cls = hr_plane_class(sa.planes, sa.ca_total, hr_plane_fits_gather);
-    if (cls == 0) return false;
     HrFusedArgs fa;
     fa.m = ma;
     fa.s = sa;
-    fa.HS = hr_fused_head_stride(ma.nq);
-    const bool per_ray_M = (cfg.shading == HR_SHADING_SH);      // RGB shading keeps ONE decode matrix per sample wavefront (basis_mat itself)
-    const size_t LDS_MAX = 160 * 1024;
-    auto lds_for = [&](int tm, int nbuf, int ns, int rpw) {
-        return (size_t)tm * 2 * (256 + 8) * sizeof(HR_SPLIT_E) + (size_t)nbuf * tm * fa.HS * sizeof(float) +
-               (size_t)ns * (per_ray_M ? rpw : 1) * 3 * sa.ca_total * sizeof(float) + 32 + HR_GATHER_ONES * sizeof(float);
-    };
-    // ---- 64-ray tiles, one head buffer: the static nets whose head fits next to the activations
-    if (!cfg.video && cls == 1 && (ZP == 16 || ZP == 32) && ma.n_tiles[L - 1] <= 12) {     // (a wavefront holds at most three output tiles of the last Linear)
-        // Eight sample wavefronts by default (1.97 vs 2.75 ms per DoNeRF frame with four, profiles/r05_frame_waves_ab.txt).  For part of round 5 the
-        // default was four: with eight, repeated launches of the SAME frame differed in one ray of ~1e5 now and then -- traced to packed-fp32
-        // instructions the compiler formed in the sample role, and removed by building without them (hyperreel_amd/build.py, DESIGN 4).
-        const int NS = (sample_waves == 4) ? 4 : 8;
-        const int RPW = 64 / ZP;
-        const size_t lds = lds_for(64, 1, NS, RPW);
-        const size_t xin = (size_t)64 * 2 * (ma.k0p + 8) * sizeof(HR_SPLIT_E);
-        if (lds <= LDS_MAX && xin <= (size_t)NS * RPW * fa.HS * sizeof(float)) {       // the overlay must stay inside the first ray groups' rows
-            if (probe || ma.n_rays <= 0) return true;
-            fa.m_copies = per_ray_M ? RPW : 1;
-            fa.n_tiles = (int)((ma.n_rays + 63) / 64);
-            const int grid = fa.n_tiles < n_cus ? fa.n_tiles : n_cus;
-#define HR_FUSED_CASE(Z_, H_, N_) return hr_launch_fused_t<Z_, H_, N_, 1, 2, 2, 1>(cfg, fa, lds, grid, stream)
+    fa.HS = P.head_stride, fa.m_copies = P.m_copies, fa.n_tiles = P.n_tiles;
+    if (P.tile_rays == 64) {
+#define HR_FUSED_CASE(Z_, H_, N_) return hr_launch_fused_t<Z_, H_, N_, 1, 2, 2, 1>(cfg, fa, P.lds, P.grid, stream)
 #define HR_FUSED_TEX(Z_, N_) do { if (half) HR_FUSED_CASE(Z_, true, N_); else HR_FUSED_CASE(Z_, false, N_); } while (0)
-            if (ZP == 32) {
-                if (NS == 4) HR_FUSED_TEX(32, 4); else HR_FUSED_TEX(32, 8);
-            } else {
-                if (NS == 4) HR_FUSED_TEX(16, 4); else HR_FUSED_TEX(16, 8);
-            }
-#undef HR_FUSED_TEX
-#undef HR_FUSED_CASE
+        if (P.zp == 32) {
+            if (P.ns == 4) HR_FUSED_TEX(32, 4); else HR_FUSED_TEX(32, 8);
+        } else {
+            if (P.ns == 4) HR_FUSED_TEX(16, 4); else HR_FUSED_TEX(16, 8);
         }
-    }
-    // ---- 32-ray tiles: wider heads (the keyframe families' 480 / 960 columns) and the video gather.  32 samples per ray: two head
-    //      buffers; 64 samples per ray: one (the 123 KB tile leaves no room).  Every weight then crosses the CU once per 32 rays
-    //      instead of once per 64, and the two-kernel plan is as fast or faster (800x800 frames: technicolor 2.16 vs 2.06 ms,
-    //      immersive 2.45 vs 2.46, neural_3d 4.92 vs 4.39): this plan is what frame_mode 2 asks for -- no head workspace
-    //      traffic -- not the default
-    if (frame_mode < 2) return false;
-    if (ZP != 32 && ZP != 64) return false;
-    {
-        const int NS = 8, RPW = 64 / ZP, NBUF = (ZP == 32) ? 2 : 1;
-        const size_t lds = lds_for(32, NBUF, NS, RPW);
-        const size_t xin = (size_t)32 * 2 * (ma.k0p + 8) * sizeof(HR_SPLIT_E);
-        if (lds > LDS_MAX) return false;
-        if (xin > (size_t)(NBUF == 2 ? 32 : NS * RPW) * fa.HS * sizeof(float)) return false;
-        if (probe || ma.n_rays <= 0) return true;
-        fa.m_copies = per_ray_M ? RPW : 1;
-        fa.n_tiles = (int)((ma.n_rays + 31) / 32);
-        const int grid = fa.n_tiles < n_cus ? fa.n_tiles : n_cus;
-#define HR_FUSED_CASE(Z_, H_, P_, B_) return hr_launch_fused_t<Z_, H_, 8, P_, 1, 4, B_>(cfg, fa, lds, grid, stream)
-#define HR_FUSED_TEX(Z_, B_) do { if (half) { if (cls == 1) HR_FUSED_CASE(Z_, true, 1, B_); else HR_FUSED_CASE(Z_, true, 2, B_); } \
-                                  else { if (cls == 1) HR_FUSED_CASE(Z_, false, 1, B_); else HR_FUSED_CASE(Z_, false, 2, B_); } } while (0)
-        if (ZP == 32) HR_FUSED_TEX(32, 2); else HR_FUSED_TEX(64, 1);
 #undef HR_FUSED_TEX
 #undef HR_FUSED_CASE
     }
+#define HR_FUSED_CASE(Z_, H_, P_, B_) return hr_launch_fused_t<Z_, H_, 8, P_, 1, 4, B_>(cfg, fa, P.lds, P.grid, stream)
+#define HR_FUSED_TEX(Z_, B_) do { if (half) { if (P.pclass == 1) HR_FUSED_CASE(Z_, true, 1, B_); else HR_FUSED_CASE(Z_, true, 2, B_); } \
+                                  else { if (P.pclass == 1) HR_FUSED_CASE(Z_, false, 1, B_); else HR_FUSED_CASE(Z_, false, 2, B_); } } while (0)
+    if (P.zp == 32) HR_FUSED_TEX(32, 2); else HR_FUSED_TEX(64, 1);
+#undef HR_FUSED_TEX
+#undef HR_FUSED_CASE
     return false;
 }

@@ -96,7 +96,7 @@ struct HR_HIDDEN hr_model {
     DevMem<int> redo_list;                // the second pass's rays
     DevMem<int> wide_list;                // the third pass's rays
     DevMem<unsigned> redo_count;          // [0] second-pass counter, [1] its copy, [2] third-pass counter, [3] its copy
-    int redo_cap = 0;                    // entries the list holds (hr_model_reserve); a call uses max(32 768, n_rays / 16) of them
+    int redo_cap = 0;                    // entries the list holds (hr_model_reserve); a call uses hr_redo_list_cap of them
     int wide_cap = 0;
     float redo_band = 0.0f;              // the margins of THIS model (calibrate_band; hr_math.h HrRisk): of zc,
     float redo_band_q = 0.0f;            //   of a point coordinate per unit of amplification,
@@ -159,10 +159,6 @@ static inline int layer_in(const hr_config& c, int l)
     return c.mlp_hidden + (((c.mlp_skip_mask >> l) & 1) ? c.mlp_in : 0);
 }
 
-// samples whose head values one MLP row produces: all Z of a ray, or Z / casc_in_z per coarse point
-static inline int samples_per_row(const hr_config& c) { return c.casc_in_z > 0 ? c.z_channels / c.casc_in_z : c.z_channels; }
-static inline int rows_per_ray(const hr_config& c) { return c.casc_in_z > 0 ? c.casc_in_z : 1; }
-
 static inline int layer_out(const hr_config& c, int l) { return (l == c.mlp_layers - 1) ? samples_per_row(c) * c.preds_per_z : c.mlp_hidden; }
 
 // a ray with a live sample beyond it (60 degrees off a plane's normal; a sphere nearly tangent) is not what the margins of the verified fast
@@ -193,6 +189,5 @@ HR_HIDDEN void launch_front(hr_model* m, const float* rays, int64_t n, hipStream
 HR_HIDDEN bool launch_frame(hr_model* m, const float* rays, int64_t n, float* rgb, bool probe, hipStream_t st);
 HR_HIDDEN void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st,
                                const hr_maps* maps = nullptr);
-HR_HIDDEN int redo_list_cap(const hr_model* m, int64_t n_rays);
 
 #endif  // HR_MODEL_H

@@ -1,8 +1,11 @@
-// Host-side decisions shared by hr_model_finalize, the render launchers and the training launcher: plane-pair geometry, plane class,
-// the training step's launch plan.  Plain C++ (no HIP types); the CPU suite compiles it as it is (tests/host_math/hr_plan_host.cpp).
+// Host-side decisions shared by hr_model_create / finalize, the render launchers and the training launcher: plane-pair geometry, plane
+// class, the render call's launch plans (live head columns, launch sizing, the sample kernel, the frame kernel, a frame's time tap),
+// the training step's launch plan.  Plain C++ (no HIP types, no hr_model, no getenv); the CPU suite compiles it as it is
+// (tests/host_math/hr_plan_host.cpp).
 #ifndef HR_PLAN_H
 #define HR_PLAN_H
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -91,6 +94,274 @@ static inline int hr_plane_class(const HrGridPlane* pl, int ca_total, Fits fits)
     if (ok(1, 1, 8) && ok(2, 1, 12) && ca_total == 16) return 1;
     if (pl[1].cd4 + pl[1].ca4 == 0 && pl[2].cd4 + pl[2].ca4 == 0 && ca_total == 8) return 2;
     return 0;
+}
+
+// ---------------------------------------------------------------- rendering (api_model.hip, api_render.hip, sample_kernel.inc, fused_impl.inc)
+// Which of the P per-sample head columns does the path read?  Columns that are not read are dropped from the last Linear (fewer
+// MFMAs, smaller head).  Shipped cases: the three sphere / cylinder origin channels when origin_scale_factor == 0
+// (primitive.py:410-412 multiplies them by zero) and `point_sigma` in models whose point_offset stage reads `sigma` instead.
+// col[i]: user column i -> live column (-1: dropped; prune off keeps every column below preds_per_z); *kcfg: the configuration the
+// kernels see, preds_per_z = *p_live and the fields' offsets remapped.
+static inline void hr_live_columns(const hr_config& c, bool prune, int col[64], int* p_live, hr_config* kcfg)
+{
+    bool live[64] = {};
+    auto mark = [&](const hr_head_field& f, int first, int count) {
+        if (f.offset < 0) return;
+        for (int i = first; i < first + count && f.offset + i < 64; ++i) live[f.offset + i] = true;
+    };
+    int z_anchor = 0;                 // a z_vals channel that is always read
+    if (c.isect_type == HR_ISECT_SPHERE || c.isect_type == HR_ISECT_CYLINDER) {
+        z_anchor = 3;
+        mark(c.f_z_vals, 3, 1);
+        if (c.origin_scale != 0.0f) mark(c.f_z_vals, 0, 3);
+    } else if (c.isect_type == HR_ISECT_DEFORMABLE_VOXEL_GRID) {
+        z_anchor = 3;
+        mark(c.f_z_vals, 3, 1);
+        if (c.dvg_normal_scale != 0.0f) mark(c.f_z_vals, 0, 3);
+    } else if (c.isect_type == HR_ISECT_SPHERE_NEW || c.isect_type == HR_ISECT_CYLINDER_NEW) {
+        z_anchor = 7;
+        mark(c.f_z_vals, 6, 2);
+        // kept contiguous up to the anchor so that offset + channel stays valid after compaction
+        if (c.resize_scale != 0.0f || c.origin_scale != 0.0f) mark(c.f_z_vals, 3, 3);
+        if (c.origin_scale != 0.0f) mark(c.f_z_vals, 0, 3);
+    } else {
+        mark(c.f_z_vals, 0, 1);
+    }
+    mark(c.f_isect_sigma, 0, 1);
+    if (c.point_offset) {
+        mark(c.f_point_offset, 0, 3);
+        mark(c.f_offset_sigma, 0, 1);
+    }
+    mark(c.f_color_scale, 0, 3);
+    mark(c.f_color_shift, 0, 3);
+    mark(c.f_color_scale_global, 0, c.f_color_scale_global.channels == 9 ? 9 : 3);    // 9: the head is a 3x3 `color_transform_global`
+    mark(c.f_color_shift_global, 0, 3);
+    if (c.advect && c.use_spatial_flow) mark(c.f_spatial_flow, 0, 3);
+    int n = 0;
+    for (int i = 0; i < 64; ++i) {
+        const bool keep = (i < c.preds_per_z) && (live[i] || !prune);
+        col[i] = keep ? n++ : -1;
+    }
+    *p_live = n;
+    *kcfg = c;
+    kcfg->preds_per_z = n;
+    auto remap = [&](hr_head_field& f, int anchor) {   // anchor: a channel of the field that is always live
+        if (f.offset < 0) return;
+        f.offset = col[f.offset + anchor] - anchor;
+    };
+    remap(kcfg->f_z_vals, z_anchor);   // may become negative: only the live channels are read then
+    remap(kcfg->f_isect_sigma, 0);
+    if (c.point_offset) { remap(kcfg->f_point_offset, 0); remap(kcfg->f_offset_sigma, 0); }
+    else { kcfg->f_point_offset.offset = -1; kcfg->f_offset_sigma.offset = -1; }
+    remap(kcfg->f_color_scale, 0);
+    remap(kcfg->f_color_shift, 0);
+    remap(kcfg->f_color_scale_global, 0);
+    remap(kcfg->f_color_shift_global, 0);
+    if (c.advect && c.use_spatial_flow) remap(kcfg->f_spatial_flow, 0); else kcfg->f_spatial_flow.offset = -1;
+}
+
+// samples whose head values one MLP row produces: all Z of a ray, or Z / casc_in_z per coarse point
+static inline int samples_per_row(const hr_config& c) { return c.casc_in_z > 0 ? c.z_channels / c.casc_in_z : c.z_channels; }
+static inline int rows_per_ray(const hr_config& c) { return c.casc_in_z > 0 ? c.casc_in_z : 1; }
+// float4 quads of one head row with p_live live columns per sample
+static inline int hr_head_quads(const hr_config& c, int p_live) { return (samples_per_row(c) * p_live + 3) / 4; }
+
+// ---- launch sizing
+// Rays per launch when the caller reserves nothing.  131072 rays per launch measured best among 16k..640k (DoNeRF: a 185 MB head).  The head of a chunk
+// should still be in the 256 MB Infinity Cache when the sample kernel reads it: wide heads (Neural-3D: 64 samples x 15 columns = 3840 bytes per ray) get
+// fewer rays per launch -- measured on the 800x800 frames (profiles/r04_z_chunk_sweep.txt): neural_3d 4.44 ms at 131 072 rays (503 MB), 4.18 at 65 536
+// (252 MB), 4.24 at 49 152; the 1920-byte heads (technicolor, immersive: 252 MB at 131 072) are best there.  (The cap, 163 840 = 231 MB of DoNeRF head: the
+// largest that still sits in the cache next to the grids' hot lines -- and with hr_even_chunk an 800x800 frame is 4 launches of 160 000 rays instead of
+// 4 x 131 072 + 115 712: 1.717 vs 1.729 ms, profiles/r06_chunk_sweep.txt; 213 376: 1.824)
+static inline int64_t hr_default_chunk(int64_t nq, int rows_per_ray)
+{
+    int64_t rays = (256ll << 20) / (nq * 16 * rows_per_ray);
+    if (rays >= 16384) rays &= ~(int64_t)16383;
+    return rays > 163840 ? 163840 : (rays < 4096 ? 4096 : rays);
+}
+
+// rays per launch of a call of n rays: as many launches as the workspace of `chunk` rays demands, of equal size (a short last launch
+// leaves the chip half empty for a whole kernel)
+static inline int64_t hr_even_chunk(int64_t chunk, int64_t n)
+{
+    if (n <= chunk) return chunk;
+    const int64_t k = (n + chunk - 1) / chunk;
+    const int64_t per = (((n + k - 1) / k) + 63) & ~(int64_t)63;
+    return per < chunk ? per : chunk;
+}
+
+// Verified fast path: entries of the ray list one hr_render call of n rays may fill: a sixteenth of its rays, at least 32 768 (never
+// more than the rays there are, or the buffer's buffer_cap).  The second pass's launches are sized for it -- ~1.7 ns per workgroup that
+// finds nothing to do -- and the calibration gives the fast path up above a twentieth (HR_VERIFY_LISTED_LIMIT)
+static inline int hr_redo_list_cap(int64_t n, int buffer_cap)
+{
+    int64_t cap = n / 16 > 32768 ? n / 16 : 32768;
+    cap = (cap + 63) & ~(int64_t)63;
+    if (cap > n) cap = (n + 63) & ~(int64_t)63;
+    return (int)(cap < buffer_cap ? cap : buffer_cap);
+}
+
+// ... and of its third pass's list: 128 tiles (rays outside the calibrated range are the exception)
+static inline int hr_wide_cap(int64_t chunk) { return (int)(chunk < 8192 ? chunk : 8192); }
+
+// ---- the stand-alone sample kernel (sample_kernel.inc)
+// dynamic LDS of a workgroup: 256 / ZP rays x head rows x (a row's floats + 4), the rays' decode matrices, and above 64 samples (a ray
+// spans several wavefronts) 256 floats of cross-wave scratch
+static inline size_t hr_sample_lds_bytes(int nq, int ca_total, int ZP, int rows_per_ray)
+{
+    const int RPB = 256 / ZP;
+    return ((size_t)RPB * rows_per_ray * (nq * 4 + 4) + (size_t)RPB * 3 * ca_total + (ZP > 64 ? 256 : 0)) * sizeof(float);
+}
+
+#define HR_LDS_PER_WORKGROUP ((size_t)160 * 1024)
+// true: hr_model_create refuses a level of configuration c with p_live live head columns; *bytes: the sample kernel's request.
+// The margin set aside next to it: 4096 bytes for the kernel's static words (the ray records, hr_gather_ones) and the 256-float
+// cross-wave scratch, reserved for every sample count although hr_sample_lds_bytes asks for it only above 64 samples -- the bound has
+// always counted it, and the set of accepted configurations stays what it was.
+static inline bool hr_sample_lds_refused(const hr_config& c, int p_live, size_t* bytes)
+{
+    HrGridPlane pl[3];
+    int ca_total = 0, n_basis_cols = 0;
+    (void)hr_plane_geometry(c, pl, &ca_total, &n_basis_cols);      // (an inconsistent geometry is refused by hr_model_finalize)
+    const int zp = hr_round_zp(c.z_channels);
+    *bytes = hr_sample_lds_bytes(hr_head_quads(c, p_live), ca_total, zp, rows_per_ray(c));
+    return *bytes + 4096 + (zp > 64 ? 0 : 256 * sizeof(float)) > HR_LDS_PER_WORKGROUP;
+}
+
+// What hr_launch_samples chooses for a launch: samples per ray rounded up (ZP), plane class, line form, grid and LDS
+struct HrSamplePlan {
+    int zp, pclass, all_lines, big_lds;
+    unsigned blocks;
+    size_t lds;
+};
+
+// planes: as the kernel gets them (inside hr_render_frame a keyframe net's time planes are lines); rows_emitted: the coarse level of a
+// cascade, whose kernel writes the point MLP's input rows
+static inline HrSamplePlan hr_sample_plan(const hr_config& cfg, const HrGridPlane* planes, int ca_total, int nq, int rows_per_ray, int64_t n_rays,
+                                          bool rows_emitted)
+{
+    HrSamplePlan P = HrSamplePlan();
+    const int ZP = P.zp = hr_round_zp(cfg.z_channels);
+    const int RPB = 256 / ZP;
+    P.blocks = (unsigned)((n_rays + RPB - 1) / RPB);
+    P.lds = hr_sample_lds_bytes(nq, ca_total, ZP, rows_per_ray);
+    // few samples x many head columns can exceed the 64 KiB a kernel gets by default (e.g. 32 rays x 8 x 64 floats)
+    P.big_lds = P.lds > 64 * 1024;
+    // the shipped [8, 4, 4] / [8, 0, 0] decompositions get the class-specialised gather of their texel format (sample_core.inc); ZP >= 8
+    // keeps a quad inside one ray, video nets additionally need two keyframes
+    P.pclass = (!rows_emitted && (!cfg.video || cfg.num_keyframes >= 2)) ? hr_plane_class(planes, ca_total, hr_plane_fits_gather) : 0;
+    // every second factor a line (static nets; a keyframe net inside hr_render_frame): the gather compiled for two line taps
+    P.all_lines = P.pclass != 0;
+    for (int j = 0; j < 3; ++j)
+        if (planes[j].cd4 + planes[j].ca4 > 0 && planes[j].bw != 1) P.all_lines = 0;
+    return P;
+}
+
+// f(ZP, HALF, PC, NB) as integral constants: the instantiation KERNEL<ZP, HALF, PC, NB> of plan P.  Per ZP and texel format the
+// compiled set is (PC, NB) in {(0, 4), (1, 2), (1, 4), (2, 2), (2, 4)}: the generic gather has no line form.
+template <class F>
+static inline void hr_sample_dispatch(const HrSamplePlan& P, bool half, F&& f)
+{
+    auto cls = [&](auto zp, auto h, auto pc) {
+        if constexpr (decltype(pc)::value != 0)
+            if (P.all_lines) return f(zp, h, pc, std::integral_constant<int, 2>());
+        f(zp, h, pc, std::integral_constant<int, 4>());
+    };
+    auto tex = [&](auto zp, auto h) {
+        if (P.pclass == 1) cls(zp, h, std::integral_constant<int, 1>());
+        else if (P.pclass == 2) cls(zp, h, std::integral_constant<int, 2>());
+        else cls(zp, h, std::integral_constant<int, 0>());
+    };
+    hr_with_zp(P.zp, [&](auto zp) { if (half) tex(zp, std::true_type()); else tex(zp, std::false_type()); });
+}
+
+// ---- hr_render_frame: the time tap every ray of a frame shares, as hr_sample_body computes it from a ray's last column -- the host's
+// copy of hr_base_time, hr_normalize_time and hr_make_tap (hr_math.h: device-only under hipcc), float32 throughout; held to them bit
+// for bit by tests/test_render_plan_host.py
+struct HrTimeTap { int i0, i1; float w0, w1; };      // clamped keyframe rows; their weights, zero for a row that does not exist
+static inline HrTimeTap hr_frame_time_tap(const hr_config& c, float time)
+{
+    float base_t = 0.0f;
+    if (c.advect && c.num_keyframes > 0) {
+        const float tt = fminf(fmaxf(time * c.flow_fac, 0.0f), c.flow_kmax);
+        base_t = rintf(tt - 1e-5f) * c.flow_inv_fac;
+    }
+    const float g = (base_t * c.time_scale + c.time_offset) * 2.0f - 1.0f;
+    const int n = c.num_keyframes;
+    const float ix = ((g + 1.0f) / 2.0f) * (float)(n - 1);
+    const float f0 = floorf(ix), f1 = f0 + 1.0f;
+    const int i0 = (int)f0, i1 = i0 + 1;
+    const bool ok0 = i0 >= 0 && i0 < n, ok1 = i1 >= 0 && i1 < n;
+    return HrTimeTap{ok0 ? i0 : 0, ok1 ? i1 : 0, ok0 ? f1 - ix : 0.0f, ok1 ? ix - f0 : 0.0f};
+}
+
+// ---- the frame kernel (fused_impl.inc)
+#define HR_GATHER_ONES (2 * 16 + 8)      // floats of the class-specialised gather's constant block in the caller's LDS (sample_core.inc)
+
+struct HrFramePlanIn {
+    int64_t n_rays;
+    int frame_mode;             // HR_OPT_FRAME_KERNEL: 0 = never, 1 = where it fits and is expected to be the faster plan, 2 = wherever it fits
+    int sample_waves;           // HR_OPT_SAMPLE_WAVES: 0 (the plan's choice), 4 or 8
+    bool cascade;               // a level of a point_prediction cascade (several head rows per ray, or rows emitted)
+    bool verified;              // the verified fast path is on: a two-pass plan over the HBM workspace
+    bool split_mlp;             // the active arithmetic is a split one (the exact-fp32 MLP, v_mfma_f32_16x16x4_f32, keeps its own kernel)
+    size_t split_elem;          // bytes of a split element (HR_SPLIT_E)
+    int nq, k0p, last_tiles;    // float4 quads of a head row; mlp_in padded to a multiple of 16; 32-column output tiles of the last Linear
+    int cus;                    // compute units of the device: only the grid depends on it
+};
+
+// Everything HR_FUSED_LAUNCH needs to pick and launch HR_FUSED_KERNEL<zp, HALF, ns, pclass, tile_rays / 32, nb, nbuf>
+struct HrFramePlan {
+    int fits;                   // 0: the call takes the two-kernel path
+    int zp, pclass;
+    int tile_rays;              // 64: the static nets whose head fits next to the activations; 32: wider heads, the video gather
+    int ns, nb, nbuf;           // sample wavefronts, taps of a second factor (2: lines), head buffers
+    int m_copies;               // decode matrices per sample wavefront in LDS
+    int head_stride;            // floats per head row in LDS
+    int n_tiles, grid;
+    size_t lds;
+};
+
+// planes: as the kernel gets them (see hr_sample_plan)
+static inline HrFramePlan hr_frame_plan(const hr_config& cfg, const HrGridPlane* planes, int ca_total, const HrFramePlanIn& in)
+{
+    HrFramePlan P = HrFramePlan();
+    const int ZP = P.zp = hr_round_zp(cfg.z_channels), L = cfg.mlp_layers;
+    if (!in.frame_mode || in.cascade || in.verified || !in.split_mlp || in.n_rays > ((int64_t)1 << 36)) return P;
+    // (0 layers: ZeroMLP; a skip connection into the last Linear: the input tile is gone by then)
+    if (cfg.mlp_hidden != 256 || L < 2 || ((cfg.mlp_skip_mask >> (L - 1)) & 1)) return P;
+    // the shipped decompositions [8, 4, 4] / [8, 0, 0], in either texel format: the class-specialised gathers (others: two-kernel path)
+    if ((P.pclass = hr_plane_class(planes, ca_total, hr_plane_fits_gather)) == 0) return P;
+    P.head_stride = in.nq * 4;
+    while ((P.head_stride & 7) != 4) P.head_stride += 4;    // 16-byte row stride = 4 mod 8 words: the 8 lanes of a ds_write_b128 group hit 8 bank quads
+    const bool per_ray_M = (cfg.shading == HR_SHADING_SH);      // RGB shading keeps ONE decode matrix per sample wavefront (basis_mat itself)
+    const int RPW = 64 / (ZP < 64 ? ZP : 64);                   // rays per sample wavefront and pass
+    auto fit = [&](int tile_rays, int nbuf, int ns, int nb, int overlay_rows) {
+        const size_t lds = (size_t)tile_rays * 2 * (256 + 8) * in.split_elem + (size_t)nbuf * tile_rays * P.head_stride * sizeof(float) +
+                           (size_t)ns * (per_ray_M ? RPW : 1) * 3 * ca_total * sizeof(float) + 32 + HR_GATHER_ONES * sizeof(float);
+        // the MLP's input tile is overlaid on head rows: it must stay inside the rows that are free when it is written
+        const size_t xin = (size_t)tile_rays * 2 * (in.k0p + 8) * in.split_elem;
+        if (lds > HR_LDS_PER_WORKGROUP || xin > (size_t)overlay_rows * P.head_stride * sizeof(float)) return false;
+        P.fits = 1, P.tile_rays = tile_rays, P.ns = ns, P.nb = nb, P.nbuf = nbuf, P.lds = lds, P.m_copies = per_ray_M ? RPW : 1;
+        P.n_tiles = (int)((in.n_rays + tile_rays - 1) / tile_rays);
+        P.grid = P.n_tiles < in.cus ? P.n_tiles : in.cus;
+        return true;
+    };
+    // ---- 64-ray tiles, one head buffer: the static nets whose head fits next to the activations (a wavefront holds at most three
+    //      output tiles of the last Linear).  The overlay sits under the first ray groups' rows.
+    // Eight sample wavefronts by default (1.97 vs 2.75 ms per DoNeRF frame with four, profiles/r05_frame_waves_ab.txt).  For part of round 5 the
+    // default was four: with eight, repeated launches of the SAME frame differed in one ray of ~1e5 now and then -- traced to packed-fp32
+    // instructions the compiler formed in the sample role, and removed by building without them (hyperreel_amd/build.py).
+    const int NS = (in.sample_waves == 4) ? 4 : 8;
+    if (!cfg.video && P.pclass == 1 && (ZP == 16 || ZP == 32) && in.last_tiles <= 12 && fit(64, 1, NS, 2, NS * RPW)) return P;
+    // ---- 32-ray tiles: wider heads (the keyframe families' 480 / 960 columns) and the video gather.  32 samples per ray: two head
+    //      buffers (the overlay has the whole buffer about to be filled); 64 samples per ray: one (the 123 KB tile leaves no room).
+    //      Every weight then crosses the CU once per 32 rays instead of once per 64, and the two-kernel plan is as fast or faster
+    //      (800x800 frames: technicolor 2.16 vs 2.06 ms, immersive 2.45 vs 2.46, neural_3d 4.92 vs 4.39): this plan is what
+    //      frame_mode 2 asks for -- no head workspace traffic -- not the default
+    if (in.frame_mode < 2 || (ZP != 32 && ZP != 64)) return P;
+    (void)fit(32, ZP == 32 ? 2 : 1, 8, 4, ZP == 32 ? 32 : 8 * RPW);
+    return P;
 }
 
 // ---------------------------------------------------------------- the training step (train_kernel.hip)

@@ -620,7 +620,7 @@ __device__ __forceinline__ HrTapsC<NB> hr_make_taps_c(const HrGridPlane& g, cons
 // before the barrier that publishes the ray's decode matrix (sample_kernel.hip, fused_impl.inc, train_kernel.hip) -- the caller's, not a
 // __shared__ variable of this file: static LDS in front of the frame kernel's dynamic tile moved every LDS address of its MLP role and cost
 // that role, which lives on exactly 168 registers, the four accumulator tiles it then spilled (1.85 vs 1.71 ms per frame).
-#define HR_GATHER_ONES (2 * 16 + 8)
+// (HR_GATHER_ONES itself: hr_plan.h, which sizes the frame kernel's LDS with it)
 __device__ __forceinline__ void hr_gather_ones_init(float* ones)
 {
     const int t = (int)threadIdx.x;

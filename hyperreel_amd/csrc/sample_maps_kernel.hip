@@ -20,5 +20,8 @@ __global__ __launch_bounds__(256, (HrGatherTune<ZP, HALF>::MIN_BLOCKS)) void hr_
 void hr_launch_samples_maps(const hr_config& cfg, const HrSampleArgs& args, const hr_maps& maps, hipStream_t stream)
 {
     if (args.n_rays <= 0) return;
-    HR_SAMPLE_DISPATCH(hr_sample_maps_kernel, hr_sample_plan(cfg, args), cfg, stream, args.cfg_dev, args, maps);
+    const HrSamplePlan P = hr_sample_plan(cfg, args.planes, args.ca_total, args.nq, args.rows_per_ray, args.n_rays, args.rows_out != nullptr);
+    hr_sample_dispatch(P, cfg.grid_dtype == HR_GRID_FP16, [&](auto zp, auto half, auto pc, auto nb) {
+        hr_launch_sample_kernel(P, &hr_sample_maps_kernel<zp(), half(), pc(), nb()>, stream, args.cfg_dev, args, maps);
+    });
 }

@@ -855,46 +855,6 @@ def compile_model(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp3
         return None, compile_config(cfg, dataset, grid_size, mlp_precision, grid_dtype)
 
 
-def live_head_columns(hc):
-    """Per-sample head columns the path reads (mirror of analyse_live_columns in csrc/api_model.hip).
-    The library drops the others from the last Linear; `hr_render_fields` reports them as 0."""
-    live = [False] * hc.preds_per_z
-
-    def mark(f, first, count):
-        if f.offset >= 0:
-            for i in range(first, first + count):
-                live[f.offset + i] = True
-
-    t = hc.isect_type
-    if t in (ISECT['sphere'], ISECT['cylinder']):
-        mark(hc.f_z_vals, 3, 1)
-        if hc.origin_scale != 0.0:
-            mark(hc.f_z_vals, 0, 3)
-    elif t == ISECT['deformable_voxel_grid']:
-        mark(hc.f_z_vals, 3, 1)
-        if hc.dvg_normal_scale != 0.0:
-            mark(hc.f_z_vals, 0, 3)
-    elif t in (ISECT['sphere_new'], ISECT['cylinder_new']):
-        mark(hc.f_z_vals, 6, 2)
-        if hc.resize_scale != 0.0 or hc.origin_scale != 0.0:   # kept contiguous up to channel 7
-            mark(hc.f_z_vals, 3, 3)
-        if hc.origin_scale != 0.0:
-            mark(hc.f_z_vals, 0, 3)
-    else:
-        mark(hc.f_z_vals, 0, 1)
-    mark(hc.f_isect_sigma, 0, 1)
-    if hc.point_offset:
-        mark(hc.f_point_offset, 0, 3)
-        mark(hc.f_offset_sigma, 0, 1)
-    mark(hc.f_color_scale, 0, 3)
-    mark(hc.f_color_shift, 0, 3)
-    mark(hc.f_color_scale_global, 0, 3)
-    mark(hc.f_color_shift_global, 0, 3)
-    if hc.advect and hc.use_spatial_flow:
-        mark(hc.f_spatial_flow, 0, 3)
-    return live
-
-
 def upload_names(hc, coarse=None):
     """[(ABI tensor name, reference state_dict key suffix)] for hr_model_upload.  Keys carry {idx} (the
     ray_prediction stage), {pp_idx} (the point_prediction stage of a cascade) and {ct_idx} (color_transform)."""

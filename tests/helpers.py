@@ -86,19 +86,11 @@ def linf(a, b):
 
 
 def trainable_sweep_cases(cascades=False):
-    """Sweep fixtures whose model the training path differentiates (mirror of hr_train_unsupported, csrc/hr_train.h) --
-    which are also the ones oracle/torch_port.py restates.  cascades: the point_prediction models instead of the
-    single-level ones (their coarse and fine stages are checked separately)."""
+    """The sweep fixtures' single-level models, or with `cascades` the point_prediction ones (their coarse and fine stages are
+    checked separately).  The training path differentiates every one of them (tests/test_train_host.py asks hr_train_unsupported), and
+    oracle/torch_port.py restates them."""
     from hyperreel_amd import plan
-    out = []
-    for c in sweep_cases():
-        g = Golden(c)
-        if plan.is_cascade(g.cfg) != bool(cascades):
-            continue
-        with plan.at_iteration(g.iteration):
-            hc = plan.compile_model(g.cfg, g.dataset, g.grid, iteration=g.iteration)[1]
-        out.append(c)
-    return out
+    return [c for c in sweep_cases() if plan.is_cascade(Golden(c).cfg) == bool(cascades)]
 
 
 class GradGolden:
@@ -170,7 +162,21 @@ class TrainPlan(ctypes.Structure):          # mirrors HrTrainPlan (hyperreel_amd
                 ('atomics_lds', ctypes.c_size_t), ('tail_blocks', ctypes.c_uint)]
 
 
+class SamplePlan(ctypes.Structure):         # mirrors HrSamplePlan (hyperreel_amd/csrc/hr_plan.h)
+    _fields_ = [(k, ctypes.c_int) for k in ('zp', 'pclass', 'all_lines', 'big_lds')] + [('blocks', ctypes.c_uint), ('lds', ctypes.c_size_t)]
+
+
+class FramePlan(ctypes.Structure):          # mirrors HrFramePlan (hyperreel_amd/csrc/hr_plan.h)
+    _fields_ = [(k, ctypes.c_int) for k in ('fits', 'zp', 'pclass', 'tile_rays', 'ns', 'nb', 'nbuf', 'm_copies', 'head_stride', 'n_tiles', 'grid')] + \
+               [('lds', ctypes.c_size_t)]
+
+
+class TimeTap(ctypes.Structure):            # mirrors HrTimeTap (hyperreel_amd/csrc/hr_plan.h)
+    _fields_ = [('i0', ctypes.c_int), ('i1', ctypes.c_int), ('w0', ctypes.c_float), ('w1', ctypes.c_float)]
+
+
 PLANE_CLASS = ['generic', '8,4,4', '8,0,0']          # hr_plane_class
+REDO_BUFFER = 1 << 22                                # entries of the verified path's list buffer (hr_model_reserve)
 
 
 @functools.lru_cache(maxsize=None)
@@ -181,7 +187,80 @@ def plan_lib():
     deps = [src, os.path.join(here, '..', 'include', 'hyperreel_hip.h')] + [os.path.join(here, '..', 'hyperreel_amd', 'csrc', f) for f in ('hr_plan.h', 'hr_grid.h')]
     lib = ctypes.CDLL(build_host_lib(os.path.join(here, 'host_math', '_build', 'libhr_plan_host.so'), src, deps))
     assert lib.hp_sizeof_plane() == ctypes.sizeof(GridPlane) and lib.hp_sizeof_plan() == ctypes.sizeof(TrainPlan)
+    assert lib.hp_sizeof_sample_plan() == ctypes.sizeof(SamplePlan) and lib.hp_sizeof_frame_plan() == ctypes.sizeof(FramePlan)
+    assert lib.hp_sizeof_time_tap() == ctypes.sizeof(TimeTap)
+    lib.hp_default_chunk.restype = lib.hp_even_chunk.restype = ctypes.c_longlong
+    lib.hp_default_chunk.argtypes = [ctypes.c_longlong, ctypes.c_int]
+    lib.hp_even_chunk.argtypes = [ctypes.c_longlong, ctypes.c_longlong]
+    lib.hp_redo_list_cap.argtypes = [ctypes.c_longlong, ctypes.c_int]
+    lib.hp_wide_cap.argtypes = [ctypes.c_longlong]
+    lib.hp_sample_lds_bytes.restype = ctypes.c_size_t
+    lib.hp_frame_time_tap.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]
     return lib
+
+
+@functools.lru_cache(maxsize=None)
+def math_lib():
+    """Host build of hyperreel_amd/csrc/hr_math.h (tests/host_math/hr_math_host.cpp): the formulas the kernels call."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    src = os.path.join(here, 'host_math', 'hr_math_host.cpp')
+    deps = [src, os.path.join(here, '..', 'hyperreel_amd', 'csrc', 'hr_math.h'), os.path.join(here, '..', 'include', 'hyperreel_hip.h')]
+    lib = ctypes.CDLL(build_host_lib(os.path.join(here, 'host_math', '_build', 'libhr_math_host.so'), src, deps))
+    lib.hm_normalize_time.restype = ctypes.c_float
+    lib.hm_normalize_time.argtypes = [ctypes.c_void_p, ctypes.c_float]
+    lib.hm_time_tap.argtypes = [ctypes.c_void_p, ctypes.c_float] + [ctypes.c_void_p] * 4
+    return lib
+
+
+def even_chunk(chunk, n):
+    """hr_even_chunk: rays per launch of a call of n rays on a workspace of `chunk` rays."""
+    return plan_lib().hp_even_chunk(chunk, n)
+
+
+def redo_list_cap(n, buffer_cap=REDO_BUFFER):
+    """hr_redo_list_cap: entries of the verified path's list one call of n rays may fill."""
+    return plan_lib().hp_redo_list_cap(n, buffer_cap)
+
+
+def live_columns(hc, prune=True):
+    """hr_live_columns of a compiled config: (user column -> live column or -1, for all 64 slots; p_live; the kernels' config)."""
+    col, p_live, kcfg = (ctypes.c_int * 64)(), ctypes.c_int(), type(hc)()
+    plan_lib().hp_live_columns(ctypes.byref(hc), int(bool(prune)), col, ctypes.byref(p_live), ctypes.byref(kcfg))
+    return list(col), p_live.value, kcfg
+
+
+def live_head_columns(hc):
+    """Per-sample head columns the path reads, as booleans over the user's preds_per_z columns.  The library drops the others from
+    the last Linear; `hr_render_fields` reports them as 0."""
+    return [c >= 0 for c in live_columns(hc)[0][:hc.preds_per_z]]
+
+
+def sample_lds_refused(hc):
+    """(hr_model_create refuses a level of `hc` for the sample kernel's LDS, the kernel's request in bytes)."""
+    n = ctypes.c_size_t()
+    return bool(plan_lib().hp_sample_lds_refused(ctypes.byref(hc), ctypes.byref(n))), n.value
+
+
+def sample_plan(hc, n_rays=4096, rows_emitted=False, frame_lines=False):
+    """hr_sample_plan for a model of `hc` (frame_lines: inside hr_render_frame) and the instantiation (ZP, HALF, PC, NB) it launches."""
+    out, inst = SamplePlan(), (ctypes.c_int * 4)()
+    plan_lib().hp_sample_plan(ctypes.byref(hc), ctypes.c_longlong(n_rays), int(bool(rows_emitted)), int(bool(frame_lines)), ctypes.byref(out), inst)
+    return out, tuple(inst)
+
+
+def frame_plan(hc, n_rays=640000, frame_mode=1, sample_waves=0, cascade=False, verified=False, split_mlp=True, frame_lines=False):
+    """hr_frame_plan for a model of `hc` on 256 compute units with a split MLP arithmetic (HR_OPT_FRAME_KERNEL = frame_mode)."""
+    out = FramePlan()
+    plan_lib().hp_frame_plan(ctypes.byref(hc), ctypes.c_longlong(n_rays), frame_mode, sample_waves, int(bool(cascade)), int(bool(verified)),
+                             int(bool(split_mlp)), int(bool(frame_lines)), ctypes.byref(out))
+    return out
+
+
+def frame_time_tap(hc, t):
+    """hr_frame_time_tap: (i0, i1, w0, w1) of a frame at time t."""
+    out = TimeTap()
+    plan_lib().hp_frame_time_tap(ctypes.byref(hc), ctypes.c_float(t), ctypes.byref(out))
+    return out.i0, out.i1, out.w0, out.w1
 
 
 def plane_geometry(hc):

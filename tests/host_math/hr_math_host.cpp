@@ -111,6 +111,15 @@ void hm_normalize(const hr_config* c, const float* p, int n, float* out)
 
 float hm_normalize_time(const hr_config* c, float t) { return hr_normalize_time(*c, t); }
 
+// the time tap of a ray whose last column is `time`, as the sample kernels compute it (sample_core.inc: hr_base_time of an advecting
+// net, hr_normalize_time, hr_make_tap over the keyframes)
+void hm_time_tap(const hr_config* c, float time, int* i0, int* i1, float* w0, float* w1)
+{
+    const float base_t = c->advect ? hr_base_time(*c, time) : 0.0f;
+    const hr_axis_tap t = hr_make_tap(hr_normalize_time(*c, base_t), c->num_keyframes);
+    *i0 = t.i0; *i1 = t.i1; *w0 = t.w0; *w1 = t.w1;
+}
+
 // contraction of points / inverse contraction of distances (nlf/contract.py)
 void hm_contract_points(const hr_config* c, const float* p, int n, float* out)
 {

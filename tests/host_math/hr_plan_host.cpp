@@ -1,11 +1,14 @@
-// TEST-ONLY host build of hyperreel_amd/csrc/hr_plan.h (plane-pair geometry, plane class, the training step's launch plan), so that
-// the suites ask the library's own code which branch a case takes.  Nothing in the product links or loads this file.
+// TEST-ONLY host build of hyperreel_amd/csrc/hr_plan.h (plane-pair geometry, plane class, the render call's and the training step's
+// launch plans), so that the suites ask the library's own code which branch a case takes.  Nothing in the product links or loads this file.
 #include "../../hyperreel_amd/csrc/hr_plan.h"
 
 extern "C" {
 
 int hp_sizeof_plane() { return (int)sizeof(HrGridPlane); }
 int hp_sizeof_plan() { return (int)sizeof(HrTrainPlan); }
+int hp_sizeof_sample_plan() { return (int)sizeof(HrSamplePlan); }
+int hp_sizeof_frame_plan() { return (int)sizeof(HrFramePlan); }
+int hp_sizeof_time_tap() { return (int)sizeof(HrTimeTap); }
 int hp_round_zp(int z_channels) { return hr_round_zp(z_channels); }
 
 int hp_plane_geometry(const hr_config* c, HrGridPlane* out, int* ca_total, int* n_basis_cols)
@@ -29,6 +32,78 @@ void hp_train_plan(const hr_config* c, long long n_rays, int deterministic, HrTr
     (void)hr_plane_geometry(*c, planes, &ca_total, &n_basis_cols);
     const HrTrainPlanIn in = {n_rays, true, true, true, true, deterministic != 0, deterministic ? sizeof(long long) : sizeof(float), 256};
     *out = hr_train_plan(*c, planes, ca_total, n_basis_cols, in);
+}
+
+// ---- rendering
+void hp_live_columns(const hr_config* c, int prune, int* col, int* p_live, hr_config* kcfg) { hr_live_columns(*c, prune != 0, col, p_live, kcfg); }
+long long hp_default_chunk(long long nq, int rows) { return hr_default_chunk(nq, rows); }
+long long hp_even_chunk(long long chunk, long long n) { return hr_even_chunk(chunk, n); }
+int hp_redo_list_cap(long long n, int buffer_cap) { return hr_redo_list_cap(n, buffer_cap); }
+int hp_wide_cap(long long chunk) { return hr_wide_cap(chunk); }
+size_t hp_sample_lds_bytes(int nq, int ca_total, int zp, int rows) { return hr_sample_lds_bytes(nq, ca_total, zp, rows); }
+void hp_frame_time_tap(const hr_config* c, float time, HrTimeTap* out) { *out = hr_frame_time_tap(*c, time); }
+
+// What a model of *c (a level of a cascade: its own config) is rendered with: live columns with pruning on, the geometry of
+// hr_model_finalize; frame_lines: inside hr_render_frame, where a float32 keyframe net's time planes are handed over as lines
+// (render_plane, api_render.hip)
+struct Level {
+    int p_live, nq, ca_total;
+    HrGridPlane planes[3];
+};
+static Level level_of(const hr_config& c, int frame_lines)
+{
+    Level v;
+    int col[64], n_basis_cols = 0;
+    hr_config kcfg;
+    hr_live_columns(c, true, col, &v.p_live, &kcfg);
+    v.nq = hr_head_quads(c, v.p_live);
+    (void)hr_plane_geometry(c, v.planes, &v.ca_total, &n_basis_cols);
+    if (frame_lines && c.video && c.num_keyframes >= 2 && c.grid_dtype != HR_GRID_FP16)
+        for (HrGridPlane& g : v.planes)
+            if (g.bw > 1 && g.cd4 + g.ca4 > 0) { g.bh = g.bw; g.bw = 1; }
+    return v;
+}
+
+// 1: hr_model_create refuses the level for the sample kernel's LDS; *bytes: the kernel's request
+int hp_sample_lds_refused(const hr_config* c, size_t* bytes)
+{
+    return hr_sample_lds_refused(*c, level_of(*c, 0).p_live, bytes) ? 1 : 0;
+}
+
+// hr_sample_plan as the launcher calls it
+void hp_sample_plan_raw(const hr_config* c, const HrGridPlane* planes, int ca_total, int nq, int rows, long long n_rays, int rows_emitted, HrSamplePlan* out)
+{
+    *out = hr_sample_plan(*c, planes, ca_total, nq, rows, n_rays, rows_emitted != 0);
+}
+
+// the stand-alone sample kernel's plan and the instantiation <ZP, HALF, PC, NB> hr_sample_dispatch picks for it
+void hp_sample_plan(const hr_config* c, long long n_rays, int rows_emitted, int frame_lines, HrSamplePlan* out, int* inst)
+{
+    const Level v = level_of(*c, frame_lines);
+    *out = hr_sample_plan(*c, v.planes, v.ca_total, v.nq, rows_per_ray(*c), n_rays, rows_emitted != 0);
+    hr_sample_dispatch(*out, c->grid_dtype == HR_GRID_FP16, [&](auto zp, auto half, auto pc, auto nb) {
+        inst[0] = decltype(zp)::value; inst[1] = decltype(half)::value; inst[2] = decltype(pc)::value; inst[3] = decltype(nb)::value;
+    });
+}
+
+// the frame kernel's plan on a device of 256 compute units, 16-bit split elements, the split kernels' 32-column output tiles
+void hp_frame_plan(const hr_config* c, long long n_rays, int frame_mode, int sample_waves, int cascade, int verified, int split_mlp, int frame_lines,
+                   HrFramePlan* out)
+{
+    const Level v = level_of(*c, frame_lines);
+    HrFramePlanIn in = HrFramePlanIn();
+    in.n_rays = n_rays;
+    in.frame_mode = frame_mode;
+    in.sample_waves = sample_waves;
+    in.cascade = cascade != 0;
+    in.verified = verified != 0;
+    in.split_mlp = split_mlp != 0;
+    in.split_elem = 2;
+    in.nq = v.nq;
+    in.k0p = (c->mlp_in + 15) & ~15;
+    in.last_tiles = (samples_per_row(*c) * v.p_live + 31) / 32;
+    in.cus = 256;
+    *out = hr_frame_plan(*c, v.planes, v.ca_total, in);
 }
 
 }  // extern "C"

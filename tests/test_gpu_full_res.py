@@ -1,10 +1,10 @@
 """`-m gpu`: one render() call at the frame sizes the reference ships, not the 800x800 frames of the rest of the suite.
 
 Above 640 000 rays a call takes paths no smaller call reaches:
-  * the verified fast path's list (csrc/api_render.hip redo_list_cap: max(32 768, n / 16) entries) outgrows the chunk's head workspace, so
+  * the verified fast path's list (csrc/hr_plan.h hr_redo_list_cap: max(32 768, n / 16) entries) outgrows the chunk's head workspace, so
     the second pass walks it in more than one slice -- Technicolor 2048x1088 (139 264 entries over a 131 072-ray workspace), Neural-3D
     1352x1014 (85 696 over 65 536), Neural-3D 2704x2028 (342 784: six slices);
-  * even_chunk() ends 1352x1014 in a launch that is not a multiple of 64 rays;
+  * hr_even_chunk() ends 1352x1014 in a launch that is not a multiple of 64 rays;
   * the persistent frame kernel (csrc/fused_impl.inc) deals 1.6 - 3.5 times the tiles of an 800x800 frame over its workgroups;
   * the viewer path (hr_generate_rays -> render -> hr_pack_display) meets non-square frames.
 What is held: against the CPU restatement of the reference (oracle/torch_port.py) on a chosen subset of every frame, no ray over 1e-4; the
@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import even_chunk, redo_list_cap
 from hyperreel_amd import config as C
 from hyperreel_amd import scenes
 
@@ -34,22 +35,6 @@ FRAMES = {
 N3D_FULL = (2028, 2704)                     # conf/experiment/dataset/neural_3d.yaml:8 (commented out): #img_wh: [2704, 2028]
 KEYFRAME = ('technicolor_z_plane', 'neural_3d_z_plane', 'immersive_sphere')
 FOV = 40.0                                  # scenes.benchmark_rays
-
-
-def even_chunk(chunk, n):
-    """Host restatement of api_render.hip even_chunk: rays per launch of a call of n rays."""
-    if n <= chunk:
-        return chunk
-    k = -(-n // chunk)
-    return min(((-(-n // k)) + 63) & ~63, chunk)
-
-
-def redo_list_cap(n):
-    """Host restatement of api_render.hip redo_list_cap: list entries one call may fill (the buffer holds 1 << 22)."""
-    cap = (max(32768, n // 16) + 63) & ~63
-    if cap > n:
-        cap = (n + 63) & ~63
-    return min(cap, 1 << 22)
 
 
 def launch_starts(chunk, n):

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import Golden, golden_cases, initialiser_golden_cases, linf, sweep_cases
+from helpers import Golden, golden_cases, initialiser_golden_cases, linf, live_head_columns, sweep_cases
 from hyperreel_amd import config as C
 from hyperreel_amd import scenes
 
@@ -102,9 +102,8 @@ def test_mlp_head_matches_oracle(fns, case, precision):
     out = render_np(fn, g.rays, want=('head',))
     ref = orc.embed(g.rays)['_head_raw']
     # columns the path never reads are not computed (reported as 0): compare the live ones
-    from hyperreel_amd import plan
     hc = fn.model._hc
-    live = np.asarray(plan.live_head_columns(hc))
+    live = np.asarray(live_head_columns(hc))
     assert live.sum() == {'donerf_sphere_small': 11, 'neural_3d_z_plane_small': 15, 'technicolor_z_plane_small': 15}[case]
     mask = np.tile(live, hc.z_channels)
     assert np.all(out['head'][:, ~mask] == 0.0)

@@ -3,19 +3,13 @@ for the host by g++ into a test-only library) against the oracle, on the golden 
 This exercises the kernels' arithmetic and the YAML -> hr_config compiler without a GPU;
 the cross-lane parts, indexing and MFMA layouts are covered by the `-m gpu` tests."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from helpers import Golden, build_host_lib, golden_cases, linf, sweep_cases
+from helpers import Golden, golden_cases, linf, math_lib, sweep_cases
 from hyperreel_amd import plan
 from hyperreel_oracle import HyperReelOracle, eval_sh_bases_deg2, grid_sample_2d
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, 'host_math', 'hr_math_host.cpp')
-OUT = os.path.join(HERE, 'host_math', '_build', 'libhr_math_host.so')
 
 FP = C.POINTER(C.c_float)
 IP = C.POINTER(C.c_int)
@@ -27,13 +21,7 @@ def fp(a):
 
 @pytest.fixture(scope='module')
 def hm():
-    deps = [SRC, os.path.join(HERE, '..', 'hyperreel_amd', 'csrc', 'hr_math.h'),
-            os.path.join(HERE, '..', 'include', 'hyperreel_hip.h')]
-    build_host_lib(OUT, SRC, deps)
-    lib = C.CDLL(OUT)
-    lib.hm_normalize_time.restype = C.c_float
-    lib.hm_normalize_time.argtypes = [C.c_void_p, C.c_float]
-    return lib
+    return math_lib()
 
 
 def test_config_struct_layout_matches_c(hm):

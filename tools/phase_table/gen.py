@@ -54,7 +54,7 @@ def main():
     sd = scenes.make_state_dict(cfg, ds, [64, 64, 64], seed=1)
     grid = [int(v) for v in sd['model.color_model.net.gridSize']]
     hc = plan.compile_config(cfg, ds, grid, grid_dtype='fp16' if half else 'fp32')
-    # what analyse_live_columns (csrc/api_model.hip) does to preds_per_z / offsets is not replicated: dead columns only change P
+    # what hr_live_columns (csrc/hr_plan.h) does to preds_per_z / offsets is not replicated: dead columns only change P
     lines = []
     emit(hc, 'c', lines)
     Z = hc.z_channels
