@@ -117,14 +117,14 @@ static int check_train(hr_model* m, const float* rays, int64_t n)
     return HR_OK;
 }
 
-// per-sample workspace of the backward's phases (30 words per sample); grows on the first step and if the batch grows
+// per-sample workspace of the backward's phases (hr_tape_bind's HR_TAPE_WORDS per sample); grows on the first step and if the batch grows
 static int ensure_tape(hr_model* m, int64_t ns, hipStream_t st)
 {
     if (ns <= m->tape_samples) return HR_OK;
     HR_HIP(hipStreamSynchronize(st));
     m->tape.reset();
     m->tape_samples = 0;
-    HR_HIP(m->tape.alloc(sizeof(float) * 30 * (size_t)ns));       // HrTrainTape: 8 planes + 18 of taps + 3 of dL/d point + the grouped ray order (n_rays <= ns ints)
+    HR_HIP(m->tape.alloc(sizeof(float) * HR_TAPE_WORDS * (size_t)ns));
     m->tape_samples = ns;
     return HR_OK;
 }
@@ -211,8 +211,6 @@ int hr_mlp_train_forward(hr_model* m, const float* const* weights_dev, const flo
 
 static void fill_train_args(const hr_model* m, HrTrainArgs& a, const float* rays, const float* head, int64_t n, int white_bg)
 {
-    a.f_dist = a.f_points = a.f_weights = nullptr;
-    a.fx = nullptr;
     a = HrTrainArgs();
     a.cfg_dev = m->ucfg_dev;
     a.rays = rays;
@@ -301,20 +299,15 @@ int hr_train_backward(hr_model* m, const float* rays_dev, const float* head_dev,
     if (n_rays > 0 && (!head_dev || !d_rgb_dev || !d_head_dev)) return fail(HR_E_INVALID, "null head / d_rgb / d_head buffer");
     hipStream_t st = (hipStream_t)stream;
     if (!m->grad_pool) {              // packed accumulators: one allocation, made on the first step
-        size_t off_a[3] = {}, off_b[3] = {}, total = 0;
-        for (int j = 0; j < 3; ++j) {
-            const HrGridPlane& g = m->planes[j];
-            if (g.tex == 0) continue;
-            off_a[j] = total; total += (sizeof(float) * (size_t)g.aw * g.ah * g.tex + 255) & ~(size_t)255;
-            off_b[j] = total; total += (sizeof(float) * (size_t)g.bw * g.bh * g.tex + 255) & ~(size_t)255;
-        }
-        if (total > 0) {
-            HR_HIP(m->grad_pool.alloc(total));
-            m->grad_pool_bytes = total;
+        const HrGradPool pool = hr_grad_pool(m->planes, sizeof(float), 256);
+        if (pool.total > 0) {
+            HR_HIP(m->grad_pool.alloc(sizeof(float) * pool.total));
+            m->grad_pool_bytes = sizeof(float) * pool.total;
+            float* base = reinterpret_cast<float*>(static_cast<char*>(m->grad_pool));
             for (int j = 0; j < 3; ++j) {
                 if (m->planes[j].tex == 0) continue;
-                m->grad_a[j] = reinterpret_cast<float*>(m->grad_pool + off_a[j]);
-                m->grad_b[j] = reinterpret_cast<float*>(m->grad_pool + off_b[j]);
+                m->grad_a[j] = base + pool.off_a[j];
+                m->grad_b[j] = base + pool.off_b[j];
             }
         }
     }
@@ -330,15 +323,7 @@ int hr_train_backward(hr_model* m, const float* rays_dev, const float* head_dev,
     if (rc != HR_OK) return rc;
     HrTrainArgs a;
     fill_train_args(m, a, rays_dev, head_dev, n_rays, white_bg);
-    a.tape.ds = m->tape;
-    a.tape.src = reinterpret_cast<int*>(m->tape + ns);
-    a.tape.dfeat = m->tape + 2 * ns;
-    a.tape.dpre = m->tape + 3 * ns;      // 3 planes
-    a.tape.ddc = m->tape + 6 * ns;
-    a.tape.dts = m->tape + 7 * ns;
-    a.tape.taps = m->tape + 8 * ns;
-    a.tape.dp = m->tape + 26 * ns;
-    a.tape.perm = reinterpret_cast<int*>(m->tape + 29 * ns);
+    a.tape = hr_tape_bind(m->tape, ns);
     a.d_rgb = d_rgb_dev;
     a.d_head = d_head_dev;
     a.d_basis = d_basis;
@@ -350,14 +335,9 @@ int hr_train_backward(hr_model* m, const float* rays_dev, const float* head_dev,
     if (m->opt_train_det) {
         // deterministic mode: every accumulator of the step is a 64-bit fixed-point word of ONE scratch buffer (integer atomics: the
         // totals do not depend on the order of the adds); converted to the float buffers the rest of the step reads
-        size_t need = 0, off_a[3] = {}, off_b[3] = {}, n_a[3] = {}, n_b[3] = {};
-        for (int j = 0; j < 3; ++j) {
-            const HrGridPlane& g = m->planes[j];
-            if (g.tex == 0) continue;
-            n_a[j] = (size_t)g.aw * g.ah * g.tex; n_b[j] = (size_t)g.bw * g.bh * g.tex;
-            off_a[j] = need; need += n_a[j];
-            off_b[j] = need; need += n_b[j];
-        }
+        const HrGradPool pool = hr_grad_pool(m->planes, sizeof(long long), sizeof(long long));       // packed
+        const size_t *off_a = pool.off_a, *off_b = pool.off_b, *n_a = pool.n_a, *n_b = pool.n_b;
+        size_t need = pool.total;
         const size_t n_basis = basis_bytes / sizeof(float), off_basis = need;
         need += n_basis;
         const size_t n_ct = m->cfg.color_table_views > 0 ? 12 * (size_t)m->cfg.color_table_views : 0, off_ct = need;
@@ -450,9 +430,7 @@ int hr_train_rows_backward(hr_model* m, const float* rays_dev, const float* head
     a.rows = rows_scratch_dev;
     a.d_rows = d_rows_dev;
     a.d_head = d_head_dev;
-    a.tape.ds = m->tape;
-    a.tape.src = reinterpret_cast<int*>(m->tape + ns);
-    a.tape.dts = m->tape + 2 * ns;
+    a.tape = hr_tape_bind_rows(m->tape, ns);
     hr_launch_rows(m->coarse->cfg, a, (hipStream_t)stream);
     HR_HIP(hipGetLastError());
     return HR_OK;

@@ -137,7 +137,7 @@ struct HR_HIDDEN hr_model {
     size_t grad_fx_elems = 0;
     DevMem<HrFxUnit> fx_unit;            // ... and THIS model's fixed-point unit of the step (hr_train.h)
     int opt_train_det = 0;
-    DevMem<float> tape;                  // per-sample values between the backward's phases: 8 words x tape_samples
+    DevMem<float> tape;                  // per-sample values between the backward's phases: HR_TAPE_WORDS x tape_samples (hr_tape_bind)
     int64_t tape_samples = 0;
     // occupancy early-reject (hr_model_set_occupancy)
     DevMem<float> occ;

@@ -422,6 +422,28 @@ struct HrTrainPlan {
     unsigned tail_blocks;       // one thread per sample: hr_train_point_bwd_kernel (with taps), hr_train_dist_bwd_kernel
 };
 
+// The plane pairs' gradient accumulators in ONE pool, pair after pair, plane then line / time plane: offsets and counts in elements of
+// `elem` bytes, every accumulator starting on a multiple of `align` bytes (a multiple of elem).  The float pool of the default build
+// (256-byte starts) and the packed 64-bit fixed-point pool of the deterministic one.  A pair without channels takes nothing.
+struct HrGradPool {
+    size_t off_a[3], off_b[3], n_a[3], n_b[3];
+    size_t total;
+};
+static inline HrGradPool hr_grad_pool(const HrGridPlane* planes, size_t elem, size_t align)
+{
+    HrGradPool p = {};
+    const size_t step = align / elem;
+    for (int j = 0; j < 3; ++j) {
+        const HrGridPlane& g = planes[j];
+        if (g.tex == 0) continue;
+        p.n_a[j] = (size_t)g.aw * g.ah * g.tex;
+        p.n_b[j] = (size_t)g.bw * g.bh * g.tex;
+        p.off_a[j] = p.total; p.total += (p.n_a[j] + step - 1) / step * step;
+        p.off_b[j] = p.total; p.total += (p.n_b[j] + step - 1) / step * step;
+    }
+    return p;
+}
+
 static inline HrTrainPlan hr_train_plan(const hr_config& cfg, const HrGridPlane* planes, int ca_total, int n_basis_cols, const HrTrainPlanIn& in)
 {
     HrTrainPlan P = HrTrainPlan();

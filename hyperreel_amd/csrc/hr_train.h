@@ -16,9 +16,13 @@
 //   B  hr_sample_train_bwd   per (ray, sorted sample): feature-gather backward (texel scatter-adds, point gradient),
 //                            contraction / flow / offset backward
 //   C  hr_sample_distance_bwd  per (ray, original sample): intersection + head-activation backward
-// The device runs A with one thread per ray and B / C with one thread per sample (train_kernel.hip): 32x the threads
-// where the scatter-adds are.  Gradients of shared parameters are accumulated with HR_ATOMIC_ADD (hardware fp32
-// atomics on the device, plain adds in the single-threaded host build).
+// The device (train_kernel.hip) runs A in one of two mappings: one LANE per sample for rays of up to 64 samples
+// (hr_train_lanes_kernel: every shipped family's step; sort, scans and gather are lane exchanges) and one thread per ray above
+// (hr_ray_train, also the host build's form).  What the two share -- the per-sample colour, the per-ray colour transform, the alpha
+// derivative, the ray prologue -- is defined once below ("phase A's shared arithmetic") and called by both, so the host tests
+// see the arithmetic that ships.  B runs with 16 lanes per sample, one texel channel each, and C with one thread per sample.
+// Gradients of shared parameters are accumulated with HR_ATOMIC_ADD (hardware fp32 atomics on the device, plain adds in the
+// single-threaded host build).
 #ifndef HR_TRAIN_H
 #define HR_TRAIN_H
 
@@ -112,6 +116,29 @@ struct HrTrainTape {
     float* dp;        // dL / d point, 3 planes of n_rays * Z (phase B -> hr_sample_train_point_bwd)
     int* perm;        // keyframe nets, device: the batch's ray indices grouped by keyframe row (hr_train_bucket_kernel), n_rays
 };
+// The tape in one workspace: every field with its planes of ns = n_rays * Z words, in the order they lie there (taps: 3 axes x
+// 6 values; perm's n_rays ints fit one plane).  The words per sample and the binder both come from this list.
+#define HR_TAPE_FIELDS(X) X(float, ds, 1) X(int, src, 1) X(float, dfeat, 1) X(float, dpre, 3) X(float, ddc, 1) X(float, dts, 1) \
+                          X(float, taps, 18) X(float, dp, 3) X(int, perm, 1)
+#define HR_TAPE_COUNT(type, field, planes) + planes
+constexpr int HR_TAPE_WORDS = 0 HR_TAPE_FIELDS(HR_TAPE_COUNT);
+#undef HR_TAPE_COUNT
+inline HrTrainTape hr_tape_bind(float* base, int64_t ns)
+{
+    HrTrainTape t;
+    int64_t plane = 0;
+#define HR_TAPE_BIND(type, field, planes) t.field = reinterpret_cast<type*>(base + plane * ns); plane += planes;
+    HR_TAPE_FIELDS(HR_TAPE_BIND)
+#undef HR_TAPE_BIND
+    return t;
+}
+// the coarse level of a cascade (hr_ray_rows ...) keeps three planes: ds, src, dts
+inline HrTrainTape hr_tape_bind_rows(float* base, int64_t ns)
+{
+    HrTrainTape t = HrTrainTape();
+    t.ds = base; t.src = reinterpret_cast<int*>(base + ns); t.dts = base + 2 * ns;
+    return t;
+}
 
 // Workgroup-private accumulators (LDS, device only) for a texel range [lo, lo + n) of each plane pair's line / time plane: the
 // whole line of a static net, the two keyframe rows a group of rays blends between for a keyframe net.  Taps outside the
@@ -747,20 +774,25 @@ HR_FN void hr_train_fold_basis(const hr_config& c, const HrTrainArgs& a, const f
 }
 
 // Per-ray quantities every phase recomputes from the ray itself
+HR_FN void hr_train_ray_od(const hr_config& c, const float* r, float* ro, float* rd)
+{
+    for (int i = 0; i < 3; ++i) { ro[i] = r[i] - c.isect_origin[i]; rd[i] = r[3 + i]; }
+}
 struct HrTrainRay {
     float ro[3], rd[3], oc[3];
-    float time_off;
+    float base_t, time_off;
     hr_axis_tap_g tap_t;
 };
 HR_FN HrTrainRay hr_train_ray(const hr_config& c, const float* r)
 {
     HrTrainRay q;
-    for (int i = 0; i < 3; ++i) { q.ro[i] = r[i] - c.isect_origin[i]; q.rd[i] = r[3 + i]; q.oc[i] = 0.0f; }
+    hr_train_ray_od(c, r, q.ro, q.rd);
+    for (int i = 0; i < 3; ++i) q.oc[i] = 0.0f;
     if (c.contract_type != HR_CONTRACT_IDENTITY) hr_contract_point(c, q.ro[0], q.ro[1], q.ro[2], q.oc);
-    float base_t = 0.0f;
+    q.base_t = 0.0f;
     q.time_off = 0.0f;
-    if (c.advect) { base_t = hr_base_time(c, r[c.ray_dim - 1]); q.time_off = r[c.ray_dim - 1] - base_t; }
-    q.tap_t = hr_make_tap_g(c.video ? hr_normalize_time(c, base_t) : 0.0f, c.video ? c.num_keyframes : 2);
+    if (c.advect) { q.base_t = hr_base_time(c, r[c.ray_dim - 1]); q.time_off = r[c.ray_dim - 1] - q.base_t; }
+    q.tap_t = hr_make_tap_g(c.video ? hr_normalize_time(c, q.base_t) : 0.0f, c.video ? c.num_keyframes : 2);
     return q;
 }
 
@@ -775,6 +807,163 @@ HR_FN int hr_train_time_row(const hr_config& c, const float* r)
     const float ix = ((g + 1.0f) / 2.0f) * (float)(n - 1);
     const float f0 = fminf(fmaxf(floorf(ix), -1.0f), (float)(n - 1));
     return (int)f0;
+}
+
+// ---------------------------------------------------------------- phase A's shared arithmetic
+// What the two mappings of phase A have in common (hr_ray_train below: one thread per ray; hr_train_lanes_kernel in
+// train_kernel.hip: one lane per sample), as functions of values: how the samples of a ray reach them -- arrays and loops, or
+// lanes and scans -- is the mappings' business.
+
+// Stable insertion sort of n (value, index) pairs by value (sort_z, intersect_utils.py:12-16)
+HR_FN void hr_insertion_sort_kv(float* v, int* id, int n)
+{
+    for (int i = 1; i < n; ++i) {
+        const float vi = v[i];
+        const int si = id[i];
+        int j = i - 1;
+        while (j >= 0 && v[j] > vi) { v[j + 1] = v[j]; id[j + 1] = id[j]; --j; }
+        v[j + 1] = vi; id[j + 1] = si;
+    }
+}
+
+// Colour of one sample from its decoded pre-activations.  raw: the SH clamp / sigmoid (0 where the sample's weight is below the
+// threshold: `app` false), sc: color_scale + 1, rr = raw * sc + color_shift, the scale and shift from the sample's head row hk
+HR_FN void hr_sample_color(const hr_config& c, const float* pre, bool app, const float* hk, float* raw, float* sc, float* rr)
+{
+    HR_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        raw[i] = 0.0f;
+        sc[i] = 1.0f;
+        if (app) raw[i] = (c.shading == HR_SHADING_SH) ? fmaxf(pre[i] + 0.5f, 0.0f) : 1.0f / (1.0f + expf(-pre[i]));
+        rr[i] = raw[i];
+        if (c.f_color_scale.offset >= 0) {
+            sc[i] = hr_apply_act(c.f_color_scale.act, hk[c.f_color_scale.offset + i]) + 1.0f;
+            rr[i] = raw[i] * sc[i] + hr_apply_act(c.f_color_shift.act, hk[c.f_color_shift.offset + i]);
+        }
+    }
+}
+
+// ... and its backward: g = dL/d (the ray's un-transformed colour), so dL/d rr = wgt * g.  Adds the color_scale / color_shift
+// gradients to the sample's d_head row dhk and returns dL/d pre
+HR_FN void hr_sample_color_bwd(const hr_config& c, float wgt, const float* g, const float* raw, const float* sc, const float* pre, bool app,
+                               const float* hk, float* dhk, float* dpre)
+{
+    HR_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        const float dr = wgt * g[i];
+        if (c.f_color_scale.offset >= 0) {
+            const float hs = hk[c.f_color_scale.offset + i], hh = hk[c.f_color_shift.offset + i];
+            dhk[c.f_color_scale.offset + i] += dr * raw[i] * hr_act_grad(c.f_color_scale.act, hs);
+            dhk[c.f_color_shift.offset + i] += dr * hr_act_grad(c.f_color_shift.act, hh);
+        }
+        const float draw = dr * sc[i];
+        if (!app) dpre[i] = 0.0f;
+        else if (c.shading == HR_SHADING_SH) dpre[i] = (pre[i] + 0.5f > 0.0f) ? draw : 0.0f;
+        else dpre[i] = draw * raw[i] * (1.0f - raw[i]);
+    }
+}
+
+// The per-ray transform of the composited colour: at most one of three forms applies
+enum { HR_RAY_COLOR_NONE = 0,
+       HR_RAY_COLOR_HEAD_MATRIX,   // transform_color_one with the 3x3 and shift from sample 0's head values (`color_transform_global`)
+       HR_RAY_COLOR_HEAD_SCALE,    // scale_shift_color_one (tensorf_utils.py:275-281): sample 0's head values
+       HR_RAY_COLOR_TABLE };       // transform_color_one with the ray's camera's row of the colour table (tensorf_utils.py:308-320, point.py:588-594)
+struct HrRayColor {
+    int form;
+    float tcol[9];                 // the activated 3x3 (the two matrix forms)
+    float gscale[3];               // scale + 1 (HEAD_SCALE)
+    int cam;                       // clamped camera id (TABLE)
+};
+// cpre: the composited colour; head: the ray's head (sample 0's row first).  Returns the final colour in col
+HR_FN void hr_ray_color(const hr_config& c, const HrTrainArgs& a, const float* r, const float* head, const float* cpre, float* col, HrRayColor& q)
+{
+    const hr_head_field& fs = c.f_color_scale_global;
+    const hr_head_field& fh = c.f_color_shift_global;
+    const float c0 = cpre[0], c1 = cpre[1], c2 = cpre[2];
+    q.form = HR_RAY_COLOR_NONE;
+    q.cam = 0;
+    HR_UNROLL
+    for (int i = 0; i < 9; ++i) q.tcol[i] = 0.0f;
+    HR_UNROLL
+    for (int i = 0; i < 3; ++i) { q.gscale[i] = 1.0f; col[i] = cpre[i]; }
+    if (fs.offset >= 0 && fs.channels == 9) q.form = HR_RAY_COLOR_HEAD_MATRIX;
+    else if (fs.offset >= 0) q.form = HR_RAY_COLOR_HEAD_SCALE;
+    else if (a.color_table) q.form = HR_RAY_COLOR_TABLE;
+    if (q.form == HR_RAY_COLOR_HEAD_SCALE) {
+        HR_UNROLL
+        for (int i = 0; i < 3; ++i) {
+            q.gscale[i] = hr_apply_act(fs.act, head[fs.offset + i]) + 1.0f;
+            col[i] = cpre[i] * q.gscale[i] + hr_apply_act(fh.act, head[fh.offset + i]);
+        }
+    } else if (q.form != HR_RAY_COLOR_NONE) {
+        const bool table = q.form == HR_RAY_COLOR_TABLE;
+        const float* e = head + fs.offset;         // the nine matrix entries, then (table) the three shifts
+        if (table) {
+            q.cam = (int)rintf(r[c.ray_dim - 2]);
+            q.cam = q.cam < 0 ? 0 : (q.cam > c.color_table_views - 1 ? c.color_table_views - 1 : q.cam);
+            e = a.color_table + 12 * q.cam;
+        }
+        HR_UNROLL
+        for (int i = 0; i < 9; ++i) q.tcol[i] = hr_apply_act(table ? c.color_table_t_act : fs.act, e[i]);
+        HR_UNROLL
+        for (int i = 0; i < 3; ++i) {
+            const float n = cpre[i] + ((c0 * q.tcol[3 * i] + c1 * q.tcol[3 * i + 1]) + c2 * q.tcol[3 * i + 2]);
+            col[i] = n + (table ? hr_apply_act(c.color_table_s_act, e[9 + i]) : hr_apply_act(fh.act, head[fh.offset + i]));
+        }
+    }
+}
+
+// ... and its backward: g (dL/d final colour) becomes dL/d cpre.  The `owner` of the ray -- hr_ray_train's thread, sample 0's lane of
+// the lanes kernel -- also adds the gradients of the transform's own parameters: sample 0's d_head row dh0, or the colour table's
+HR_FN void hr_ray_color_bwd(const hr_config& c, const HrTrainArgs& a, const float* head, const HrRayColor& q, const float* cpre, bool owner,
+                            float* dh0, float* g)
+{
+    const hr_head_field& fs = c.f_color_scale_global;
+    const hr_head_field& fh = c.f_color_shift_global;
+    if (q.form == HR_RAY_COLOR_HEAD_SCALE) {
+        HR_UNROLL
+        for (int i = 0; i < 3; ++i) {
+            if (owner) {
+                dh0[fs.offset + i] += g[i] * cpre[i] * hr_act_grad(fs.act, head[fs.offset + i]);
+                dh0[fh.offset + i] += g[i] * hr_act_grad(fh.act, head[fh.offset + i]);
+            }
+            g[i] = g[i] * q.gscale[i];             // everything upstream sees the gradient of the un-scaled colour
+        }
+    } else if (q.form != HR_RAY_COLOR_NONE) {
+        const bool table = q.form == HR_RAY_COLOR_TABLE;
+        const float* e = table ? a.color_table + 12 * q.cam : nullptr;
+        hr_acc_t* de = table ? a.d_color_table + 12 * q.cam : nullptr;
+        float gn[3] = {g[0], g[1], g[2]};
+        HR_UNROLL
+        for (int i = 0; i < 3; ++i) {
+            if (owner) {
+                if (table) HR_ATOMIC_ADD(de + 9 + i, g[i] * hr_act_grad(c.color_table_s_act, e[9 + i]));
+                else dh0[fh.offset + i] += g[i] * hr_act_grad(fh.act, head[fh.offset + i]);
+            }
+            HR_UNROLL
+            for (int j = 0; j < 3; ++j) {
+                if (owner) {
+                    if (table) HR_ATOMIC_ADD(de + 3 * i + j, g[i] * cpre[j] * hr_act_grad(c.color_table_t_act, e[3 * i + j]));
+                    else dh0[fs.offset + 3 * i + j] += g[i] * cpre[j] * hr_act_grad(fs.act, head[fs.offset + 3 * i + j]);
+                }
+                gn[j] += g[i] * q.tcol[3 * i + j];
+            }
+        }
+        g[0] = gn[0]; g[1] = gn[1]; g[2] = gn[2];
+    }
+}
+
+// Backward of alpha = 1 - exp(-sigma delta distance_scale), w = alpha T, T_next = T ((1 - alpha) + 1e-10), for one sample: dw = dL/d w,
+// S = the sum of dw_j w_j over the ray's later samples.  Returns dL/d density feature and dL/d delta
+HR_FN void hr_alpha_bwd(const hr_config& c, float dw, float T, float S, float alpha, float delta, float sigma, float feat, bool valid,
+                        float* dfeat, float* ddelta)
+{
+    const float inc = (1.0f - alpha) + 1e-10f;
+    const float dalpha = dw * T - S / inc;
+    const float e = 1.0f - alpha;
+    const float dsigma = dalpha * e * (delta * c.distance_scale);
+    *dfeat = valid ? dsigma * hr_density_grad(c, feat) : 0.0f;
+    *ddelta = dalpha * e * sigma * c.distance_scale;
 }
 
 // Phase B: the sample of sorted rank k of `ray`.  M / dM: the ray's decode matrix and its gradient accumulator (3 * CA).
@@ -853,9 +1042,8 @@ HR_FN void hr_sample_train_point_bwd(const hr_config& c, const HrTrainArgs& a, i
 HR_FN void hr_sample_train_dist_bwd(const hr_config& c, const HrTrainArgs& a, int64_t ray, int k)
 {
     const int64_t s = ray * c.z_channels + k;
-    const float* r = a.rays + ray * c.ray_dim;
-    const float ro[3] = {r[0] - c.isect_origin[0], r[1] - c.isect_origin[1], r[2] - c.isect_origin[2]};
-    const float rd[3] = {r[3], r[4], r[5]};
+    float ro[3], rd[3];
+    hr_train_ray_od(c, a.rays + ray * c.ray_dim, ro, rd);
     hr_sample_distance_bwd(c, a.head + s * c.preds_per_z, k, ro, rd, a.tape.dts[s], a.d_head + s * c.preds_per_z);
 }
 
@@ -866,13 +1054,11 @@ HR_FN void hr_ray_train(const hr_config& c, const HrTrainArgs& a, int64_t ray)
     const int Z = c.z_channels, P = c.preds_per_z, CA = a.ca_total;
     const float* r = a.rays + ray * c.ray_dim;
     const float* head = a.head + ray * (int64_t)Z * P;
-    const float ro[3] = {r[0] - c.isect_origin[0], r[1] - c.isect_origin[1], r[2] - c.isect_origin[2]};
-    const float rd[3] = {r[3], r[4], r[5]};
-    const float t_ray = r[c.ray_dim - 1];
+    const HrTrainRay q = hr_train_ray(c, r);
 
     // decode matrix of the ray (RGB: basis_mat rows; SH: basis rows folded with the view direction's SH basis)
     float sh[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (c.shading == HR_SHADING_SH) hr_sh_deg2(rd[0], rd[1], rd[2], sh);
+    if (c.shading == HR_SHADING_SH) hr_sh_deg2(q.rd[0], q.rd[1], q.rd[2], sh);
     float M[3 * HR_TRAIN_MAX_CA];
     for (int cc = 0; cc < 3; ++cc)
         for (int pos = 0; pos < CA; ++pos) M[cc * CA + pos] = hr_train_decode_coef(c, a, sh, cc, pos);
@@ -880,32 +1066,20 @@ HR_FN void hr_ray_train(const hr_config& c, const HrTrainArgs& a, int64_t ray)
     // ---- forward
     float ds[ZP];                 // sorted pre-contraction distances
     int src[ZP];                  // original sample index of each rank
-    for (int k = 0; k < Z; ++k) { ds[k] = hr_sample_distance(c, head + k * P, k, ro, rd); src[k] = k; }
-    if (c.sort)
-        for (int i = 1; i < Z; ++i) {             // stable insertion sort (sort_z, intersect_utils.py:12-16)
-            const float v = ds[i];
-            const int s = src[i];
-            int j = i - 1;
-            while (j >= 0 && ds[j] > v) { ds[j + 1] = ds[j]; src[j + 1] = src[j]; --j; }
-            ds[j + 1] = v; src[j + 1] = s;
-        }
-    float oc[3] = {0.f, 0.f, 0.f};
-    if (c.contract_type != HR_CONTRACT_IDENTITY) hr_contract_point(c, ro[0], ro[1], ro[2], oc);
-    float base_t = 0.0f, time_off = 0.0f;
-    if (c.advect) { base_t = hr_base_time(c, t_ray); time_off = t_ray - base_t; }
-    const hr_axis_tap_g tap_t = hr_make_tap_g(c.video ? hr_normalize_time(c, base_t) : 0.0f, c.video ? c.num_keyframes : 2);
+    for (int k = 0; k < Z; ++k) { ds[k] = hr_sample_distance(c, head + k * P, k, q.ro, q.rd); src[k] = k; }
+    if (c.sort) hr_insertion_sort_kv(ds, src, Z);
 
     float dc[ZP], feat[ZP], pre[ZP][3], trans[ZP], alpha[ZP], wgt[ZP];
     bool valid[ZP];
     for (int k = 0; k < Z; ++k) {
         float p[3];
-        hr_sample_point(c, head + k * P, ds[k], ro, rd, oc, time_off, p, &dc[k]);
+        hr_sample_point(c, head + k * P, ds[k], q.ro, q.rd, q.oc, q.time_off, p, &dc[k]);
         valid[k] = hr_sample_valid(c, p, dc[k]);
         feat[k] = 0.0f; pre[k][0] = 0.0f; pre[k][1] = 0.0f; pre[k][2] = 0.0f;
         if (valid[k]) {
             hr_axis_tap_g ax[3];
             for (int i = 0; i < 3; ++i) ax[i] = hr_make_tap_g(hr_normalize_coord(c, p[i], i), c.grid[i]);
-            hr_train_gather(a, ax, tap_t, M, CA, &feat[k], pre[k]);
+            hr_train_gather(a, ax, q.tap_t, M, CA, &feat[k], pre[k]);
         }
     }
     float T = 1.0f, acc_w = 0.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
@@ -916,100 +1090,24 @@ HR_FN void hr_ray_train(const hr_config& c, const HrTrainArgs& a, int64_t ray)
         trans[k] = T;
         wgt[k] = alpha[k] * T;
         T = T * ((1.0f - alpha[k]) + 1e-10f);
-        float rr[3] = {0.f, 0.f, 0.f};
-        if (wgt[k] > c.weight_thresh)
-            for (int i = 0; i < 3; ++i)
-                rr[i] = (c.shading == HR_SHADING_SH) ? fmaxf(pre[k][i] + 0.5f, 0.0f) : 1.0f / (1.0f + expf(-pre[k][i]));
-        if (c.f_color_scale.offset >= 0) {
-            const float* hk = head + k * P;
-            for (int i = 0; i < 3; ++i)
-                rr[i] = rr[i] * (hr_apply_act(c.f_color_scale.act, hk[c.f_color_scale.offset + i]) + 1.0f) +
-                        hr_apply_act(c.f_color_shift.act, hk[c.f_color_shift.offset + i]);
-        }
+        float raw[3], sc[3], rr[3];
+        hr_sample_color(c, pre[k], wgt[k] > c.weight_thresh, head + k * P, raw, sc, rr);
         c0 += wgt[k] * rr[0]; c1 += wgt[k] * rr[1]; c2 += wgt[k] * rr[2];
         acc_w += wgt[k];
     }
     if (a.white_bg) { const float bg = 1.0f - acc_w; c0 += bg; c1 += bg; c2 += bg; }
-    const float cpre[3] = {c0, c1, c2};          // the composited colour before the per-ray scale / shift
-    float gscale[3] = {1.0f, 1.0f, 1.0f};
-    const bool head_transform = c.f_color_scale_global.offset >= 0 && c.f_color_scale_global.channels == 9;
-    float thead[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (head_transform) {                        // transform_color_one, the matrix from the head (`color_transform_global`)
-        const hr_head_field& fs = c.f_color_scale_global;
-        const hr_head_field& fh = c.f_color_shift_global;
-        for (int i = 0; i < 9; ++i) thead[i] = hr_apply_act(fs.act, head[fs.offset + i]);
-        const float n0 = c0 + ((c0 * thead[0] + c1 * thead[1]) + c2 * thead[2]);
-        const float n1 = c1 + ((c0 * thead[3] + c1 * thead[4]) + c2 * thead[5]);
-        const float n2 = c2 + ((c0 * thead[6] + c1 * thead[7]) + c2 * thead[8]);
-        c0 = n0 + hr_apply_act(fh.act, head[fh.offset + 0]);
-        c1 = n1 + hr_apply_act(fh.act, head[fh.offset + 1]);
-        c2 = n2 + hr_apply_act(fh.act, head[fh.offset + 2]);
-    }
-    else if (c.f_color_scale_global.offset >= 0) {    // scale_shift_color_one (tensorf_utils.py:275-281): sample 0's head values
-        const hr_head_field& fs = c.f_color_scale_global;
-        const hr_head_field& fh = c.f_color_shift_global;
-        for (int i = 0; i < 3; ++i) gscale[i] = hr_apply_act(fs.act, head[fs.offset + i]) + 1.0f;
-        c0 = c0 * gscale[0] + hr_apply_act(fh.act, head[fh.offset + 0]);
-        c1 = c1 * gscale[1] + hr_apply_act(fh.act, head[fh.offset + 1]);
-        c2 = c2 * gscale[2] + hr_apply_act(fh.act, head[fh.offset + 2]);
-    }
-    else if (a.color_table) {                    // transform_color_one (tensorf_utils.py:308-320, point.py:588-594)
-        int id = (int)rintf(r[c.ray_dim - 2]);
-        id = id < 0 ? 0 : (id > c.color_table_views - 1 ? c.color_table_views - 1 : id);
-        const float* e = a.color_table + 12 * id;
-        float t[9];
-        for (int i = 0; i < 9; ++i) t[i] = hr_apply_act(c.color_table_t_act, e[i]);
-        const float n0 = c0 + ((c0 * t[0] + c1 * t[1]) + c2 * t[2]);
-        const float n1 = c1 + ((c0 * t[3] + c1 * t[4]) + c2 * t[5]);
-        const float n2 = c2 + ((c0 * t[6] + c1 * t[7]) + c2 * t[8]);
-        c0 = n0 + hr_apply_act(c.color_table_s_act, e[9]);
-        c1 = n1 + hr_apply_act(c.color_table_s_act, e[10]);
-        c2 = n2 + hr_apply_act(c.color_table_s_act, e[11]);
-    }
-    if (a.rgb) { a.rgb[ray * 3 + 0] = c0; a.rgb[ray * 3 + 1] = c1; a.rgb[ray * 3 + 2] = c2; }
+    const float cpre[3] = {c0, c1, c2};          // the composited colour before the per-ray transform
+    float col[3];
+    HrRayColor rc;
+    hr_ray_color(c, a, r, head, cpre, col, rc);
+    if (a.rgb) { a.rgb[ray * 3 + 0] = col[0]; a.rgb[ray * 3 + 1] = col[1]; a.rgb[ray * 3 + 2] = col[2]; }
     if (!a.d_rgb) return;
 
     // ---- backward
     float g[3] = {a.d_rgb[ray * 3 + 0], a.d_rgb[ray * 3 + 1], a.d_rgb[ray * 3 + 2]};
     float* dhead = a.d_head + ray * (int64_t)Z * P;
     for (int i = 0; i < Z * P; ++i) dhead[i] = 0.0f;
-    if (head_transform) {
-        const hr_head_field& fs = c.f_color_scale_global;
-        const hr_head_field& fh = c.f_color_shift_global;
-        float gn[3] = {g[0], g[1], g[2]};
-        for (int i = 0; i < 3; ++i) {
-            dhead[fh.offset + i] += g[i] * hr_act_grad(fh.act, head[fh.offset + i]);
-            for (int j = 0; j < 3; ++j) {
-                dhead[fs.offset + 3 * i + j] += g[i] * cpre[j] * hr_act_grad(fs.act, head[fs.offset + 3 * i + j]);
-                gn[j] += g[i] * thead[3 * i + j];
-            }
-        }
-        g[0] = gn[0]; g[1] = gn[1]; g[2] = gn[2];
-    }
-    else if (c.f_color_scale_global.offset >= 0) {
-        const hr_head_field& fs = c.f_color_scale_global;
-        const hr_head_field& fh = c.f_color_shift_global;
-        for (int i = 0; i < 3; ++i) {
-            dhead[fs.offset + i] += g[i] * cpre[i] * hr_act_grad(fs.act, head[fs.offset + i]);
-            dhead[fh.offset + i] += g[i] * hr_act_grad(fh.act, head[fh.offset + i]);
-            g[i] = g[i] * gscale[i];             // everything below sees the gradient of the un-scaled colour
-        }
-    }
-    else if (a.color_table) {
-        int id = (int)rintf(r[c.ray_dim - 2]);
-        id = id < 0 ? 0 : (id > c.color_table_views - 1 ? c.color_table_views - 1 : id);
-        const float* e = a.color_table + 12 * id;
-        hr_acc_t* de = a.d_color_table + 12 * id;
-        float gn[3] = {g[0], g[1], g[2]};
-        for (int i = 0; i < 3; ++i) {
-            HR_ATOMIC_ADD(de + 9 + i, g[i] * hr_act_grad(c.color_table_s_act, e[9 + i]));
-            for (int j = 0; j < 3; ++j) {
-                HR_ATOMIC_ADD(de + 3 * i + j, g[i] * cpre[j] * hr_act_grad(c.color_table_t_act, e[3 * i + j]));
-                gn[j] += g[i] * hr_apply_act(c.color_table_t_act, e[3 * i + j]);
-            }
-        }
-        g[0] = gn[0]; g[1] = gn[1]; g[2] = gn[2];
-    }
+    hr_ray_color_bwd(c, a, head, rc, cpre, true, dhead, g);
     const float gsum = a.white_bg ? (g[0] + g[1] + g[2]) : 0.0f;
     float ddc[ZP];                // dL / d final distance
     float dfeat[ZP];
@@ -1017,43 +1115,18 @@ HR_FN void hr_ray_train(const hr_config& c, const HrTrainArgs& a, int64_t ray)
     float S = 0.0f;               // sum over later samples of dw_j * w_j
     for (int k = Z - 1; k >= 0; --k) {
         // colour of the sample again (cheap) for dw = g . rgb_k - [white] sum(g)
-        float rr[3] = {0.f, 0.f, 0.f}, raw[3] = {0.f, 0.f, 0.f};
         const bool app = wgt[k] > c.weight_thresh;
-        if (app)
-            for (int i = 0; i < 3; ++i)
-                raw[i] = (c.shading == HR_SHADING_SH) ? fmaxf(pre[k][i] + 0.5f, 0.0f) : 1.0f / (1.0f + expf(-pre[k][i]));
-        const float* hk = head + k * P;
-        float* dhk = dhead + k * P;
-        float dpre[3];
-        for (int i = 0; i < 3; ++i) {
-            float sc = 1.0f;
-            rr[i] = raw[i];
-            const float dr = wgt[k] * g[i];
-            if (c.f_color_scale.offset >= 0) {
-                const float hs = hk[c.f_color_scale.offset + i], hh = hk[c.f_color_shift.offset + i];
-                sc = hr_apply_act(c.f_color_scale.act, hs) + 1.0f;
-                rr[i] = raw[i] * sc + hr_apply_act(c.f_color_shift.act, hh);
-                dhk[c.f_color_scale.offset + i] += dr * raw[i] * hr_act_grad(c.f_color_scale.act, hs);
-                dhk[c.f_color_shift.offset + i] += dr * hr_act_grad(c.f_color_shift.act, hh);
-            }
-            const float draw = dr * sc;
-            if (!app) dpre[i] = 0.0f;
-            else if (c.shading == HR_SHADING_SH) dpre[i] = (pre[k][i] + 0.5f > 0.0f) ? draw : 0.0f;
-            else dpre[i] = draw * raw[i] * (1.0f - raw[i]);
-        }
+        float raw[3], sc[3], rr[3], dpre[3];
+        hr_sample_color(c, pre[k], app, head + k * P, raw, sc, rr);
+        hr_sample_color_bwd(c, wgt[k], g, raw, sc, pre[k], app, head + k * P, dhead + k * P, dpre);
         pre[k][0] = dpre[0]; pre[k][1] = dpre[1]; pre[k][2] = dpre[2];          // reuse the storage for dL/d pre
         const float dw = (g[0] * rr[0] + g[1] * rr[1] + g[2] * rr[2]) - gsum;
-        const float inc = (1.0f - alpha[k]) + 1e-10f;
-        const float dalpha = dw * trans[k] - S / inc;
-        S += dw * wgt[k];
-        // alpha = 1 - exp(-sigma * delta * scale)
         const float delta = (k == Z - 1) ? 1e10f : (dc[k + 1] - dc[k]);
         const float sigma = valid[k] ? hr_density(c, feat[k]) : 0.0f;
-        const float e = 1.0f - alpha[k];
-        const float dsigma = dalpha * e * (delta * c.distance_scale);
-        dfeat[k] = valid[k] ? dsigma * hr_density_grad(c, feat[k]) : 0.0f;
+        float ddelta;
+        hr_alpha_bwd(c, dw, trans[k], S, alpha[k], delta, sigma, feat[k], valid[k], &dfeat[k], &ddelta);
+        S += dw * wgt[k];
         if (k < Z - 1) {
-            const float ddelta = dalpha * e * sigma * c.distance_scale;
             ddc[k + 1] += ddelta;
             ddc[k] -= ddelta;
         }
@@ -1099,14 +1172,7 @@ HR_FN void hr_ray_rows(const hr_config& c, const HrRowsArgs& a, int64_t ray)
     float ds[ZP];
     int src[ZP];
     for (int k = 0; k < Z; ++k) { ds[k] = hr_sample_distance(c, head + k * P, k, q.ro, q.rd); src[k] = k; }
-    if (c.sort)
-        for (int i = 1; i < Z; ++i) {
-            const float v = ds[i];
-            const int s = src[i];
-            int j = i - 1;
-            while (j >= 0 && ds[j] > v) { ds[j + 1] = ds[j]; src[j + 1] = src[j]; --j; }
-            ds[j + 1] = v; src[j + 1] = s;
-        }
+    if (c.sort) hr_insertion_sort_kv(ds, src, Z);
     for (int k = 0; k < Z; ++k) {
         float p[3], dc;
         hr_sample_point(c, head + k * P, ds[k], q.ro, q.rd, q.oc, q.time_off, p, &dc);
@@ -1143,9 +1209,8 @@ HR_FN void hr_sample_rows_bwd(const hr_config& c, const HrRowsArgs& a, int64_t r
 HR_FN void hr_sample_rows_dist_bwd(const hr_config& c, const HrRowsArgs& a, int64_t ray, int k)
 {
     const int64_t s = ray * c.z_channels + k;
-    const float* r = a.rays + ray * c.ray_dim;
-    const float ro[3] = {r[0] - c.isect_origin[0], r[1] - c.isect_origin[1], r[2] - c.isect_origin[2]};
-    const float rd[3] = {r[3], r[4], r[5]};
+    float ro[3], rd[3];
+    hr_train_ray_od(c, a.rays + ray * c.ray_dim, ro, rd);
     hr_sample_distance_bwd(c, a.head + s * c.preds_per_z, k, ro, rd, a.tape.dts[s], a.d_head + s * c.preds_per_z);
 }
 

@@ -4,8 +4,8 @@
 //
 // Mapping: a training batch is 16 384 rays (conf/experiment/training/*.yaml: batch_size), i.e. 0.5 M samples against
 // the 20 M of a rendered frame, so the step is latency- and atomics-bound rather than bandwidth-bound.
-//   phase A (forward, compositing backward): one thread per ray, 64-thread workgroups -> one wavefront on each of the
-//     256 CUs; the ray's samples are walked with the intermediates in registers / scratch;
+//   phase A (forward, compositing backward): one lane per (ray, sample) for rays of up to 64 samples (hr_train_lanes_kernel), one
+//     thread per ray above (hr_train_kernel: the ray's samples are walked with the intermediates in registers / scratch);
 //   phase B (gather backward): 16 lanes per (ray, sample), ONE TEXEL CHANNEL PER LANE: texel gradients go straight to
 //     HBM through hardware fp32 atomics (global_atomic_add_f32) on the channel-last packed layout, and the channels of a
 //     tap are one contiguous 32..64-byte run per instruction.  The memory system retires atomics per cache-line request,
@@ -42,8 +42,9 @@ __global__ __launch_bounds__(64) void hr_train_kernel(const hr_config* __restric
 // ---------------------------------------------------------------------------------------------------------
 // Phase A, one LANE per (ray, sample) -- the mapping of the render kernels (sample_core.inc): the ZP samples of a ray sit in
 // adjacent lanes, the sort is a bitonic network over lane exchanges, the transmittance an inclusive product scan, the colour a
-// butterfly sum, and the compositing backward one suffix-sum scan.  Same arithmetic as hr_ray_train (which stays: ZP > 64,
-// and the host build the CPU tests check against torch.autograd), with the forward's gather done by the render path's
+// butterfly sum, and the compositing backward one suffix-sum scan.  The per-sample and per-ray arithmetic is hr_ray_train's, by
+// calling the same functions (hr_train.h, "phase A's shared arithmetic"; hr_ray_train stays for ZP > 64 and as the host build the
+// CPU tests check against torch.autograd), with the forward's gather done by the render path's
 // cooperative gather (hr_gather_844 / hr_gather_plane_coop: same values).  32x the lanes of the one-thread-per-ray walk and
 // no per-lane scratch arrays.
 template <int ZP>
@@ -97,22 +98,16 @@ __global__ __launch_bounds__(256) void hr_train_lanes_kernel(const hr_config* __
     const float* r = a.rays + rr_ * c.ray_dim;
     const float* head = a.head + rr_ * (int64_t)Z * P;
     const float* hk = head + (lane_ok ? k : 0) * P;
-    const float ro[3] = {r[0] - c.isect_origin[0], r[1] - c.isect_origin[1], r[2] - c.isect_origin[2]};
-    const float rd[3] = {r[3], r[4], r[5]};
-    const float t_ray = r[c.ray_dim - 1];
+    const HrTrainRay q = hr_train_ray(c, r);
 
     // ---- forward
     float dist = __builtin_inff();
     int src = k;
-    if (lane_ok) dist = hr_sample_distance(c, hk, k, ro, rd);
+    if (lane_ok) dist = hr_sample_distance(c, hk, k, q.ro, q.rd);
     if (c.sort) hr_bitonic_sort_kv<ZP>(dist, src, k);
-    float oc[3] = {0.f, 0.f, 0.f};
-    if (c.contract_type != HR_CONTRACT_IDENTITY) hr_contract_point(c, ro[0], ro[1], ro[2], oc);
-    float base_t = 0.0f, time_off = 0.0f;
-    if (c.advect) { base_t = hr_base_time(c, t_ray); time_off = t_ray - base_t; }
     float p[3] = {0.f, 0.f, 0.f};
     float dist_c = 0.0f;
-    if (lane_ok) hr_sample_point(c, hk, dist, ro, rd, oc, time_off, p, &dist_c);
+    if (lane_ok) hr_sample_point(c, hk, dist, q.ro, q.rd, q.oc, q.time_off, p, &dist_c);
     const float dist_next = __shfl_down(dist_c, 1, 64);
     const float delta = (k == Z - 1) ? 1e10f : (dist_next - dist_c);
     const bool valid = lane_ok && hr_sample_valid(c, p, dist_c);
@@ -123,7 +118,7 @@ __global__ __launch_bounds__(256) void hr_train_lanes_kernel(const hr_config* __
             pn[0] = hr_normalize_coord(c, p[0], 0);
             pn[1] = hr_normalize_coord(c, p[1], 1);
             pn[2] = hr_normalize_coord(c, p[2], 2);
-            pn[3] = c.video ? hr_normalize_time(c, base_t) : 0.0f;
+            pn[3] = c.video ? hr_normalize_time(c, q.base_t) : 0.0f;
             if (a.d_rgb && a.tape.taps) {          // what phase B needs of this sample's position: the three axis taps
                 const int64_t NS = a.n_rays * Z, s = ray * Z + k;
 #pragma unroll
@@ -174,17 +169,7 @@ __global__ __launch_bounds__(256) void hr_train_lanes_kernel(const hr_config* __
     const bool app = lane_ok && (wgt > c.weight_thresh);
     const float pre[3] = {pre0, pre1, pre2};
     float raw[3] = {0.f, 0.f, 0.f}, sc[3] = {1.f, 1.f, 1.f}, rr[3] = {0.f, 0.f, 0.f};
-    if (lane_ok) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            if (app) raw[i] = (c.shading == HR_SHADING_SH) ? fmaxf(pre[i] + 0.5f, 0.0f) : 1.0f / (1.0f + expf(-pre[i]));
-            rr[i] = raw[i];
-            if (c.f_color_scale.offset >= 0) {
-                sc[i] = hr_apply_act(c.f_color_scale.act, hk[c.f_color_scale.offset + i]) + 1.0f;
-                rr[i] = raw[i] * sc[i] + hr_apply_act(c.f_color_shift.act, hk[c.f_color_shift.offset + i]);
-            }
-        }
-    }
+    if (lane_ok) hr_sample_color(c, pre, app, hk, raw, sc, rr);
     float c0 = wgt * rr[0], c1 = wgt * rr[1], c2 = wgt * rr[2], acc_w = wgt;
 #pragma unroll
     for (int d = ZP >> 1; d > 0; d >>= 1) {        // every lane of the ray ends up with the ray's sums
@@ -194,44 +179,11 @@ __global__ __launch_bounds__(256) void hr_train_lanes_kernel(const hr_config* __
         acc_w += __shfl_xor(acc_w, d, 64);
     }
     if (a.white_bg) { const float bg = 1.0f - acc_w; c0 += bg; c1 += bg; c2 += bg; }
-    const float cpre[3] = {c0, c1, c2};            // the composited colour before the per-ray scale / shift
-    float gscale[3] = {1.0f, 1.0f, 1.0f};
-    float tcol[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int cam = 0;
-    const bool head_transform = c.f_color_scale_global.offset >= 0 && c.f_color_scale_global.channels == 9;
-    if (head_transform) {                          // transform_color_one, the matrix from the head (`color_transform_global`): sample 0's nine values
-        const hr_head_field& fs = c.f_color_scale_global;
-        const hr_head_field& fh = c.f_color_shift_global;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) tcol[i] = hr_apply_act(fs.act, head[fs.offset + i]);
-        const float n0 = c0 + ((c0 * tcol[0] + c1 * tcol[1]) + c2 * tcol[2]);
-        const float n1 = c1 + ((c0 * tcol[3] + c1 * tcol[4]) + c2 * tcol[5]);
-        const float n2 = c2 + ((c0 * tcol[6] + c1 * tcol[7]) + c2 * tcol[8]);
-        c0 = n0 + hr_apply_act(fh.act, head[fh.offset + 0]);
-        c1 = n1 + hr_apply_act(fh.act, head[fh.offset + 1]);
-        c2 = n2 + hr_apply_act(fh.act, head[fh.offset + 2]);
-    } else if (c.f_color_scale_global.offset >= 0) {      // scale_shift_color_one (tensorf_utils.py:275-281): sample 0's head values
-        const hr_head_field& fs = c.f_color_scale_global;
-        const hr_head_field& fh = c.f_color_shift_global;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) gscale[i] = hr_apply_act(fs.act, head[fs.offset + i]) + 1.0f;
-        c0 = c0 * gscale[0] + hr_apply_act(fh.act, head[fh.offset + 0]);
-        c1 = c1 * gscale[1] + hr_apply_act(fh.act, head[fh.offset + 1]);
-        c2 = c2 * gscale[2] + hr_apply_act(fh.act, head[fh.offset + 2]);
-    } else if (a.color_table) {                    // transform_color_one (tensorf_utils.py:308-320, point.py:588-594)
-        cam = (int)rintf(r[c.ray_dim - 2]);
-        cam = cam < 0 ? 0 : (cam > c.color_table_views - 1 ? c.color_table_views - 1 : cam);
-        const float* e = a.color_table + 12 * cam;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) tcol[i] = hr_apply_act(c.color_table_t_act, e[i]);
-        const float n0 = c0 + ((c0 * tcol[0] + c1 * tcol[1]) + c2 * tcol[2]);
-        const float n1 = c1 + ((c0 * tcol[3] + c1 * tcol[4]) + c2 * tcol[5]);
-        const float n2 = c2 + ((c0 * tcol[6] + c1 * tcol[7]) + c2 * tcol[8]);
-        c0 = n0 + hr_apply_act(c.color_table_s_act, e[9]);
-        c1 = n1 + hr_apply_act(c.color_table_s_act, e[10]);
-        c2 = n2 + hr_apply_act(c.color_table_s_act, e[11]);
-    }
-    if (a.rgb && ray_ok && k == 0) { a.rgb[ray * 3 + 0] = c0; a.rgb[ray * 3 + 1] = c1; a.rgb[ray * 3 + 2] = c2; }
+    const float cpre[3] = {c0, c1, c2};            // the composited colour before the per-ray transform
+    float col[3];
+    HrRayColor rc;
+    hr_ray_color(c, a, r, head, cpre, col, rc);
+    if (a.rgb && ray_ok && k == 0) { a.rgb[ray * 3 + 0] = col[0]; a.rgb[ray * 3 + 1] = col[1]; a.rgb[ray * 3 + 2] = col[2]; }
     if (!a.d_rgb) return;
 
     // ---- backward of the compositing
@@ -241,63 +193,11 @@ __global__ __launch_bounds__(256) void hr_train_lanes_kernel(const hr_config* __
     float* dhk = dhead + (lane_ok ? k : 0) * P;
     if (lane_ok)
         for (int i = 0; i < P; ++i) dhk[i] = 0.0f;
-    if (head_transform) {
-        const hr_head_field& fs = c.f_color_scale_global;
-        const hr_head_field& fh = c.f_color_shift_global;
-        float gn[3] = {g[0], g[1], g[2]};
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            if (lane_ok && k == 0) dhk[fh.offset + i] += g[i] * hr_act_grad(fh.act, head[fh.offset + i]);     // sample 0's row is this lane's own
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                if (lane_ok && k == 0) dhk[fs.offset + 3 * i + j] += g[i] * cpre[j] * hr_act_grad(fs.act, head[fs.offset + 3 * i + j]);
-                gn[j] += g[i] * tcol[3 * i + j];
-            }
-        }
-        g[0] = gn[0]; g[1] = gn[1]; g[2] = gn[2];
-    } else if (c.f_color_scale_global.offset >= 0) {
-        const hr_head_field& fs = c.f_color_scale_global;
-        const hr_head_field& fh = c.f_color_shift_global;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            if (lane_ok && k == 0) {               // sample 0's row is this lane's own
-                dhk[fs.offset + i] += g[i] * cpre[i] * hr_act_grad(fs.act, head[fs.offset + i]);
-                dhk[fh.offset + i] += g[i] * hr_act_grad(fh.act, head[fh.offset + i]);
-            }
-            g[i] = g[i] * gscale[i];               // everything below sees the gradient of the un-scaled colour
-        }
-    } else if (a.color_table) {
-        const float* e = a.color_table + 12 * cam;
-        hr_acc_t* de = a.d_color_table + 12 * cam;
-        float gn[3] = {g[0], g[1], g[2]};
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            if (ray_ok && k == 0) HR_ATOMIC_ADD(de + 9 + i, g[i] * hr_act_grad(c.color_table_s_act, e[9 + i]));
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                if (ray_ok && k == 0) HR_ATOMIC_ADD(de + 3 * i + j, g[i] * cpre[j] * hr_act_grad(c.color_table_t_act, e[3 * i + j]));
-                gn[j] += g[i] * tcol[3 * i + j];
-            }
-        }
-        g[0] = gn[0]; g[1] = gn[1]; g[2] = gn[2];
-    }
+    // sample 0's row is lane 0's own; the colour table's adds come from lane 0 of every ray of the batch
+    hr_ray_color_bwd(c, a, head, rc, cpre, k == 0 && (rc.form == HR_RAY_COLOR_TABLE ? ray_ok : lane_ok), dhk, g);
     const float gsum = a.white_bg ? (g[0] + g[1] + g[2]) : 0.0f;
     float dpre[3] = {0.f, 0.f, 0.f};
-    if (lane_ok) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float dr = wgt * g[i];
-            if (c.f_color_scale.offset >= 0) {
-                const float hs = hk[c.f_color_scale.offset + i], hh = hk[c.f_color_shift.offset + i];
-                dhk[c.f_color_scale.offset + i] += dr * raw[i] * hr_act_grad(c.f_color_scale.act, hs);
-                dhk[c.f_color_shift.offset + i] += dr * hr_act_grad(c.f_color_shift.act, hh);
-            }
-            const float draw = dr * sc[i];
-            if (!app) dpre[i] = 0.0f;
-            else if (c.shading == HR_SHADING_SH) dpre[i] = (pre[i] + 0.5f > 0.0f) ? draw : 0.0f;
-            else dpre[i] = draw * raw[i] * (1.0f - raw[i]);
-        }
-    }
+    if (lane_ok) hr_sample_color_bwd(c, wgt, g, raw, sc, pre, app, hk, dhk, dpre);
     const float dw = lane_ok ? ((g[0] * rr[0] + g[1] * rr[1] + g[2] * rr[2]) - gsum) : 0.0f;
     float suf = dw * wgt;                          // inclusive suffix sum of dw_j * w_j over the ray's later lanes
 #pragma unroll
@@ -306,11 +206,9 @@ __global__ __launch_bounds__(256) void hr_train_lanes_kernel(const hr_config* __
         if (k + d < ZP) suf += o;
     }
     const float S = suf - dw * wgt;                // sum over j > k
-    const float dalpha = dw * T - S / inc;
-    const float e1 = 1.0f - alpha;
-    const float dsigma = dalpha * e1 * (delta * c.distance_scale);
-    const float dfeat = valid ? dsigma * hr_density_grad(c, feat) : 0.0f;
-    const float ddelta = (lane_ok && k < Z - 1) ? dalpha * e1 * sigma * c.distance_scale : 0.0f;
+    float dfeat, ddelta;                           // (a lane without a sample has alpha 0: the helper's 1 - alpha + 1e-10 is this kernel's inc = 1)
+    hr_alpha_bwd(c, dw, T, S, alpha, delta, sigma, feat, valid, &dfeat, &ddelta);
+    if (!(lane_ok && k < Z - 1)) ddelta = 0.0f;
     float ddelta_prev = __shfl_up(ddelta, 1, 64);
     if (k == 0) ddelta_prev = 0.0f;
     if (lane_ok) {                                 // hand the per-sample upstream gradients to phases B and C

@@ -184,7 +184,7 @@ def plan_lib():
     """Host build of hyperreel_amd/csrc/hr_plan.h (tests/host_math/hr_plan_host.cpp): the library's own geometry and dispatch decisions."""
     here = os.path.dirname(os.path.abspath(__file__))
     src = os.path.join(here, 'host_math', 'hr_plan_host.cpp')
-    deps = [src, os.path.join(here, '..', 'include', 'hyperreel_hip.h')] + [os.path.join(here, '..', 'hyperreel_amd', 'csrc', f) for f in ('hr_plan.h', 'hr_grid.h')]
+    deps = [src, os.path.join(here, '..', 'include', 'hyperreel_hip.h')] + [os.path.join(here, '..', 'hyperreel_amd', 'csrc', f) for f in ('hr_plan.h', 'hr_grid.h', 'hr_train.h', 'hr_math.h')]
     lib = ctypes.CDLL(build_host_lib(os.path.join(here, 'host_math', '_build', 'libhr_plan_host.so'), src, deps))
     assert lib.hp_sizeof_plane() == ctypes.sizeof(GridPlane) and lib.hp_sizeof_plan() == ctypes.sizeof(TrainPlan)
     assert lib.hp_sizeof_sample_plan() == ctypes.sizeof(SamplePlan) and lib.hp_sizeof_frame_plan() == ctypes.sizeof(FramePlan)

@@ -1,6 +1,7 @@
 // TEST-ONLY host build of hyperreel_amd/csrc/hr_plan.h (plane-pair geometry, plane class, the render call's and the training step's
 // launch plans), so that the suites ask the library's own code which branch a case takes.  Nothing in the product links or loads this file.
 #include "../../hyperreel_amd/csrc/hr_plan.h"
+#include "../../hyperreel_amd/csrc/hr_train.h"
 
 extern "C" {
 
@@ -32,6 +33,27 @@ void hp_train_plan(const hr_config* c, long long n_rays, int deterministic, HrTr
     (void)hr_plane_geometry(*c, planes, &ca_total, &n_basis_cols);
     const HrTrainPlanIn in = {n_rays, true, true, true, true, deterministic != 0, deterministic ? sizeof(long long) : sizeof(float), 256};
     *out = hr_train_plan(*c, planes, ca_total, n_basis_cols, in);
+}
+
+// The training tape bound to `base` for ns samples: byte offsets of the nine fields from base in HrTrainTape's order {ds, src, dfeat, dpre,
+// ddc, dts, taps, dp, perm} (-1: not bound); rows: the coarse level's three-plane form.  Returns the words per sample of the full form.
+int hp_tape_layout(float* base, long long ns, int rows, long long* off)
+{
+    const HrTrainTape t = rows ? hr_tape_bind_rows(base, ns) : hr_tape_bind(base, ns);
+    const void* f[9] = {t.ds, t.src, t.dfeat, t.dpre, t.ddc, t.dts, t.taps, t.dp, t.perm};
+    for (int i = 0; i < 9; ++i) off[i] = f[i] ? (long long)((const char*)f[i] - (const char*)base) : -1;
+    return HR_TAPE_WORDS;
+}
+
+// hr_grad_pool of a model of *c: out = {off_a[3], off_b[3], n_a[3], n_b[3], total} in elements
+void hp_grad_pool(const hr_config* c, size_t elem, size_t align, size_t* out)
+{
+    HrGridPlane planes[3];
+    int ca_total = 0, n_basis_cols = 0;
+    (void)hr_plane_geometry(*c, planes, &ca_total, &n_basis_cols);
+    const HrGradPool p = hr_grad_pool(planes, elem, align);
+    for (int j = 0; j < 3; ++j) { out[j] = p.off_a[j]; out[3 + j] = p.off_b[j]; out[6 + j] = p.n_a[j]; out[9 + j] = p.n_b[j]; }
+    out[12] = p.total;
 }
 
 // ---- rendering

@@ -28,10 +28,9 @@ int ht_train(const hr_config* c, const float* rays, const float* head, long long
     a.color_table = color_table; a.d_color_table = d_color_table;
     // the tape between the phases (the device keeps it in a workspace of the model)
     const size_t NS = (size_t)n * c->z_channels;
-    std::vector<float> ds(NS), dfeat(NS), dpre(3 * NS), ddc(NS), dts(NS);
-    std::vector<int> src(NS);
-    a.tape.ds = ds.data(); a.tape.src = src.data(); a.tape.dfeat = dfeat.data(); a.tape.dpre = dpre.data();
-    a.tape.ddc = ddc.data(); a.tape.dts = dts.data();
+    std::vector<float> tape(HR_TAPE_WORDS * NS);
+    a.tape = hr_tape_bind(tape.data(), (int64_t)NS);
+    a.tape.taps = nullptr; a.tape.dp = nullptr; a.tape.perm = nullptr;      // the lane-per-sample phase A's, device only
     hr_with_zp(hr_round_zp(c->z_channels), [&](auto zp) {
         for (long long i = 0; i < n; ++i) hr_ray_train<decltype(zp)::value>(*c, a, i);
     });
@@ -76,9 +75,8 @@ int ht_rows(const hr_config* c, const float* rays, const float* head, long long 
     a.row_dim = row_dim; a.n_inputs = n_inputs;
     for (int i = 0; i < n_inputs; ++i) { a.kind[i] = kind[i]; a.len[i] = len[i]; }
     const size_t NS = (size_t)n * c->z_channels;
-    std::vector<float> ds(NS), dts(NS);
-    std::vector<int> src(NS);
-    a.tape.ds = ds.data(); a.tape.src = src.data(); a.tape.dts = dts.data();
+    std::vector<float> tape(3 * NS);
+    a.tape = hr_tape_bind_rows(tape.data(), (int64_t)NS);
     hr_with_zp(hr_round_zp(c->z_channels), [&](auto zp) {
         for (long long i = 0; i < n; ++i) hr_ray_rows<decltype(zp)::value>(*c, a, i);
     });

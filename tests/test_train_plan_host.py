@@ -144,3 +144,73 @@ def test_the_train_class_is_generic_from_2_to_the_30_elements():
     big_line[2].bh = 1 << 27                                                # 2^27 texels x 8 floats
     assert lib.hp_plane_class(big_line, 16, 1) == 0 and lib.hp_plane_class(big_line, 16, 0) == 1
     assert lib.hp_plane_class(planes(64), 16, 1) == 1 and lib.hp_plane_class(planes(64), 12, 1) == 0
+
+
+# HrTrainTape's fields in workspace order with their planes of ns = n_rays x Z words: 1 + 1 + 1 + 3 + 1 + 1 + 18 + 3 + 1 = 30 words per sample
+TAPE = (('ds', 1), ('src', 1), ('dfeat', 1), ('dpre', 3), ('ddc', 1), ('dts', 1), ('taps', 18), ('dp', 3), ('perm', 1))
+
+
+def _tape_layout(ns, rows=False):
+    import ctypes
+    lib = plan_lib()
+    lib.hp_tape_layout.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]
+    off = (ctypes.c_longlong * 9)()
+    words = lib.hp_tape_layout(1 << 20, ns, int(rows), off)       # an address only: nothing is read or written
+    return words, list(off)
+
+
+@pytest.mark.parametrize('n_rays,z', [(1, 1), (3, 8), (95, 16), (48, 200)])
+def test_the_tape_layout_equals_the_hand_derived_planes(n_rays, z):
+    """hr_tape_bind cuts the workspace hr_train_backward allocates (HR_TAPE_WORDS floats per sample) into the planes above, 4-byte words."""
+    ns = n_rays * z
+    words, off = _tape_layout(ns)
+    assert words == 30 == sum(p for _, p in TAPE)
+    first = dict(ds=0, src=1, dfeat=2, dpre=3, ddc=6, dts=7, taps=8, dp=26, perm=29)      # first plane of each field, counted by hand
+    spans = []
+    for (name, planes), o in zip(TAPE, off):
+        assert o == first[name] * ns * 4, name
+        spans.append((o, o + planes * ns * 4, name))
+    for i, (lo, hi, a) in enumerate(spans):
+        assert 0 <= lo < hi <= 30 * ns * 4, a
+        for lo2, hi2, b in spans[i + 1:]:
+            assert hi <= lo2 or hi2 <= lo, (a, b)                     # pairwise disjoint
+    assert max(hi for _, hi, _ in spans) == 30 * ns * 4                # the last byte of the allocation
+    perm_lo, perm_hi, _ = spans[-1]
+    assert perm_hi - perm_lo >= 4 * n_rays                             # the grouped ray order: n_rays ints
+    # the coarse level of a cascade: ds, src, dts in the first three planes, nothing else bound
+    words, off = _tape_layout(ns, rows=True)
+    assert words == 30 and off == [0, 4 * ns, -1, -1, -1, 8 * ns, -1, -1, -1]
+
+
+def _grad_pool(hc, elem, align):
+    import ctypes
+    lib = plan_lib()
+    lib.hp_grad_pool.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    out = (ctypes.c_size_t * 13)()
+    lib.hp_grad_pool(ctypes.byref(hc), elem, align, out)
+    v = list(out)
+    return dict(off_a=v[0:3], off_b=v[3:6], n_a=v[6:9], n_b=v[9:12], total=v[12])
+
+
+def test_the_gradient_pool_of_a_static_844_net():
+    """[8, 4, 4] on 28 x 24 x 20 (GEOMETRY['static_844']): planes of 28 x 24 x 16, 28 x 20 x 8 and 24 x 20 x 8 floats, lines of 20 x 16, 24 x 8 and
+    28 x 8.  Float pool, 256-byte (64-float) starts: every size but the last line's 224 floats is a multiple of 64; that one is rounded to 256.
+    Fixed-point pool: the same elements packed."""
+    hc = _config('donerf_sphere', [28, 24, 20])
+    n_a, n_b = [10752, 4480, 3840], [320, 192, 224]
+    assert [28 * 24 * 16, 28 * 20 * 8, 24 * 20 * 8] == n_a and [20 * 16, 24 * 8, 28 * 8] == n_b
+    assert all(n % 64 == 0 for n in n_a + n_b[:2]) and n_b[2] % 64 == 32
+    packed = dict(off_a=[0, 11072, 15744], off_b=[10752, 15552, 19584], n_a=n_a, n_b=n_b, total=19808)
+    assert _grad_pool(hc, 8, 8) == packed
+    assert _grad_pool(hc, 4, 256) == dict(packed, total=19808 + 32)          # 79 360 bytes = 310 x 256
+    assert (19808 + 32) * 4 == 310 * 256
+
+
+def test_the_gradient_pool_of_a_net_with_empty_pairs():
+    """Keyframe [8, 0, 0] on 27 x 23 x 19: pair 0 alone, plane 27 x 23 x 16 = 9936 floats (155.25 x 64 -> 9984 in the float pool), time plane
+    12 rows x 19 x 16 = 3648 = 57 x 64; pairs 1 and 2 take nothing and keep offset 0."""
+    hc = _config('technicolor_z_plane', [27, 23, 19])
+    assert hc.num_keyframes == K and (27 * 23 * 16, K * 19 * 16) == (9936, 3648)
+    want = dict(off_a=[0, 0, 0], off_b=[9936, 0, 0], n_a=[9936, 0, 0], n_b=[3648, 0, 0], total=13584)
+    assert _grad_pool(hc, 8, 8) == want
+    assert _grad_pool(hc, 4, 256) == dict(want, off_b=[9984, 0, 0], total=9984 + 3648)

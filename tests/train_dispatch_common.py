@@ -34,6 +34,10 @@ BRANCH = {
     'seeded_donerf_sphere_z96': dict(PER_RAY, zp=128, z=96, n_den=[8, 4, 4], video=False, phase_b='lines'),
     'seeded_donerf_cylinder_z200': dict(PER_RAY, zp=256, z=200, n_den=[8, 4, 4], video=False, phase_b='lines'),
     'seeded_technicolor_z_plane_z12': dict(LANES, zp=16, z=12, plane_class='8,0,0', video=True, keyed=True, phase_b='lines'),
+    # the per-ray colour transforms on the thread-per-ray kernel (no fixture has one above 64 samples): the per-camera colour table, and
+    # the 3x3 from the head (`color_transform_global`)
+    'seeded_immersive_z_plane_z96': dict(PER_RAY, zp=128, z=96, video=False, phase_b='lines', views=5),
+    'seeded_color_transform_global_head_z96': dict(PER_RAY, zp=128, z=96, video=False, phase_b='lines', head_matrix=True),
     # pair 0's line alone is 2400 texels x 16 channels x 4 B = 150 KiB, the cap of hr_launch_gather_bwd_lines: the default build's fall-back
     'lds_fallback': dict(LANES, zp=32, z=32, plane_class='8,4,4', video=False, phase_b='atomics', over_cap=True),
     # a keyframe net whose rows of all three pairs exceed the cap together (128 B x 1115 + 64 B x (24 + 20) + 8128 B = 153 664 B against
@@ -46,6 +50,9 @@ DETERMINISTIC = ['shiny_z_plane_tiny', 'stanford_z_plane_small', 'catacaustics_v
                  'technicolor_cascaded']
 SEEDED = {'seeded_donerf_sphere_z96': ('donerf_sphere', 96), 'seeded_donerf_cylinder_z200': ('donerf_cylinder', 200),
           'seeded_technicolor_z_plane_z12': ('technicolor_z_plane', 12)}
+# ... and from a fixture's config instead of a model YAML's, both z_channels keys set
+SEEDED_FIXTURE = {'seeded_immersive_z_plane_z96': ('sweep/immersive_z_plane', 96),
+                  'seeded_color_transform_global_head_z96': ('sweep/variant_color_transform_global_head', 96)}
 
 
 @functools.lru_cache(maxsize=None)
@@ -60,6 +67,20 @@ def _scene(name):
         else:
             rays = scenes.random_rays(48, 2, video)
         return SimpleNamespace(cfg=cfg, dataset=ds, state_dict=sd, iteration=None, grid=grid, rays=np.ascontiguousarray(rays, np.float32))
+    if name in SEEDED_FIXTURE:
+        fixture, z = SEEDED_FIXTURE[name]
+        g = Golden(fixture)
+        cfg, ds, grid = g.cfg, g.dataset, [24, 20, 16]
+        cfg.embedding.embeddings.ray_prediction_0.z_channels = cfg.embedding.embeddings.ray_intersect_0.z_channels = z
+        sd = scenes.make_state_dict(cfg, ds, grid, seed=4, density='dense', app_scale=1.0)
+        timed = g.rays.shape[1] > 6                      # camera id and time columns
+        if 'z_plane' in fixture:
+            rays = scenes.random_rays(48, 2, timed, pos_mean=(0, 0, 1.0), pos_std=0.15, dir_mean=(0, 0, -1.2), dir_std=0.5)
+        else:
+            rays = scenes.random_rays(48, 2, timed)
+        if ds.get('val_all', False):                     # every camera of the colour table
+            rays[:, 6] = np.arange(48) % ds['total_images_per_frame']
+        return SimpleNamespace(cfg=cfg, dataset=ds, state_dict=sd, iteration=g.iteration, grid=grid, rays=np.ascontiguousarray(rays, np.float32))
     if name == 'lds_fallback':
         cfg, ds, grid = C.model_config('donerf_sphere'), C.dataset_scalars('donerf_sphere'), [12, 12, 2400]
         sd = scenes.make_state_dict(cfg, ds, grid, seed=4, density='dense', app_scale=1.0)
@@ -112,6 +133,8 @@ def _assert_branch(name, n_rays=None, deterministic=False):
         assert list(hc.n_den) == want.pop('n_den'), name
     if 'views' in want:
         assert hc.color_table_views == want.pop('views'), name
+    if want.pop('head_matrix', False):
+        assert hc.f_color_scale_global.offset >= 0 and hc.f_color_scale_global.channels == 9, name
     if want.pop('over_cap', False):
         assert got['lds_bytes'] > 150 * 1024 and not got['keyed'], (name, got)
     if deterministic:                                    # train_det_kernel.hip: the global-atomics kernel for everything
