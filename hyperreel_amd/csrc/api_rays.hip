@@ -1,6 +1,6 @@
 // C ABI, camera rays, light-field rays and the training feed: hr_generate_rays_ndc, hr_generate_rays_lightfield, hr_generate_rays_epi,
-// hr_rayset_* (kernels: rays_kernel.hip; arithmetic: hr_camera.h, hr_lightfield.h).
-// No model handle.  The set owns its device memory; hr_rayset_batch / hr_rayset_order enqueue one kernel and nothing else.
+// hr_rayset_* (kernels: rays_kernel.hip; arithmetic: hr_camera.h, hr_lightfield.h, hr_sample_rng.h).
+// No model handle.  The set owns its device memory; hr_rayset_batch / hr_rayset_order / hr_rayset_sample enqueue one kernel and nothing else.
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -229,6 +229,23 @@ int hr_rayset_order(const hr_rayset* set, int64_t first, int64_t n, uint64_t see
     HrRaySetArgs a = set_args(set, first, n, seed, epoch);
     a.elements = elements_dev;
     hr_launch_rayset_batch(a, (hipStream_t)stream);
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}
+
+int hr_rayset_sample(const hr_rayset* set, int64_t n, uint64_t seed, uint64_t step, const uint64_t* step_dev, float* coords_dev, float* rgb_dev,
+                     float* weight_dev, int64_t* elements_dev_or_null, void* stream)
+{
+    if (!set) return fail(HR_E_INVALID, "hr_rayset_sample: null set");
+    if (n < 0) return fail(HR_E_INVALID, "hr_rayset_sample: %lld rows", (long long)n);
+    if (n > ((int64_t)1 << 38)) return fail(HR_E_INVALID, "hr_rayset_sample: more than 2^38 rows in one call");
+    if (n == 0) return HR_OK;              // nothing to launch
+    if (!coords_dev && !rgb_dev && !weight_dev && !elements_dev_or_null) return fail(HR_E_INVALID, "hr_rayset_sample: every output is NULL");
+    if (set->prefix[set->n_images] < 1) return fail(HR_E_INVALID, "hr_rayset_sample: the set holds no rays to draw from");
+    HrRaySetArgs a = set_args(set, 0, n, 0, 0);
+    a.coords = coords_dev; a.rgb = rgb_dev; a.weight = weight_dev;
+    a.elements = elements_dev_or_null;
+    hr_launch_rayset_sample(a, seed, step, step_dev, (hipStream_t)stream);
     HR_HIP(hipGetLastError());
     return HR_OK;
 }

@@ -36,8 +36,8 @@ int hr_linear_backward(const float* x_dev, int64_t ldx, const float* w_dev, cons
     if (rows > 0x7fffffff) return fail(HR_E_INVALID, "more than 2^31 rows");
     if (rows == 0) {
         if (!dw_dev || !db_dev) return fail(HR_E_INVALID, "null argument");
-        HR_HIP(hipMemsetAsync(dw_dev, 0, sizeof(float) * (size_t)out * in, (hipStream_t)stream));
-        HR_HIP(hipMemsetAsync(db_dev, 0, sizeof(float) * (size_t)out, (hipStream_t)stream));
+        hr_launch_fill_zero(HrFillBatch{{dw_dev, db_dev}, {(size_t)out * in, (size_t)out}, 2}, (hipStream_t)stream);     // (a kernel: no memset node)
+        HR_HIP(hipGetLastError());
         return HR_OK;
     }
     hr_launch_linear_backward(x_dev, ldx, w_dev, y_dev, ldy, dy_dev, ld_dy, rows, in, out, leaky_slope, dx_dev, ld_dx, dw_dev, db_dev, workspace_dev,
@@ -96,6 +96,53 @@ int hr_adam_step(float* const* param_dev, const float* const* grad_dev, float* c
         b.first_block[k + 1] = b.first_block[k] + (int)blocks;
     }
     if (b.count > 0) flush();
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}
+
+int hr_adam_step_dev(float* const* param_dev, const float* const* grad_dev, float* const* exp_avg_dev, float* const* exp_avg_sq_dev, const int64_t* n,
+                     const double* hp, const int32_t* lr_index, int32_t n_lr, const float* lr_dev, int64_t* step_dev, int32_t n_tensors, void* stream)
+{
+    if (n_tensors < 0 || (n_tensors > 0 && (!param_dev || !grad_dev || !exp_avg_dev || !exp_avg_sq_dev || !n || !hp || !lr_index || !lr_dev || !step_dev)))
+        return fail(HR_E_INVALID, "hr_adam_step_dev: null argument");
+    // validate everything before the first launch: a refused call must leave no tensor stepped
+    bool any = false;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (n[i] < 0) return fail(HR_E_INVALID, "hr_adam_step_dev: tensor %d has a negative size", i);
+        if (n[i] == 0) continue;
+        if (!param_dev[i] || !grad_dev[i] || !exp_avg_dev[i] || !exp_avg_sq_dev[i]) return fail(HR_E_INVALID, "hr_adam_step_dev: tensor %d has a null buffer", i);
+        const double b1 = hp[4 * i], b2 = hp[4 * i + 1];
+        if (!(b1 >= 0.0 && b1 < 1.0) || !(b2 >= 0.0 && b2 < 1.0)) return fail(HR_E_INVALID, "hr_adam_step_dev: tensor %d: betas in [0, 1) required", i);
+        if (lr_index[i] < 0 || lr_index[i] >= n_lr) return fail(HR_E_INVALID, "hr_adam_step_dev: tensor %d reads learning rate %d of %d", i, (int)lr_index[i], (int)n_lr);
+        if ((n[i] + 4095) / 4096 > 0x3fffffff) return fail(HR_E_INVALID, "hr_adam_step_dev: tensor %d is too large", i);
+        any = true;
+    }
+    if (!any) return HR_OK;
+    HrAdamDevBatch b;
+    b.count = 0;
+    b.first_block[0] = 0;
+    b.lr = lr_dev;
+    b.step = step_dev;
+    auto flush = [&]() {
+        hr_launch_adam_dev(b, (hipStream_t)stream);
+        b.count = 0;
+        b.first_block[0] = 0;
+    };
+    for (int i = 0; i < n_tensors; ++i) {
+        if (n[i] == 0) continue;
+        const double b1 = hp[4 * i], b2 = hp[4 * i + 1], eps = hp[4 * i + 2], wd = hp[4 * i + 3];
+        const int64_t blocks = (n[i] + 4095) / 4096;
+        if (b.count == HR_ADAM_MAX_TENSORS || (int64_t)b.first_block[b.count] + blocks > 0x7fffffff) flush();
+        const int k = b.count++;
+        b.p[k] = param_dev[i]; b.g[k] = grad_dev[i]; b.m[k] = exp_avg_dev[i]; b.v[k] = exp_avg_sq_dev[i]; b.n[k] = n[i];
+        b.beta1[k] = b1; b.beta2d[k] = b2;
+        b.omb1[k] = (float)(1.0 - b1); b.beta2[k] = (float)b2; b.omb2[k] = (float)(1.0 - b2); b.eps[k] = (float)eps; b.weight_decay[k] = (float)wd;
+        b.lr_index[k] = lr_index[i];
+        b.first_block[k + 1] = b.first_block[k] + (int)blocks;
+    }
+    if (b.count > 0) flush();
+    // the count advances in a launch of its own, behind every block of the step on the stream: none of them can read the new value
+    hr_launch_adam_advance(step_dev, (hipStream_t)stream);
     HR_HIP(hipGetLastError());
     return HR_OK;
 }
@@ -311,13 +358,21 @@ int hr_train_backward(hr_model* m, const float* rays_dev, const float* head_dev,
             }
         }
     }
-    // cleared per step on the stream, in one go (the deterministic mode overwrites them from its fixed-point sums instead)
-    if (m->grad_pool && !m->opt_train_det) HR_HIP(hipMemsetAsync(m->grad_pool, 0, m->grad_pool_bytes, st));
     const size_t basis_bytes = m->raw["basis_mat.weight"].bytes;
-    // basis_mat's gradient needs no re-layout: accumulate in the caller's buffer (or a scratch nobody reads)
+    // basis_mat's gradient needs no re-layout: accumulate in the caller's buffer
     float* d_basis = grads->basis;
     if (!d_basis) return fail(HR_E_INVALID, "hr_train_backward: grads->basis is NULL");
-    if (basis_bytes > 0) HR_HIP(hipMemsetAsync(d_basis, 0, basis_bytes, st));
+    if (m->cfg.color_table_views > 0 && !grads->color_table) return fail(HR_E_INVALID, "hr_train_backward: grads->color_table is NULL");
+    // The step's accumulators are cleared on the stream by ONE fill kernel (no memset node: the step is meant to be replayed from a graph,
+    // DESIGN 10).  Default build: the packed texel gradients, basis_mat's and the colour table's.  Deterministic build: its fixed-point
+    // scratch alone -- hr_launch_fixed_to_float overwrites every element of those three from it, so they need no clear.
+    HrFillBatch clear = {};
+    if (!m->opt_train_det) {
+        if (m->grad_pool) { clear.p[clear.count] = reinterpret_cast<float*>(static_cast<char*>(m->grad_pool)); clear.n[clear.count++] = m->grad_pool_bytes / sizeof(float); }
+        if (basis_bytes > 0) { clear.p[clear.count] = d_basis; clear.n[clear.count++] = basis_bytes / sizeof(float); }
+        if (m->cfg.color_table_views > 0) { clear.p[clear.count] = grads->color_table; clear.n[clear.count++] = 12 * (size_t)m->cfg.color_table_views; }
+        hr_launch_fill_zero(clear, st);
+    }
     const int64_t ns = n_rays * m->cfg.z_channels;
     rc = ensure_tape(m, ns, st);
     if (rc != HR_OK) return rc;
@@ -327,11 +382,7 @@ int hr_train_backward(hr_model* m, const float* rays_dev, const float* head_dev,
     a.d_rgb = d_rgb_dev;
     a.d_head = d_head_dev;
     a.d_basis = d_basis;
-    if (m->cfg.color_table_views > 0) {
-        if (!grads->color_table) return fail(HR_E_INVALID, "hr_train_backward: grads->color_table is NULL");
-        HR_HIP(hipMemsetAsync(grads->color_table, 0, sizeof(float) * 12 * (size_t)m->cfg.color_table_views, st));
-        a.d_color_table = grads->color_table;
-    }
+    if (m->cfg.color_table_views > 0) a.d_color_table = grads->color_table;
     if (m->opt_train_det) {
         // deterministic mode: every accumulator of the step is a 64-bit fixed-point word of ONE scratch buffer (integer atomics: the
         // totals do not depend on the order of the adds); converted to the float buffers the rest of the step reads
@@ -348,7 +399,8 @@ int hr_train_backward(hr_model* m, const float* rays_dev, const float* head_dev,
             HR_HIP(m->grad_fx.alloc(sizeof(long long) * need));
             m->grad_fx_elems = need;
         }
-        HR_HIP(hipMemsetAsync(m->grad_fx, 0, sizeof(long long) * need, st));
+        clear.p[0] = reinterpret_cast<float*>(static_cast<long long*>(m->grad_fx)); clear.n[0] = need * (sizeof(long long) / sizeof(float)); clear.count = 1;
+        hr_launch_fill_zero(clear, st);
         if (!m->fx_unit) HR_HIP(m->fx_unit.alloc(sizeof(HrFxUnit)));
         HrTrainArgs ad = a;
         ad.fx = m->fx_unit;

@@ -261,6 +261,8 @@ struct HrRaySetArgs {
     int64_t* elements;           // (n): the set element of each row
 };
 void hr_launch_rayset_batch(const HrRaySetArgs& a, hipStream_t stream);
+// rows [0, a.n) drawn with replacement (hr_sample_rng.h): first / key / indices of `a` are not read
+void hr_launch_rayset_sample(const HrRaySetArgs& a, uint64_t seed, uint64_t step, const uint64_t* step_dev, hipStream_t stream);
 
 // layout kernels (pack_kernels.hip)
 // dst[y][x][c_off + c] = src[c][y][x] for c < C  (dst texel stride = tex floats)
@@ -294,6 +296,31 @@ struct HrAdamBatch {
     int count;
 };
 void hr_launch_adam(const HrAdamBatch& b, hipStream_t stream);
+// the same step with the count and the learning rates read from device memory (hr_adam_step_dev): step_size and inv_sqrt_bc2 are formed in the kernel
+struct HrAdamDevBatch {
+    float* p[HR_ADAM_MAX_TENSORS];
+    const float* g[HR_ADAM_MAX_TENSORS];
+    float* m[HR_ADAM_MAX_TENSORS];
+    float* v[HR_ADAM_MAX_TENSORS];
+    int64_t n[HR_ADAM_MAX_TENSORS];
+    double beta1[HR_ADAM_MAX_TENSORS], beta2d[HR_ADAM_MAX_TENSORS];
+    float omb1[HR_ADAM_MAX_TENSORS], beta2[HR_ADAM_MAX_TENSORS], omb2[HR_ADAM_MAX_TENSORS];
+    float eps[HR_ADAM_MAX_TENSORS], weight_decay[HR_ADAM_MAX_TENSORS];
+    int lr_index[HR_ADAM_MAX_TENSORS];
+    int first_block[HR_ADAM_MAX_TENSORS + 1];
+    int count;
+    const float* lr;             // device: one float per parameter group
+    const int64_t* step;         // device: steps already done
+};
+void hr_launch_adam_dev(const HrAdamDevBatch& b, hipStream_t stream);
+void hr_launch_adam_advance(int64_t* step_dev, hipStream_t stream);       // *step_dev += 1, one thread, after everything before it on the stream
+// zero fill of up to four float buffers in one launch (n in floats; empty entries are skipped)
+struct HrFillBatch {
+    float* p[4];
+    size_t n[4];
+    int count;
+};
+void hr_launch_fill_zero(const HrFillBatch& b, hipStream_t stream);
 // the training step's re-layouts in ONE launch per direction (reference (C, H, W) tensors <-> packed channel-last texels): up to 12 jobs
 struct HrLayoutJob { const float* src; float* dst; int C, H, W, tex, c_off; };
 struct HrLayoutBatch { HrLayoutJob job[12]; int n; };

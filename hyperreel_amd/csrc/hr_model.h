@@ -130,7 +130,7 @@ struct HR_HIDDEN hr_model {
     DevMem<hr_config> ucfg_dev;
     float* grad_a[3] = {};               // training: packed texel-gradient accumulators of the plane pairs -- slices of grad_pool
     float* grad_b[3] = {};
-    DevMem<char> grad_pool;              // ONE allocation (cleared by one memset per step)
+    DevMem<char> grad_pool;              // ONE allocation (cleared by one fill kernel per step)
     size_t grad_pool_bytes = 0;
     HrMlpTiles train_tiles;              // training forward (hr_mlp_train_forward): bf16 split tiles of the CURRENT parameter values, re-packed on the device every step
     DevMem<long long> grad_fx;           // deterministic training (HR_OPT_TRAIN_DETERMINISTIC): ONE 64-bit fixed-point buffer for every accumulator of a step

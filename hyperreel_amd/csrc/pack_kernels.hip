@@ -401,18 +401,10 @@ void hr_launch_pack_split_bf16(const HrPackDesc& d, hipStream_t stream)
 // _single_tensor_adam: grad += wd * p; exp_avg.lerp_(grad, 1 - beta1); exp_avg_sq = beta2 * exp_avg_sq + (1 - beta2) grad^2;
 // denom = sqrt(exp_avg_sq) / sqrt(bias_correction2) + eps; p -= (lr / bias_correction1) * exp_avg / denom).  HBM-bound: 16 bytes read and
 // 12 written per parameter; the foreach form torch runs by default makes eleven passes over the same arrays.
-__global__ __launch_bounds__(256) void hr_adam_kernel(const HrAdamBatch b)
+// the 4096 elements from `base` on of one tensor: the arithmetic both forms of the step share
+__device__ __forceinline__ void hr_adam_block(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                              int64_t base, float step_size, float isb2, float omb1, float b2, float omb2, float eps, float wd)
 {
-    int t = 0;
-    const int blk = (int)blockIdx.x;
-    while (t + 1 < b.count && b.first_block[t + 1] <= blk) ++t;              // (wave-uniform: scalar loads from the kernel arguments)
-    float* __restrict__ p = b.p[t];
-    const float* __restrict__ g = b.g[t];
-    float* __restrict__ m = b.m[t];
-    float* __restrict__ v = b.v[t];
-    const int64_t n = b.n[t];
-    const float step_size = b.step_size[t], isb2 = b.inv_sqrt_bc2[t], omb1 = b.omb1[t], b2 = b.beta2[t], omb2 = b.omb2[t], eps = b.eps[t], wd = b.weight_decay[t];
-    const int64_t base = (int64_t)(blk - b.first_block[t]) * 4096;
     auto one = [&](float& pv, float gv, float& mv, float& vv) {
         if (wd != 0.0f) gv = __builtin_fmaf(wd, pv, gv);
         mv = mv + omb1 * (gv - mv);                          // lerp_(grad, 1 - beta1), weight < 0.5
@@ -436,8 +428,85 @@ __global__ __launch_bounds__(256) void hr_adam_kernel(const HrAdamBatch b)
     }
 }
 
+__global__ __launch_bounds__(256) void hr_adam_kernel(const HrAdamBatch b)
+{
+    int t = 0;
+    const int blk = (int)blockIdx.x;
+    while (t + 1 < b.count && b.first_block[t + 1] <= blk) ++t;              // (wave-uniform: scalar loads from the kernel arguments)
+    hr_adam_block(b.p[t], b.g[t], b.m[t], b.v[t], b.n[t], (int64_t)(blk - b.first_block[t]) * 4096, b.step_size[t], b.inv_sqrt_bc2[t], b.omb1[t],
+                  b.beta2[t], b.omb2[t], b.eps[t], b.weight_decay[t]);
+}
+
+// hr_adam_step_dev: the step count and the learning rate come from device memory; what hr_adam_step derives from them on the host (the bias
+// corrections, in double) is derived here, by every lane for itself: two pow of wave-uniform arguments per 4096 elements, issued while the
+// block's first loads are in flight.  The count is only READ here: hr_adam_advance_kernel stores the new one after the last block has ended.
+__global__ __launch_bounds__(256) void hr_adam_dev_kernel(const HrAdamDevBatch b)
+{
+    int t = 0;
+    const int blk = (int)blockIdx.x;
+    while (t + 1 < b.count && b.first_block[t + 1] <= blk) ++t;
+    const double step = (double)(*b.step + 1);
+    const double lr = (double)b.lr[b.lr_index[t]];
+    const double bc1 = 1.0 - pow(b.beta1[t], step), bc2 = 1.0 - pow(b.beta2d[t], step);
+    const float step_size = (float)(lr / bc1), isb2 = (float)(1.0 / sqrt(bc2));
+    hr_adam_block(b.p[t], b.g[t], b.m[t], b.v[t], b.n[t], (int64_t)(blk - b.first_block[t]) * 4096, step_size, isb2, b.omb1[t], b.beta2[t], b.omb2[t],
+                  b.eps[t], b.weight_decay[t]);
+}
+
+__global__ void hr_adam_advance_kernel(int64_t* step)
+{
+    *step = *step + 1;
+}
+
 void hr_launch_adam(const HrAdamBatch& b, hipStream_t stream)
 {
     if (b.count <= 0 || b.first_block[b.count] <= 0) return;
     hipLaunchKernelGGL(hr_adam_kernel, dim3((unsigned)b.first_block[b.count]), dim3(256), 0, stream, b);
+}
+
+void hr_launch_adam_dev(const HrAdamDevBatch& b, hipStream_t stream)
+{
+    if (b.count <= 0 || b.first_block[b.count] <= 0) return;
+    hipLaunchKernelGGL(hr_adam_dev_kernel, dim3((unsigned)b.first_block[b.count]), dim3(256), 0, stream, b);
+}
+
+void hr_launch_adam_advance(int64_t* step_dev, hipStream_t stream)
+{
+    hipLaunchKernelGGL(hr_adam_advance_kernel, dim3(1), dim3(1), 0, stream, step_dev);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Zero fill of up to four buffers of floats in ONE launch: what the training step clears per call.  A kernel, not hipMemsetAsync: a memset
+// node did not survive the second replay of a captured graph on this runtime, and the step is meant to be replayed.
+// blockIdx.y = the buffer; 16-byte stores where the buffer starts on a 16-byte boundary, 4-byte stores for the rest and for the tail.
+__global__ __launch_bounds__(256) void hr_fill_zero_kernel(const HrFillBatch b)
+{
+    float* __restrict__ p = b.p[blockIdx.y];
+    const size_t n = b.n[blockIdx.y];
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    size_t done = 0;
+    if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        const size_t n4 = n / 4;
+        float4* __restrict__ q = reinterpret_cast<float4*>(p);
+        for (size_t i = tid; i < n4; i += stride) q[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        done = n4 * 4;
+    }
+    for (size_t i = done + tid; i < n; i += stride) p[i] = 0.0f;
+}
+
+void hr_launch_fill_zero(const HrFillBatch& b, hipStream_t stream)
+{
+    HrFillBatch c = {};
+    size_t most = 0;
+    for (int i = 0; i < b.count; ++i) {
+        if (!b.p[i] || b.n[i] == 0) continue;
+        c.p[c.count] = b.p[i]; c.n[c.count] = b.n[i];
+        ++c.count;
+        if (b.n[i] > most) most = b.n[i];
+    }
+    if (c.count == 0) return;
+    size_t blocks = (most / 4 + 255) / 256;                   // one 16-byte store per lane and pass
+    if (blocks < 1) blocks = 1;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(hr_fill_zero_kernel, dim3((unsigned)blocks, (unsigned)c.count), dim3(256), 0, stream, c);
 }

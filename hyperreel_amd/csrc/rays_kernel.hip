@@ -1,10 +1,11 @@
 // Camera rays with NDC (hr_generate_rays_ndc), two-plane light-field rays (hr_generate_rays_lightfield, hr_generate_rays_epi) and the
-// training feed (hr_rayset_batch / hr_rayset_order).  One lane per ray; the arithmetic is hr_camera.h's and hr_lightfield.h's, which
+// training feed (hr_rayset_batch / hr_rayset_order / hr_rayset_sample).  One lane per ray; the arithmetic is hr_camera.h's, hr_lightfield.h's and hr_sample_rng.h's, which
 // the CPU suite compiles for the host.  Launch-bound at a training batch (16 384 rays: 64
 // workgroups); nothing to tune beyond the stores: a lane owns a whole output row and writes it in 16- or 8-byte pieces when the
 // buffer is aligned for that, so a wavefront's stores cover a contiguous 64 * row bytes.
 #include "hr_camera.h"
 #include "hr_lightfield.h"
+#include "hr_sample_rng.h"
 #include "hr_kernels.h"
 
 namespace {
@@ -54,13 +55,11 @@ __global__ __launch_bounds__(256) void hr_generate_rays_lightfield_kernel(const 
     }
 }
 
-// row -> set element -> image (binary search in the prefix sums) -> pixel (closed form) -> ray, colour, weight
+// set element -> image (binary search in the prefix sums) -> pixel (closed form) -> ray, colour, weight: output row t of a call.  Shared by
+// hr_rayset_batch (the epoch's order, or the caller's indices) and hr_rayset_sample (draws with replacement): the same bits for the same element
 template <bool VEC, bool LF>
-__global__ __launch_bounds__(256) void hr_rayset_batch_kernel(const HrRaySetArgs a)
+__device__ __forceinline__ void rayset_write_row(const HrRaySetArgs& a, int64_t t, int64_t e)
 {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= a.n) return;
-    const int64_t e = a.indices ? a.indices[t] : (int64_t)hr_perm((uint64_t)a.size, a.key, (uint64_t)(a.first + t));
     if (a.elements) a.elements[t] = e;
     if (!a.coords && !a.rgb && !a.weight) return;
     const bool inside = e >= 0 && e < a.size;           // only a caller's own index can be outside
@@ -92,6 +91,27 @@ __global__ __launch_bounds__(256) void hr_rayset_batch_kernel(const HrRaySetArgs
     if (a.coords) store_ray<VEC>(a.coords + t * a.ray_dim, v, a.ray_dim);
     if (a.rgb) { float* o = a.rgb + t * 3; o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; }
     if (a.weight) a.weight[t] = wgt;
+}
+
+template <bool VEC, bool LF>
+__global__ __launch_bounds__(256) void hr_rayset_batch_kernel(const HrRaySetArgs a)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.n) return;
+    const int64_t e = a.indices ? a.indices[t] : (int64_t)hr_perm((uint64_t)a.size, a.key, (uint64_t)(a.first + t));
+    rayset_write_row<VEC, LF>(a, t, e);
+}
+
+// row t = element hr_sample_element(size, seed, s, t), s = *step_dev when given (read by every lane: one cached word), else `step`.
+// An empty set (size 0) has no element to draw: -1, which rayset_write_row turns into a NaN row of weight 0.
+template <bool VEC, bool LF>
+__global__ __launch_bounds__(256) void hr_rayset_sample_kernel(const HrRaySetArgs a, uint64_t seed, uint64_t step, const uint64_t* __restrict__ step_dev)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.n) return;
+    const uint64_t s = step_dev ? *step_dev : step;
+    const int64_t e = a.size > 0 ? (int64_t)hr_sample_element((uint64_t)a.size, seed, s, (uint64_t)t) : -1;
+    rayset_write_row<VEC, LF>(a, t, e);
 }
 
 bool rows_aligned(const float* p, int ray_dim)
@@ -145,5 +165,19 @@ void hr_launch_rayset_batch(const HrRaySetArgs& a, hipStream_t stream)
     } else {
         if (vec) hipLaunchKernelGGL((hr_rayset_batch_kernel<true, false>), grid, dim3(256), 0, stream, a);
         else hipLaunchKernelGGL((hr_rayset_batch_kernel<false, false>), grid, dim3(256), 0, stream, a);
+    }
+}
+
+void hr_launch_rayset_sample(const HrRaySetArgs& a, uint64_t seed, uint64_t step, const uint64_t* step_dev, hipStream_t stream)
+{
+    if (a.n <= 0) return;
+    const dim3 grid((unsigned)((a.n + 255) / 256));
+    const bool vec = !a.coords || rows_aligned(a.coords, a.ray_dim);
+    if (a.lightfield) {
+        if (vec) hipLaunchKernelGGL((hr_rayset_sample_kernel<true, true>), grid, dim3(256), 0, stream, a, seed, step, step_dev);
+        else hipLaunchKernelGGL((hr_rayset_sample_kernel<false, true>), grid, dim3(256), 0, stream, a, seed, step, step_dev);
+    } else {
+        if (vec) hipLaunchKernelGGL((hr_rayset_sample_kernel<true, false>), grid, dim3(256), 0, stream, a, seed, step, step_dev);
+        else hipLaunchKernelGGL((hr_rayset_sample_kernel<false, false>), grid, dim3(256), 0, stream, a, seed, step, step_dev);
     }
 }

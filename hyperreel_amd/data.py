@@ -204,6 +204,61 @@ class DeviceRaySet:
                                                    C.c_void_p(out['weight'].data_ptr()), self._stream()), 'hr_rayset_batch')
         return out
 
+    def _outputs(self, n, out):
+        """Fresh output tensors of n rows, or the caller's after a shape / dtype / device check."""
+        if out is None:
+            return {'coords': torch.empty((n, self.ray_dim), dtype=torch.float32, device=self.device),
+                    'rgb': torch.empty((n, 3), dtype=torch.float32, device=self.device),
+                    'weight': torch.empty((n, 1), dtype=torch.float32, device=self.device)}
+        for k, cols in (('coords', self.ray_dim), ('rgb', 3), ('weight', 1)):
+            t = out[k]
+            if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n, cols):
+                raise ValueError(f"out['{k}'] must be a contiguous float32 ({n}, {cols}) tensor on the set's device")
+        return out
+
+    @staticmethod
+    def check_step_tensor(step_tensor, device):
+        """The device word hr_rayset_sample reads its step from: one int64 or uint64 element on `device` (HipAdam's step_tensor is one)."""
+        if not isinstance(step_tensor, torch.Tensor):
+            raise TypeError('step_tensor must be a torch tensor')
+        if step_tensor.dtype not in (torch.int64, torch.uint64):
+            raise ValueError(f'step_tensor must be int64 or uint64, got {step_tensor.dtype}')
+        if step_tensor.numel() != 1:
+            raise ValueError(f'step_tensor must hold one element, got {tuple(step_tensor.shape)}')
+        if step_tensor.device != torch.device(device):
+            raise ValueError(f"step_tensor is on {step_tensor.device}, the set on {device}")
+        return step_tensor
+
+    def sample(self, n, step=0, seed=0, step_tensor=None, out=None, want_elements=False):
+        """n rows drawn WITH replacement (hr_rayset_sample): what RandomSampler(replacement=True) feeds the reference's loop under
+        `sample_with_replacement: True`, every shipped training config's setting -- uniform and independent over the set, fixed by
+        (seed, step, row), not torch's stream.  `step`: this training step's number; or `step_tensor`, a one-element int64 / uint64
+        tensor on the set's device that the kernel reads when it runs (HipAdam(capturable=True).step_tensor): a captured call then
+        draws a new batch on every replay.  Returns the dict of `batch` (fresh tensors, or `out`'s), plus 'elements' (n int64: the
+        set element of each row; taken from out['elements'] when `out` has it) with want_elements."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f'sample: n = {n}')
+        if step_tensor is not None:
+            self.check_step_tensor(step_tensor, self.device)
+        had_out = out is not None
+        out = self._outputs(n, out)
+        elements = None
+        if want_elements:
+            elements = out.get('elements') if had_out else None
+            if elements is None:
+                elements = torch.empty((n,), dtype=torch.int64, device=self.device)
+            elif elements.dtype != torch.int64 or elements.device != self.device or not elements.is_contiguous() or tuple(elements.shape) != (n,):
+                raise ValueError(f"out['elements'] must be a contiguous int64 ({n},) tensor on the set's device")
+            out = dict(out, elements=elements)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().hr_rayset_sample(self._h, n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF,
+                                                    C.c_void_p(step_tensor.data_ptr()) if step_tensor is not None else None,
+                                                    C.c_void_p(out['coords'].data_ptr()), C.c_void_p(out['rgb'].data_ptr()),
+                                                    C.c_void_p(out['weight'].data_ptr()),
+                                                    C.c_void_p(elements.data_ptr()) if elements is not None else None, self._stream()), 'hr_rayset_sample')
+        return out
+
     def order(self, first, n, epoch=0, seed=0):
         """The set elements of rows [first, first + n) of the epoch's order: (n) int64 on the device."""
         out = torch.empty((int(n),), dtype=torch.int64, device=self.device)

@@ -12,6 +12,7 @@ hardware wants it:
     torch.autograd.Function over the C ABI (hr_train_forward / hr_train_backward).
 Gradients arrive on the reference's own parameters (planes, lines, basis_mat, MLP weights), so the reference's optimizers,
 schedulers and regularizers apply unchanged.  There is no CPU path: the tensors must live on the HIP device.
+`GraphedStep` records the whole step -- the batch draw, forward, loss, backward and Adam -- once and replays it.
 """
 import ctypes as C
 
@@ -372,3 +373,120 @@ def tv_loss(plane, weight=1.0):
 def l1_mean(plane):
     """torch.mean(torch.abs(plane)) (density_L1, nlf/nets/tensorf_base.py:1024-1035)."""
     return PlaneReg.apply(plane)[2] / plane.numel()
+
+
+class GraphedStep:
+    """The whole training step as ONE replayed graph (torch.cuda.graph over the library's launches):
+
+        gs = GraphedStep(model, optimizer, rayset, batch_size, loss=HipImageLoss('mse'), seed=0, white_bg=None, regularizer=None, warmup=3)
+        out = gs.step()        # one replay: {'loss', 'sse'} as device tensors, no host synchronisation
+
+    One iteration is  rayset.sample(batch_size, step_tensor=optimizer.step_tensor, seed=seed, out=fixed buffers)  ->
+    model.forward_train  ->  loss.step_loss  ->  + regularizer(model) when given (tv_loss / l1_mean terms)  ->
+    zero_grad(set_to_none=True)  ->  backward  ->  optimizer.step().  What changes from step to step lives on the device: the
+    optimizer's step count, which is also the sampler's step, and the learning rates (`optimizer.sync_hyperparameters()`, called by
+    step() before the replay).
+
+    Construction runs `warmup` (>= 1) iterations eagerly on a side stream -- GENUINE training steps: they update the parameters and
+    advance the count, and they are what sizes the library's lazily grown workspaces and allocates the moments -- and then records one
+    iteration on a single stream (no parallel branches), which is not executed.  After construction `warmup` steps have been taken.
+
+    optimizer: HipAdam(capturable=True) holding every trainable parameter of the model.  white_bg: the background of every step; None
+    takes the configuration's `white_bg and not black_bg` -- a recorded step cannot redraw the reference's per-step coin
+    (tensorf_no_sample.py:236), so a model that trains with the coin needs one GraphedStep per background, or the eager loop.
+    step() returns the SAME two tensors every time (the graph's outputs: `loss` is the differentiated total, `sse` the squared-error
+    sum of train/psnr); clone what must outlive the next replay.
+
+    Anything that replaces parameters or changes the compiled configuration -- set_iter inside a schedule window or across a grid
+    growth, upsample_volume_grid, load_state_dict, a new optimizer state -- makes the recording stale: step() raises and names
+    recapture().  Cascade models (point_prediction) are refused."""
+
+    def __init__(self, model, optimizer, rayset, batch_size, loss, seed=0, white_bg=None, regularizer=None, warmup=3):
+        from .optim import HipAdam
+        if not isinstance(optimizer, HipAdam) or not optimizer.capturable:
+            raise TypeError('GraphedStep needs a HipAdam(capturable=True) optimizer: the step count and the learning rates of any other one live on '
+                            'the host, and a recorded step would repeat them')
+        if not hasattr(loss, 'step_loss'):
+            raise TypeError('GraphedStep: loss must be a hyperreel_amd.losses.HipImageLoss')
+        if int(batch_size) < 1 or int(warmup) < 1:
+            raise ValueError('GraphedStep: batch_size >= 1 and warmup >= 1 (the first eager step sizes the workspaces and allocates the moments)')
+        if model._compile(model.grid_size)[0] is not None:
+            raise NotImplementedError('GraphedStep: point_prediction cascades re-create their native model when a schedule moves; use the eager loop')
+        self.model, self.optimizer, self.rayset, self.loss = model, optimizer, rayset, loss
+        self.batch_size, self.seed, self.regularizer = int(batch_size), int(seed), regularizer
+        net_cfg = model.cfg['color']['net']
+        self.white_bg = (bool(net_cfg.get('white_bg', False)) and not bool(net_cfg.get('black_bg', False))) if white_bg is None else bool(white_bg)
+        dev = rayset.device
+        self.batch = {'coords': torch.empty((self.batch_size, rayset.ray_dim), dtype=torch.float32, device=dev),
+                      'rgb': torch.empty((self.batch_size, 3), dtype=torch.float32, device=dev),
+                      'weight': torch.empty((self.batch_size, 1), dtype=torch.float32, device=dev)}
+        self.graph = None
+        self.recapture(warmup=warmup)
+
+    def _iteration(self):
+        b = self.rayset.sample(self.batch_size, step_tensor=self.optimizer.step_tensor, seed=self.seed, out=self.batch)
+        rgb = self.model.forward_train(b['coords'], white_bg=self.white_bg)
+        loss, sse = self.loss.step_loss(rgb, b['rgb'], b['weight'])
+        if self.regularizer is not None:
+            loss = loss + self.regularizer(self.model)
+        self.optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        self.optimizer.step()
+        return loss.detach(), sse
+
+    def _fingerprint(self):
+        """What the recording holds pointers to: the parameters, their moments, and the compiled configuration."""
+        ps = tuple((id(p), p.data_ptr(), tuple(p.shape)) for p in self.model.parameters())
+        st = self.optimizer.state
+        ms = tuple((st[p]['exp_avg'].data_ptr(), st[p]['exp_avg_sq'].data_ptr()) if p in st and 'exp_avg' in st[p] else None
+                   for g in self.optimizer.param_groups for p in g['params'])
+        return ps, ms, self.model._native_cfg
+
+    def recapture(self, optimizer=None, warmup=1):
+        """Runs `warmup` eager iterations (genuine steps; >= 1 whenever parameters were replaced: the native model and the moments are
+        rebuilt by an eager step) and records the iteration again.  optimizer: the new HipAdam(capturable=True) when the parameters were
+        replaced (its count starts where its state says: 0 for a fresh one)."""
+        from .optim import HipAdam
+        if optimizer is not None:
+            if not isinstance(optimizer, HipAdam) or not optimizer.capturable:
+                raise TypeError('GraphedStep.recapture needs a HipAdam(capturable=True) optimizer')
+            self.optimizer = optimizer
+        held = {id(p) for g in self.optimizer.param_groups for p in g['params']}
+        missing = [n for n, p in self.model.named_parameters() if p.requires_grad and id(p) not in held]
+        if missing:
+            raise ValueError(f'GraphedStep: the optimizer does not hold {missing[:3]}{" ..." if len(missing) > 3 else ""} -- after parameters were '
+                             'replaced, build a new HipAdam(capturable=True) over model.parameters() and pass it to recapture(optimizer=...)')
+        self.graph = None
+        self._out = None
+        dev = self.rayset.device
+        self.optimizer.sync_hyperparameters()
+        with torch.cuda.device(dev):
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                for _ in range(int(warmup)):
+                    self._iteration()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            self.optimizer.zero_grad(set_to_none=True)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):                   # one stream: the recording has no parallel branches
+                loss, sse = self._iteration()
+        self.graph, self._out = graph, {'loss': loss, 'sse': sse}
+        self._cur_iter = self.model.cur_iter
+        self._key = self._fingerprint()
+
+    def step(self):
+        """One replay.  Returns {'loss', 'sse'}: device tensors, overwritten by the next replay."""
+        m = self.model
+        if m.cur_iter != self._cur_iter:                     # set_iter since the recording: do the compiled constants still hold?
+            coarse, hc = m._compile(m.grid_size)
+            if bytes(hc) + (bytes(coarse) if coarse is not None else b'') != m._native_cfg:
+                raise RuntimeError(f'GraphedStep: set_iter({m.cur_iter}) changed the compiled configuration the recorded step was built from '
+                                   f'(recorded at {self._cur_iter}); call gs.recapture()')
+            self._cur_iter = m.cur_iter
+        if self.graph is None or self._fingerprint() != self._key:
+            raise RuntimeError('GraphedStep: parameters, optimizer state or the native model were replaced since the step was recorded (grid '
+                               'growth, upsample_volume_grid, load_state_dict ...); call gs.recapture() -- with a new optimizer over the new parameters')
+        self.optimizer.sync_hyperparameters()
+        self.graph.replay()
+        return self._out

@@ -528,6 +528,19 @@ int hr_rayset_batch(const hr_rayset* set, int64_t first, int64_t n, uint64_t see
                     float* coords_dev, float* rgb_dev, float* weight_dev, void* stream);
 /* elements_dev[j] (n int64) = the set element of row first + j of that order: which ray each row of hr_rayset_batch is. */
 int hr_rayset_order(const hr_rayset* set, int64_t first, int64_t n, uint64_t seed, uint64_t epoch, int64_t* elements_dev, void* stream);
+/* n rows drawn WITH replacement -- the sampler every shipped training config asks for (sample_with_replacement: True ->
+ * RandomSampler(replacement=True, num_samples=num_iters * batch_size), nlf/__init__.py:222-230).  Output row j is set element
+ * e(seed, s, j), uniform and independent over [0, size): a counter-based generator (Philox4x32-10, key = seed, counter = (j, s)) whose
+ * 64-bit draw is mapped by multiply-high with size (csrc/hr_sample_rng.h; bias below size / 2^64).  It replaces that sampler and does
+ * not reproduce torch's stream.  s = step when step_dev is NULL, else the 64-bit word at step_dev (DEVICE memory, read when the
+ * kernel runs: a captured launch draws a new batch on every replay once the word has changed -- hr_adam_step_dev's counter serves).
+ * Row j depends on (seed, s, j) alone, not on n.  The rows hold exactly what hr_rayset_batch(indices_dev = those elements) writes;
+ * elements_dev_or_null (n int64) receives the elements.  Any output may be NULL, not all four (HR_E_INVALID when n > 0); n < 0, a
+ * null set and a set without rays are HR_E_INVALID; n == 0 succeeds and launches nothing.  One kernel on `stream`: no allocation, no
+ * synchronisation, no memset, every output element written; capturable in a hipGraph.  Additive: no existing struct or signature moved
+ * (HR_ABI_VERSION stays). */
+int hr_rayset_sample(const hr_rayset* set, int64_t n, uint64_t seed, uint64_t step, const uint64_t* step_dev, float* coords_dev, float* rgb_dev,
+                     float* weight_dev, int64_t* elements_dev_or_null, void* stream);
 
 /* Grid management: F.interpolate(plane, size=(h2, w2), mode='bilinear', align_corners=True) of one
  * (1, C, H, W) float32 plane or line, as TensorVMSplit.up_sampling_VM / TensorVMKeyframeTime.up_sampling_VM apply it
@@ -716,6 +729,17 @@ int hr_plane_reg_backward(const float* plane_dev, int32_t channels, int32_t h, i
  * (amsgrad / maximize off), evaluated in fp32. */
 int hr_adam_step(float* const* param_dev, const float* const* grad_dev, float* const* exp_avg_dev, float* const* exp_avg_sq_dev, const int64_t* n,
                  const double* hp, int32_t n_tensors, void* stream);
+/* hr_adam_step with the step count and the learning rates in DEVICE memory, so that one captured launch performs a new step on every
+ * replay.  The pointer arrays, n and n_tensors as above.  hp holds FOUR doubles per tensor: beta1, beta2, eps, weight_decay (host).
+ * *step_dev (int64) is the 0-based count of steps already done: the call performs step t = *step_dev + 1 with hr_adam_step's arithmetic,
+ * the bias corrections 1 - beta^t evaluated in double on the device (pow), the step size (double)lr / (1 - beta1^t) rounded to float as
+ * there.  Tensor i's learning rate is lr_dev[lr_index[i]] (floats in device memory, one per parameter group; lr_index is host memory,
+ * every entry in [0, n_lr)).  After every tensor has been stepped a stream-ordered single-thread launch stores t into *step_dev: no
+ * workgroup of this call can see the advanced count, and the next call on the stream sees it.  Only kernels on `stream`: no allocation,
+ * no synchronisation, no memset; capturable in a hipGraph.  A call with nothing to step (n_tensors == 0, or every n[i] == 0) leaves
+ * the counter alone.  Additive: no existing struct or signature moved (HR_ABI_VERSION stays). */
+int hr_adam_step_dev(float* const* param_dev, const float* const* grad_dev, float* const* exp_avg_dev, float* const* exp_avg_sq_dev, const int64_t* n,
+                     const double* hp, const int32_t* lr_index, int32_t n_lr, const float* lr_dev, int64_t* step_dev, int32_t n_tensors, void* stream);
 
 /* The two stages of hr_render on their own, for profiling: the sample-prediction MLP
  * (rays -> raw head in the workspace) and the per-sample stage (head -> rgb).  n_rays
