@@ -1,4 +1,4 @@
-// C ABI, camera rays, light-field rays and the training feed: hr_generate_rays_ndc, hr_generate_rays_lightfield, hr_generate_rays_epi,
+// C ABI, camera rays, light-field rays and the training feed: hr_generate_rays_ndc, hr_generate_rays_fisheye, hr_generate_rays_lightfield, hr_generate_rays_epi,
 // hr_rayset_* (kernels: rays_kernel.hip; arithmetic: hr_camera.h, hr_lightfield.h, hr_sample_rng.h).
 // No model handle.  The set owns its device memory; hr_rayset_batch / hr_rayset_order / hr_rayset_sample enqueue one kernel and nothing else.
 #include <hip/hip_runtime.h>
@@ -31,6 +31,18 @@ int check_ndc(const hr_ndc* ndc, const char* who)
                     (double)ndc->fy);
     return HR_OK;
 }
+
+// NULL: no distortion.  A pair whose model is not increasing on [0, pi / 2] has no inverse to compute
+int check_fisheye(const hr_fisheye* fe, const char* who)
+{
+    if (fe && !hr_fisheye_invertible(fe->k1, fe->k2))
+        return fail(HR_E_INVALID, "%s: hr_fisheye (k1 %g, k2 %g) is not invertible: 1 + 3 k1 t^2 + 5 k2 t^4 must stay positive on [0, pi / 2]", who,
+                    (double)fe->k1, (double)fe->k2);
+    return HR_OK;
+}
+
+// NULL or all-zero: no distortion given, the pinhole camera
+bool undistorted(const hr_fisheye* fe) { return !fe || (fe->k1 == 0.0f && fe->k2 == 0.0f); }
 
 int check_lightfield(const hr_lightfield* lf, float a, float b, const char* who)
 {
@@ -113,6 +125,23 @@ int hr_generate_rays_ndc(const hr_camera* cam, const hr_ndc* ndc, int32_t ray_di
     return HR_OK;
 }
 
+int hr_generate_rays_fisheye(const hr_camera* cam, const hr_fisheye* fisheye, const hr_ndc* ndc, int32_t ray_dim, int64_t first_pixel,
+                             int64_t n_pixels, float* rays_dev, void* stream)
+{
+    if (int rc = check_fisheye(fisheye, "hr_generate_rays_fisheye")) return rc;
+    if (undistorted(fisheye)) return hr_generate_rays_ndc(cam, ndc, ray_dim, first_pixel, n_pixels, rays_dev, stream);     // the same kernel: the same bits
+    if (!cam || (n_pixels > 0 && !rays_dev)) return fail(HR_E_INVALID, "hr_generate_rays_fisheye: null argument");
+    if (ray_dim != 6 && ray_dim != 8) return fail(HR_E_INVALID, "hr_generate_rays_fisheye: ray_dim must be 6 or 8");
+    if (cam->width < 1 || cam->height < 1 || cam->fx == 0.0f || cam->fy == 0.0f) return fail(HR_E_INVALID, "hr_generate_rays_fisheye: bad camera");
+    if (first_pixel < 0 || n_pixels < 0 || first_pixel + n_pixels > (int64_t)cam->width * cam->height)
+        return fail(HR_E_INVALID, "hr_generate_rays_fisheye: pixel range outside the image");
+    if (int rc = check_ndc(ndc, "hr_generate_rays_fisheye")) return rc;
+    if (n_pixels == 0) return HR_OK;        // an empty range: nothing to launch
+    hr_launch_generate_rays_fisheye(*cam, *fisheye, ndc, ray_dim, first_pixel, n_pixels, rays_dev, (hipStream_t)stream);
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}
+
 // the set's tables and pixel store; `s` is deleted on failure
 static int rayset_alloc(hr_rayset* s, hr_rayset** out, const char* who)
 {
@@ -178,6 +207,13 @@ static int rayset_commit(hr_rayset* set, int i, const HrRayImage& image, const u
 
 int hr_rayset_set_image(hr_rayset* set, int32_t i, const hr_camera* cam, int32_t every, int32_t offset, const uint8_t* rgb_host_or_dev)
 {
+    return hr_rayset_set_image_fisheye(set, i, cam, nullptr, every, offset, rgb_host_or_dev);
+}
+
+// (messages name hr_rayset_set_image: the plain call is this one without a distortion)
+int hr_rayset_set_image_fisheye(hr_rayset* set, int32_t i, const hr_camera* cam, const hr_fisheye* fisheye, int32_t every, int32_t offset,
+                                const uint8_t* rgb_host_or_dev)
+{
     if (!set || !cam || !rgb_host_or_dev) return fail(HR_E_INVALID, "hr_rayset_set_image: null argument");
     if (set->lightfield) return fail(HR_E_INVALID, "hr_rayset_set_image: the set holds light-field views (hr_rayset_create_lightfield): use hr_rayset_set_view");
     if (i < 0 || i >= set->n_images) return fail(HR_E_INVALID, "hr_rayset_set_image: image %d of %d", (int)i, set->n_images);
@@ -185,8 +221,10 @@ int hr_rayset_set_image(hr_rayset* set, int32_t i, const hr_camera* cam, int32_t
     if (cam->width != set->width || cam->height != set->height || cam->fx == 0.0f || cam->fy == 0.0f)
         return fail(HR_E_INVALID, "hr_rayset_set_image: bad camera (%d x %d in a set of %d x %d, fx %g, fy %g)", (int)cam->width, (int)cam->height,
                     set->width, set->height, (double)cam->fx, (double)cam->fy);
+    if (int rc = check_fisheye(fisheye, "hr_rayset_set_image_fisheye")) return rc;
     HrRayImage im = HrRayImage();
     im.cam = *cam;
+    if (!undistorted(fisheye)) { im.fe = *fisheye; im.has_fe = 1; }
     im.every = every; im.offset = offset;
     return rayset_commit(set, i, im, rgb_host_or_dev);
 }

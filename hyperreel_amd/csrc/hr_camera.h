@@ -1,6 +1,8 @@
 // Camera arithmetic shared by the ray kernels (pack_kernels.hip: hr_generate_rays; rays_kernel.hip: hr_generate_rays_ndc,
-// hr_rayset_batch) and, compiled by the host compiler, by the CPU suite (tests/host_math/hr_camera_host.cpp):
+// hr_generate_rays_fisheye, hr_rayset_batch) and, compiled by the host compiler, by the CPU suite (tests/host_math/hr_camera_host.cpp,
+// hr_fisheye_host.cpp):
 //   hr_pixel_ray        pixel + camera -> the ray the reference's dataset stores (pinhole, optionally NDC)
+//   hr_pixel_ray_fisheye  the same for a fisheye camera's own pixel: hr_fisheye_undistort first (Immersive's training rays)
 //   hr_subsample_*      the k-th pixel of the checkerboard rule (x + y + offset) % every == 0, in closed form
 //   hr_perm             a keyed bijection of [0, n): the epoch's order
 // IEEE division and square root throughout: these values feed the intersections, whose comparisons must fall as the reference's.
@@ -51,6 +53,121 @@ HR_CAM_FN void hr_pixel_ray(const hr_camera& cam, const hr_ndc* ndc, int x, int 
     out[3] = sx * (wx / wz - ox_oz);
     out[4] = sy * (wy / wz - oy_oz);
     out[5] = 1.0f - o2;
+}
+
+// ---- fisheye cameras (datasets/immersive.py:43-48, 514-564): the equidistant model theta_d = theta (1 + k1 theta^2 + k2 theta^4),
+// inverted per pixel as cv2.fisheye.undistortPoints(K = I, D = (k1, k2, 0, 0)) does for the reference.  The contract is the inverse
+// itself, so the solver is ours: Newton from theta = theta_d, a fixed count, every lane the same instructions.
+
+// The model has an inverse on [0, pi / 2] when theta_d(theta) increases there: 1 + 3 k1 u + 5 k2 u^2 > 0 for u = theta^2 in
+// [0, (pi / 2)^2].  A quadratic in u that is 1 at u = 0: its minimum is at the far end or, when it opens upwards, at its vertex.
+HR_CAM_FN bool hr_fisheye_invertible(float k1, float k2)
+{
+    if (!isfinite(k1) || !isfinite(k2)) return false;
+    const double a = 5.0 * (double)k2, b = 3.0 * (double)k1, U = 1.5707963267948966 * 1.5707963267948966;
+    if (1.0 + b * U + a * U * U <= 0.0) return false;
+    if (a > 0.0) {
+        const double u = -b / (2.0 * a);
+        if (u > 0.0 && u < U && 1.0 + b * u + a * u * u <= 0.0) return false;
+    }
+    return true;
+}
+
+// Float32 Newton steps on theta (1 + k1 theta^2 + k2 theta^4) - theta_d from theta = theta_d.  The float32 iterate never comes to
+// rest -- the residual is a difference of two nearly equal numbers, so every further step keeps moving some iterates by up to 3 ulp --
+// but its largest distance to the root stops shrinking: over theta_d in [0, 1.3] and the pairs the tests use that happens after 3
+// steps (2.2e-1, 1.0e-2, 2.7e-5, 1.66e-7, 1.57e-7, 1.52e-7, 1.57e-7, ... for (0.2, -0.02), the slowest; single iterates still gain
+// fractions of an ulp until the 5th).  6 steps: the margin is for invertible pairs stronger than those, and costs nothing in a
+// launch-bound kernel (tests/test_fisheye_host.py prints the table).
+#define HR_FISHEYE_NEWTON_STEPS 6
+
+HR_CAM_FN float hr_fisheye_theta(float k1, float k2, float theta_d, int steps)
+{
+    float th = theta_d;
+    for (int i = 0; i < steps; ++i) {
+        const float t2 = th * th, t4 = t2 * t2;
+        const float f = th * (1.0f + k1 * t2 + k2 * t4) - theta_d;
+        const float fp = 1.0f + 3.0f * k1 * t2 + 5.0f * k2 * t4;
+        th = th - f / fp;
+    }
+    return th;
+}
+
+// tan on [0, pi / 2) out of IEEE operations alone.  tanf would be libm's on the host and the device library's in a kernel: two
+// functions that round differently, where the CPU suite's build of this header has to give the kernels' bits.  On [0, pi / 4]
+// tan x = x + x^3 P(x^2), P a degree-6 minimax fit of (tan x - x) / x^3 (relative error of tan 1.3e-9 before rounding); above,
+// 1 / tan(pi / 2 - x) with pi / 2 in two pieces (the subtraction of the first is exact there).  Within 3 ulp of tan on [0, 1.55].
+HR_CAM_FN float hr_tan_quadrant(float x)
+{
+    const bool flip = x > 0.785398163f;
+    const float a = flip ? (1.5707963705062866f - x) + -4.371138828673793e-08f : x;
+    const float z = a * a;
+    float p = 0.004376267548650503f;
+    p = p * z + 8.95429911906831e-05f;
+    p = p * z + 0.010835813358426094f;
+    p = p * z + 0.02128218486905098f;
+    p = p * z + 0.054059918969869614f;
+    p = p * z + 0.13332663476467133f;
+    p = p * z + 0.33333349227905273f;
+    const float t = a + (a * z) * p;
+    return flip ? 1.0f / t : t;
+}
+
+// (dx, dy) on the distorted image plane -> (dx', dy') on the pinhole one.  A point within 1e-8 of the axis is returned unchanged, as
+// OpenCV returns it (a factor of exactly 1: the same bits, and no branch).
+HR_CAM_FN void hr_fisheye_undistort(float k1, float k2, float dx, float dy, float* ox, float* oy)
+{
+    const float theta_d = sqrtf(dx * dx + dy * dy);
+    const float theta = hr_fisheye_theta(k1, k2, theta_d, HR_FISHEYE_NEWTON_STEPS);
+    const bool on_axis = theta_d <= 1e-8f;
+    const float s = on_axis ? 1.0f : hr_tan_quadrant(theta) / theta_d;
+    *ox = s * dx;
+    *oy = s * dy;
+}
+
+// hr_pixel_ray for a fisheye camera's own pixel: the undistorted direction (dx', dy', -1) is normalised before get_rays rotates and
+// normalises it again (immersive.py:550-558), which the pinhole path never does -- so the rotation and NDC statements of hr_pixel_ray
+// are repeated here on the new direction, and hr_pixel_ray itself stays as it was.  hr_pixel_ray_lens always
+// undistorts; hr_pixel_ray_fisheye adds the interface's convention that a NULL or all-zero hr_fisheye means "no distortion given": the
+// pinhole camera, hr_pixel_ray's bits (include/hyperreel_hip.h; the model itself would make (0, 0) the lens theta_d = theta).
+HR_CAM_FN void hr_pixel_ray_lens(const hr_camera& cam, const hr_fisheye& fe, const hr_ndc* ndc, int x, int y, float* out)
+{
+    const float i = (float)x, j = (float)y;
+    float dx = (i - cam.cx + 0.5f) / cam.fx;
+    float dy = -(j - cam.cy + 0.5f) / cam.fy;
+    float dz = -1.0f;
+    hr_fisheye_undistort(fe.k1, fe.k2, dx, dy, &dx, &dy);
+    const float n0 = fmaxf(sqrtf(dx * dx + dy * dy + dz * dz), 1e-12f);     // F.normalize of the camera-space direction
+    dx = dx / n0; dy = dy / n0; dz = dz / n0;
+    float wx = dx * cam.c2w[0] + dy * cam.c2w[1] + dz * cam.c2w[2];
+    float wy = dx * cam.c2w[4] + dy * cam.c2w[5] + dz * cam.c2w[6];
+    float wz = dx * cam.c2w[8] + dy * cam.c2w[9] + dz * cam.c2w[10];
+    const float nrm = fmaxf(sqrtf(wx * wx + wy * wy + wz * wz), 1e-12f);
+    wx = wx / nrm; wy = wy / nrm; wz = wz / nrm;
+    const float px = cam.c2w[3], py = cam.c2w[7], pz = cam.c2w[11];
+    if (!ndc) {
+        out[0] = px; out[1] = py; out[2] = pz;
+        out[3] = wx; out[4] = wy; out[5] = wz;
+        return;
+    }
+    const float sx = (float)(-1.0 / ((double)ndc->width / (2.0 * (double)ndc->fx)));
+    const float sy = (float)(-1.0 / ((double)ndc->height / (2.0 * (double)ndc->fy)));
+    const float t = -(ndc->near + pz) / wz;
+    const float ox = px + t * wx, oy = py + t * wy, oz = pz + t * wz;
+    const float ox_oz = ox / oz, oy_oz = oy / oz;
+    const float o2 = 1.0f + (2.0f * ndc->near) / oz;
+    out[0] = sx * ox_oz;
+    out[1] = sy * oy_oz;
+    out[2] = o2;
+    out[3] = sx * (wx / wz - ox_oz);
+    out[4] = sy * (wy / wz - oy_oz);
+    out[5] = 1.0f - o2;
+}
+
+HR_CAM_FN void hr_pixel_ray_fisheye(const hr_camera& cam, const hr_fisheye* fe, const hr_ndc* ndc, int x, int y, float* out)
+{
+    if (fe && (fe->k1 != 0.0f || fe->k2 != 0.0f)) hr_pixel_ray_lens(cam, *fe, ndc, x, y, out);
+    else hr_pixel_ray(cam, ndc, x, y, out);
 }
 
 // ---- checkerboard subsampling (datasets/technicolor.py:211-236, datasets/neural_3d.py:168-185): pixel (x, y) is kept when

@@ -1,4 +1,4 @@
-// Camera rays with NDC (hr_generate_rays_ndc), two-plane light-field rays (hr_generate_rays_lightfield, hr_generate_rays_epi) and the
+// Camera rays with NDC (hr_generate_rays_ndc), fisheye cameras' rays (hr_generate_rays_fisheye), two-plane light-field rays (hr_generate_rays_lightfield, hr_generate_rays_epi) and the
 // training feed (hr_rayset_batch / hr_rayset_order / hr_rayset_sample).  One lane per ray; the arithmetic is hr_camera.h's, hr_lightfield.h's and hr_sample_rng.h's, which
 // the CPU suite compiles for the host.  Launch-bound at a training batch (16 384 rays: 64
 // workgroups); nothing to tune beyond the stores: a lane owns a whole output row and writes it in 16- or 8-byte pieces when the
@@ -41,6 +41,22 @@ __global__ __launch_bounds__(256) void hr_generate_rays_ndc_kernel(const hr_came
     }
 }
 
+// hr_generate_rays_ndc_kernel's shape with hr_pixel_ray_lens per pixel (a NULL hr_fisheye never gets here: the pinhole kernels serve it)
+template <bool VEC>
+__global__ __launch_bounds__(256) void hr_generate_rays_fisheye_kernel(const hr_camera cam, const hr_fisheye fe, const hr_ndc ndc, int has_ndc, int ray_dim,
+                                                                       int64_t first_pixel, int64_t n_pixels, float* __restrict__ rays)
+{
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n_pixels; t += (int64_t)gridDim.x * 256) {
+        const int64_t p = first_pixel + t;
+        float v[8];
+        // two calls, not has_ndc ? &ndc : nullptr: with the select the by-value ndc was copied to scratch (24 bytes a lane)
+        if (has_ndc) hr_pixel_ray_lens(cam, fe, &ndc, (int)(p % cam.width), (int)(p / cam.width), v);
+        else hr_pixel_ray_lens(cam, fe, nullptr, (int)(p % cam.width), (int)(p / cam.width), v);
+        v[6] = cam.cam_id; v[7] = cam.time;
+        store_ray<VEC>(rays + t * ray_dim, v, ray_dim);
+    }
+}
+
 // a view at (a, b) = (s, t), or with EPI the slice at (a, b) = (v, t): row p = y * width + x of the list
 template <bool VEC, bool EPI>
 __global__ __launch_bounds__(256) void hr_generate_rays_lightfield_kernel(const hr_lightfield lf, float a, float b, int64_t first, int64_t n,
@@ -76,7 +92,7 @@ __device__ __forceinline__ void rayset_write_row(const HrRaySetArgs& a, int64_t 
         if (LF) {
             hr_lightfield_ray(a.lf, im.s, im.t, x, y, v);
         } else {
-            hr_pixel_ray(im.cam, a.has_ndc ? &a.ndc : nullptr, x, y, v);
+            hr_pixel_ray_fisheye(im.cam, im.has_fe ? &im.fe : nullptr, a.has_ndc ? &a.ndc : nullptr, x, y, v);
             v[6] = im.cam.cam_id; v[7] = im.cam.time;
         }
         if (a.rgb) {
@@ -133,6 +149,21 @@ void hr_launch_generate_rays_ndc(const hr_camera& cam, const hr_ndc* ndc, int ra
                            first_pixel, n_pixels, rays);
     else
         hipLaunchKernelGGL(hr_generate_rays_ndc_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, cam, nd, ndc ? 1 : 0, ray_dim,
+                           first_pixel, n_pixels, rays);
+}
+
+void hr_launch_generate_rays_fisheye(const hr_camera& cam, const hr_fisheye& fe, const hr_ndc* ndc, int ray_dim, int64_t first_pixel,
+                                     int64_t n_pixels, float* rays, hipStream_t stream)
+{
+    if (n_pixels <= 0) return;
+    int64_t blocks = (n_pixels + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    const hr_ndc nd = ndc ? *ndc : hr_ndc();
+    if (rows_aligned(rays, ray_dim))
+        hipLaunchKernelGGL(hr_generate_rays_fisheye_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, cam, fe, nd, ndc ? 1 : 0, ray_dim,
+                           first_pixel, n_pixels, rays);
+    else
+        hipLaunchKernelGGL(hr_generate_rays_fisheye_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, cam, fe, nd, ndc ? 1 : 0, ray_dim,
                            first_pixel, n_pixels, rays);
 }
 

@@ -6,6 +6,9 @@ slice batches out of it (format_batch, base.py:278-284).  A DeviceRaySet keeps t
 one camera and one subsample rule per image, and computes a batch's rays when they are drawn.  Nothing here reads
 files: decoding images stays with the caller.  No CPU path: a missing library or a failing call raises.
 
+Immersive's fisheye cameras (datasets/immersive.py:43-48, 514-523) pass `distortions=`: each image's (k1, k2), undistorted per ray on the
+device.
+
 DeviceRaySet.from_lightfield does the same for the two-plane light-field datasets (datasets/lightfield.py,
 datasets/stanford.py): a position (s, t) on the camera plane per view instead of a camera."""
 import ctypes as C
@@ -14,14 +17,14 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from .plan import hr_camera, hr_lightfield, hr_ndc
+from .plan import hr_camera, hr_fisheye, hr_lightfield, hr_ndc
 
 # subsample rules of the reference's datasets that are not the checkerboard: named so that the refusal can say which
 UNSUPPORTED_RULES = {
     'random_subsample': 'datasets/neural_3d.py:152-166 draws np.random.permutation per image',
     'importance_subsample': 'datasets/neural_3d.py:191-204 thresholds the difference to the previous frame',
     'test_subsample': 'datasets/neural_3d.py:187-189 masks on a ray coordinate',
-    'fisheye': "datasets/immersive.py:43-48,514-523 undistorts through cv2's fisheye model",
+    'fisheye': 'a camera model, not a subsample rule: pass distortions= (datasets/immersive.py:43-48,514-523; DESIGN 3h)',
 }
 
 
@@ -49,6 +52,21 @@ def make_camera(pose, K, width, height, cam_id=0.0, time=0.0):
     cam.width, cam.height = int(width), int(height)
     cam.cam_id, cam.time = float(cam_id), float(time)
     return cam
+
+
+def make_fisheye(distortion):
+    """None | hr_fisheye | (k1, k2) -> hr_fisheye or None: the first two coefficients of a camera's radial distortion, what
+    ImmersiveDataset.get_coords passes to cv2.fisheye.undistortPoints as D = (k1, k2, 0, 0) (datasets/immersive.py:43-48).  Longer
+    sequences are refused: the reference reads two coefficients and so does the kernel.  (0, 0) means no distortion: the library treats
+    it as the pinhole camera, like None (include/hyperreel_hip.h says how that differs from OpenCV's reading of zeros)."""
+    if distortion is None or isinstance(distortion, hr_fisheye):
+        return distortion
+    k = np.asarray(distortion, np.float64).reshape(-1)
+    if k.shape != (2,) or not np.isfinite(k).all():
+        raise ValueError(f'fisheye distortion needs exactly two finite coefficients (k1, k2); got {distortion!r}')
+    out = hr_fisheye()
+    out.k1, out.k2 = float(k[0]), float(k[1])
+    return out
 
 
 def make_lightfield(width, height, aspect=None, st_scale=1.0, uv_scale=1.0, near=-1.0, far=0.0):
@@ -93,9 +111,10 @@ class DeviceRaySet:
     """images_u8: (n, H, W, 3) uint8 (numpy, or a torch tensor on the host or the device), RGB as Image.convert("RGB") holds
     them; poses (n, 3, 4); intrinsics (n, 3, 3) or one (3, 3); times, cam_ids: (n) or None (6-column rays); img_wh = (W, H);
     ndc: None | dict(fx, fy, near, width, height) | hr_ndc; subsample: None (every pixel) or one (every, offset) per image
-    (DeviceRaySet.video_rule builds the reference's).  Element e of the set is row e of the reference's all_inputs."""
+    (DeviceRaySet.video_rule builds the reference's); distortions: None (pinhole cameras) or (n, 2), each image's fisheye (k1, k2)
+    (ImmersiveDataset.distortions[idx][:2]).  Element e of the set is row e of the reference's all_inputs."""
 
-    def __init__(self, images_u8, poses, intrinsics, times, cam_ids, img_wh, ndc=None, subsample=None, device=None):
+    def __init__(self, images_u8, poses, intrinsics, times, cam_ids, img_wh, ndc=None, subsample=None, device=None, distortions=None):
         if isinstance(subsample, str):
             why = UNSUPPORTED_RULES.get(subsample)
             raise NotImplementedError(f'subsample rule {subsample!r} is not supported' + (f' ({why})' if why else '')
@@ -113,6 +132,11 @@ class DeviceRaySet:
         rules = [(1, 0)] * n if subsample is None else [(int(e), int(o)) for e, o in subsample]
         if not (len(images_u8) == len(Ks) == len(times) == len(cam_ids) == len(rules) == n):
             raise ValueError('images, poses, intrinsics, times, cam_ids and subsample must describe the same number of images')
+        if distortions is not None:
+            distortions = np.asarray(distortions, np.float64)
+            if distortions.shape != (n, 2):
+                raise ValueError(f'distortions must be None or an ({n}, 2) array of (k1, k2) per image, got shape {distortions.shape}')
+            distortions = [make_fisheye(d) for d in distortions]
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.width, self.height, self.n_images = W, H, n
         self._ndc = make_ndc(ndc)
@@ -123,8 +147,12 @@ class DeviceRaySet:
             for i in range(n):
                 img = _as_u8_image(images_u8[i], i, H, W)
                 cam = make_camera(poses[i], Ks[i], W, H, cam_ids[i], times[i])
-                _lib.check(L.hr_rayset_set_image(self._h, i, C.byref(cam), rules[i][0], rules[i][1], C.c_void_p(img.data_ptr())),
-                           'hr_rayset_set_image')
+                if distortions is None:
+                    _lib.check(L.hr_rayset_set_image(self._h, i, C.byref(cam), rules[i][0], rules[i][1], C.c_void_p(img.data_ptr())),
+                               'hr_rayset_set_image')
+                else:
+                    _lib.check(L.hr_rayset_set_image_fisheye(self._h, i, C.byref(cam), C.byref(distortions[i]), rules[i][0], rules[i][1],
+                                                             C.c_void_p(img.data_ptr())), 'hr_rayset_set_image_fisheye')
         self._size = int(L.hr_rayset_size(self._h))
 
     @classmethod

@@ -6,7 +6,7 @@ raises.  The product never routes through PyTorch ops or the CPU oracle.
 import ctypes as C
 import os
 
-from .plan import hr_camera, hr_config, hr_fields, hr_lightfield, hr_maps, hr_ndc
+from .plan import hr_camera, hr_config, hr_fields, hr_fisheye, hr_lightfield, hr_maps, hr_ndc
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, '_build', 'libhyperreel_hip.so')
@@ -75,11 +75,14 @@ SYMBOLS = [
     ('hr_shard_range', C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ('hr_generate_rays', C.c_int, [C.POINTER(hr_camera), C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     ('hr_generate_rays_ndc', C.c_int, [C.POINTER(hr_camera), C.POINTER(hr_ndc), C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    ('hr_generate_rays_fisheye', C.c_int, [C.POINTER(hr_camera), C.POINTER(hr_fisheye), C.POINTER(hr_ndc), C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                           C.c_void_p]),
     ('hr_generate_rays_lightfield', C.c_int, [C.POINTER(hr_lightfield), C.c_float, C.c_float, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     ('hr_generate_rays_epi', C.c_int, [C.POINTER(hr_lightfield), C.c_float, C.c_float, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     ('hr_rayset_create', C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(hr_ndc), C.POINTER(C.c_void_p)]),
     ('hr_rayset_destroy', None, [C.c_void_p]),
     ('hr_rayset_set_image', C.c_int, [C.c_void_p, C.c_int32, C.POINTER(hr_camera), C.c_int32, C.c_int32, C.c_void_p]),
+    ('hr_rayset_set_image_fisheye', C.c_int, [C.c_void_p, C.c_int32, C.POINTER(hr_camera), C.POINTER(hr_fisheye), C.c_int32, C.c_int32, C.c_void_p]),
     ('hr_rayset_create_lightfield', C.c_int, [C.c_int32, C.POINTER(hr_lightfield), C.POINTER(C.c_void_p)]),
     ('hr_rayset_set_view', C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
     ('hr_rayset_size', C.c_int64, [C.c_void_p]),

@@ -861,12 +861,14 @@ class HipLightfieldModel(nn.Module):
             return True
         return False
 
-    def generate_rays(self, pose, K, width, height, time=None, cam_id=0.0, pixel_range=None, device=None, ndc=None):
+    def generate_rays(self, pose, K, width, height, time=None, cam_id=0.0, pixel_range=None, device=None, ndc=None, fisheye=None):
         """get_coords_from_camera (datasets/base.py:485-518) on the device: 3x4 camera-to-world
         `pose`, 3x3 intrinsics `K` -> rays (n, 6|8) for pixels [lo, hi) of the row-major image
         (whole image by default).  80 bytes cross the PCIe bus instead of the ray list.
         ndc: dict(fx, fy, near, width, height) or an hr_ndc -- the DATASET's to_ndc arguments (datasets/technicolor.py:355-358),
-        for nets trained on use_ndc datasets: the rays then pass through get_ndc_rays_fx_fy (hr_generate_rays_ndc)."""
+        for nets trained on use_ndc datasets: the rays then pass through get_ndc_rays_fx_fy (hr_generate_rays_ndc).
+        fisheye: (k1, k2) or an hr_fisheye -- the camera's radial distortion, for the rays of an Immersive camera's own pixels
+        (datasets/immersive.py:514-523; hr_generate_rays_fisheye).  None: a pinhole camera, the call and the bits of before."""
         import ctypes as C
         import numpy as np
         from .plan import hr_camera
@@ -885,7 +887,13 @@ class HipLightfieldModel(nn.Module):
         rd = self._hc.ray_dim
         rays = torch.empty((hi - lo, rd), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            if ndc is None:
+            if fisheye is not None:
+                from .data import make_fisheye, make_ndc
+                fe, nd = make_fisheye(fisheye), make_ndc(ndc)
+                _lib.check(L.hr_generate_rays_fisheye(C.byref(cam), C.byref(fe), C.byref(nd) if nd is not None else None, rd, lo, hi - lo,
+                                                      C.c_void_p(rays.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                           'hr_generate_rays_fisheye')
+            elif ndc is None:
                 _lib.check(L.hr_generate_rays(C.byref(cam), rd, lo, hi - lo, C.c_void_p(rays.data_ptr()),
                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_generate_rays')
             else:
@@ -895,10 +903,10 @@ class HipLightfieldModel(nn.Module):
                                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_generate_rays_ndc')
         return rays
 
-    def render_camera(self, pose, K, width, height, time=None, cam_id=0.0, pixel_range=None, ndc=None):
+    def render_camera(self, pose, K, width, height, time=None, cam_id=0.0, pixel_range=None, ndc=None, fisheye=None):
         """The viewer's frame path (utils/gui_utils.py:139-212, nlf/__init__.py:754-807) without
         its host round trips: pose -> rays -> rgb, all on the device and on the current stream."""
-        return self.render(self.generate_rays(pose, K, width, height, time, cam_id, pixel_range, ndc=ndc), frame_time=time)['rgb']
+        return self.render(self.generate_rays(pose, K, width, height, time, cam_id, pixel_range, ndc=ndc, fisheye=fisheye), frame_time=time)['rgb']
 
     def _lightfield_rays(self, epi, a, b, lightfield, pixel_range, device):
         import ctypes as C

@@ -99,6 +99,11 @@ class hr_ndc(C.Structure):
     _fields_ = [('fx', C.c_float), ('fy', C.c_float), ('near', C.c_float), ('width', C.c_int32), ('height', C.c_int32)]
 
 
+class hr_fisheye(C.Structure):
+    """Radial distortion (k1, k2) of a fisheye camera's equidistant model (include/hyperreel_hip.h)."""
+    _fields_ = [('k1', C.c_float), ('k2', C.c_float)]
+
+
 class hr_lightfield(C.Structure):
     """Two-plane light field: the arguments of get_lightfield_rays / get_epi_rays besides the position (include/hyperreel_hip.h)."""
     _fields_ = [('width', C.c_int32), ('height', C.c_int32), ('aspect', C.c_float), ('st_scale', C.c_float), ('uv_scale', C.c_float),

@@ -269,6 +269,16 @@ typedef struct hr_ndc {
     int32_t width, height;
 } hr_ndc;
 
+/* Radial distortion of a fisheye camera (the Immersive dataset: datasets/immersive.py:43-48, 514-523): the first two coefficients of
+ * the equidistant model, theta_d = theta (1 + k1 theta^2 + k2 theta^4), which the reference hands to cv2.fisheye.undistortPoints as
+ * D = (k1, k2, 0, 0) with K = I.  An all-zero hr_fisheye means "no distortion given" and is the pinhole camera, exactly like a NULL one.
+ * (This is a convention of this interface, not of the model: OpenCV treats k1 = k2 = 0 as the plain equidistant lens theta_d = theta,
+ * whose pixels still move by tan(theta_d) / theta_d.  A caller who means that lens passes a coefficient too small to matter, such as
+ * k1 = 1e-30f.) */
+typedef struct hr_fisheye {
+    float k1, k2;
+} hr_fisheye;
+
 /* Two-plane light field (the Stanford configs: datasets/lightfield.py, datasets/stanford.py): what get_lightfield_rays and
  * get_epi_rays (utils/ray_utils.py:14-78) take besides the position on the camera plane.  A ray starts at (s, t) * st_scale on the
  * plane z = near and passes through (u, v) * uv_scale on the plane z = far.  The reference's use_inf, center_u and center_v are
@@ -469,6 +479,21 @@ int hr_generate_rays(const hr_camera* cam, int32_t ray_dim, int64_t first_pixel,
  * ndc == NULL: exactly hr_generate_rays (the same bits). */
 int hr_generate_rays_ndc(const hr_camera* cam, const hr_ndc* ndc, int32_t ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays_dev,
                          void* stream);
+/* The rays of a fisheye camera's own pixels, as ImmersiveDataset.get_coords builds them for training and validation
+ * (datasets/immersive.py:514-564).  Pixel (x, y):
+ *   (dx, dy) = ((x - cx + 0.5) / fx, -(y - cy + 0.5) / fy)                          the pinhole direction's first two components
+ *   theta_d = |(dx, dy)|;  theta solves theta (1 + k1 theta^2 + k2 theta^4) = theta_d;  (dx', dy') = (dx, dy) tan(theta) / theta_d
+ *                                                                                    (unchanged when theta_d <= 1e-8)
+ *   direction = normalize(dx', dy', -1), rotated by the pose and normalised again; origin = the pose's translation;
+ *   then get_ndc_rays_fx_fy when ndc is given.
+ * The contract is this inverse of the equidistant model, solved by a fixed number of Newton steps from theta = theta_d
+ * (csrc/hr_camera.h), not OpenCV's iteration count or its non-convergence sentinel.  fisheye == NULL or
+ * k1 == k2 == 0: exactly hr_generate_rays_ndc (the same kernel, the same bits) -- the reference's render split (distortion = None, line 507).  Ranges, ray_dim, ndc and the launch contract as for
+ * hr_generate_rays_ndc: one kernel on `stream`, no allocation, no synchronisation, no memset, every output element written;
+ * capturable in a hipGraph.  HR_E_INVALID before any launch, besides that call's reasons: a non-finite coefficient, or a pair for
+ * which 1 + 3 k1 t^2 + 5 k2 t^4 <= 0 somewhere on [0, pi / 2] -- theta_d(theta) is then not increasing and has no inverse. */
+int hr_generate_rays_fisheye(const hr_camera* cam, const hr_fisheye* fisheye, const hr_ndc* ndc, int32_t ray_dim, int64_t first_pixel,
+                             int64_t n_pixels, float* rays_dev, void* stream);
 
 /* rays_dev[n_pixels, 6] for pixels [first_pixel, first_pixel + n_pixels) of the row-major U x V view at camera-plane position
  * (s, t): get_lightfield_rays (utils/ray_utils.py:14-45) in its order of float32 operations.  Pixel (x, y):
@@ -502,6 +527,12 @@ void hr_rayset_destroy(hr_rayset* set);
  * offset >= 0) and height * width * 3 bytes of RGB, row-major, host or device memory -- what Image.convert("RGB") holds before ToTensor
  * (get_rgb, technicolor.py:398-417).  Synchronous (set-up, not the training loop).  Images not yet set hold no rays. */
 int hr_rayset_set_image(hr_rayset* set, int32_t i, const hr_camera* cam, int32_t every, int32_t offset, const uint8_t* rgb_host_or_dev);
+/* The same for an image of a fisheye camera: the image's rays are hr_generate_rays_fisheye's, bit for bit; everything else --
+ * elements, order, colours, weights, hr_rayset_batch / _order / _sample -- is unchanged, and images with and without distortion mix
+ * in one set.  fisheye == NULL or both coefficients zero: exactly hr_rayset_set_image.  HR_E_INVALID for the pairs
+ * hr_generate_rays_fisheye refuses and on a light-field set. */
+int hr_rayset_set_image_fisheye(hr_rayset* set, int32_t i, const hr_camera* cam, const hr_fisheye* fisheye, int32_t every, int32_t offset,
+                                const uint8_t* rgb_host_or_dev);
 /* A set whose images are views of one two-plane light field (datasets/lightfield.py, datasets/stanford.py): n_views images of
  * lf->width x lf->height, ray_dim 6, *lf copied.  Element e is views in index order, row-major within a view (after the view's
  * checkerboard rule) -- the order prepare_train_data concatenates in when the caller lists the views as its loops do, t outer and s
