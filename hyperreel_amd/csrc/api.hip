@@ -63,18 +63,6 @@ int hr_allgather_tiles(void* nccl_comm, const float* tile_dev, float* full_dev, 
     return HR_OK;
 }
 
-int hr_generate_rays(const hr_camera* cam, int32_t ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays_dev, void* stream)
-{
-    if (!cam || (n_pixels > 0 && !rays_dev)) return fail(HR_E_INVALID, "null argument");
-    if (ray_dim != 6 && ray_dim != 8) return fail(HR_E_INVALID, "ray_dim must be 6 or 8");
-    if (cam->width < 1 || cam->height < 1 || cam->fx == 0.0f || cam->fy == 0.0f) return fail(HR_E_INVALID, "bad camera");
-    if (first_pixel < 0 || n_pixels < 0 || first_pixel + n_pixels > (int64_t)cam->width * cam->height)
-        return fail(HR_E_INVALID, "pixel range outside the image");
-    hr_launch_generate_rays(*cam, ray_dim, first_pixel, n_pixels, rays_dev, (hipStream_t)stream);
-    HR_HIP(hipGetLastError());
-    return HR_OK;
-}
-
 int hr_upsample_plane(const float* src_dev, int32_t channels, int32_t h, int32_t w, float* dst_dev, int32_t h2, int32_t w2, void* stream)
 {
     if (channels < 0 || h < 1 || w < 1 || h2 < 1 || w2 < 1) return fail(HR_E_INVALID, "bad plane shape");

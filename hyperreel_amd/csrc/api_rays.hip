@@ -1,5 +1,6 @@
-// C ABI, camera rays, light-field rays and the training feed: hr_generate_rays_ndc, hr_generate_rays_fisheye, hr_generate_rays_lightfield, hr_generate_rays_epi,
-// hr_rayset_* (kernels: rays_kernel.hip; arithmetic: hr_camera.h, hr_lightfield.h, hr_sample_rng.h).
+// C ABI, camera rays, light-field rays and the training feed: hr_generate_rays, hr_generate_rays_ndc, hr_generate_rays_fisheye (one set of checks, one
+// routine: generate_pixels), hr_generate_rays_lightfield, hr_generate_rays_epi, hr_rayset_* (kernels: rays_kernel.hip; arithmetic: hr_camera.h,
+// hr_lightfield.h, hr_sample_rng.h).
 // No model handle.  The set owns its device memory; hr_rayset_batch / hr_rayset_order / hr_rayset_sample enqueue one kernel and nothing else.
 #include <hip/hip_runtime.h>
 
@@ -43,6 +44,30 @@ int check_fisheye(const hr_fisheye* fe, const char* who)
 
 // NULL or all-zero: no distortion given, the pinhole camera
 bool undistorted(const hr_fisheye* fe) { return !fe || (fe->k1 == 0.0f && fe->k2 == 0.0f); }
+
+// the arguments every camera pixel-list call shares
+int check_pixel_call(const hr_camera* cam, int ray_dim, int64_t first, int64_t n, const float* rays, const char* who)
+{
+    if (!cam || (n > 0 && !rays)) return fail(HR_E_INVALID, "%s: null argument", who);
+    if (ray_dim != 6 && ray_dim != 8) return fail(HR_E_INVALID, "%s: ray_dim must be 6 or 8", who);
+    if (cam->width < 1 || cam->height < 1 || cam->fx == 0.0f || cam->fy == 0.0f) return fail(HR_E_INVALID, "%s: bad camera", who);
+    const int64_t size = (int64_t)cam->width * cam->height;
+    if (first < 0 || n < 0 || first > size || n > size - first) return fail(HR_E_INVALID, "%s: pixel range outside the image", who);
+    return HR_OK;
+}
+
+// fisheye, ndc: NULL where the entry point has none.  A NULL or all-zero fisheye is the pinhole camera
+int generate_pixels(const hr_camera* cam, const hr_fisheye* fisheye, const hr_ndc* ndc, int ray_dim, int64_t first, int64_t n, float* rays_dev,
+                    void* stream, const char* who)
+{
+    if (int rc = check_fisheye(fisheye, who)) return rc;
+    if (int rc = check_pixel_call(cam, ray_dim, first, n, rays_dev, who)) return rc;
+    if (int rc = check_ndc(ndc, who)) return rc;
+    if (n == 0) return HR_OK;              // an empty range: nothing to launch
+    hr_launch_generate_rays(*cam, undistorted(fisheye) ? nullptr : fisheye, ndc, ray_dim, first, n, rays_dev, (hipStream_t)stream);
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}
 
 int check_lightfield(const hr_lightfield* lf, float a, float b, const char* who)
 {
@@ -110,36 +135,21 @@ int hr_generate_rays_epi(const hr_lightfield* lf, float v, float t, int64_t firs
     return generate_lightfield(lf, true, v, t, first, n, rays_dev, stream, "hr_generate_rays_epi");
 }
 
+int hr_generate_rays(const hr_camera* cam, int32_t ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays_dev, void* stream)
+{
+    return generate_pixels(cam, nullptr, nullptr, ray_dim, first_pixel, n_pixels, rays_dev, stream, "hr_generate_rays");
+}
+
 int hr_generate_rays_ndc(const hr_camera* cam, const hr_ndc* ndc, int32_t ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays_dev,
                          void* stream)
 {
-    if (!cam || (n_pixels > 0 && !rays_dev)) return fail(HR_E_INVALID, "hr_generate_rays_ndc: null argument");
-    if (ray_dim != 6 && ray_dim != 8) return fail(HR_E_INVALID, "hr_generate_rays_ndc: ray_dim must be 6 or 8");
-    if (cam->width < 1 || cam->height < 1 || cam->fx == 0.0f || cam->fy == 0.0f) return fail(HR_E_INVALID, "hr_generate_rays_ndc: bad camera");
-    if (first_pixel < 0 || n_pixels < 0 || first_pixel + n_pixels > (int64_t)cam->width * cam->height)
-        return fail(HR_E_INVALID, "hr_generate_rays_ndc: pixel range outside the image");
-    if (int rc = check_ndc(ndc, "hr_generate_rays_ndc")) return rc;
-    if (!ndc) hr_launch_generate_rays(*cam, ray_dim, first_pixel, n_pixels, rays_dev, (hipStream_t)stream);     // the same kernel: the same bits
-    else hr_launch_generate_rays_ndc(*cam, ndc, ray_dim, first_pixel, n_pixels, rays_dev, (hipStream_t)stream);
-    HR_HIP(hipGetLastError());
-    return HR_OK;
+    return generate_pixels(cam, nullptr, ndc, ray_dim, first_pixel, n_pixels, rays_dev, stream, "hr_generate_rays_ndc");
 }
 
 int hr_generate_rays_fisheye(const hr_camera* cam, const hr_fisheye* fisheye, const hr_ndc* ndc, int32_t ray_dim, int64_t first_pixel,
                              int64_t n_pixels, float* rays_dev, void* stream)
 {
-    if (int rc = check_fisheye(fisheye, "hr_generate_rays_fisheye")) return rc;
-    if (undistorted(fisheye)) return hr_generate_rays_ndc(cam, ndc, ray_dim, first_pixel, n_pixels, rays_dev, stream);     // the same kernel: the same bits
-    if (!cam || (n_pixels > 0 && !rays_dev)) return fail(HR_E_INVALID, "hr_generate_rays_fisheye: null argument");
-    if (ray_dim != 6 && ray_dim != 8) return fail(HR_E_INVALID, "hr_generate_rays_fisheye: ray_dim must be 6 or 8");
-    if (cam->width < 1 || cam->height < 1 || cam->fx == 0.0f || cam->fy == 0.0f) return fail(HR_E_INVALID, "hr_generate_rays_fisheye: bad camera");
-    if (first_pixel < 0 || n_pixels < 0 || first_pixel + n_pixels > (int64_t)cam->width * cam->height)
-        return fail(HR_E_INVALID, "hr_generate_rays_fisheye: pixel range outside the image");
-    if (int rc = check_ndc(ndc, "hr_generate_rays_fisheye")) return rc;
-    if (n_pixels == 0) return HR_OK;        // an empty range: nothing to launch
-    hr_launch_generate_rays_fisheye(*cam, *fisheye, ndc, ray_dim, first_pixel, n_pixels, rays_dev, (hipStream_t)stream);
-    HR_HIP(hipGetLastError());
-    return HR_OK;
+    return generate_pixels(cam, fisheye, ndc, ray_dim, first_pixel, n_pixels, rays_dev, stream, "hr_generate_rays_fisheye");
 }
 
 // the set's tables and pixel store; `s` is deleted on failure
@@ -190,6 +200,14 @@ int hr_rayset_create_lightfield(int32_t n_views, const hr_lightfield* lf, hr_ray
 
 void hr_rayset_destroy(hr_rayset* set) { delete set; }
 
+// slot i of the set (`what`: "image" / "view") and its subsample rule
+static int check_slot(const hr_rayset* set, int i, int every, int offset, const char* who, const char* what)
+{
+    if (i < 0 || i >= set->n_images) return fail(HR_E_INVALID, "%s: %s %d of %d", who, what, i, set->n_images);
+    if (every < 1 || offset < 0) return fail(HR_E_INVALID, "%s: subsample rule every %d, offset %d (every >= 1, offset >= 0)", who, every, offset);
+    return HR_OK;
+}
+
 // pixels and table entry of image i, then the prefix sums from i on
 static int rayset_commit(hr_rayset* set, int i, const HrRayImage& image, const uint8_t* rgb_host_or_dev)
 {
@@ -216,8 +234,7 @@ int hr_rayset_set_image_fisheye(hr_rayset* set, int32_t i, const hr_camera* cam,
 {
     if (!set || !cam || !rgb_host_or_dev) return fail(HR_E_INVALID, "hr_rayset_set_image: null argument");
     if (set->lightfield) return fail(HR_E_INVALID, "hr_rayset_set_image: the set holds light-field views (hr_rayset_create_lightfield): use hr_rayset_set_view");
-    if (i < 0 || i >= set->n_images) return fail(HR_E_INVALID, "hr_rayset_set_image: image %d of %d", (int)i, set->n_images);
-    if (every < 1 || offset < 0) return fail(HR_E_INVALID, "hr_rayset_set_image: subsample rule every %d, offset %d (every >= 1, offset >= 0)", (int)every, (int)offset);
+    if (int rc = check_slot(set, i, every, offset, "hr_rayset_set_image", "image")) return rc;
     if (cam->width != set->width || cam->height != set->height || cam->fx == 0.0f || cam->fy == 0.0f)
         return fail(HR_E_INVALID, "hr_rayset_set_image: bad camera (%d x %d in a set of %d x %d, fx %g, fy %g)", (int)cam->width, (int)cam->height,
                     set->width, set->height, (double)cam->fx, (double)cam->fy);
@@ -233,8 +250,7 @@ int hr_rayset_set_view(hr_rayset* set, int32_t i, float s, float t, int32_t ever
 {
     if (!set || !rgb_host_or_dev) return fail(HR_E_INVALID, "hr_rayset_set_view: null argument");
     if (!set->lightfield) return fail(HR_E_INVALID, "hr_rayset_set_view: the set holds posed images (hr_rayset_create): use hr_rayset_set_image");
-    if (i < 0 || i >= set->n_images) return fail(HR_E_INVALID, "hr_rayset_set_view: view %d of %d", (int)i, set->n_images);
-    if (every < 1 || offset < 0) return fail(HR_E_INVALID, "hr_rayset_set_view: subsample rule every %d, offset %d (every >= 1, offset >= 0)", (int)every, (int)offset);
+    if (int rc = check_slot(set, i, every, offset, "hr_rayset_set_view", "view")) return rc;
     if (!isfinite(s) || !isfinite(t)) return fail(HR_E_INVALID, "hr_rayset_set_view: non-finite position (%g, %g)", (double)s, (double)t);
     HrRayImage im = HrRayImage();
     im.every = every; im.offset = offset;

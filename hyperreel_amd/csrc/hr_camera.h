@@ -1,6 +1,7 @@
-// Camera arithmetic shared by the ray kernels (pack_kernels.hip: hr_generate_rays; rays_kernel.hip: hr_generate_rays_ndc,
-// hr_generate_rays_fisheye, hr_rayset_batch) and, compiled by the host compiler, by the CPU suite (tests/host_math/hr_camera_host.cpp,
-// hr_fisheye_host.cpp):
+// Camera arithmetic shared by the ray kernels (rays_kernel.hip: the pixel-list kernel behind hr_generate_rays, hr_generate_rays_ndc and
+// hr_generate_rays_fisheye, and hr_rayset_batch / hr_rayset_sample) and, compiled by the host compiler, by the CPU suite
+// (tests/host_math/hr_camera_host.cpp, hr_fisheye_host.cpp; tests/test_camera_pin.py pins the bits):
+//   hr_pixel_plane, hr_camera_to_world, hr_world_to_ndc   the one camera pipeline's stages
 //   hr_pixel_ray        pixel + camera -> the ray the reference's dataset stores (pinhole, optionally NDC)
 //   hr_pixel_ray_fisheye  the same for a fisheye camera's own pixel: hr_fisheye_undistort first (Immersive's training rays)
 //   hr_subsample_*      the k-th pixel of the checkerboard rule (x + y + offset) % every == 0, in closed form
@@ -22,17 +23,19 @@
 #define HR_CAM_FN static inline
 #endif
 
-// Camera -> ray (utils/ray_utils.py:98-135, datasets/base.py:485-518): pixel centres +0.5, directions (x, -y, -1) / focal,
-// rotated by the pose, normalised; origin = pose translation.  With `ndc`: get_ndc_rays_fx_fy (utils/ray_utils.py:137-164) in
-// its operation order, with the DATASET's W, H, fx, fy, near (datasets/technicolor.py:355-358), which need not be the frame's.
-// The two scalar factors -1 / (W / (2 fx)) are Python floats in the reference (double arithmetic, rounded once when they meet
-// the float32 tensor), so they are formed in double here.
-HR_CAM_FN void hr_pixel_ray(const hr_camera& cam, const hr_ndc* ndc, int x, int y, float* out)
+// Camera -> ray in the stages it has, each written once; hr_pixel_ray and hr_pixel_ray_lens below only chain them.
+// Stage 1, pixel -> camera plane (utils/ray_utils.py:98-135, datasets/base.py:485-518): pixel centres +0.5, directions (x, -y, -1) / focal.
+HR_CAM_FN void hr_pixel_plane(const hr_camera& cam, int x, int y, float* dx, float* dy)
 {
     const float i = (float)x, j = (float)y;
-    const float dx = (i - cam.cx + 0.5f) / cam.fx;
-    const float dy = -(j - cam.cy + 0.5f) / cam.fy;
-    const float dz = -1.0f;
+    *dx = (i - cam.cx + 0.5f) / cam.fx;
+    *dy = -(j - cam.cy + 0.5f) / cam.fy;
+}
+
+// Stage 2, camera-space direction -> world ray (get_rays, utils/ray_utils.py:117-135): rotated by the pose, normalised; origin = pose
+// translation.  out[0..2] origin, out[3..5] direction.
+HR_CAM_FN void hr_camera_to_world(const hr_camera& cam, float dx, float dy, float dz, float* out)
+{
     float wx = dx * cam.c2w[0] + dy * cam.c2w[1] + dz * cam.c2w[2];
     float wy = dx * cam.c2w[4] + dy * cam.c2w[5] + dz * cam.c2w[6];
     float wz = dx * cam.c2w[8] + dy * cam.c2w[9] + dz * cam.c2w[10];
@@ -40,19 +43,35 @@ HR_CAM_FN void hr_pixel_ray(const hr_camera& cam, const hr_ndc* ndc, int x, int 
     wx = wx / nrm; wy = wy / nrm; wz = wz / nrm;
     out[0] = cam.c2w[3]; out[1] = cam.c2w[7]; out[2] = cam.c2w[11];
     out[3] = wx; out[4] = wy; out[5] = wz;
-    if (!ndc) return;
+}
+
+// Stage 3, world ray -> NDC ray, in place: get_ndc_rays_fx_fy (utils/ray_utils.py:137-164) in its operation order, with the DATASET's
+// W, H, fx, fy, near (datasets/technicolor.py:355-358), which need not be the frame's.  The two scalar factors -1 / (W / (2 fx)) are
+// Python floats in the reference (double arithmetic, rounded once when they meet the float32 tensor), so they are formed in double here.
+HR_CAM_FN void hr_world_to_ndc(const hr_ndc* ndc, float* ray)
+{
+    const float wx = ray[3], wy = ray[4], wz = ray[5];
     const float sx = (float)(-1.0 / ((double)ndc->width / (2.0 * (double)ndc->fx)));
     const float sy = (float)(-1.0 / ((double)ndc->height / (2.0 * (double)ndc->fy)));
-    const float t = -(ndc->near + out[2]) / wz;               // shift the origin to the near plane
-    const float ox = out[0] + t * wx, oy = out[1] + t * wy, oz = out[2] + t * wz;
+    const float t = -(ndc->near + ray[2]) / wz;               // shift the origin to the near plane
+    const float ox = ray[0] + t * wx, oy = ray[1] + t * wy, oz = ray[2] + t * wz;
     const float ox_oz = ox / oz, oy_oz = oy / oz;
     const float o2 = 1.0f + (2.0f * ndc->near) / oz;
-    out[0] = sx * ox_oz;
-    out[1] = sy * oy_oz;
-    out[2] = o2;
-    out[3] = sx * (wx / wz - ox_oz);
-    out[4] = sy * (wy / wz - oy_oz);
-    out[5] = 1.0f - o2;
+    ray[0] = sx * ox_oz;
+    ray[1] = sy * oy_oz;
+    ray[2] = o2;
+    ray[3] = sx * (wx / wz - ox_oz);
+    ray[4] = sy * (wy / wz - oy_oz);
+    ray[5] = 1.0f - o2;
+}
+
+// The pinhole camera: plane -> world (dx, dy, -1) -> NDC when `ndc` is given.
+HR_CAM_FN void hr_pixel_ray(const hr_camera& cam, const hr_ndc* ndc, int x, int y, float* out)
+{
+    float dx, dy;
+    hr_pixel_plane(cam, x, y, &dx, &dy);
+    hr_camera_to_world(cam, dx, dy, -1.0f, out);
+    if (ndc) hr_world_to_ndc(ndc, out);
 }
 
 // ---- fisheye cameras (datasets/immersive.py:43-48, 514-564): the equidistant model theta_d = theta (1 + k1 theta^2 + k2 theta^4),
@@ -125,43 +144,20 @@ HR_CAM_FN void hr_fisheye_undistort(float k1, float k2, float dx, float dy, floa
     *oy = s * dy;
 }
 
-// hr_pixel_ray for a fisheye camera's own pixel: the undistorted direction (dx', dy', -1) is normalised before get_rays rotates and
-// normalises it again (immersive.py:550-558), which the pinhole path never does -- so the rotation and NDC statements of hr_pixel_ray
-// are repeated here on the new direction, and hr_pixel_ray itself stays as it was.  hr_pixel_ray_lens always
-// undistorts; hr_pixel_ray_fisheye adds the interface's convention that a NULL or all-zero hr_fisheye means "no distortion given": the
-// pinhole camera, hr_pixel_ray's bits (include/hyperreel_hip.h; the model itself would make (0, 0) the lens theta_d = theta).
+// hr_pixel_ray for a fisheye camera's own pixel: plane -> hr_fisheye_undistort -> normalise -> world -> NDC when `ndc` is given.  The
+// undistorted direction (dx', dy', -1) is normalised before get_rays rotates and normalises it again (immersive.py:550-558), which the
+// pinhole path never does.  hr_pixel_ray_lens always undistorts; hr_pixel_ray_fisheye adds the interface's convention that a NULL or
+// all-zero hr_fisheye means "no distortion given": the pinhole camera, hr_pixel_ray's bits (include/hyperreel_hip.h; the model itself
+// would make (0, 0) the lens theta_d = theta).
 HR_CAM_FN void hr_pixel_ray_lens(const hr_camera& cam, const hr_fisheye& fe, const hr_ndc* ndc, int x, int y, float* out)
 {
-    const float i = (float)x, j = (float)y;
-    float dx = (i - cam.cx + 0.5f) / cam.fx;
-    float dy = -(j - cam.cy + 0.5f) / cam.fy;
-    float dz = -1.0f;
+    float dx, dy, dz = -1.0f;
+    hr_pixel_plane(cam, x, y, &dx, &dy);
     hr_fisheye_undistort(fe.k1, fe.k2, dx, dy, &dx, &dy);
     const float n0 = fmaxf(sqrtf(dx * dx + dy * dy + dz * dz), 1e-12f);     // F.normalize of the camera-space direction
     dx = dx / n0; dy = dy / n0; dz = dz / n0;
-    float wx = dx * cam.c2w[0] + dy * cam.c2w[1] + dz * cam.c2w[2];
-    float wy = dx * cam.c2w[4] + dy * cam.c2w[5] + dz * cam.c2w[6];
-    float wz = dx * cam.c2w[8] + dy * cam.c2w[9] + dz * cam.c2w[10];
-    const float nrm = fmaxf(sqrtf(wx * wx + wy * wy + wz * wz), 1e-12f);
-    wx = wx / nrm; wy = wy / nrm; wz = wz / nrm;
-    const float px = cam.c2w[3], py = cam.c2w[7], pz = cam.c2w[11];
-    if (!ndc) {
-        out[0] = px; out[1] = py; out[2] = pz;
-        out[3] = wx; out[4] = wy; out[5] = wz;
-        return;
-    }
-    const float sx = (float)(-1.0 / ((double)ndc->width / (2.0 * (double)ndc->fx)));
-    const float sy = (float)(-1.0 / ((double)ndc->height / (2.0 * (double)ndc->fy)));
-    const float t = -(ndc->near + pz) / wz;
-    const float ox = px + t * wx, oy = py + t * wy, oz = pz + t * wz;
-    const float ox_oz = ox / oz, oy_oz = oy / oz;
-    const float o2 = 1.0f + (2.0f * ndc->near) / oz;
-    out[0] = sx * ox_oz;
-    out[1] = sy * oy_oz;
-    out[2] = o2;
-    out[3] = sx * (wx / wz - ox_oz);
-    out[4] = sy * (wy / wz - oy_oz);
-    out[5] = 1.0f - o2;
+    hr_camera_to_world(cam, dx, dy, dz, out);
+    if (ndc) hr_world_to_ndc(ndc, out);
 }
 
 HR_CAM_FN void hr_pixel_ray_fisheye(const hr_camera& cam, const hr_fisheye* fe, const hr_ndc* ndc, int x, int y, float* out)

@@ -228,15 +228,12 @@ struct HrBandArgs {
 };
 void hr_launch_band_probe(const HrBandArgs& a, int z_channels, hipStream_t stream);
 
-void hr_launch_generate_rays(const hr_camera& cam, int ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays, hipStream_t stream);
-
-// camera rays with NDC and the training feed (rays_kernel.hip; arithmetic: hr_camera.h)
-void hr_launch_generate_rays_ndc(const hr_camera& cam, const hr_ndc* ndc, int ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays,
-                                 hipStream_t stream);
-// a fisheye camera's own rays (rays_kernel.hip; arithmetic: hr_camera.h hr_pixel_ray_fisheye); ndc may be NULL
-void hr_launch_generate_rays_fisheye(const hr_camera& cam, const hr_fisheye& fe, const hr_ndc* ndc, int ray_dim, int64_t first_pixel,
-                                     int64_t n_pixels, float* rays, hipStream_t stream);
-// two-plane light-field rays (rays_kernel.hip; arithmetic: hr_lightfield.h).  epi: (a, b) = (v, t) of get_epi_rays, else (s, t) of the view
+// ray kernels (rays_kernel.hip; arithmetic: hr_camera.h, hr_lightfield.h, hr_sample_rng.h)
+// a camera's rays for pixels [first_pixel, + n_pixels) of the row-major image.  fe: the lens to undistort, NULL for a pinhole camera (an
+// all-zero pair is the caller's to turn into NULL); ndc: NULL for world rays
+void hr_launch_generate_rays(const hr_camera& cam, const hr_fisheye* fe, const hr_ndc* ndc, int ray_dim, int64_t first_pixel, int64_t n_pixels,
+                             float* rays, hipStream_t stream);
+// two-plane light-field rays.  epi: (a, b) = (v, t) of get_epi_rays, else (s, t) of the view
 void hr_launch_generate_rays_lightfield(const hr_lightfield& lf, bool epi, float a, float b, int64_t first, int64_t n, float* rays, hipStream_t stream);
 // one image of a device-resident training set: its camera -- or, in a light-field set, its position (s, t) on the camera plane -- and
 // its subsample rule (x + y + offset) % every == 0

@@ -1,5 +1,4 @@
 // One-time layout transforms run by hr_model_finalize (not on the render path).
-#include "hr_camera.h"
 #include "hr_kernels.h"
 #include "hr_math.h"
 
@@ -56,25 +55,6 @@ void hr_launch_head_export(const float* head, float* out, int64_t n_rays, int Z,
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(hr_head_export_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, head, out, n_rays, Z, P, P_live, nq,
                        rows_per_ray, map);
-}
-
-// Camera -> rays: hr_pixel_ray (hr_camera.h) per pixel of the row-major image [+ cam_id, time].
-__global__ void hr_generate_rays_kernel(const hr_camera cam, int ray_dim, int64_t first_pixel, int64_t n_pixels, float* __restrict__ rays)
-{
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_pixels; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t p = first_pixel + t;
-        float* r = rays + t * ray_dim;
-        hr_pixel_ray(cam, nullptr, (int)(p % cam.width), (int)(p / cam.width), r);
-        if (ray_dim == 8) { r[6] = cam.cam_id; r[7] = cam.time; }
-    }
-}
-
-void hr_launch_generate_rays(const hr_camera& cam, int ray_dim, int64_t first_pixel, int64_t n_pixels, float* rays, hipStream_t stream)
-{
-    if (n_pixels <= 0) return;
-    int64_t blocks = (n_pixels + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(hr_generate_rays_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, cam, ray_dim, first_pixel, n_pixels, rays);
 }
 
 // upsample_bilinear2d with align_corners=True, ATen's arithmetic (UpSample.h area_pixel_compute_scale / _source_index,

@@ -28,6 +28,18 @@ UNSUPPORTED_RULES = {
 }
 
 
+def current_stream(device):
+    """The stream argument of the C ABI's calls: torch's current stream on `device`."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _refuse_rule(rule):
+    """Raises for a subsample rule that is not the checkerboard, saying which of the reference's it is when it is one of them."""
+    why = UNSUPPORTED_RULES.get(rule) if isinstance(rule, str) else None
+    raise NotImplementedError(f'subsample rule {rule!r} is not supported' + (f' ({why})' if why else '')
+                              + ': only the checkerboard rule (x + y + offset) % every == 0 is')
+
+
 def make_ndc(ndc):
     """None | hr_ndc | dict(fx, fy, near, width, height) -> hr_ndc or None."""
     if ndc is None or isinstance(ndc, hr_ndc):
@@ -116,44 +128,36 @@ class DeviceRaySet:
 
     def __init__(self, images_u8, poses, intrinsics, times, cam_ids, img_wh, ndc=None, subsample=None, device=None, distortions=None):
         if isinstance(subsample, str):
-            why = UNSUPPORTED_RULES.get(subsample)
-            raise NotImplementedError(f'subsample rule {subsample!r} is not supported' + (f' ({why})' if why else '')
-                                      + ': only the checkerboard rule (x + y + offset) % every == 0 is')
+            _refuse_rule(subsample)
         L = _lib.load()
         W, H = int(img_wh[0]), int(img_wh[1])
         poses = np.asarray(poses, np.float32)
         n = poses.shape[0]
         Ks = np.asarray(intrinsics, np.float32)
         Ks = np.broadcast_to(Ks, (n, 3, 3)) if Ks.ndim == 2 else Ks
-        video = times is not None
-        self.ray_dim = 8 if video else 6
+        self.ray_dim = 8 if times is not None else 6
         times = np.zeros(n) if times is None else np.asarray(times, np.float64)
         cam_ids = np.zeros(n) if cam_ids is None else np.asarray(cam_ids, np.float64)
-        rules = [(1, 0)] * n if subsample is None else [(int(e), int(o)) for e, o in subsample]
-        if not (len(images_u8) == len(Ks) == len(times) == len(cam_ids) == len(rules) == n):
-            raise ValueError('images, poses, intrinsics, times, cam_ids and subsample must describe the same number of images')
         if distortions is not None:
             distortions = np.asarray(distortions, np.float64)
             if distortions.shape != (n, 2):
                 raise ValueError(f'distortions must be None or an ({n}, 2) array of (k1, k2) per image, got shape {distortions.shape}')
             distortions = [make_fisheye(d) for d in distortions]
-        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        self.width, self.height, self.n_images = W, H, n
         self._ndc = make_ndc(ndc)
-        self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(L.hr_rayset_create(n, W, H, self.ray_dim, C.byref(self._ndc) if self._ndc is not None else None, C.byref(self._h)),
-                       'hr_rayset_create')
-            for i in range(n):
-                img = _as_u8_image(images_u8[i], i, H, W)
-                cam = make_camera(poses[i], Ks[i], W, H, cam_ids[i], times[i])
-                if distortions is None:
-                    _lib.check(L.hr_rayset_set_image(self._h, i, C.byref(cam), rules[i][0], rules[i][1], C.c_void_p(img.data_ptr())),
-                               'hr_rayset_set_image')
-                else:
-                    _lib.check(L.hr_rayset_set_image_fisheye(self._h, i, C.byref(cam), C.byref(distortions[i]), rules[i][0], rules[i][1],
-                                                             C.c_void_p(img.data_ptr())), 'hr_rayset_set_image_fisheye')
-        self._size = int(L.hr_rayset_size(self._h))
+
+        def create(handle):
+            _lib.check(L.hr_rayset_create(n, W, H, self.ray_dim, C.byref(self._ndc) if self._ndc is not None else None, handle), 'hr_rayset_create')
+
+        def set_image(i, every, offset, pixels):
+            cam = make_camera(poses[i], Ks[i], W, H, cam_ids[i], times[i])
+            if distortions is None:
+                _lib.check(L.hr_rayset_set_image(self._h, i, C.byref(cam), every, offset, pixels), 'hr_rayset_set_image')
+            else:
+                _lib.check(L.hr_rayset_set_image_fisheye(self._h, i, C.byref(cam), C.byref(distortions[i]), every, offset, pixels),
+                           'hr_rayset_set_image_fisheye')
+
+        self._fill(images_u8, n, W, H, subsample, device, create, set_image, (Ks, times, cam_ids),
+                   'images, poses, intrinsics, times, cam_ids and subsample must describe the same number of images')
 
     @classmethod
     def from_lightfield(cls, images_u8, st, lightfield, subsample=None, device=None):
@@ -162,33 +166,43 @@ class DeviceRaySet:
         prepare_train_data visits them, t outer and s inner (datasets/lightfield.py:106-141); lightfield: make_lightfield(...).
         Element e is row e of that order's concatenated get_lightfield_rays; rays have 6 columns."""
         if isinstance(subsample, str):
-            why = UNSUPPORTED_RULES.get(subsample)
-            raise NotImplementedError(f'subsample rule {subsample!r} is not supported' + (f' ({why})' if why else '')
-                                      + ': only the checkerboard rule (x + y + offset) % every == 0 is')
+            _refuse_rule(subsample)
         if not isinstance(lightfield, hr_lightfield):
             raise TypeError('lightfield must be an hr_lightfield (data.make_lightfield)')
         L = _lib.load()
         st = np.asarray(st, np.float64).reshape(-1, 2)
         n = st.shape[0]
-        W, H = int(lightfield.width), int(lightfield.height)
-        rules = [(1, 0)] * n if subsample is None else [(int(e), int(o)) for e, o in subsample]
-        if not (len(images_u8) == len(rules) == n):
-            raise ValueError('images, st and subsample must describe the same number of views')
         self = cls.__new__(cls)
         self.ray_dim = 6
-        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        self.width, self.height, self.n_images = W, H, n
         self._ndc = None
         self._lightfield = lightfield
+
+        def create(handle):
+            _lib.check(L.hr_rayset_create_lightfield(n, C.byref(lightfield), handle), 'hr_rayset_create_lightfield')
+
+        def set_view(i, every, offset, pixels):
+            _lib.check(L.hr_rayset_set_view(self._h, i, float(st[i, 0]), float(st[i, 1]), every, offset, pixels), 'hr_rayset_set_view')
+
+        self._fill(images_u8, n, int(lightfield.width), int(lightfield.height), subsample, device, create, set_view, (),
+                   'images, st and subsample must describe the same number of views')
+        return self
+
+    def _fill(self, images_u8, n, W, H, subsample, device, create, set_one, per_image, mismatch):
+        """The constructors' shared tail: one checkerboard rule per image, every per-image sequence n long (else ValueError(mismatch)),
+        the device, the handle -- create(pointer to it) -- then set_one(i, every, offset, pixels pointer) for each image in turn, and the
+        set's size.  Both callables check their own C call."""
+        rules = [(1, 0)] * n if subsample is None else [(int(e), int(o)) for e, o in subsample]
+        if not all(len(seq) == n for seq in (images_u8, rules, *per_image)):
+            raise ValueError(mismatch)
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.width, self.height, self.n_images = W, H, n
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(L.hr_rayset_create_lightfield(n, C.byref(lightfield), C.byref(self._h)), 'hr_rayset_create_lightfield')
+            create(C.byref(self._h))
             for i in range(n):
                 img = _as_u8_image(images_u8[i], i, H, W)
-                _lib.check(L.hr_rayset_set_view(self._h, i, float(st[i, 0]), float(st[i, 1]), rules[i][0], rules[i][1], C.c_void_p(img.data_ptr())),
-                           'hr_rayset_set_view')
-        self._size = int(L.hr_rayset_size(self._h))
-        return self
+                set_one(i, rules[i][0], rules[i][1], C.c_void_p(img.data_ptr()))
+        self._size = int(_lib.load().hr_rayset_size(self._h))
 
     def __len__(self):
         return self._size
@@ -201,7 +215,7 @@ class DeviceRaySet:
     __del__ = close
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return current_stream(self.device)
 
     def batch(self, batch_idx, batch_size, epoch=0, seed=0, indices=None, out=None):
         """Rows [batch_idx * batch_size, + batch_size) of the epoch's order (the last batch of an epoch is short), or the set
@@ -216,15 +230,7 @@ class DeviceRaySet:
             n = min(int(batch_size), self._size - first)
             if n <= 0:
                 raise IndexError(f'batch {batch_idx} of {batch_size} starts beyond the set\'s {self._size} rays')
-        if out is None:
-            out = {'coords': torch.empty((n, self.ray_dim), dtype=torch.float32, device=self.device),
-                   'rgb': torch.empty((n, 3), dtype=torch.float32, device=self.device),
-                   'weight': torch.empty((n, 1), dtype=torch.float32, device=self.device)}
-        else:
-            for k, cols in (('coords', self.ray_dim), ('rgb', 3), ('weight', 1)):
-                t = out[k]
-                if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n, cols):
-                    raise ValueError(f"out['{k}'] must be a contiguous float32 ({n}, {cols}) tensor on the set's device")
+        out = self._outputs(n, out)
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().hr_rayset_batch(self._h, first, n, int(seed), int(epoch),
                                                    C.c_void_p(indices.data_ptr()) if indices is not None else None,
@@ -304,8 +310,7 @@ class DeviceRaySet:
         keyframe_offset, any other every round(1 / subsample_frac)-th with the running frame_offset.  The counters start at the
         given values (Neural 3D resets both to the video's index per video, neural_3d.py:225-226).  Returns [(every, offset)]."""
         if rule != 'regular_subsample':
-            why = UNSUPPORTED_RULES.get(rule)
-            raise NotImplementedError(f'subsample rule {rule!r} is not supported' + (f' ({why})' if why else ''))
+            _refuse_rule(rule)
         frames = [int(frame)] if np.isscalar(frame) else [int(f) for f in frame]
         out = []
         for f in frames:

@@ -8,6 +8,7 @@ nn.Parameters under exactly the reference's state_dict keys (SURVEY.md section 5
 reference checkpoints load by name.  The modules hold weights only -- all arithmetic
 happens in libhyperreel_hip.so, which receives the tensors through hr_model_upload.
 """
+import ctypes as C
 import math
 
 import torch
@@ -15,7 +16,8 @@ from torch import nn
 
 from . import lib as _lib
 from .config import n_to_reso, to_plain
-from .plan import compile_model, hr_fields, hr_maps, upload_names
+from .data import current_stream, make_camera, make_fisheye, make_ndc
+from .plan import compile_model, hr_fields, hr_lightfield, hr_maps, upload_names
 
 MAT_MODE = [[0, 1], [0, 2], [1, 2]]
 VEC_MODE = [2, 1, 0]
@@ -188,7 +190,6 @@ class HostTensorVM(nn.Module):
         """TensorBase.getDenseAlpha (tensorf_base.py:381-401) / TensorVMKeyframeTime.getDenseAlpha (tensorf_dynamic.py:499-536):
         alpha = 1 - exp(-sigma * 0.01) on a dense (n0, n1, n2) lattice of the box (keyframe nets: the maximum over the
         frames), points the current mask rejects get 0.  One HIP launch (hr_dense_alpha) on the owner's native model."""
-        import ctypes as C
         owner = self._owner() if getattr(self, '_owner', None) is not None else None
         if owner is None:
             raise RuntimeError('getDenseAlpha needs the owning HipLightfieldModel (its native handle)')
@@ -308,7 +309,6 @@ class HostTensorVM(nn.Module):
         TensorVMKeyframeTime.upsample_volume_grid (nlf/nets/tensorf_dynamic.py:395-441): every plane and line is
         resized bilinearly (align_corners=True) to the new grid by hr_upsample_plane; planes of a video net whose density
         plane has no components are re-created as zeros, as in the reference.  Parameters must live on the HIP device."""
-        import ctypes as C
         L = _lib.load()
         N = [int(v) for v in res_target]
 
@@ -495,7 +495,6 @@ class HipLightfieldModel(nn.Module):
 
     def _sync_schedule(self, hc=None, coarse=None):
         """Hands the configuration compiled at cur_iter to an existing native handle if it differs from what it holds."""
-        import ctypes as C
         if hc is None:
             coarse, hc = self._compile(self.grid_size)
         blob = bytes(hc) + (bytes(coarse) if coarse is not None else b'')
@@ -529,7 +528,6 @@ class HipLightfieldModel(nn.Module):
         dev = tensors[0][1].device
         if dev.type != 'cuda':
             raise RuntimeError('HipLightfieldModel must live on a HIP device (model.cuda()); there is no CPU path')
-        import ctypes as C
         def create():
             h = C.c_void_p()
             if coarse is None:
@@ -566,7 +564,6 @@ class HipLightfieldModel(nn.Module):
 
     def _sync_occupancy(self):
         """Hands the colour net's current mask volume to the native model (or clears it)."""
-        import ctypes as C
         net = self.color_model.net
         vol = getattr(net, 'alpha_volume', None) if self.use_occupancy else None
         key = None if vol is None else (vol.data_ptr(), vol._version, tuple(vol.shape), net.alpha_aabb.data_ptr(), net.alpha_aabb._version)
@@ -632,7 +629,6 @@ class HipLightfieldModel(nn.Module):
 
     def frame_kernel_active(self):
         """True when render() of this model runs as the single persistent frame kernel (head tile in LDS)."""
-        import ctypes as C
         v = C.c_int32(0)
         _lib.check(_lib.load().hr_model_get_option(self.native(), _lib.HR_OPT_FRAME_KERNEL_ACTIVE, C.byref(v)), 'hr_model_get_option')
         return bool(v.value)
@@ -642,7 +638,6 @@ class HipLightfieldModel(nn.Module):
         return self._get_option(_lib.HR_OPT_CHUNK_RAYS)
 
     def _get_option(self, opt):
-        import ctypes as C
         v = C.c_int32(0)
         _lib.check(_lib.load().hr_model_get_option(self.native(), opt, C.byref(v)), 'hr_model_get_option')
         return int(v.value)
@@ -672,7 +667,6 @@ class HipLightfieldModel(nn.Module):
     def verify_info(self):
         """hr_model_verify_info as a dict: the band of the verified fast path for THIS model and the f16f8-vs-f16x3 measurement on the
         calibration rays it was derived from (band = max(floor, 4 x the largest difference of a distance / length / point))."""
-        import ctypes as C
         v = _lib.hr_verify_info()
         _lib.check(_lib.load().hr_model_verify_info(self.native(), C.byref(v)), 'hr_model_verify_info')
         return {k: getattr(v, k) for k, _ in v._fields_}
@@ -688,7 +682,6 @@ class HipLightfieldModel(nn.Module):
 
     def calibrate(self, rays):
         """Re-decides the MLP arithmetic on the caller's rays (hr_model_calibrate); returns the per-layer activation maxima."""
-        import ctypes as C
         self.native()
         rays = self._check_rays(rays)
         out = (C.c_float * 8)()
@@ -737,7 +730,6 @@ class HipLightfieldModel(nn.Module):
         'distances' (B,1) = sum_k w_k d_k (depth), 'points' (B,3) = sum_k w_k p_k (expected point), 'acc' (B,1) = sum_k w_k (opacity) --
         the reference's fields=['distances', 'points'] and acc_map.  maps_out: {name: existing contiguous float32 device tensor} to
         render those maps into (a captured graph's fixed buffers).  `want` and `maps` are exclusive."""
-        import ctypes as C
         h = self.native()
         self._sync_occupancy()
         L = _lib.load()
@@ -869,38 +861,17 @@ class HipLightfieldModel(nn.Module):
         for nets trained on use_ndc datasets: the rays then pass through get_ndc_rays_fx_fy (hr_generate_rays_ndc).
         fisheye: (k1, k2) or an hr_fisheye -- the camera's radial distortion, for the rays of an Immersive camera's own pixels
         (datasets/immersive.py:514-523; hr_generate_rays_fisheye).  None: a pinhole camera, the call and the bits of before."""
-        import ctypes as C
-        import numpy as np
-        from .plan import hr_camera
         self.native()
-        L = _lib.load()
         dev = torch.device(device) if device is not None else next(self.parameters()).device
         lo, hi = (0, int(width) * int(height)) if pixel_range is None else (int(pixel_range[0]), int(pixel_range[1]))
-        cam = hr_camera()
-        p = np.asarray(pose, np.float32)[:3, :4].reshape(-1)
-        for i in range(12):
-            cam.c2w[i] = float(p[i])
-        Km = np.asarray(K, np.float32)
-        cam.fx, cam.fy, cam.cx, cam.cy = float(Km[0, 0]), float(Km[1, 1]), float(Km[0, 2]), float(Km[1, 2])
-        cam.width, cam.height = int(width), int(height)
-        cam.cam_id, cam.time = float(cam_id), float(0.0 if time is None else time)
+        cam = make_camera(pose, K, width, height, cam_id, 0.0 if time is None else time)
+        fe, nd = make_fisheye(fisheye), make_ndc(ndc)
         rd = self._hc.ray_dim
         rays = torch.empty((hi - lo, rd), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            if fisheye is not None:
-                from .data import make_fisheye, make_ndc
-                fe, nd = make_fisheye(fisheye), make_ndc(ndc)
-                _lib.check(L.hr_generate_rays_fisheye(C.byref(cam), C.byref(fe), C.byref(nd) if nd is not None else None, rd, lo, hi - lo,
-                                                      C.c_void_p(rays.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                           'hr_generate_rays_fisheye')
-            elif ndc is None:
-                _lib.check(L.hr_generate_rays(C.byref(cam), rd, lo, hi - lo, C.c_void_p(rays.data_ptr()),
-                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_generate_rays')
-            else:
-                from .data import make_ndc
-                nd = make_ndc(ndc)
-                _lib.check(L.hr_generate_rays_ndc(C.byref(cam), C.byref(nd), rd, lo, hi - lo, C.c_void_p(rays.data_ptr()),
-                                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_generate_rays_ndc')
+        with torch.cuda.device(dev):                    # NULL for both optional pointers: hr_generate_rays itself
+            _lib.check(_lib.load().hr_generate_rays_fisheye(C.byref(cam), C.byref(fe) if fe is not None else None,
+                                                            C.byref(nd) if nd is not None else None, rd, lo, hi - lo,
+                                                            C.c_void_p(rays.data_ptr()), current_stream(dev)), 'hr_generate_rays_fisheye')
         return rays
 
     def render_camera(self, pose, K, width, height, time=None, cam_id=0.0, pixel_range=None, ndc=None, fisheye=None):
@@ -909,8 +880,6 @@ class HipLightfieldModel(nn.Module):
         return self.render(self.generate_rays(pose, K, width, height, time, cam_id, pixel_range, ndc=ndc, fisheye=fisheye), frame_time=time)['rgb']
 
     def _lightfield_rays(self, epi, a, b, lightfield, pixel_range, device):
-        import ctypes as C
-        from .plan import hr_lightfield
         if not isinstance(lightfield, hr_lightfield):
             raise TypeError('lightfield must be an hr_lightfield (data.make_lightfield)')
         self.native()
@@ -924,8 +893,7 @@ class HipLightfieldModel(nn.Module):
         rays = torch.empty((hi - lo, 6), dtype=torch.float32, device=dev)
         fn, name = (L.hr_generate_rays_epi, 'hr_generate_rays_epi') if epi else (L.hr_generate_rays_lightfield, 'hr_generate_rays_lightfield')
         with torch.cuda.device(dev):
-            _lib.check(fn(C.byref(lightfield), float(a), float(b), lo, hi - lo, C.c_void_p(rays.data_ptr()),
-                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), name)
+            _lib.check(fn(C.byref(lightfield), float(a), float(b), lo, hi - lo, C.c_void_p(rays.data_ptr()), current_stream(dev)), name)
         return rays
 
     def generate_lightfield_rays(self, s, t, lightfield, pixel_range=None, device=None):
@@ -958,7 +926,6 @@ class HipLightfieldModel(nn.Module):
     def pack_display(self, rgb, height, width, transpose=False, flip=False, rgba8=True):
         """The viewer's hand-over (utils/gui_utils.py:174-205) on the device: rgb (H*W, 3) as rendered -> the displayed
         buffer, transposed / flipped as NeRFGUI does on the host, as 8-bit RGBA (to8b, utils/__init__.py:47) or fp32 RGB."""
-        import ctypes as C
         oh, ow = (width, height) if transpose else (height, width)
         rgb = rgb.contiguous().float()
         if rgb.device.type != 'cuda' or rgb.numel() != height * width * 3:

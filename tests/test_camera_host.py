@@ -160,6 +160,9 @@ def test_video_rule_reproduces_the_fixtures():
             DeviceRaySet.video_rule([0, 1], rule=rule)
         with pytest.raises(NotImplementedError, match=rule):
             DeviceRaySet(None, None, None, None, None, (4, 4), subsample=rule)
+    for rule in (None, b'regular_subsample', 3):              # anything that is not the one supported name, a string or not
+        with pytest.raises(NotImplementedError, match='not supported'):
+            DeviceRaySet.video_rule([0, 1], rule=rule)
 
 
 @pytest.mark.reference

@@ -198,6 +198,14 @@ def test_non_invertible_pairs_are_refused(hf):
     refused(L.hr_generate_rays_fisheye(C.byref(cam), C.byref(good), None, 7, 0, 16, _ptr(buf), None), 'ray_dim')
     refused(L.hr_generate_rays_fisheye(C.byref(cam), C.byref(good), None, 6, 24 * 14 - 2, 4, _ptr(buf), None), 'pixel range')
     refused(L.hr_generate_rays_fisheye(C.byref(cam), C.byref(good), None, 6, -1, 4, _ptr(buf), None), 'pixel range')
+    # a range whose first + n does not fit int64 is outside the image like any other; the three camera entries share the check, and
+    # each message names its entry
+    big = 2 ** 63 - 1
+    refused(L.hr_generate_rays_fisheye(C.byref(cam), C.byref(good), None, 6, big, 4, _ptr(buf), None), 'hr_generate_rays_fisheye: pixel range')
+    refused(L.hr_generate_rays_fisheye(C.byref(cam), C.byref(good), None, 6, 4, big, _ptr(buf), None), 'hr_generate_rays_fisheye: pixel range')
+    refused(L.hr_generate_rays_ndc(C.byref(cam), None, 6, big, 4, _ptr(buf), None), 'hr_generate_rays_ndc: pixel range')
+    refused(L.hr_generate_rays(C.byref(cam), 6, big, big, _ptr(buf), None), 'hr_generate_rays: pixel range')
+    refused(L.hr_generate_rays(C.byref(cam), 5, 0, 4, _ptr(buf), None), 'hr_generate_rays: ray_dim')
     bad_ndc = data.make_ndc(dict(fx=0.0, fy=1.0, near=1.0, width=8, height=8))
     refused(L.hr_generate_rays_fisheye(C.byref(cam), C.byref(good), C.byref(bad_ndc), 6, 0, 4, _ptr(buf), None), 'hr_ndc')
     assert L.hr_generate_rays_fisheye(C.byref(cam), C.byref(good), None, 6, 5, 0, None, None) == 0          # an empty range: nothing to launch

@@ -72,7 +72,7 @@ def test_generate_rays_against_the_host_header_and_the_oracle(name):
                 for first, n in _ranges(size):
                     part = _abi_rays(name, pair, ndc, rd, first, n)
                     assert torch.equal(_bits(part), _bits(full[first:first + n])), (name, rd, first, n)
-                first, n = _ranges(size)[1]                     # off a 16-byte boundary: the scalar-store form of the kernel
+                first, n = _ranges(size)[1]                     # off a 16-byte boundary: the same stores take it
                 part = _abi_rays(name, pair, ndc, rd, first, n, misalign=1)
                 assert torch.equal(_bits(part), _bits(full[first:first + n]))
 

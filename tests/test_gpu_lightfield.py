@@ -74,7 +74,7 @@ def test_view_rays_against_the_reference_and_the_host_header(name):
         for first, n in _ranges(size):
             part = _abi_rays(lf, False, s, t, first, n)
             assert torch.equal(_bits(part), _bits(full[first:first + n])), (name, i, first, n)
-        # a range into a buffer that starts off an 8-byte boundary (the scalar-store form of the kernel)
+        # a range into a buffer that starts off an 8-byte boundary (the same stores take it)
         first, n = _ranges(size)[1]
         flat = torch.full((n * 6 + 1,), float('nan'), device='cuda')
         part = _abi_rays(lf, False, s, t, first, n, base=flat[1:].view(n, 6))

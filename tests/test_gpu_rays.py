@@ -1,4 +1,4 @@
-"""`-m gpu`: camera rays with NDC (hr_generate_rays_ndc, generate_rays / render_camera with ndc=) and the device-resident training
+"""`-m gpu`: camera rays, plain and with NDC (hr_generate_rays, hr_generate_rays_ndc, generate_rays / render_camera with ndc=) and the device-resident training
 feed (hr_rayset_*, hyperreel_amd.data.DeviceRaySet) against the reference's own rays and all_inputs (tests/golden/camera, written
 by tools/make_camera_golden.py) and against hyperreel_amd/csrc/hr_camera.h compiled for the host.
 
@@ -72,6 +72,40 @@ def test_null_ndc_is_generate_rays():
             assert n == 0 or not torch.isnan(a).any()
 
 
+@pytest.mark.parametrize('name', ['centred', 'short_focal'])
+def test_the_plain_entry_against_the_host_header(name):
+    """hr_generate_rays itself (test_null_ndc_is_generate_rays compares two entries of one kernel) on fisheye_common's 24 x 14 cameras --
+    336 pixels: two workgroups, the second partly empty -- bit for bit the host-compiled hr_pixel_ray, into rows on 16- / 8-byte
+    boundaries and into rows one float off them (the kernel's 16- and 8-byte stores take either), whole image and sub-ranges, the empty
+    ones too: every element of the range written, the 64 guard floats on either side untouched."""
+    import fisheye_common as FC
+    from test_gpu_fisheye import GUARD, _ranges
+    L, hf = _lib.load(), FC.host_lib()
+    W, H = FC.CASES[name][:2]
+    size = W * H
+    assert (W, H) == (24, 14) and 256 < size < 512
+    cam = FC.camera_of(name, 3.0, 0.25)
+    host = np.full((size, 6), np.nan, np.float32)
+    hf.hf_pinhole_rays(C.byref(cam), None, 0, size, host.ctypes.data_as(C.c_void_p))
+    assert not np.isnan(host).any()
+    for rd in (6, 8):
+        for misalign in (0, 1):
+            for first, n in [(0, size)] + _ranges(size):
+                flat = torch.full((GUARD + misalign + n * rd + GUARD,), float('nan'), device='cuda')
+                out = flat[GUARD + misalign:GUARD + misalign + n * rd].view(n, rd)
+                assert n == 0 or out.data_ptr() % 16 == 4 * misalign
+                rc = L.hr_generate_rays(C.byref(cam), rd, first, n, C.c_void_p(out.data_ptr()), _stream())
+                assert rc == 0, L.hr_last_error()
+                torch.cuda.synchronize()
+                what = (name, rd, misalign, first, n)
+                assert torch.isnan(flat[:GUARD + misalign]).all() and torch.isnan(flat[GUARD + misalign + n * rd:]).all(), what
+                got = out.cpu().numpy()
+                assert not np.isnan(got).any(), what
+                assert np.array_equal(got[:, :6].view(np.uint32), host[first:first + n].view(np.uint32)), what
+                if rd == 8:
+                    assert np.array_equal(got[:, 6:], np.broadcast_to(np.float32([3.0, 0.25]), (n, 2))), what
+
+
 @pytest.mark.parametrize('name', CC.CASES)
 def test_generate_rays_against_the_reference_and_the_host_header(name):
     """Whole frames of every full-resolution image of the fixture: within the bar of the reference's rays, and bit for bit what
@@ -93,7 +127,7 @@ def test_generate_rays_against_the_reference_and_the_host_header(name):
         host = np.empty((W * H, 6), np.float32)
         hc.hc_pixel_rays(C.byref(cam), C.byref(nd) if nd is not None else None, 0, W * H, host.ctypes.data_as(C.c_void_p))
         assert np.array_equal(got[:, :6].view(np.uint32), host.view(np.uint32)), (name, i)
-        # a pixel sub-range into a buffer that starts off a 16-byte boundary (the scalar-store form of the kernel)
+        # a pixel sub-range into a buffer that starts off a 16-byte boundary (the same stores take it)
         lo, n = W + 3, 2 * W + 5
         flat = torch.full((n * rd + 1,), float('nan'), device='cuda')
         part = _abi_rays(cam, nd, rd, lo, n, base=flat[1:].view(n, rd)).cpu().numpy()
