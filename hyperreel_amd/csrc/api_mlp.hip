@@ -9,223 +9,46 @@
 
 #include "hr_model.h"
 
-namespace {
-
-// float -> bf16 bits, round to nearest even (finite inputs)
-uint16_t bf16_rne(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-// float -> IEEE half bits and back (round to nearest even; overflow -> inf like the hardware conversion)
-uint16_t f16_rne(float f)
-{
-    const _Float16 h = (_Float16)f;
-    uint16_t u;
-    memcpy(&u, &h, 2);
-    return u;
-}
-
-float f16_to_float(uint16_t u)
-{
-    _Float16 h;
-    memcpy(&h, &u, 2);
-    return (float)h;
-}
-
-// OCP e4m3 (what v_mfma_scale_f32_32x32x64_f8f6f4 reads with cbsz / blgp = 0): 1-4-3, bias 7, no infinities, 0x7f = NaN, largest 448;
-// round-to-nearest-even, subnormals down to 2^-9.  The packed weights stay below 2^8 by construction, so nothing saturates here.
-uint8_t e4m3_rne(float f)
-{
-    const uint8_t sign = std::signbit(f) ? 0x80 : 0;
-    float a = fabsf(f);
-    if (!(a == a)) return 0x7f;
-    if (a > 448.0f) a = 448.0f;
-    if (a < ldexpf(1.0f, -10)) return sign;                    // below half the smallest subnormal (a tie at 2^-10 goes to even = 0)
-    int e = 0;
-    (void)frexpf(a, &e);                                       // a = m * 2^e, m in [0.5, 1)
-    int ex = e - 1;                                            // a = 1.xxx * 2^ex
-    if (ex < -6) ex = -6;                                      // subnormal range: fixed quantum 2^-9
-    const float q = ldexpf(1.0f, ex - 3);                      // spacing
-    const float r = nearbyintf(a / q);                         // ties to even (default rounding mode)
-    float v = r * q;
-    if (v > 448.0f) v = 448.0f;
-    if (v < ldexpf(1.0f, -6)) return (uint8_t)(sign | (int)(v / ldexpf(1.0f, -9)));
-    (void)frexpf(v, &e);
-    const int E = e - 1 + 7;
-    const int M = (int)(v / ldexpf(1.0f, e - 1 - 3)) - 8;
-    return (uint8_t)(sign | (E << 3) | M);
-}
-float bf16_to_float(uint16_t h)
-{
-    uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-}  // namespace
-
-// The MLP's weights re-laid out for the active arithmetic (m->active_precision).  Called by hr_model_finalize and again by
-// hr_model_calibrate when the calibration changes that choice.
-// f16 + fp8 split: how far above the calibration's largest activation of a layer the fp8 image of that layer's output still is finite
-// (e4m3 keeps 4 significant bits over the 15 octaves below that; the correction products it feeds are 2^-11 of the result)
-static const float HR_F8_HEADROOM = 16.0f;
-
 // fp8 image of hidden Linear l's output (f16 + fp8 split only): e4m3(x * 2^-Ea) with the calibration's largest |pre-activation| of that layer
-// (act_max[l + 1]) times HR_F8_HEADROOM at or below 448 -- beyond 448 * 2^Ea the image saturates and the kernels say so (HR_OPT_MLP_F8_SATURATED).  Depends on the
-// calibration only, not on the packed weights: hr_model_calibrate refreshes it without re-packing.
+// (act_max[l + 1]) times HR_F8_HEADROOM at or below 448 (hr_f8_exponent, hr_mlp_pack.h) -- beyond 448 * 2^Ea the image saturates and the
+// kernels say so (HR_OPT_MLP_F8_SATURATED).  Depends on the calibration only, not on the packed weights: hr_model_calibrate refreshes it
+// without re-packing.
 static void f8_exponents(hr_model* m)
 {
     for (int l = 0; l < HR_MAX_LAYERS; ++l) {
-        m->xexp[l] = 0;
-        if (m->active_precision != HR_MLP_F16F8 || l + 1 >= m->cfg.mlp_layers) continue;
-        const float mx = m->act_max[l + 1] * HR_F8_HEADROOM;
-        int e = 0;
-        if (mx > 0.0f && std::isfinite(mx)) {
-            (void)frexpf(mx / 448.0f, &e);              // mx / 448 = f * 2^e, f in [0.5, 1): mx <= 448 * 2^e
-            e = e < -30 ? -30 : (e > 30 ? 30 : e);
-        }
-        m->xexp[l] = e;
+        const bool hidden_f8 = m->active_precision == HR_MLP_F16F8 && l + 1 < m->cfg.mlp_layers;
+        m->xexp[l] = hidden_f8 ? hr_f8_exponent(m->act_max[l + 1]) : 0;
     }
 }
 
-// Linear l as the kernels compute it (pack_mlp_as, and on the device hr_mlp_train_forward): output tiles of tile_n features
-HrMlpLayer mlp_layer(const hr_model* m, int l, int tile_n)
-{
-    const hr_config& c = m->cfg;
-    HrMlpLayer g = {};
-    g.k0p = (c.mlp_in + 15) & ~15;
-    g.n_out = samples_per_row(c) * m->p_live;
-    g.P_user = c.preds_per_z;
-    g.P_live = m->p_live;
-    for (int i = 0, j = 0; i < g.P_user && i < 64; ++i)
-        if (m->col_map.col[i] >= 0) g.live_cols[j++] = i;
-    g.first = (l == 0);
-    g.skip = (c.mlp_skip_mask >> l) & 1;
-    g.last = (l == c.mlp_layers - 1);
-    g.N_user = layer_out(c, l);
-    g.Kt = layer_in(c, l);
-    g.N = g.last ? g.n_out : g.N_user;
-    g.Kp = g.first ? g.k0p : (g.skip ? g.k0p + c.mlp_hidden : c.mlp_hidden);
-    g.nt = (g.N + tile_n - 1) / tile_n;
-    return g;
-}
-
-// one packing of the MLP in `precision` -> t
+// One packing of the MLP's weights in `precision` -> t (layout, roundings and scalings: hr_mlp_pack.h).  Called by hr_model_finalize
+// and again by hr_model_calibrate when the calibration changes the active arithmetic.
 static int pack_mlp_as(hr_model* m, const int precision, HrMlpTiles& t)
 {
     const hr_config& c = m->cfg;
     char name[64];
     t.bytes = 0;
-    // ---- MLP: MFMA B-operand tiles (layout documented in hr_kernels.h)
-    const bool split = (precision != HR_MLP_FP32);
-    const bool f8lo = (precision == HR_MLP_F16F8);
-    const bool half = (precision == HR_MLP_F16X3 || precision == HR_MLP_F16X2 || f8lo);
-    const int tile_n = split ? 32 : 16;
+    HrPackedLayer pk;
     for (int l = 0; l < c.mlp_layers; ++l) {
-        const HrMlpLayer g = mlp_layer(m, l, tile_n);
-        const bool first = g.first, skip = g.skip, last = g.last;
-        const int N_user = g.N_user, Kt = g.Kt, N = g.N, Kp = g.Kp, nt = g.nt, P_user = g.P_user, P_live = g.P_live;
-        const int* live_cols = g.live_cols;
-        std::vector<float> w((size_t)N_user * Kt), b(N_user);
+        const HrMlpLayer g = mlp_layer(c, m->p_live, m->col_map, l, hr_pack_tile_n(precision));
+        std::vector<float> w((size_t)g.N_user * g.Kt), b(g.N_user);
         snprintf(name, sizeof(name), "mlp.%d.weight", l);
         HR_HIP(hipMemcpy(w.data(), m->raw[name].p, w.size() * sizeof(float), hipMemcpyDeviceToHost));
         snprintf(name, sizeof(name), "mlp.%d.bias", l);
         HR_HIP(hipMemcpy(b.data(), m->raw[name].p, b.size() * sizeof(float), hipMemcpyDeviceToHost));
-        // torch weight element for (output feature n, kernel K index kk); 0 outside the matrix
-        auto wk = [&](int n, int kk) -> float {
-            int col = -1;                                                 // torch in-feature index
-            if (first) {
-                if (kk < c.mlp_in) col = kk;
-            } else if (skip) {
-                if (kk < g.k0p) { if (kk < c.mlp_in) col = kk; }
-                else col = c.mlp_in + (kk - g.k0p);                      // cat([input, x]), mlp.py:166-168
-            } else {
-                col = kk;
-            }
-            if (!(n < N && col >= 0 && col < Kt)) return 0.0f;
-            // last layer: kernel row n = k*P_live + c' is the user's row k*P + live_cols[c']
-            const int row = last ? (n / P_live) * P_user + live_cols[n % P_live] : n;
-            return w[(size_t)row * Kt + col];
-        };
+        hr_pack_mlp_layer(g, precision, w, b, pk);
         t.wpack[l].reset();
         t.wsplit[l].reset();
         t.bias[l].reset();
-        // fp16 modes: the weights of these MLPs are ~1/sqrt(fan_in), so the low half w - half(w) (~2^-12 w) would be a
-        // subnormal half with an ABSOLUTE rounding error of 2^-25.  Packing w * 2^s (exact), with s putting the largest
-        // weight of the layer into [2^13, 2^14), keeps every low half of a weight above max|w| * 2^-16 normal; the
-        // epilogue multiplies the accumulator by 2^-s (exact again).  bf16 halves have the fp32 exponent range: s = 0.
-        float wmul = 1.0f;
-        t.winv[l] = 1.0f;
-        if (half) {
-            float mx = 0.0f;
-            for (float v : w) mx = fmaxf(mx, fabsf(v));
-            if (mx > 0.0f && std::isfinite(mx)) {
-                int e = 0;
-                (void)frexpf(mx, &e);                       // mx = f * 2^e, f in [0.5, 1)
-                int sft = 14 - e;
-                sft = sft < -14 ? -14 : (sft > 40 ? 40 : sft);
-                wmul = ldexpf(1.0f, sft);
-                t.winv[l] = ldexpf(1.0f, -sft);
-            }
-        }
-        if (!split) {
-            std::vector<float> pk((size_t)(Kp / 16) * nt * 64 * 4, 0.0f);
-            for (int kt = 0; kt < Kp / 16; ++kt)
-                for (int t = 0; t < nt; ++t)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int s = 0; s < 4; ++s)
-                            pk[(((size_t)kt * nt + t) * 64 + lane) * 4 + s] = wk(16 * t + (lane & 15), 16 * kt + 4 * (lane >> 4) + s);
-            HR_HIP(t.wpack[l].alloc(pk.size() * sizeof(float)));
-            HR_HIP(hipMemcpy(t.wpack[l], pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-            t.bytes += (int64_t)pk.size() * sizeof(float);
-        } else {
-            // hi = bf16(w), lo = bf16(w - hi), both round-to-nearest-even (layout: hr_kernels.h)
-            std::vector<uint16_t> pk((size_t)(Kp / 16) * nt * 2 * 64 * 8, 0);
-            for (int kt = 0; kt < Kp / 16; ++kt)
-                for (int t = 0; t < nt; ++t)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const float v = wk(32 * t + (lane & 31), 16 * kt + 8 * (lane >> 5) + j) * wmul;
-                            const uint16_t hi = half ? f16_rne(v) : bf16_rne(v);
-                            const uint16_t lo = half ? f16_rne(v - f16_to_float(hi)) : bf16_rne(v - bf16_to_float(hi));
-                            const size_t base = ((((size_t)kt * nt + t) * 2) * 64 + lane) * 8 + j;
-                            pk[base] = hi;
-                            pk[base + 64 * 8] = lo;
-                        }
-            if (f8lo) {
-                // f16 + fp8 split (mlp_split_core.inc, hr_accumulate_f8): over the HIDDEN k-steps (those past the input segment of the first / skip
-                // layer, which keeps three f16 products) the 16 bytes of a lane's "lo" half become the fp8 images of the SAME 8 weights its f16 half
-                // holds: e4m3((w' - half(w')) * 2^6) x 8, then e4m3(w' * 2^-6) x 8
-                const int kseg = first ? Kp / 16 : (skip ? g.k0p / 16 : 0);
-                uint8_t* bytes = reinterpret_cast<uint8_t*>(pk.data());
-                for (int kt = kseg; kt < Kp / 16; ++kt)
-                    for (int t = 0; t < nt; ++t)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 8; ++j) {
-                                const float v = wk(32 * t + (lane & 31), 16 * kt + 8 * (lane >> 5) + j) * wmul;
-                                const size_t at = (((((size_t)kt * nt + t) * 2 + 1) * 64 + lane) * 8) * 2;
-                                bytes[at + j] = e4m3_rne(ldexpf(v - f16_to_float(f16_rne(v)), 6));
-                                bytes[at + 8 + j] = e4m3_rne(ldexpf(v, -6));
-                            }
-            }
-            HR_HIP(t.wsplit[l].alloc(pk.size() * sizeof(uint16_t)));
-            HR_HIP(hipMemcpy(t.wsplit[l], pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            t.bytes += (int64_t)pk.size() * sizeof(uint16_t);
-        }
-        const int nb = nt * tile_n;
-        std::vector<float> bp(nb, 0.0f);
-        // split kernels: the accumulators START from the bias (mlp_split_core.inc, hr_acc_init_bias), in the accumulator's unit: b * 2^s (exact;
-        // 1 for bf16 halves and for the exact-fp32 kernel, which adds its bias in the epilogue)
-        for (int i = 0; i < N; ++i) bp[i] = b[last ? (i / P_live) * P_user + live_cols[i % P_live] : i] * wmul;
-        HR_HIP(t.bias[l].alloc(nb * sizeof(float)));
-        HR_HIP(hipMemcpy(t.bias[l], bp.data(), nb * sizeof(float), hipMemcpyHostToDevice));
-        t.n_tiles[l] = nt;
-        t.bytes += (int64_t)nb * sizeof(float);
+        void* tiles = nullptr;
+        if (precision == HR_MLP_FP32) { HR_HIP(t.wpack[l].alloc(pk.tiles.size())); tiles = t.wpack[l]; }
+        else { HR_HIP(t.wsplit[l].alloc(pk.tiles.size())); tiles = t.wsplit[l]; }
+        HR_HIP(hipMemcpy(tiles, pk.tiles.data(), pk.tiles.size(), hipMemcpyHostToDevice));
+        HR_HIP(t.bias[l].alloc(pk.bias.size() * sizeof(float)));
+        HR_HIP(hipMemcpy(t.bias[l], pk.bias.data(), pk.bias.size() * sizeof(float), hipMemcpyHostToDevice));
+        t.winv[l] = pk.winv;
+        t.n_tiles[l] = g.nt;
+        t.bytes += (int64_t)(pk.tiles.size() + pk.bias.size() * sizeof(float));
     }
     return HR_OK;
 }
@@ -238,7 +61,7 @@ static const float HR_VERIFY_RGB_LIMIT = 6e-5f;   // on <= 65 536 calibration ra
 int pack_mlp(hr_model* m)
 {
     f8_exponents(m);
-    const HrMlpLayer g = mlp_layer(m, 0, 16);
+    const HrMlpLayer g = mlp_layer(m->cfg, m->p_live, m->col_map, 0, 16);
     m->k0p = g.k0p;
     m->n_out = g.n_out;
     int rc = pack_mlp_as(m, m->active_precision, m->tiles[0]);

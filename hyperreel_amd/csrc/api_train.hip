@@ -211,28 +211,21 @@ int hr_mlp_train_forward(hr_model* m, const float* const* weights_dev, const flo
     if (L < 2 || c.mlp_hidden != 256) return fail(HR_E_INVALID, "hr_mlp_train_forward needs hidden width 256 and at least two layers");
     if (!weights_dev || !biases_dev || !acts_dev || !act_ld || !act_off || (n_rays > 0 && !head_dev)) return fail(HR_E_INVALID, "null argument");
     hipStream_t st = (hipStream_t)stream;
-    // ---- the current parameter values -> bf16 hi / lo tiles, on the device (what pack_mlp does on the host at finalize)
+    // ---- the current parameter values -> bf16 hi / lo tiles, on the device (what pack_mlp does on the host at finalize: hr_mlp_pack.h)
     const int P_user = c.preds_per_z, P_live = m->p_live;
     const int k0p = m->k0p, n_out = m->n_out;
     HrMlpTiles& t = m->train_tiles;
     for (int l = 0; l < L; ++l) {
         if (!weights_dev[l] || !biases_dev[l]) return fail(HR_E_INVALID, "hr_mlp_train_forward: layer %d has no weights", l);
-        const HrMlpLayer g = mlp_layer(m, l, 32);
-        HrPackDesc d = {};
-        d.w = weights_dev[l]; d.b = biases_dev[l];
-        d.last = g.last; d.first = g.first; d.skip = g.skip;
-        d.N_user = g.N_user; d.Kt = g.Kt; d.N = g.N; d.nt = g.nt; d.Kp = g.Kp;
-        d.mlp_in = c.mlp_in; d.k0p = g.k0p; d.P_user = g.P_user; d.P_live = g.P_live;
-        memcpy(d.live_cols, g.live_cols, sizeof(d.live_cols));
-        if (!t.wsplit[l] || t.n_tiles[l] != d.nt) {
+        const HrMlpLayer g = mlp_layer(c, m->p_live, m->col_map, l, 32);
+        if (!t.wsplit[l] || t.n_tiles[l] != g.nt) {
             t.wsplit[l].reset();
             t.bias[l].reset();
-            HR_HIP(t.wsplit[l].alloc(sizeof(uint16_t) * (size_t)(d.Kp / 16) * d.nt * 2 * 64 * 8));
-            HR_HIP(t.bias[l].alloc(sizeof(float) * (size_t)d.nt * 32));
-            t.n_tiles[l] = d.nt;
+            HR_HIP(t.wsplit[l].alloc(sizeof(uint16_t) * (size_t)(g.Kp / 16) * g.nt * 2 * 64 * 8));
+            HR_HIP(t.bias[l].alloc(sizeof(float) * (size_t)g.nt * 32));
+            t.n_tiles[l] = g.nt;
         }
-        d.wsplit = t.wsplit[l]; d.bias = t.bias[l];
-        hr_launch_pack_split_bf16(d, st);
+        hr_launch_pack_split_bf16(g, weights_dev[l], biases_dev[l], t.wsplit[l], t.bias[l], st);
     }
     HrMlpTaps taps = {};
     for (int l = 0; l + 1 < L; ++l) { taps.act[l] = acts_dev[l]; taps.ld[l] = act_ld[l]; taps.off[l] = act_off[l]; }

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/hyperreel_hip.h"
+#include "hr_mlp_pack.h"
 
 // More than 64 KiB of dynamic LDS has to be opted into per kernel AND per device (hipFuncAttributeMaxDynamicSharedMemorySize).
 // `cache`: one static per kernel instantiation; a process that renders on several GPUs (viewer + trainer, DataParallel-style
@@ -47,12 +48,7 @@ inline int hr_current_device_cus()
 }
 
 // ---------------------------------------------------------------- MLP (mlp_kernel.hip)
-// Weights of layer L are stored as MFMA B-operand tiles for v_mfma_f32_16x16x4_f32:
-//   wpack[L][((kt * n_tiles[L]) + nt) * 64 + lane] = float4{ W[n][k0], W[n][k0+1], W[n][k0+2], W[n][k0+3] }
-//   with n = 16*nt + (lane & 15), k0 = 16*kt + 4*(lane >> 4)
-// (W[n][k] = torch weight (out=n, in=k) in the kernel's K order; zero outside the real matrix).
-// K order: plain layers: hidden index.  Layer 0: input feature index, padded to k0p.
-// Skip layers: [input features padded to k0p | hidden].
+// Weights: pre-tiled MFMA A operands, see hr_mlp_pack.h for the layout, the K order and the roundings.
 // Layout of the raw MLP head in the workspace ("HQ"): rays in blocks of 64, features in quads,
 //   float index(ray, n) = (((ray / 64) * nq + n / 4) * 64 + ray % 64) * 4 + n % 4,  nq = ceil(n_out / 4)
 // The MLP's 32x32 accumulator tile holds 4 consecutive features of one ray per lane, so a
@@ -159,23 +155,10 @@ struct HrMlpTaps {
 };
 void hr_launch_mlp_train_bf16x3(const hr_config& cfg, const HrMlpArgs& args, const HrMlpTaps& taps, hipStream_t stream);
 // one layer's reference-layout weights (N_user, Kt) / bias (N_user) in device memory -> the split kernels' bf16 hi / lo tiles and padded
-// bias, on the device (what pack_mlp does on the host at finalize; the training step re-packs every step)
-struct HrPackDesc {
-    const float* w;
-    const float* b;
-    void* wsplit;
-    float* bias;
-    int N_user, Kt;         // the torch matrix
-    int N, nt, Kp;          // rows the kernel computes, their 32-row tiles, padded K
-    int first, skip, last;
-    int mlp_in, k0p;
-    int P_user, P_live;
-    int live_cols[64];      // last layer: live column c' of a sample -> the user's column
-};
-void hr_launch_pack_split_bf16(const HrPackDesc& d, hipStream_t stream);
+// bias, on the device (what hr_pack_mlp_layer does on the host at finalize; the training step re-packs every step).  g: 32-row tiles
+void hr_launch_pack_split_bf16(const HrMlpLayer& g, const float* w, const float* b, uint16_t* wsplit, float* bias, hipStream_t stream);
 void hr_launch_mlp(const hr_config& cfg, const HrMlpArgs& args, hipStream_t stream);
-// split-precision form: wsplit[L][(((kt * n_tiles[L] + nt) * 2 + part) * 64 + lane)] = 8 bf16 of
-//   W[n = 32*nt + (lane & 31)][k = 16*kt + 8*(lane >> 5) + 0..7], part 0 = hi (bf16(w)), 1 = lo (bf16(w - hi))
+// split-precision forms (hi / lo tiles: hr_mlp_pack.h)
 void hr_launch_mlp_bf16x3(const hr_config& cfg, const HrMlpArgs& args, hipStream_t stream);
 void hr_launch_mlp_f16x3(const hr_config& cfg, const HrMlpArgs& args, hipStream_t stream);   // same layouts, fp16 halves
 void hr_launch_mlp_f16x2(const hr_config& cfg, const HrMlpArgs& args, hipStream_t stream);   // fp16, weights unsplit
@@ -268,11 +251,6 @@ void hr_launch_rayset_sample(const HrRaySetArgs& a, uint64_t seed, uint64_t step
 
 // layout kernels (pack_kernels.hip)
 // dst[y][x][c_off + c] = src[c][y][x] for c < C  (dst texel stride = tex floats)
-// Per-sample head columns the path actually reads (hr_model_finalize drops the others from the
-// last Linear): col[c] = position of user column c among the live ones, or -1.
-struct HrColMap {
-    int col[64];
-};
 // diagnostics export of the raw head in the user's (n, Z*P) layout; pruned columns read as 0
 void hr_launch_head_export(const float* head, float* out, int64_t n_rays, int Z, int P, int P_live, int nq, int rows_per_ray,
                            const HrColMap& map,

@@ -62,7 +62,7 @@ struct HR_HIDDEN DevBuf {
     size_t bytes = 0;
 };
 
-// One packing of the MLP: MFMA B-operand tiles per Linear (layout documented in hr_kernels.h)
+// One packing of the MLP: MFMA A-operand tiles per Linear (layout: hr_mlp_pack.h)
 struct HR_HIDDEN HrMlpTiles {
     DevMem<float4> wpack[HR_MAX_LAYERS];     // HR_MLP_FP32: fp32 tiles
     DevMem<uint16_t> wsplit[HR_MAX_LAYERS];  // the split arithmetics: hi / lo tiles
@@ -153,30 +153,11 @@ struct HR_HIDDEN hr_model {
     int n_cus = 0;
 };
 
-static inline int layer_in(const hr_config& c, int l)
-{
-    if (l == 0) return c.mlp_in;
-    return c.mlp_hidden + (((c.mlp_skip_mask >> l) & 1) ? c.mlp_in : 0);
-}
-
-static inline int layer_out(const hr_config& c, int l) { return (l == c.mlp_layers - 1) ? samples_per_row(c) * c.preds_per_z : c.mlp_hidden; }
-
 // a ray with a live sample beyond it (60 degrees off a plane's normal; a sphere nearly tangent) is not what the margins of the verified fast
 // path are measured on -- its errors are the geometry's, the MLP's two-plane / Pluecker inputs included -- and is always listed
 constexpr float HR_VERIFY_AMP_CUT = 2.0f;
 
 // ---- api_mlp.hip
-// Linear l as the kernels compute it, in output tiles of tile_n features; with the model's k0p / n_out and live head columns
-struct HR_HIDDEN HrMlpLayer {
-    int N_user, Kt;          // the torch matrix
-    int N, Kp, nt;           // rows the kernels compute, padded K, output tiles
-    bool first, skip, last;
-    int k0p;                 // mlp_in padded to a multiple of 16
-    int n_out;               // head columns of one MLP row
-    int P_user, P_live;
-    int live_cols[64];       // live column c' of a sample -> the user's column
-};
-HR_HIDDEN HrMlpLayer mlp_layer(const hr_model* m, int l, int tile_n);
 HR_HIDDEN int resolve_precision(hr_model* m, const float* rays_dev, int64_t n, hipStream_t st);
 HR_HIDDEN int pack_mlp(hr_model* m);
 HR_HIDDEN int calibrate_band(hr_model* m, hipStream_t st);

@@ -333,46 +333,31 @@ void hr_launch_fixed_to_float(const long long* src, float* dst, int64_t n, const
 
 
 // ---------------------------------------------------------------- device-side weight packing for the training step's fused MLP forward
-// Same layout and roundings as pack_mlp (api_mlp.hip) for the bf16 split: wsplit[(((kt * nt + t) * 2 + part) * 64 + lane) * 8 + j] =
-// W[n = 32 t + (lane & 31)][k = 16 kt + 8 (lane >> 5) + j], part 0 = bf16(w), part 1 = bf16(w - hi); K order: layer 0 the input features
-// padded to k0p, skip layers [input padded to k0p | hidden]; last layer: kernel row n = k * P_live + c' is the user's row
-// k * P_user + live_cols[c'] (BaseMLP's weights, nlf/nets/mlp.py:127-172, as torch stores them: (out, in)).
-__global__ __launch_bounds__(256) void hr_pack_split_bf16_kernel(const HrPackDesc d)
+// The bf16 split of hr_mlp_pack.h (its layout, K order, row map and rounding; what hr_pack_mlp_layer does on the host) from BaseMLP's
+// weights as torch stores them (nlf/nets/mlp.py:127-172: (out, in)).  A lane per 16-bit word of a part, in the tiles' own order.
+__global__ __launch_bounds__(256) void hr_pack_split_bf16_kernel(const HrMlpLayer g, const float* __restrict__ w, const float* __restrict__ b,
+                                                                 uint16_t* __restrict__ wsplit, float* __restrict__ bias)
 {
-    const int64_t total = (int64_t)(d.Kp / 16) * d.nt * 64 * 8;
-    uint16_t* out = reinterpret_cast<uint16_t*>(d.wsplit);
+    const int64_t total = (int64_t)(g.Kp / 16) * g.nt * 64 * 8;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int j = (int)(i & 7), lane = (int)((i >> 3) & 63);
         const int64_t tt = i >> 9;
-        const int t = (int)(tt % d.nt), kt = (int)(tt / d.nt);
-        const int n = 32 * t + (lane & 31), kk = 16 * kt + 8 * (lane >> 5) + j;
-        int col = -1;
-        if (d.first) { if (kk < d.mlp_in) col = kk; }
-        else if (d.skip) { if (kk < d.k0p) { if (kk < d.mlp_in) col = kk; } else col = d.mlp_in + (kk - d.k0p); }
-        else col = kk;
-        float v = 0.0f;
-        if (n < d.N && col >= 0 && col < d.Kt) {
-            const int row = d.last ? (n / d.P_live) * d.P_user + d.live_cols[n % d.P_live] : n;
-            v = d.w[(int64_t)row * d.Kt + col];
-        }
-        const __bf16 hi = (__bf16)v;
-        const __bf16 lo = (__bf16)(v - (float)hi);
-        const int64_t base = (((tt * 2) * 64 + lane) * 8) + j;
-        out[base] = __builtin_bit_cast(uint16_t, hi);
-        out[base + 64 * 8] = __builtin_bit_cast(uint16_t, lo);
+        const int t = (int)(tt % g.nt), kt = (int)(tt / g.nt);
+        const HrSplitPair p = hr_split_bf16(hr_pack_element(g, w, hr_split_tile_n(t, lane), hr_split_tile_k(kt, lane, j)));
+        wsplit[hr_split_tile_index(g, kt, t, 0, lane, j)] = p.hi;
+        wsplit[hr_split_tile_index(g, kt, t, 1, lane, j)] = p.lo;
     }
     if (blockIdx.x == 0)
-        for (int i = threadIdx.x; i < d.nt * 32; i += 256)
-            d.bias[i] = i < d.N ? d.b[d.last ? (i / d.P_live) * d.P_user + d.live_cols[i % d.P_live] : i] : 0.0f;
+        for (int i = threadIdx.x; i < g.nt * 32; i += 256) bias[i] = hr_pack_bias(g, b, i);
 }
 
-void hr_launch_pack_split_bf16(const HrPackDesc& d, hipStream_t stream)
+void hr_launch_pack_split_bf16(const HrMlpLayer& g, const float* w, const float* b, uint16_t* wsplit, float* bias, hipStream_t stream)
 {
-    const int64_t total = (int64_t)(d.Kp / 16) * d.nt * 64 * 8;
+    const int64_t total = (int64_t)(g.Kp / 16) * g.nt * 64 * 8;
     if (total <= 0) return;
     int64_t blocks = (total + 255) / 256;
     if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(hr_pack_split_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d);
+    hipLaunchKernelGGL(hr_pack_split_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g, w, b, wsplit, bias);
 }
 
 
