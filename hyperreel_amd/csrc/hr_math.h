@@ -11,13 +11,17 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/hyperreel_hip.h"
 
 #if defined(__HIPCC__)
 #define HR_FN __device__ __forceinline__
+#define HR_HD __host__ __device__ __forceinline__      // the few functions host code of a hipcc translation unit calls too (hr_plan.h)
 #define HR_UNROLL _Pragma("unroll")      // small fixed-trip loops over float[3]: keep the arrays in registers
 #else
 #define HR_FN static inline
+#define HR_HD static inline
 #define HR_UNROLL
 #endif
 
@@ -110,7 +114,8 @@ HR_FN float hr_apply_act_post(const hr_act& a, float x)
 
 // ---------------------------------------------------------------- ray features (MLP input)
 // utils/intersect_utils.py:127-150  (|d| < 1e-5 -> 1e12)
-HR_FN float hr_axis_plane_t(float val, float o, float d)
+template <class T>
+HR_FN T hr_axis_plane_t(T val, float o, float d)
 {
     float dd = (fabsf(d) < 1e-5f) ? 1e12f : d;
     return HR_DIV(val - o, dd);
@@ -296,43 +301,62 @@ struct HrRisk {
 #define HR_RISK_ABS(risk, x, y) do { if (risk) (risk)->hit = (risk)->hit || (fabsf((x) - (y)) <= (risk)->band_zc * (risk)->dlen); } while (0)
 
 // ---------------------------------------------------------------- ray / primitive intersection
+// The geometry below is written ONCE over a number type T: float for the render kernels, hr_dual (hr_train.h: a value and 8 forward-mode
+// partials) for the training backward of the intersections that read several head channels.  The statements and their order are the
+// reference's; with T = float they are the render path's arithmetic bit for bit.  Besides + - * with T and float operands a number type
+// supplies: T(float), a literal; hr_val, the value -- every comparison and HrRisk read values only; hr_div and hr_sqrt; hr_max against a
+// float; hr_norm3; hr_inverse_contract_distance; hr_zval and hr_isect_one_m for the pointer its samples come as.  The float forms (the
+// last three with the functions they belong to):
+HR_FN float hr_val(float x) { return x; }
+HR_FN float hr_div(float a, float b) { return HR_DIV(a, b); }
+HR_FN float hr_sqrt(float x) { return HR_SQRT(x); }
+HR_FN float hr_max(float a, float b) { return fmaxf(a, b); }
+HR_FN float hr_norm3(const float* v) { return HR_SQRT(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }     // torch.norm of a 3-vector
+
 // utils/intersect_utils.py:45-84 (sphere) and :86-125 (cylinder: the xz components)
-HR_FN float hr_quadratic_t(float oo, float dd, float od, float radius, HrRisk* risk = nullptr)
+template <class T>
+HR_FN T hr_quadratic_t(T oo, T dd, T od, T radius, HrRisk* risk = nullptr)
 {
-    float a = dd;
-    float b = 2.0f * od;
-    float cc = oo - radius * radius;
-    float disc = b * b - 4.0f * a * cc;
+    T a = dd;
+    T b = 2.0f * od;
+    T cc = oo - radius * radius;
+    T disc = b * b - 4.0f * a * cc;
     // at risk: the discriminant's sign -- only the radius depends on the head, d disc = 8 a r d r -- and the radius' sign
     float band_r = 0.0f;
     if (risk) {
         band_r = risk->band_zc * risk->dlen;
-        risk->hit = risk->hit || (fabsf(disc) <= 8.0f * a * fabsf(radius) * band_r) || (fabsf(radius) <= band_r);
+        risk->hit = risk->hit || (fabsf(hr_val(disc)) <= 8.0f * hr_val(a) * fabsf(hr_val(radius)) * band_r) || (fabsf(hr_val(radius)) <= band_r);
     }
-    disc = (disc < 0.0f) ? 0.0f : disc;
-    float sq = HR_SQRT(disc + 1e-8f);
-    float t1 = HR_DIV(-b + sq, 2.0f * a);
-    float t2 = HR_DIV(-b - sq, 2.0f * a);
+    // a miss is the constant 0.  The float form selects it below, after both roots (the render kernels' instructions); a wider number
+    // type leaves here instead of carrying its partials through roots it then drops: the same value, a third fewer registers in phase C
+    if constexpr (!std::is_same<T, float>::value)
+        if (hr_val(disc) <= 0.0f) return T(0.0f);
+    disc = (hr_val(disc) < 0.0f) ? T(0.0f) : disc;
+    T sq = hr_sqrt(disc + 1e-8f);
+    T t1 = hr_div(-b + sq, 2.0f * a);
+    T t2 = hr_div(-b - sq, 2.0f * a);
     if (risk) {
         // d t / d r = +- 2 r / sq for both roots (a cancels); ... and the sign of the near root (which root is returned)
-        risk->amp = (disc <= 0.0f) ? 0.0f : 2.0f * fabsf(radius) * HR_RCP_BAND(sq);
-        risk->hit = risk->hit || (disc > 0.0f && fabsf(t2) <= band_r * risk->amp);
+        risk->amp = (hr_val(disc) <= 0.0f) ? 0.0f : 2.0f * fabsf(hr_val(radius)) * HR_RCP_BAND(hr_val(sq));
+        risk->hit = risk->hit || (hr_val(disc) > 0.0f && fabsf(hr_val(t2)) <= band_r * risk->amp);
     }
-    t1 = (disc <= 0.0f) ? 0.0f : t1;
-    t2 = (disc <= 0.0f) ? 0.0f : t2;
-    return ((t2 < 0.0f) || (radius < 0.0f)) ? t1 : t2;
+    t1 = (hr_val(disc) <= 0.0f) ? T(0.0f) : t1;             // a miss: the constant 0
+    t2 = (hr_val(disc) <= 0.0f) ? T(0.0f) : t2;
+    return ((hr_val(t2) < 0.0f) || (hr_val(radius) < 0.0f)) ? t1 : t2;
 }
 
 HR_FN float hr_sign(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
 
-// F.normalize(p=2, eps=1e-12) of a 3-vector, in place
-HR_FN void hr_normalize3(float* v)
+// F.normalize(p=2, eps=1e-12) of a 3-vector, in place (below the eps: divided by the eps, a constant)
+template <class T>
+HR_FN void hr_normalize3(T* v)
 {
-    float n = fmaxf(HR_SQRT(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), 1e-12f);
-    v[0] = HR_DIV(v[0], n); v[1] = HR_DIV(v[1], n); v[2] = HR_DIV(v[2], n);
+    const T n = hr_max(hr_norm3(v), 1e-12f);
+    v[0] = hr_div(v[0], n); v[1] = hr_div(v[1], n); v[2] = hr_div(v[2], n);
 }
 
-HR_FN void hr_cross3(const float* a, const float* b, float* r)
+template <class T>
+HR_FN void hr_cross3(const T* a, const T* b, T* r)
 {
     r[0] = a[1] * b[2] - a[2] * b[1];
     r[1] = a[2] * b[0] - a[0] * b[2];
@@ -341,20 +365,22 @@ HR_FN void hr_cross3(const float* a, const float* b, float* r)
 
 // pluecker_pos (nlf/param.py:297-307): the point of the line (o, d) closest to the origin,
 // d_hat x (o x d_hat) with d_hat = normalize(d)
-HR_FN void hr_pluecker_pos(const float* o, const float* d, float* pos)
+template <class T>
+HR_FN void hr_pluecker_pos(const T* o, const T* d, T* pos)
 {
-    float dn[3] = {d[0], d[1], d[2]};
+    T dn[3] = {d[0], d[1], d[2]};
     hr_normalize3(dn);
-    float m[3];
+    T m[3];
     hr_cross3(o, dn, m);
     hr_cross3(dn, m, pos);
 }
 
 // sign(d . diff) * |diff|  (primitive.py:171-173, :532-534)
-HR_FN float hr_signed_base_distance(const float* d, const float* diff)
+template <class T>
+HR_FN T hr_signed_base_distance(const T* d, const T* diff)
 {
-    float dt = d[0] * diff[0] + d[1] * diff[1] + d[2] * diff[2];
-    return hr_sign(dt) * HR_SQRT(diff[0] * diff[0] + diff[1] * diff[1] + diff[2] * diff[2]);
+    const T dt = d[0] * diff[0] + d[1] * diff[1] + d[2] * diff[2];
+    return hr_sign(hr_val(dt)) * hr_norm3(diff);
 }
 
 // z_vals channel `ch` of a sample: head activation -> intersect activation * (1 - sigma)  (base.py:161-162)
@@ -374,60 +400,68 @@ HR_FN float hr_inverse_contract_slope(const hr_config& c, float zc, float r)
 }
 
 // process_z_vals (base.py:128-140): anchor + scale, then back from the contracted sample space
-HR_FN float hr_process_z(const hr_config& c, float z, float scale, float anchor, HrRisk* risk = nullptr)
+template <class T>
+HR_FN T hr_process_z(const hr_config& c, T z, float scale, float anchor, HrRisk* risk = nullptr)
 {
     z = z * scale + anchor;
-    const float zc = z;
+    const float zc = hr_val(z);
     if (c.contract_samples) z = hr_inverse_contract_distance(c, z);
     if (risk) {
         risk->zc = zc;
-        risk->dlen = c.contract_samples ? hr_inverse_contract_slope(c, zc, z) : 1.0f;
+        risk->dlen = c.contract_samples ? hr_inverse_contract_slope(c, zc, hr_val(z)) : 1.0f;
     }
     return z;
 }
 
+// The intersections below read the sample's z_vals through hr_zval(c, hk, ch, one_m), whose overload for the type of `hk` decides T: from
+// `const float*`, the P raw head values of the sample, a channel is activated when it is read (above); the training backward hands in
+// `const hr_dual*`, the activated channels seeded with their own partial (hr_train.h).
+
 // IntersectSphereNew / IntersectCylinderNew .intersect (primitive.py:498-545, :313-363): the ray is
 // moved into the primitive's frame, intersected, and samples whose primitive the ray misses are
 // recycled as offsets from the ray's closest point to the axis/centre.
-HR_FN float hr_isect_new(const hr_config& c, const float* hk, int k, float one_m, const float* ro, const float* rd, HrRisk* risk = nullptr)
+template <class H>
+HR_FN auto hr_isect_new(const hr_config& c, H hk, int k, float one_m, const float* ro, const float* rd, HrRisk* risk = nullptr)
+    -> decltype(hr_zval(c, hk, 0, one_m))
 {
-    float org[3] = {0.0f, 0.0f, 0.0f};
+    typedef decltype(hr_zval(c, hk, 0, one_m)) T;
+    T org[3] = {0.0f, 0.0f, 0.0f};
     if (c.origin_scale != 0.0f)
         HR_UNROLL
         for (int i = 0; i < 3; ++i) org[i] = hr_zval(c, hk, i, one_m) * c.origin_scale;
-    float rs[3] = {c.resize_initial[0], c.resize_initial[1], c.resize_initial[2]};
+    T rs[3] = {c.resize_initial[0], c.resize_initial[1], c.resize_initial[2]};
     if (c.resize_scale != 0.0f)
         HR_UNROLL
         for (int i = 0; i < 3; ++i) rs[i] = hr_zval(c, hk, 3 + i, one_m) * c.resize_scale + c.resize_initial[i];
-    const float raw = hr_process_z(c, hr_zval(c, hk, 6, one_m), c.z_scale, c.samples[k]);
-    const float radius = hr_process_z(c, hr_zval(c, hk, 7, one_m), c.z_scale, c.samples[k], risk);
-    float o[3], d[3];
+    const T raw = hr_process_z(c, hr_zval(c, hk, 6, one_m), c.z_scale, c.samples[k]);
+    const T radius = hr_process_z(c, hr_zval(c, hk, 7, one_m), c.z_scale, c.samples[k], risk);
+    T o[3], d[3];
     HR_UNROLL
     for (int i = 0; i < 3; ++i) { o[i] = (ro[i] - org[i]) * rs[i]; d[i] = rd[i] * rs[i]; }
-    const float dnorm = HR_SQRT(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);     // torch.norm(rays_d)
-    float dn[3] = {d[0], d[1], d[2]};
+    const T dnorm = hr_norm3(d);                                               // torch.norm(rays_d)
+    T dn[3] = {d[0], d[1], d[2]};
     hr_normalize3(dn);
-    float t, min_radius, base_distance;
+    T t, min_radius, base_distance;
     if (c.isect_type == HR_ISECT_SPHERE_NEW) {
         t = hr_quadratic_t(o[0] * o[0] + o[1] * o[1] + o[2] * o[2], dn[0] * dn[0] + dn[1] * dn[1] + dn[2] * dn[2],
                            o[0] * dn[0] + o[1] * dn[1] + o[2] * dn[2], radius, risk);
-        float pos[3];
+        T pos[3];
         hr_pluecker_pos(o, dn, pos);                                           // also min_sphere_radius' vector
-        min_radius = HR_SQRT(pos[0] * pos[0] + pos[1] * pos[1] + pos[2] * pos[2]);
-        const float diff[3] = {pos[0] - o[0], pos[1] - o[1], pos[2] - o[2]};
+        min_radius = hr_norm3(pos);
+        const T diff[3] = {pos[0] - o[0], pos[1] - o[1], pos[2] - o[2]};
         base_distance = hr_signed_base_distance(dn, diff);
     } else {
         t = hr_quadratic_t(o[0] * o[0] + o[2] * o[2], dn[0] * dn[0] + dn[2] * dn[2], o[0] * dn[0] + o[2] * dn[2], radius, risk);
-        const float oc[3] = {o[0], 0.0f, o[2]}, dc[3] = {dn[0], 0.0f, dn[2]};
-        float pos[3];
+        const T oc[3] = {o[0], 0.0f, o[2]}, dc[3] = {dn[0], 0.0f, dn[2]};
+        T pos[3];
         hr_pluecker_pos(oc, dc, pos);
-        min_radius = HR_SQRT(pos[0] * pos[0] + pos[1] * pos[1] + pos[2] * pos[2]);
-        const float diff[3] = {pos[0] - oc[0], pos[1] - oc[1], pos[2] - oc[2]};
-        base_distance = HR_DIV(hr_signed_base_distance(dc, diff), HR_SQRT(dc[0] * dc[0] + dc[1] * dc[1] + dc[2] * dc[2]));
+        min_radius = hr_norm3(pos);
+        const T diff[3] = {pos[0] - oc[0], pos[1] - oc[1], pos[2] - oc[2]};
+        base_distance = hr_div(hr_signed_base_distance(dc, diff), hr_norm3(dc));
     }
-    HR_RISK_ABS(risk, fabsf(radius), min_radius + 4.0f * c.z_scale);
-    if (fabsf(radius) < min_radius + 4.0f * c.z_scale) t = raw + base_distance;
-    return HR_DIV(t, dnorm + 1e-5f);
+    HR_RISK_ABS(risk, fabsf(hr_val(radius)), hr_val(min_radius) + 4.0f * c.z_scale);
+    if (fabsf(hr_val(radius)) < hr_val(min_radius) + 4.0f * c.z_scale) t = raw + base_distance;
+    return hr_div(t, dnorm + 1e-5f);
 }
 
 // Pre-sort distance of sample k (Intersect.forward, intersect/base.py:142-203):
@@ -438,10 +472,11 @@ HR_FN float hr_isect_new(const hr_config& c, const float* hk, int k, float one_m
 // (sx, sy, sz): q = {o.o, d.d, o.d} of the scaled origin and direction.  With the shipped origin_scale_factor of 0 the scale is a constant of
 // the model and q a constant of the RAY: the sample kernel computes it once per ray (sample_core.inc, hr_ray_constants) and hands it to
 // hr_sample_distance, which otherwise calls this per sample -- the same operations in the same order either way.
-HR_FN void hr_quadratic_ray_terms(const hr_config& c, const float* ro, const float* rd, float sx, float sy, float sz, float* q)
+template <class T>
+HR_FN void hr_quadratic_ray_terms(const hr_config& c, const float* ro, const float* rd, T sx, T sy, T sz, T* q)
 {
-    float ox = ro[0] * sx, oy = ro[1] * sy, oz = ro[2] * sz;     // primitive.py:425-431
-    float dx = rd[0] * sx, dy = rd[1] * sy, dz = rd[2] * sz;
+    T ox = ro[0] * sx, oy = ro[1] * sy, oz = ro[2] * sz;     // primitive.py:425-431
+    T dx = rd[0] * sx, dy = rd[1] * sy, dz = rd[2] * sz;
     if (c.isect_type == HR_ISECT_SPHERE) {
         q[0] = ox * ox + oy * oy + oz * oz;
         q[1] = dx * dx + dy * dy + dz * dz;
@@ -453,31 +488,39 @@ HR_FN void hr_quadratic_ray_terms(const hr_config& c, const float* ro, const flo
     }
 }
 
-// quad: hr_quadratic_ray_terms of this ray for the model's constant centre-scale, or NULL (read only where origin_scale == 0)
-HR_FN float hr_sample_distance(const hr_config& c, const float* hk, int k, const float* ro, const float* rd, HrRisk* risk = nullptr,
-                               const float* quad = nullptr)
+// 1 - sigma of the intersect-sigma head (base.py:161-162)
+HR_FN float hr_isect_one_m(const hr_config& c, const float* hk)
 {
     float sigma = 0.0f;
     if (c.f_isect_sigma.offset >= 0) sigma = hr_apply_act(c.f_isect_sigma.act, hk[c.f_isect_sigma.offset]);
-    float one_m = 1.0f - sigma;
-    float dist;
+    return 1.0f - sigma;
+}
+
+// quad: hr_quadratic_ray_terms of this ray for the model's constant centre-scale, or NULL (read only where origin_scale == 0)
+template <class H>
+HR_FN auto hr_sample_distance(const hr_config& c, H hk, int k, const float* ro, const float* rd, HrRisk* risk = nullptr,
+                              const float* quad = nullptr) -> decltype(hr_zval(c, hk, 0, 0.0f))
+{
+    typedef decltype(hr_zval(c, hk, 0, 0.0f)) T;
+    float one_m = hr_isect_one_m(c, hk);
+    T dist;
     if (risk) risk->amp = 1.0f;
     if (c.isect_type == HR_ISECT_Z_PLANE) {
-        float z = hr_process_z(c, hr_zval(c, hk, 0, one_m), c.z_scale, c.samples[k], risk);   // base.py:129
+        T z = hr_process_z(c, hr_zval(c, hk, 0, one_m), c.z_scale, c.samples[k], risk);   // base.py:129
         dist = hr_axis_plane_t(z, ro[2], rd[2]);                     // z.py:88-95
         if (risk) risk->amp = hr_axis_plane_amp(rd[2]);
     } else if (c.isect_type == HR_ISECT_SPHERE || c.isect_type == HR_ISECT_CYLINDER) {
         // origins = z[:3] * origin_scale_factor + origin_initial (primitive.py:410-412).  With the
         // shipped origin_scale_factor of 0 the three channels are multiplied by zero; they are then
         // not read at all (and hr_model_finalize drops those columns from the last Linear).
-        float sx = c.origin_initial[0], sy = c.origin_initial[1], sz = c.origin_initial[2];
+        T sx = c.origin_initial[0], sy = c.origin_initial[1], sz = c.origin_initial[2];
         if (c.origin_scale != 0.0f) {
             sx = hr_zval(c, hk, 0, one_m) * c.origin_scale + c.origin_initial[0];
             sy = hr_zval(c, hk, 1, one_m) * c.origin_scale + c.origin_initial[1];
             sz = hr_zval(c, hk, 2, one_m) * c.origin_scale + c.origin_initial[2];
         }
-        float radius = hr_process_z(c, hr_zval(c, hk, 3, one_m), c.z_scale, c.samples[k], risk);
-        float q_[3];
+        T radius = hr_process_z(c, hr_zval(c, hk, 3, one_m), c.z_scale, c.samples[k], risk);
+        T q_[3];
         if (quad && c.origin_scale == 0.0f) { q_[0] = quad[0]; q_[1] = quad[1]; q_[2] = quad[2]; }
         else hr_quadratic_ray_terms(c, ro, rd, sx, sy, sz, q_);
         dist = hr_quadratic_t(q_[0], q_[1], q_[2], radius, risk);
@@ -486,7 +529,7 @@ HR_FN float hr_sample_distance(const hr_config& c, const float* hk, int k, const
     } else if (c.isect_type == HR_ISECT_VOXEL_GRID) {
         // voxel.py:72-112: samples are (Z/3, 3) axis planes; sample k is a plane orthogonal to axis k % 3
         const int axis = k % 3;
-        float z = hr_process_z(c, hr_zval(c, hk, 0, one_m), c.voxel_scale[axis], c.samples[k], risk);
+        T z = hr_process_z(c, hr_zval(c, hk, 0, one_m), c.voxel_scale[axis], c.samples[k], risk);
         const float o = (axis == 0) ? ro[0] : (axis == 1) ? ro[1] : ro[2];
         const float d = (axis == 0) ? rd[0] : (axis == 1) ? rd[1] : rd[2];
         if (c.isect_outward) z = z * hr_sign(d);
@@ -496,41 +539,43 @@ HR_FN float hr_sample_distance(const hr_config& c, const float* hk, int k, const
         // voxel.py:184-213: a plane per sample, normal = normalize(z[:3]*scale + start_normal[k % axes]),
         // offset = processed z[3]; intersect_plane (intersect_utils.py:210-236)
         const int axis = k % c.dvg_axes;
-        float n[3];
+        T n[3];
         HR_UNROLL
         for (int i = 0; i < 3; ++i) n[i] = c.dvg_normals[3 * axis + i];
         if (c.dvg_normal_scale != 0.0f)
             HR_UNROLL
             for (int i = 0; i < 3; ++i) n[i] = hr_zval(c, hk, i, one_m) * c.dvg_normal_scale + c.dvg_normals[3 * axis + i];
         hr_normalize3(n);
-        const float dplane = hr_process_z(c, hr_zval(c, hk, 3, one_m), c.z_scale, c.samples[k], risk);
-        const float o_n = (ro[0] * n[0] + ro[1] * n[1]) + ro[2] * n[2];
-        float d_n = (rd[0] * n[0] + rd[1] * n[1]) + rd[2] * n[2];
-        HR_RISK_ABS(risk, fabsf(d_n), 1e-5f);
-        d_n = (fabsf(d_n) < 1e-5f) ? 1e12f : d_n;
-        dist = HR_DIV(dplane - o_n, d_n);
-        if (risk) risk->amp = HR_RCP_BAND(fabsf(d_n));
+        const T dplane = hr_process_z(c, hr_zval(c, hk, 3, one_m), c.z_scale, c.samples[k], risk);
+        const T o_n = (ro[0] * n[0] + ro[1] * n[1]) + ro[2] * n[2];
+        T d_n = (rd[0] * n[0] + rd[1] * n[1]) + rd[2] * n[2];
+        HR_RISK_ABS(risk, fabsf(hr_val(d_n)), 1e-5f);
+        d_n = (fabsf(hr_val(d_n)) < 1e-5f) ? T(1e12f) : d_n;
+        dist = hr_div(dplane - o_n, d_n);
+        if (risk) risk->amp = HR_RCP_BAND(fabsf(hr_val(d_n)));
     } else {                                                         // euclidean_distance_unified, primitive.py:162-176
-        float z = hr_process_z(c, hr_zval(c, hk, 0, one_m), c.z_scale, c.samples[k], risk);
+        T z = hr_process_z(c, hr_zval(c, hk, 0, one_m), c.z_scale, c.samples[k], risk);
         float pos[3];
         hr_pluecker_pos(ro, rd, pos);
         const float diff[3] = {pos[0] - ro[0], pos[1] - ro[1], pos[2] - ro[2]};
         dist = z + hr_signed_base_distance(rd, diff);
     }
     if (!c.isect_mask_off) {
+        const float dv = hr_val(dist);
         if (risk) {
             const float band_d = risk->band_zc * risk->dlen * risk->amp;
-            risk->hit = risk->hit || (fabsf(dist - c.near) <= band_d) || (fabsf(dist - c.far) <= band_d);
+            risk->hit = risk->hit || (fabsf(dv - c.near) <= band_d) || (fabsf(dv - c.far) <= band_d);
         }
-        bool mask = (dist <= c.near) || (dist >= c.far);             // base.py:194
-        dist = mask ? 0.0f : dist;
+        bool mask = (dv <= c.near) || (dv >= c.far);                 // base.py:194
+        dist = mask ? T(0.0f) : dist;
     }
-    if (risk) risk->hit = risk->hit || (dist != 0.0f && risk->amp_cut > 0.0f && risk->amp > risk->amp_cut);
+    const float dv = hr_val(dist);
+    if (risk) risk->hit = risk->hit || (dv != 0.0f && risk->amp_cut > 0.0f && risk->amp > risk->amp_cut);
     return dist;
 }
 
 // get_base_time, utils/flow_utils.py:10-35 (jitter off).  rintf == torch.round (half to even).
-HR_FN float hr_base_time(const hr_config& c, float t)
+HR_HD float hr_base_time(const hr_config& c, float t)
 {
     if (c.num_keyframes <= 0) return 0.0f;
     float tt = t * c.flow_fac;
@@ -602,7 +647,7 @@ HR_FN float hr_normalize_coord(const hr_config& c, float v, int axis)
 }
 
 // normalize_time_coord (tensorf_dynamic.py:615-616)
-HR_FN float hr_normalize_time(const hr_config& c, float base_t)
+HR_HD float hr_normalize_time(const hr_config& c, float base_t)
 {
     return (base_t * c.time_scale + c.time_offset) * 2.0f - 1.0f;
 }
@@ -641,7 +686,7 @@ struct hr_axis_tap {
     int i1;            // clamped index of the high tap
     float w0, w1;      // weights, already zeroed for out-of-range taps
 };
-HR_FN hr_axis_tap hr_make_tap(float g, int n)
+HR_HD hr_axis_tap hr_make_tap(float g, int n)
 {
     hr_axis_tap t;
     float ix = ((g + 1.0f) / 2.0f) * (float)(n - 1);
@@ -702,6 +747,25 @@ HR_FN hr_axis_tap_c hr_make_tap_in(float g, int n)
     t.w0 = lo ? b : (hi ? 0.0f : a);            // floor == -1: the only tap in range is texel 0, reached as the base
     t.w1 = lo ? 0.0f : (hi ? a : b);            // floor == n - 1: the only tap in range is texel n - 1, reached as base + 1
     return t;
+}
+
+// The index arithmetic of the taps above by itself -- the unnormalised coordinate, its floor, and whether the low tap floor(ix) and the
+// high tap floor(ix) + 1 lie on the axis of n texels -- for what needs the flags or the row and not the weights (hr_train.h: the tap's
+// derivative, the keyframe row of a ray).  The three render forms above keep their own statements: the device code the compiler makes of
+// the sample kernels depends on their order.
+struct hr_tap_index {
+    float ix, f0;
+    bool ok0, ok1;
+};
+HR_FN hr_tap_index hr_tap_ix(float g, int n)
+{
+    hr_tap_index x;
+    x.ix = ((g + 1.0f) / 2.0f) * (float)(n - 1);
+    x.f0 = floorf(x.ix);
+    const int i0 = (int)x.f0, i1 = i0 + 1;
+    x.ok0 = (i0 >= 0) && (i0 < n);
+    x.ok1 = (i1 >= 0) && (i1 < n);
+    return x;
 }
 
 // ---------------------------------------------------------------- display pack

@@ -13,6 +13,7 @@
 
 #include "../../include/hyperreel_hip.h"
 #include "hr_grid.h"
+#include "hr_math.h"
 
 // z_channels rounded up to a power of two, at least 8: the sample count the per-ray kernels are compiled for (8 ... 256)
 static inline int hr_round_zp(int z_channels)
@@ -275,24 +276,13 @@ static inline void hr_sample_dispatch(const HrSamplePlan& P, bool half, F&& f)
     hr_with_zp(P.zp, [&](auto zp) { if (half) tex(zp, std::true_type()); else tex(zp, std::false_type()); });
 }
 
-// ---- hr_render_frame: the time tap every ray of a frame shares, as hr_sample_body computes it from a ray's last column -- the host's
-// copy of hr_base_time, hr_normalize_time and hr_make_tap (hr_math.h: device-only under hipcc), float32 throughout; held to them bit
-// for bit by tests/test_render_plan_host.py
+// ---- hr_render_frame: the time tap every ray of a frame shares, as hr_sample_body computes it from a ray's last column (hr_math.h)
 struct HrTimeTap { int i0, i1; float w0, w1; };      // clamped keyframe rows; their weights, zero for a row that does not exist
 static inline HrTimeTap hr_frame_time_tap(const hr_config& c, float time)
 {
-    float base_t = 0.0f;
-    if (c.advect && c.num_keyframes > 0) {
-        const float tt = fminf(fmaxf(time * c.flow_fac, 0.0f), c.flow_kmax);
-        base_t = rintf(tt - 1e-5f) * c.flow_inv_fac;
-    }
-    const float g = (base_t * c.time_scale + c.time_offset) * 2.0f - 1.0f;
-    const int n = c.num_keyframes;
-    const float ix = ((g + 1.0f) / 2.0f) * (float)(n - 1);
-    const float f0 = floorf(ix), f1 = f0 + 1.0f;
-    const int i0 = (int)f0, i1 = i0 + 1;
-    const bool ok0 = i0 >= 0 && i0 < n, ok1 = i1 >= 0 && i1 < n;
-    return HrTimeTap{ok0 ? i0 : 0, ok1 ? i1 : 0, ok0 ? f1 - ix : 0.0f, ok1 ? ix - f0 : 0.0f};
+    const float base_t = c.advect ? hr_base_time(c, time) : 0.0f;
+    const hr_axis_tap t = hr_make_tap(hr_normalize_time(c, base_t), c.num_keyframes);
+    return HrTimeTap{t.i0, t.i1, t.w0, t.w1};
 }
 
 // ---- the frame kernel (fused_impl.inc)

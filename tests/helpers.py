@@ -212,6 +212,18 @@ def math_lib():
     return lib
 
 
+@functools.lru_cache(maxsize=None)
+def train_lib():
+    """Host build of hyperreel_amd/csrc/hr_train.h (tests/host_math/hr_train_host.cpp): the training path's per-ray / per-sample phases."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    src = os.path.join(here, 'host_math', 'hr_train_host.cpp')
+    deps = [src, os.path.join(here, '..', 'include', 'hyperreel_hip.h')] + [os.path.join(here, '..', 'hyperreel_amd', 'csrc', f) for f in ('hr_train.h', 'hr_mask.h', 'hr_math.h', 'hr_grid.h', 'hr_plan.h')]
+    lib = ctypes.CDLL(build_host_lib(os.path.join(here, 'host_math', '_build', 'libhr_train_host.so'), src, deps))
+    lib.ht_unsupported.restype = ctypes.c_char_p
+    assert lib.ht_sizeof_plane() == ctypes.sizeof(GridPlane)
+    return lib
+
+
 def even_chunk(chunk, n):
     """hr_even_chunk: rays per launch of a call of n rays on a workspace of `chunk` rays."""
     return plan_lib().hp_even_chunk(chunk, n)

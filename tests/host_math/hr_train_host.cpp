@@ -51,6 +51,20 @@ int ht_train(const hr_config* c, const float* rays, const float* head, long long
     return 0;
 }
 
+// phase C alone: hr_sample_distance_bwd of every sample for dt (n, Z) = dL/d (masked distance), added to d_head (n, Z * P; zeroed by the caller)
+void ht_distance_bwd(const hr_config* c, const float* rays, const float* head, long long n, const float* dt, float* d_head)
+{
+    const int Z = c->z_channels, P = c->preds_per_z;
+    for (long long i = 0; i < n; ++i) {
+        float ro[3], rd[3];
+        hr_train_ray_od(*c, rays + (size_t)i * c->ray_dim, ro, rd);
+        for (int k = 0; k < Z; ++k) {
+            const size_t s = (size_t)i * Z + k;
+            hr_sample_distance_bwd(*c, head + s * P, k, ro, rd, dt[s], d_head + s * P);
+        }
+    }
+}
+
 // dense alpha of the grid (hr_mask.h) the way the device does it, one point after the other
 void ht_dense_alpha(const hr_config* c, const HrGridPlane* planes, const int* n, float length, int num_frames, const float* prev_volume,
                     const int* pn, const float* prev_aabb, float* alpha)

@@ -19,7 +19,10 @@ CASES = ['donerf_sphere_small', 'donerf_cylinder_small', 'technicolor_z_plane_sm
          # harmless in the forward (masked), but torch.autograd carries the NaN into every MLP gradient of the reference, so there is nothing to match
          'sweep/variant_donerf_contract',
          # transform_color_one fed from the head (`color_transform_global`, 9 channels of sample 0)
-         'sweep/variant_color_transform_global_head']
+         'sweep/variant_color_transform_global_head',
+         # intersections that read several head channels per sample: phase C carries forward-mode duals through the shared geometry (hr_math.h)
+         # (not sweep/variant_cylinder_new: torch.autograd returns NaN for every MLP gradient of the restatement there, so there is nothing to match)
+         'sweep/immersive_sphere_new', 'sweep/variant_sphere_new_origins_only', 'sweep/shiny_z_deformable', 'sweep/variant_deformable_3axes']
 
 
 def _reference_grads(g, rays, G, white):

@@ -39,7 +39,7 @@ def _bind(lib):
 @functools.lru_cache(maxsize=None)
 def host_lib():
     src = os.path.join(HERE, 'host_math', 'hr_mlp_pack_host.cpp')
-    deps = [src, os.path.join(HERE, '..', 'include', 'hyperreel_hip.h')] + [os.path.join(HERE, '..', 'hyperreel_amd', 'csrc', f) for f in ('hr_mlp_pack.h', 'hr_plan.h', 'hr_grid.h')]
+    deps = [src, os.path.join(HERE, '..', 'include', 'hyperreel_hip.h')] + [os.path.join(HERE, '..', 'hyperreel_amd', 'csrc', f) for f in ('hr_mlp_pack.h', 'hr_plan.h', 'hr_grid.h', 'hr_math.h')]
     return _bind(C.CDLL(build_host_lib(os.path.join(HERE, 'host_math', '_build', 'libhr_mlp_pack_host.so'), src, deps)))
 
 

@@ -3,33 +3,21 @@ against torch.autograd on the CPU restatement of the reference (oracle/torch_por
 raw MLP output, every plane / line and basis_mat, on the five benchmark families.  The device build wraps the same
 source in one thread per ray; the `-m gpu` test checks that build against this one's expectations."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import Golden, GridPlane, build_host_lib, plane_geometry, trainable_sweep_cases
+from helpers import Golden, GridPlane, plane_geometry, train_lib, trainable_sweep_cases
 from hyperreel_amd import plan
 from torch_port import TorchPort
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, 'host_math', 'hr_train_host.cpp')
-OUT = os.path.join(HERE, 'host_math', '_build', 'libhr_train_host.so')
-CSRC = os.path.join(HERE, '..', 'hyperreel_amd', 'csrc')
 
 FP = C.POINTER(C.c_float)
 
 
 @pytest.fixture(scope='module')
 def ht():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ('hr_train.h', 'hr_mask.h', 'hr_math.h', 'hr_grid.h', 'hr_plan.h')] + [os.path.join(HERE, '..', 'include', 'hyperreel_hip.h')]
-    build_host_lib(OUT, SRC, deps)
-    lib = C.CDLL(OUT)
-    lib.ht_unsupported.restype = C.c_char_p
-    assert lib.ht_sizeof_plane() == C.sizeof(GridPlane)
-    return lib
+    return train_lib()
 
 
 def pack_grids(port, hc):
