@@ -218,9 +218,25 @@ int hr_model_upload(hr_model* m, const char* name, const void* ptr, size_t bytes
     return HR_OK;
 }
 
+// The end of hr_model_finalize: the default workspace, then the MLP's new state into the model with its margins measured (set_mlp_state,
+// which first synchronises the device -- the tiles are fresh --, so whatever finalize launched is done as well).  Finalized only if
+// all of it succeeded.
+static int finalize_end(hr_model* m, HrMlpState& mlp)
+{
+    HR_HIP(hipGetLastError());
+    if (m->chunk == 0 && !m->is_coarse) {
+        const int rc = hr_model_reserve(m, hr_default_chunk(hr_head_quads(m->cfg, m->p_live), rows_per_ray(m->cfg)));
+        if (rc != HR_OK) return rc;
+    }
+    const int rc = set_mlp_state(m, mlp, nullptr);
+    m->finalized = rc == HR_OK;
+    return rc;
+}
+
 int hr_model_finalize(hr_model* m)
 {
     if (!m) return fail(HR_E_INVALID, "null argument");
+    m->finalized = false;              // until all of it has succeeded (finalize_end)
     if (m->coarse) {
         int rc = hr_model_finalize(m->coarse.get());
         if (rc != HR_OK) return rc;
@@ -233,22 +249,19 @@ int hr_model_finalize(hr_model* m)
     m->packed_bytes = 0;
     char name[64];
 
-    // ---- MLP: which arithmetic (the fp16 split needs every activation below 65504), then MFMA operand tiles
+    // ---- MLP: which arithmetic (the fp16 split needs every activation below 65504), then MFMA operand tiles -- built aside; they reach the
+    // model at the end, once the workspace their margins are measured with exists.  (A re-finalize: the tiles and rays made from the
+    // weights before go first, as the grids do below)
     if (!m->flags) HR_HIP(m->flags.alloc(sizeof(unsigned)));
     HR_HIP(hipMemset(m->flags, 0, sizeof(unsigned)));
+    m->mlp.pack.reset();
+    m->mlp.calib.reset();
+    HrMlpState mlp;
     {
-        int rc = resolve_precision(m, nullptr, 0, nullptr);
+        const int rc = build_mlp_state(m, nullptr, 0, nullptr, false, mlp);
         if (rc != HR_OK) return rc;
-        rc = pack_mlp(m);
-        if (rc != HR_OK) return rc;
-        m->packed_bytes += m->mlp_bytes;
     }
-
-    if (m->is_coarse) {      // coarse level of a cascade: no grids
-        HR_HIP(hipDeviceSynchronize());
-        m->finalized = true;
-        return HR_OK;
-    }
+    if (m->is_coarse) return finalize_end(m, mlp);      // coarse level of a cascade: no grids
 
     // ---- grids: channel-last texels, density | appearance interleaved per plane pair
     const bool cols_ok = hr_plane_geometry(c, m->planes, &m->ca_total, &m->n_basis_cols);
@@ -318,14 +331,7 @@ int hr_model_finalize(hr_model* m)
         if (c.video && c.grid_dtype != HR_GRID_FP16 && p.bw > 1 && p.cd4 + p.ca4 > 0)
             HR_HIP(m->frame_line[j].alloc(sizeof(float) * (size_t)p.bw * p.tex));
     }
-    HR_HIP(hipDeviceSynchronize());
-    HR_HIP(hipGetLastError());
-    m->finalized = true;
-    if (m->chunk == 0) {
-        const int rc = hr_model_reserve(m, hr_default_chunk(hr_head_quads(m->cfg, m->p_live), rows_per_ray(m->cfg)));
-        if (rc != HR_OK) return rc;
-    }
-    return calibrate_band(m, nullptr);
+    return finalize_end(m, mlp);
 }
 
 // the configuration with every schedule-dependent constant blanked: what hr_model_update_config may not change
@@ -355,7 +361,7 @@ int hr_model_update_config(hr_model* m, const hr_config* cfg, void* stream)
     analyse_live_columns(m);                                  // same live columns (structure unchanged): rebuilds kcfg
     if (m->kcfg_dev) HR_HIP(hipMemcpy(m->kcfg_dev, &m->kcfg, sizeof(hr_config), hipMemcpyHostToDevice));
     if (m->ucfg_dev) HR_HIP(hipMemcpy(m->ucfg_dev, &m->cfg, sizeof(hr_config), hipMemcpyHostToDevice));
-    m->band_stale = true;                                     // the activations' constants feed the distances: measured again before the next render
+    m->mlp.band_stale = true;                                   // the activations' constants feed the distances: measured again before the next render
     return HR_OK;
 }
 
@@ -470,9 +476,9 @@ int hr_model_get_option(hr_model* m, int32_t option, int32_t* value)
     else if (option == HR_OPT_MLP_PRECISION_ACTIVE || option == HR_OPT_MLP_CALIBRATED || option == HR_OPT_MLP_OVERFLOW || option == HR_OPT_MLP_F8_SATURATED ||
              option == HR_OPT_MLP_VERIFIED || option == HR_OPT_REDO_OVERFLOW || option == HR_OPT_REDO_COUNT || option == HR_OPT_WIDE_COUNT) {
         if (!m->finalized) return fail(HR_E_STATE, "hr_model_finalize has not been called");
-        if (option == HR_OPT_MLP_PRECISION_ACTIVE) *value = m->active_precision;
-        else if (option == HR_OPT_MLP_CALIBRATED) *value = m->calibrated;
-        else if (option == HR_OPT_MLP_VERIFIED) *value = m->verified;
+        if (option == HR_OPT_MLP_PRECISION_ACTIVE) *value = m->mlp.active_precision;
+        else if (option == HR_OPT_MLP_CALIBRATED) *value = m->mlp.calibrated;
+        else if (option == HR_OPT_MLP_VERIFIED) *value = m->mlp.verified;
         else if (option == HR_OPT_REDO_COUNT || option == HR_OPT_WIDE_COUNT) {
             unsigned n = 0;
             if (m->redo_count) HR_HIP(hipMemcpy(&n, m->redo_count + (option == HR_OPT_REDO_COUNT ? 1 : 3), sizeof(unsigned), hipMemcpyDeviceToHost));      // the pass's copy
@@ -503,7 +509,7 @@ int64_t hr_model_device_bytes(const hr_model* m)
     if (!m) return 0;
     int64_t raw = 0;
     for (auto& kv : m->raw) raw += (int64_t)kv.second.bytes;
-    return raw + m->packed_bytes + (int64_t)sizeof(float) * m->chunk * m->cfg.z_channels * m->p_live +
+    return raw + m->packed_bytes + (m->mlp.pack ? m->mlp.pack->bytes : 0) + (int64_t)sizeof(float) * m->chunk * m->cfg.z_channels * m->p_live +
            (m->rows ? (int64_t)sizeof(float) * m->chunk * m->cfg.casc_in_z * m->cfg.casc_row_dim : 0) + hr_model_device_bytes(m->coarse.get());
 }
 

@@ -8,7 +8,7 @@
 void launch_mlp(const hr_model* m, const hr_config& c, const HrMlpArgs& a, hipStream_t st, int tier)
 {
     if (c.mlp_layers == 0) return;               // ZeroMLP: the workspace already holds the (all-zero) head
-    const int prec = tier == 1 ? HR_MLP_F16X3 : (tier == 2 ? HR_MLP_BF16X3 : m->active_precision);
+    const int prec = tier == 1 ? HR_MLP_F16X3 : (tier == 2 ? HR_MLP_BF16X3 : m->mlp.active_precision);
     if (prec == HR_MLP_BF16X3) hr_launch_mlp_bf16x3(c, a, st);
     else if (prec == HR_MLP_F16X3) hr_launch_mlp_f16x3(c, a, st);
     else if (prec == HR_MLP_F16X2) hr_launch_mlp_f16x2(c, a, st);
@@ -18,7 +18,7 @@ void launch_mlp(const hr_model* m, const hr_config& c, const HrMlpArgs& a, hipSt
 
 void fill_mlp_args(const hr_model* m, HrMlpArgs& a, const float* rays, int64_t n, int tier)
 {
-    const HrMlpTiles& t = m->tiles[tier];
+    const HrMlpTiles& t = m->mlp.pack->tiles[tier];
     a.rays = rays;
     a.n_rays = n;
     a.head = m->head;
@@ -27,7 +27,7 @@ void fill_mlp_args(const hr_model* m, HrMlpArgs& a, const float* rays, int64_t n
         a.wsplit[l] = t.wsplit[l];
         a.bias[l] = t.bias[l];
         a.winv[l] = t.winv[l];
-        a.xexp[l] = tier > 0 ? 0 : m->xexp[l];
+        a.xexp[l] = tier > 0 ? 0 : m->mlp.xexp[l];
         a.n_tiles[l] = t.n_tiles[l];
     }
     a.ray0 = 0;
@@ -38,9 +38,9 @@ void fill_mlp_args(const hr_model* m, HrMlpArgs& a, const float* rays, int64_t n
     a.redo_list = nullptr;
     a.redo_count = nullptr;
     a.redo_cap = 0;
-    a.n_out = m->n_out;
-    a.nq = (m->n_out + 3) / 4;
-    a.k0p = m->k0p;
+    a.n_out = m->mlp.pack->n_out;
+    a.nq = (m->mlp.pack->n_out + 3) / 4;
+    a.k0p = m->mlp.pack->k0p;
     a.trace = nullptr;
     a.flags = m->flags;
 }
@@ -64,7 +64,7 @@ void fill_sample_args(const hr_model* m, HrSampleArgs& a, const float* rays, int
     a.cfg_dev = m->kcfg_dev;
     a.rays = rays;
     a.head = m->head;
-    a.nq = (m->n_out + 3) / 4;
+    a.nq = (m->mlp.pack->n_out + 3) / 4;
     a.n_rays = n;
     a.rgb = rgb;
     a.fields = hr_fields();
@@ -145,10 +145,10 @@ void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int
 // The frame kernel (fused_impl.inc) for the whole ray list; false: hr_frame_plan says the call does not fit it (nothing launched)
 bool launch_frame(hr_model* m, const float* rays, int64_t n, float* rgb, bool probe, hipStream_t st)
 {
-    const int prec = m->active_precision, L = m->cfg.mlp_layers;
+    const int prec = m->mlp.active_precision, L = m->cfg.mlp_layers;
     const bool split = prec == HR_MLP_BF16X3 || prec == HR_MLP_F16X3 || prec == HR_MLP_F16X2 || prec == HR_MLP_F16F8;      // their elements: 16 bits (HrMlpTiles::wsplit)
-    const HrFramePlanIn in = {n, m->opt_frame_kernel, m->opt_sample_waves, m->coarse || m->is_coarse, m->verified != 0, split, sizeof(uint16_t),
-                              (m->n_out + 3) / 4, m->k0p, L > 0 ? m->tiles[0].n_tiles[L - 1] : 0, m->n_cus};
+    const HrFramePlanIn in = {n, m->opt_frame_kernel, m->opt_sample_waves, m->coarse || m->is_coarse, m->mlp.verified != 0, split, sizeof(uint16_t),
+                              (m->mlp.pack->n_out + 3) / 4, m->mlp.pack->k0p, L > 0 ? m->mlp.pack->tiles[0].n_tiles[L - 1] : 0, m->n_cus};
     const HrGridPlane planes[3] = {render_plane(m, 0), render_plane(m, 1), render_plane(m, 2)};
     const HrFramePlan P = hr_frame_plan(m->kcfg, planes, m->ca_total, in);
     if (!P.fits) return false;
@@ -191,7 +191,7 @@ static void launch_samples(const hr_model* m, const HrSampleArgs& sa, const hr_m
 // The verified fast path over one call's rays: first pass in f16f8 with the rays at risk listed on the device, then the list
 // again with the f16x3 tiles (in slices of the chunk's head workspace), then whatever left the half range there with the bf16x3 tiles.
 // list_cap: entries of the list this call may use.  maps: every pass writes the maps of the rays it writes pixels of (launch_samples)
-void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st, const hr_maps* maps)
+void render_verified(hr_model* m, const HrBand& band, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st, const hr_maps* maps)
 {
     const hr_config& c = m->cfg;
     const int64_t per = hr_even_chunk(m->chunk, n_rays);
@@ -211,9 +211,9 @@ void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* 
         sa.redo_list = m->redo_list;
         sa.redo_count = m->redo_count;
         sa.redo_cap = list_cap;
-        sa.redo_band = m->redo_band;
-        sa.redo_band_q = m->redo_band_q;
-        sa.redo_band_off = m->redo_band_off;
+        sa.redo_band = band.band;
+        sa.redo_band_q = band.band_q;
+        sa.redo_band_off = band.band_off;
         sa.redo_amp_cut = HR_VERIFY_AMP_CUT;
         launch_samples(m, sa, maps, r0, st);
     }
@@ -278,24 +278,24 @@ static int render_impl(hr_model* m, const float* rays_dev, int64_t n_rays, float
     // verified fast path.  With diagnostics requested every output comes from ONE arithmetic: the f16x3 tiles throughout.
     // So does a model with an occupancy volume (hr_occupancy_test decides per cell from a head-dependent point; the band does not cover it),
     // and a render inside a stream capture whose band is out of date (hr_model_update_config since the last measurement: measuring synchronises).
-    bool verify = m->verified && !fields && !m->occ && n_rays < ((int64_t)1 << 31);
-    if (verify && m->band_stale) {
+    bool verify = m->mlp.verified && !fields && !m->occ && n_rays < ((int64_t)1 << 31);
+    if (verify && m->mlp.band_stale) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
         if (cs == hipStreamCaptureStatusNone) {
             rc = calibrate_band(m, st);
             if (rc != HR_OK) return rc;
-            verify = verify && m->verified;            // HR_MLP_AUTO may just have given the fast path up
+            verify = verify && m->mlp.verified;            // HR_MLP_AUTO may just have given the fast path up
         } else {
             verify = false;
         }
     }
     if (verify && n_rays > 0) {
-        render_verified(m, rays_dev, n_rays, rgb_dev, hr_redo_list_cap(n_rays, m->redo_cap), st, maps);
+        render_verified(m, m->mlp.band, rays_dev, n_rays, rgb_dev, hr_redo_list_cap(n_rays, m->redo_cap), st, maps);
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
-    const bool safe_all = m->verified != 0;
+    const bool safe_all = m->mlp.verified != 0;
     const int64_t per = hr_even_chunk(m->chunk, n_rays);
     for (int64_t r0 = 0; r0 < n_rays; r0 += per) {
         const int64_t n = (n_rays - r0 < per) ? (n_rays - r0) : per;
@@ -310,7 +310,7 @@ static int render_impl(hr_model* m, const float* rays_dev, int64_t n_rays, float
             if (fields->weights_dev) sa.fields.weights_dev = fields->weights_dev + r0 * Z;
             if (fields->head_dev)
                 hr_launch_head_export(m->head, fields->head_dev + r0 * (int64_t)Z * c.preds_per_z, n, Z, c.preds_per_z, m->p_live,
-                                      (m->n_out + 3) / 4, rows_per_ray(c), m->col_map, st);
+                                      (m->mlp.pack->n_out + 3) / 4, rows_per_ray(c), m->col_map, st);
         }
         launch_samples(m, sa, maps, r0, st);
     }

@@ -213,7 +213,7 @@ int hr_mlp_train_forward(hr_model* m, const float* const* weights_dev, const flo
     hipStream_t st = (hipStream_t)stream;
     // ---- the current parameter values -> bf16 hi / lo tiles, on the device (what pack_mlp does on the host at finalize: hr_mlp_pack.h)
     const int P_user = c.preds_per_z, P_live = m->p_live;
-    const int k0p = m->k0p, n_out = m->n_out;
+    const int k0p = m->mlp.pack->k0p, n_out = m->mlp.pack->n_out;
     HrMlpTiles& t = m->train_tiles;
     for (int l = 0; l < L; ++l) {
         if (!weights_dev[l] || !biases_dev[l]) return fail(HR_E_INVALID, "hr_mlp_train_forward: layer %d has no weights", l);

@@ -72,6 +72,39 @@ struct HR_HIDDEN HrMlpTiles {
     int64_t bytes = 0;
 };
 
+// The packed MLP, by tier: 0 = the active arithmetic.  Verified fast path: the MLP runs f16f8, rays with a comparison at risk
+// (or a range bit) are listed on the device and rendered again by a second, list-driven pass at the end of hr_render with tier 1, the
+// f16x3 tiles; tier 2: bf16x3 tiles (fp32 exponent range) for the third pass -- the tiles of the second pass in which an activation left
+// the IEEE-half range (what the reference's fp32 BaseMLP, nlf/nets/mlp.py:159-172, cannot do)
+struct HR_HIDDEN HrMlpPack {
+    HrMlpTiles tiles[3];
+    int k0p = 0;
+    int n_out = 0;
+    int64_t bytes = 0;
+};
+
+struct HR_HIDDEN HrCalibRays {
+    DevMem<float> p;
+    int64_t n = 0;
+};
+
+// Everything the choice of the MLP's arithmetic decides.  A value: api_mlp.hip builds a new one aside -- sharing the tiles or
+// the rays of the old one where they stay -- and set_mlp_state puts it in the model's place once it is complete; nothing else writes it
+// but hr_model_update_config, which marks the band stale, and hr_model_finalize, which lets go of the tiles and rays made from the
+// weights before (the model is not finalized again until the new state is in).
+struct HR_HIDDEN HrMlpState {
+    int active_precision = HR_MLP_FP32;   // the arithmetic the MLP kernels run: cfg.mlp_precision, with HR_MLP_AUTO resolved (hr_mlp_choice)
+    int verified = 0;                     // the verified fast path is on (tiles[1], tiles[2])
+    int calibrated = 0;                   // 0: not calibrated (cascade rows / unsupported width), 1: synthetic rays (finalize), 2: the caller's rays
+    float act_max[HR_MAX_LAYERS] = {};    // calibration: max |input feature|, max |pre-activation| of hidden Linear l - 1
+    int xexp[HR_MAX_LAYERS] = {};         // f16 + fp8 split: exponent of the fp8 images of hidden Linear l's output (HrMlpArgs::xexp), from act_max
+    std::shared_ptr<const HrMlpPack> pack;
+    std::shared_ptr<const HrCalibRays> calib;   // the rays the arithmetic was decided on (synthetic, or a strided sample of the caller's): kept for the band
+    HrBand band = {};                     // the margins of THIS model (calibrate_band; hr_math.h HrRisk)
+    bool band_stale = false;              // the margins are the floor, or hr_model_update_config changed the activations' constants: measured before the next render
+    hr_verify_info vinfo = {};
+};
+
 struct HR_HIDDEN hr_model {
     hr_config cfg;        // as handed over by the caller
     hr_config kcfg;       // what the kernels see: dead head columns removed (preds_per_z, field offsets)
@@ -80,32 +113,13 @@ struct HR_HIDDEN hr_model {
     bool finalized = false;
     std::map<std::string, DevBuf> raw;     // uploaded tensors, reference layout, device memory
     std::map<std::string, size_t> expect;  // name -> expected byte size
-    // packed MLP, by tier: 0 = the active arithmetic.  Verified fast path: the MLP runs f16f8, rays with a comparison at risk
-    // (or a range bit) are listed on the device and rendered again by a second, list-driven pass at the end of hr_render with tier 1, the
-    // f16x3 tiles; tier 2: bf16x3 tiles (fp32 exponent range) for the third pass -- the tiles of the second pass in which an activation left
-    // the IEEE-half range (what the reference's fp32 BaseMLP, nlf/nets/mlp.py:159-172, cannot do)
-    HrMlpTiles tiles[3];
-    int xexp[HR_MAX_LAYERS] = {};         // f16 + fp8 split: exponent of the fp8 images of hidden Linear l's output (HrMlpArgs::xexp), from act_max
-    int k0p = 0;
-    int n_out = 0;
-    int active_precision = HR_MLP_FP32;   // the arithmetic the MLP kernels run: cfg.mlp_precision, with HR_MLP_AUTO resolved (resolve_precision)
-    float act_max[HR_MAX_LAYERS] = {};    // calibration: max |input feature|, max |pre-activation| of hidden Linear l - 1
-    int calibrated = 0;                   // 0: not calibrated (cascade rows / unsupported width), 1: synthetic rays (finalize), 2: the caller's rays
+    HrMlpState mlp;                       // which arithmetic the MLP runs, its tiles, the verified fast path's margins: replaced whole (set_mlp_state)
     DevMem<unsigned> flags;               // sticky device status word (HrMlpArgs::flags)
-    int verified = 0;                     // the verified fast path is on (tiles[1], tiles[2])
     DevMem<int> redo_list;                // the second pass's rays
     DevMem<int> wide_list;                // the third pass's rays
     DevMem<unsigned> redo_count;          // [0] second-pass counter, [1] its copy, [2] third-pass counter, [3] its copy
     int redo_cap = 0;                    // entries the list holds (hr_model_reserve); a call uses hr_redo_list_cap of them
     int wide_cap = 0;
-    float redo_band = 0.0f;              // the margins of THIS model (calibrate_band; hr_math.h HrRisk): of zc,
-    float redo_band_q = 0.0f;            //   of a point coordinate per unit of amplification,
-    float redo_band_off = 0.0f;          //   of the point-offset / flow heads
-    hr_verify_info vinfo = {};
-    DevMem<float> calib_rays;            // the rays the arithmetic was decided on (synthetic, or a strided sample of the caller's): kept for the band
-    int64_t calib_n = 0;
-    bool band_stale = false;             // hr_model_update_config changed the activations' constants: the band is measured again before the next render
-    int64_t mlp_bytes = 0;
     // packed grids
     DevMem<float> grid_a[3];   // texel storage (floats, or halfs when cfg.grid_dtype == HR_GRID_FP16)
     DevMem<float> grid_b[3];
@@ -119,7 +133,7 @@ struct HR_HIDDEN hr_model {
     // workspace
     DevMem<float> head;
     int64_t chunk = 0;
-    int64_t packed_bytes = 0;
+    int64_t packed_bytes = 0;            // grids and basis (the MLP's tiles: mlp.pack->bytes)
     // point_prediction cascade (hr_model_create_cascade): `this` is the fine level (point MLP, second intersect,
     // colour); `coarse` holds the ray MLP and the first intersect and owns no grids
     DevMem<hr_config> kcfg_dev;          // device copy of kcfg for the sample kernel (the MLP kernels take it by value)
@@ -158,8 +172,8 @@ struct HR_HIDDEN hr_model {
 constexpr float HR_VERIFY_AMP_CUT = 2.0f;
 
 // ---- api_mlp.hip
-HR_HIDDEN int resolve_precision(hr_model* m, const float* rays_dev, int64_t n, hipStream_t st);
-HR_HIDDEN int pack_mlp(hr_model* m);
+HR_HIDDEN int build_mlp_state(hr_model* m, const float* rays_dev, int64_t n, hipStream_t st, bool keep_tiles, HrMlpState& s);
+HR_HIDDEN int set_mlp_state(hr_model* m, HrMlpState& s, hipStream_t st);
 HR_HIDDEN int calibrate_band(hr_model* m, hipStream_t st);
 
 // ---- api_render.hip (tier: 0 = the model's primary arithmetic; the verified fast path's later passes: 1 = its f16x3 tiles, 2 = its bf16x3 tiles)
@@ -168,7 +182,7 @@ HR_HIDDEN void fill_mlp_args(const hr_model* m, HrMlpArgs& a, const float* rays,
 HR_HIDDEN void fill_sample_args(const hr_model* m, HrSampleArgs& a, const float* rays, int64_t n, float* rgb);
 HR_HIDDEN void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int64_t redo0 = -1, int tier = 0);
 HR_HIDDEN bool launch_frame(hr_model* m, const float* rays, int64_t n, float* rgb, bool probe, hipStream_t st);
-HR_HIDDEN void render_verified(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st,
+HR_HIDDEN void render_verified(hr_model* m, const HrBand& band, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st,
                                const hr_maps* maps = nullptr);
 
 #endif  // HR_MODEL_H

@@ -1,7 +1,7 @@
 // Host-side decisions shared by hr_model_create / finalize, the render launchers and the training launcher: plane-pair geometry, plane
 // class, the render call's launch plans (live head columns, launch sizing, the sample kernel, the frame kernel, a frame's time tap),
-// the training step's launch plan.  Plain C++ (no HIP types, no hr_model, no getenv); the CPU suite compiles it as it is
-// (tests/host_math/hr_plan_host.cpp).
+// the training step's launch plan, the MLP's arithmetic (which one, whether verified, the margins' rules).  Plain C++ (no HIP types, no
+// hr_model, no getenv); the CPU suite compiles it as it is (tests/host_math/hr_plan_host.cpp).
 #ifndef HR_PLAN_H
 #define HR_PLAN_H
 
@@ -505,6 +505,96 @@ static inline HrTrainPlan hr_train_plan(const hr_config& cfg, const HrGridPlane*
     }
     P.tail_blocks = (unsigned)ceil_div(n * cfg.z_channels, 256);
     return P;
+}
+
+// ---------------------------------------------------------------- MLP arithmetic (api_mlp.hip)
+// largest activation a model may show in calibration for the fp16 split arithmetic to be used: a factor 8 below the IEEE-half maximum,
+// because calibration sees 4096 rays and a frame has 640 000
+static const float HR_F16_CALIBRATION_LIMIT = 65504.0f / 8.0f;
+static const float HR_BAND_FLOOR = 1e-6f;          // four float32 ulps of the largest |zc| (2)
+static const float HR_VERIFY_LISTED_LIMIT = 0.05f; // fraction of the calibration rays the first pass may list (a call's list holds a sixteenth of its rays)
+static const float HR_VERIFY_RGB_LIMIT = 6e-5f;   // on <= 65 536 calibration rays; the shipped families measure 1.5e-5 - 5e-5 here and 2.3e-5 - 5.4e-5 on their 640 000-ray frames
+
+// The verified fast path: f16f8 + a list-driven second pass in f16x3.  What it needs: a ray's samples inside one wavefront
+// (the list entry is written from a wave-level vote), no cascade (the point MLP's rows are internal).  (An occupancy volume adds a
+// head-dependent decision the band does not cover: hr_render then takes the f16x3 tiles throughout, see hr_render_fields.)
+// The per-sample margins (hr_math.h, HrRisk) are derived for: axis planes, sphere / cylinder with fixed origins, the euclidean distance;
+// the identity, affine and MIP-NeRF contractions.
+static inline bool hr_mlp_can_verify(const hr_config& c, bool cascade_level)
+{
+    const bool isect_ok = c.isect_type == HR_ISECT_Z_PLANE || c.isect_type == HR_ISECT_VOXEL_GRID || c.isect_type == HR_ISECT_EUCLIDEAN_UNIFIED ||
+                          ((c.isect_type == HR_ISECT_SPHERE || c.isect_type == HR_ISECT_CYLINDER) && c.origin_scale == 0.0f);
+    return !cascade_level && c.z_channels <= 64 && c.mlp_layers >= 2 && c.mlp_hidden == 256 && isect_ok && c.contract_type != HR_CONTRACT_DONERF;
+}
+
+// Which arithmetic a model's MLP runs.  act_max[l]: the calibration's largest |input feature| (l = 0) and |pre-activation| of hidden
+// Linear l - 1; all zero before a measurement, and read only when needs_calibration comes back set -- the caller then measures and asks
+// again.  HR_MLP_AUTO becomes the verified fast path (f16f8, verified) when every one of them is finite and below
+// HR_F16_CALIBRATION_LIMIT and the model can be verified, f16x3 when it cannot, and bf16x3 (fp32 exponent range) when they are not;
+// a FORCED fp16 mode that fails the test is HR_E_RANGE, a forced f16f8v on a model that cannot be verified (or a width the range
+// kernel does not cover: range_supported) HR_E_INVALID.
+struct HrMlpChoice {
+    int active_precision, verified;
+    bool needs_calibration;
+    int status;                   // HR_OK | HR_E_RANGE | HR_E_INVALID
+};
+static inline HrMlpChoice hr_mlp_choice(const hr_config& c, bool cascade_level, bool range_supported, const float* act_max)
+{
+    const int want = c.mlp_precision;
+    if (c.mlp_layers == 0 || want == HR_MLP_FP32 || want == HR_MLP_BF16X3)
+        return {(c.mlp_layers == 0 && want == HR_MLP_AUTO) ? HR_MLP_F16X3 : want, 0, false, HR_OK};
+    if (want == HR_MLP_AUTO && c.mlp_hidden != 256) return {HR_MLP_FP32, 0, false, HR_OK};      // the split kernels are written for 256-wide layers
+    if (!range_supported) return {want, 0, true, HR_E_INVALID};
+    bool fits = true;
+    for (int l = 0; l < c.mlp_layers; ++l) fits = fits && isfinite(act_max[l]) && act_max[l] < HR_F16_CALIBRATION_LIMIT;
+    const bool can_verify = hr_mlp_can_verify(c, cascade_level);
+    if (want == HR_MLP_AUTO) {
+        if (!fits) return {HR_MLP_BF16X3, 0, true, HR_OK};
+        return {can_verify ? HR_MLP_F16F8 : HR_MLP_F16X3, can_verify ? 1 : 0, true, HR_OK};
+    }
+    if (want == HR_MLP_F16F8V && !can_verify) return {want, 0, true, HR_E_INVALID};
+    if (!fits) return {want, 0, true, HR_E_RANGE};
+    return {want == HR_MLP_F16F8V ? HR_MLP_F16F8 : want, want == HR_MLP_F16F8V ? 1 : 0, true, HR_OK};
+}
+
+// The caller's calibration rays that stay with the model (the band of the verified fast path is measured on them, again after
+// hr_model_update_config): every stride-th of the n, at most 65 536
+struct HrCalibSample {
+    int64_t stride, keep;
+};
+static inline HrCalibSample hr_calib_sample(int64_t n)
+{
+    const int64_t stride = (n + 65535) / 65536;
+    return {stride, (n + stride - 1) / stride};
+}
+
+// The margins of the verified fast path (hr_math.h, HrRisk: of zc, of a point coordinate per unit of amplification, of the point-offset /
+// flow heads) from the largest differences the two arithmetics showed on the calibration rays (hr_verify_info): 4 x, never below the floor
+struct HrBand {
+    float band, band_q, band_off;
+};
+static inline HrBand hr_band_margins(float max_d_zc, float max_d_dist_n, float max_d_geo_n, float max_d_off)
+{
+    return {fmaxf(HR_BAND_FLOOR, 4.0f * fmaxf(max_d_zc, max_d_dist_n)), fmaxf(HR_BAND_FLOOR, 4.0f * max_d_geo_n), 4.0f * max_d_off};
+}
+
+// hr_verify_info::listed_frac: `listed` of the n_used well-conditioned calibration rays were listed by the first pass (not measured on
+// fewer than 64).  The CALLER's rays (calibrated == 2) are what will be rendered: the ill-conditioned ones among all N are listed too
+// (synthetic rays point anywhere; half of them graze a z-plane net's planes, which says nothing about its cameras)
+static inline float hr_listed_frac(int calibrated, int64_t N, int64_t n_used, unsigned listed)
+{
+    float frac = n_used >= 64 ? (float)((double)listed / (double)n_used) : 0.0f;
+    if (calibrated == 2) frac = (float)(((double)(N - n_used) + (double)frac * (double)n_used) / (double)N);
+    return frac;
+}
+
+// hr_verify_info::fallback -- HR_MLP_AUTO gives the fast path up (f16x3 throughout: it lists nothing and has neither problem) with
+// 1: more than a twentieth of the rays would be rendered twice (a call's list holds a sixteenth), 2: the cheap arithmetic's own error is
+// too large a share of the 1e-4 budget on this model (or not a number)
+static inline int hr_verify_fallback(float listed_frac, float max_d_rgb)
+{
+    if (!(max_d_rgb <= HR_VERIFY_RGB_LIMIT)) return 2;
+    return listed_frac > HR_VERIFY_LISTED_LIMIT ? 1 : 0;
 }
 
 #endif  // HR_PLAN_H

@@ -17,7 +17,9 @@ from torch import nn
 from . import lib as _lib
 from .config import n_to_reso, to_plain
 from .data import current_stream, make_camera, make_fisheye, make_ndc
-from .plan import compile_model, hr_fields, hr_lightfield, hr_maps, upload_names
+from .plan import MLP_PRECISION, compile_model, hr_fields, hr_lightfield, hr_maps, upload_names
+
+_MLP_PRECISION_NAME = {code: name for name, code in MLP_PRECISION.items()}      # HR_OPT_MLP_PRECISION_ACTIVE -> 'f16x3' ...
 
 MAT_MODE = [[0, 1], [0, 2], [1, 2]]
 VEC_MODE = [2, 1, 0]
@@ -644,7 +646,7 @@ class HipLightfieldModel(nn.Module):
 
     def mlp_precision_active(self):
         """The arithmetic the MLP kernels run ('auto' resolved by the library's activation-range calibration)."""
-        return {0: 'fp32', 1: 'bf16x3', 2: 'f16x3', 3: 'f16x2', 5: 'f16f8'}[self._get_option(_lib.HR_OPT_MLP_PRECISION_ACTIVE)]
+        return _MLP_PRECISION_NAME[self._get_option(_lib.HR_OPT_MLP_PRECISION_ACTIVE)]
 
     def mlp_verified(self):
         """True when render() runs the verified fast path: f16f8 first, then the rays with a comparison at risk again with the f16x3 tiles
@@ -801,8 +803,8 @@ class HipLightfieldModel(nn.Module):
         n = self._render_calls = getattr(self, '_render_calls', 0) + 1
         if not (n <= 16 or n % 256 == 0) or torch.cuda.is_current_stream_capturing():
             return False
-        active = self._get_option(_lib.HR_OPT_MLP_PRECISION_ACTIVE)
-        if active not in (2, 3, 5):                                      # f16x3, f16x2, f16f8
+        active = self.mlp_precision_active()
+        if active not in ('f16x3', 'f16x2', 'f16f8'):
             return False
         import warnings
         if self.mlp_overflowed():
@@ -822,7 +824,7 @@ class HipLightfieldModel(nn.Module):
                 self._native_key = None
                 self.native()
             return True
-        if active == 5 and self.mlp_verified() and self.redo_overflowed():
+        if active == 'f16f8' and self.mlp_verified() and self.redo_overflowed():
             # verified fast path: more than a sixteenth of the batch had a comparison inside its margin -- rays unlike the calibration's (which
             # gives the fast path up above a twentieth).  The excess kept their unverified pixels: measure the band on THESE rays (the library
             # falls back to f16x3 when they list too many) and render again; a model that still overflows leaves the fast path for good
@@ -833,7 +835,7 @@ class HipLightfieldModel(nn.Module):
                 self._native_key = None
                 self.native()
             return True
-        if active == 5 and self.mlp_f8_saturated():
+        if active == 'f16f8' and self.mlp_f8_saturated():
             # f16f8: the fp8 images of a layer's output are scaled from the calibration's largest activation of that layer.  Beyond 16x that they
             # saturate (finite, less accurate).  Where the model can be calibrated on the caller's rays, do so and render again; a cascade's
             # point MLP sees internal rows (hr_model_calibrate refuses it): say so once and carry on

@@ -331,7 +331,12 @@ int hr_model_finalize(hr_model* m);
 /* The same decision on the caller's own rays (device memory, n_rays x ray_dim): measures the activation range of the MLP
  * (BaseMLP.forward, nlf/nets/mlp.py:159-172, evaluated in plain fp32) on them, re-resolves HR_MLP_AUTO and re-packs the MLP
  * weights if the choice changes.  Synchronises `stream`.  `act_max` (may be NULL) receives mlp_layers floats: the largest
- * |input feature|, then the largest |pre-activation| of each hidden Linear.  HR_E_RANGE as for hr_model_finalize. */
+ * |input feature|, then the largest |pre-activation| of each hidden Linear.  HR_E_RANGE as for hr_model_finalize.
+ * All or nothing: a return other than HR_OK leaves everything the choice rests on as it was before the call -- the active arithmetic,
+ * HR_OPT_MLP_VERIFIED, HR_OPT_MLP_CALIBRATED, the activation maxima and fp8 exponents, the packed weights, the calibration rays the
+ * model keeps, the margins of the verified fast path and hr_verify_info -- and the model renders the same pixels.  The same holds for
+ * the measurement of the margins wherever it runs, the one hr_render makes after hr_model_update_config included: an error leaves the
+ * previous margins and hr_verify_info in place, and the measurement is due again at the next render (only one that completed clears that). */
 int hr_model_calibrate(hr_model* m, const float* rays_dev, int64_t n_rays, float* act_max, void* stream);
 
 /* Replaces the model's configuration by one that differs only in schedule-dependent constants -- the `outer` / `add`

@@ -196,6 +196,11 @@ def plan_lib():
     lib.hp_wide_cap.argtypes = [ctypes.c_longlong]
     lib.hp_sample_lds_bytes.restype = ctypes.c_size_t
     lib.hp_frame_time_tap.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]
+    lib.hp_calib_sample.argtypes = [ctypes.c_longlong, ctypes.c_void_p]
+    lib.hp_band_margins.argtypes = [ctypes.c_float] * 4 + [ctypes.c_void_p]
+    lib.hp_listed_frac.restype = ctypes.c_float
+    lib.hp_listed_frac.argtypes = [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_uint]
+    lib.hp_verify_fallback.argtypes = [ctypes.c_float, ctypes.c_float]
     return lib
 
 
@@ -273,6 +278,45 @@ def frame_time_tap(hc, t):
     out = TimeTap()
     plan_lib().hp_frame_time_tap(ctypes.byref(hc), ctypes.c_float(t), ctypes.byref(out))
     return out.i0, out.i1, out.w0, out.w1
+
+
+def mlp_choice(hc, act_max, cascade_level=False, range_supported=True):
+    """hr_mlp_choice for a compiled config and the calibration's maxima (one per Linear; the rest 0):
+    (active_precision, verified, needs_calibration, status)."""
+    a, out = (ctypes.c_float * 8)(*act_max), (ctypes.c_int * 4)()
+    plan_lib().hp_mlp_choice(ctypes.byref(hc), int(bool(cascade_level)), int(bool(range_supported)), a, out)
+    return out[0], out[1], bool(out[2]), out[3]
+
+
+def mlp_limits():
+    """(HR_F16_CALIBRATION_LIMIT, HR_BAND_FLOOR, HR_VERIFY_LISTED_LIMIT, HR_VERIFY_RGB_LIMIT) as float32."""
+    out = (ctypes.c_float * 4)()
+    plan_lib().hp_mlp_limits(out)
+    return tuple(np.float32(v) for v in out)
+
+
+def calib_sample(n):
+    """hr_calib_sample: (stride, rays kept) of n calibration rays handed over by the caller."""
+    out = (ctypes.c_longlong * 2)()
+    plan_lib().hp_calib_sample(n, out)
+    return out[0], out[1]
+
+
+def band_margins(d_zc, d_dist_n, d_geo_n, d_off):
+    """hr_band_margins: (band, band_q, band_off) as float32 from the largest differences measured."""
+    out = (ctypes.c_float * 3)()
+    plan_lib().hp_band_margins(d_zc, d_dist_n, d_geo_n, d_off, out)
+    return tuple(np.float32(v) for v in out)
+
+
+def listed_frac(calibrated, n, n_used, listed):
+    """hr_listed_frac: hr_verify_info::listed_frac (calibrated: 1 = synthetic rays, 2 = the caller's)."""
+    return np.float32(plan_lib().hp_listed_frac(calibrated, n, n_used, listed))
+
+
+def verify_fallback(frac, max_d_rgb):
+    """hr_verify_fallback: 0 = the fast path stays, 1 = too many rays listed, 2 = the images are too far apart."""
+    return plan_lib().hp_verify_fallback(frac, max_d_rgb)
 
 
 def plane_geometry(hc):

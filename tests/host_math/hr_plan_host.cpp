@@ -1,5 +1,5 @@
 // TEST-ONLY host build of hyperreel_amd/csrc/hr_plan.h (plane-pair geometry, plane class, the render call's and the training step's
-// launch plans), so that the suites ask the library's own code which branch a case takes.  Nothing in the product links or loads this file.
+// launch plans, the MLP's arithmetic), so that the suites ask the library's own code which branch a case takes.  Nothing in the product links or loads this file.
 #include "../../hyperreel_amd/csrc/hr_plan.h"
 #include "../../hyperreel_amd/csrc/hr_train.h"
 
@@ -127,5 +127,27 @@ void hp_frame_plan(const hr_config* c, long long n_rays, int frame_mode, int sam
     in.cus = 256;
     *out = hr_frame_plan(*c, v.planes, v.ca_total, in);
 }
+
+// ---- MLP arithmetic
+// out = {active_precision, verified, needs_calibration, status}
+void hp_mlp_choice(const hr_config* c, int cascade_level, int range_supported, const float* act_max, int* out)
+{
+    const HrMlpChoice ch = hr_mlp_choice(*c, cascade_level != 0, range_supported != 0, act_max);
+    out[0] = ch.active_precision; out[1] = ch.verified; out[2] = ch.needs_calibration ? 1 : 0; out[3] = ch.status;
+}
+// out = {HR_F16_CALIBRATION_LIMIT, HR_BAND_FLOOR, HR_VERIFY_LISTED_LIMIT, HR_VERIFY_RGB_LIMIT}
+void hp_mlp_limits(float* out) { out[0] = HR_F16_CALIBRATION_LIMIT; out[1] = HR_BAND_FLOOR; out[2] = HR_VERIFY_LISTED_LIMIT; out[3] = HR_VERIFY_RGB_LIMIT; }
+void hp_calib_sample(long long n, long long* out)
+{
+    const HrCalibSample k = hr_calib_sample(n);
+    out[0] = k.stride; out[1] = k.keep;
+}
+void hp_band_margins(float d_zc, float d_dist_n, float d_geo_n, float d_off, float* out)
+{
+    const HrBand b = hr_band_margins(d_zc, d_dist_n, d_geo_n, d_off);
+    out[0] = b.band; out[1] = b.band_q; out[2] = b.band_off;
+}
+float hp_listed_frac(int calibrated, long long N, long long n_used, unsigned listed) { return hr_listed_frac(calibrated, N, n_used, listed); }
+int hp_verify_fallback(float listed_frac, float max_d_rgb) { return hr_verify_fallback(listed_frac, max_d_rgb); }
 
 }  // extern "C"

@@ -126,3 +126,46 @@ def test_first_render_call_checks_the_bit_and_falls_back_to_bf16x3():
     fn = make_render_fn(g.cfg, g.dataset, g.state_dict, mlp_precision='f16x3')
     with pytest.warns(UserWarning), pytest.raises(HipRangeError):
         render_np(fn, far)
+
+
+def test_a_refused_calibration_leaves_the_model_as_it_was():
+    """include/hyperreel_hip.h, hr_model_calibrate: a call that returns an error changes nothing the MLP's arithmetic rests on.  Two
+    models from the same inputs with the verified path forced ('f16f8v': a range that does not fit is HR_E_RANGE, not a fallback); A is
+    refused a calibration on rays a million scene units away.  Afterwards A reports what it reported before and renders the same bits --
+    and it still holds the 4096 synthetic rays of hr_model_finalize, not a sample of the refused ones: when the band is measured again
+    (hr_model_update_config marks it stale, the next render measures) A and B measure the same thing.  (With the in-place code before
+    this contract the first three steps held and the last did not: A measured on the 248 refused rays -- n_rays 248, band 2.06,
+    listed_frac 2.0 -- where B reported n_rays 4096 and the floor, 1e-6.)"""
+    import ctypes as C
+    from gpu_common import make_render_fn, render_np
+    from hyperreel_amd import lib as _lib
+    from hyperreel_amd.lib import HipRangeError
+    g = Golden('donerf_sphere_small')
+    far = g.rays.copy()
+    far[:, :3] *= 1e6
+    A, B = (make_render_fn(g.cfg, g.dataset, g.state_dict, mlp_precision='f16f8v').model for _ in range(2))
+
+    def state(m):
+        return m.verify_info(), m.mlp_precision_active(), m.mlp_verified(), m._get_option(_lib.HR_OPT_MLP_CALIBRATED)
+
+    def image(m):
+        out = m.render(torch.from_numpy(g.rays).cuda())['rgb']
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    before, img = state(A), image(A)
+    assert before[1:] == ('f16f8', True, 1) and before[0]['verified'] == 1 and before[0]['n_rays'] == 4096
+    with pytest.raises(HipRangeError, match='65504'):
+        A.calibrate(torch.from_numpy(far).cuda())
+    after = state(A)
+    print('verify_info before / after the refused call:', before, after)
+    assert after == before
+    assert np.array_equal(image(A), img)
+    for m in (A, B):            # its own configuration again: nothing differs, so it is accepted, and the band is measured again by the next render
+        with torch.cuda.device('cuda'):
+            _lib.check(_lib.load().hr_model_update_config(m.native(), C.byref(m._hc), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                       'hr_model_update_config')
+    img_a, img_b = image(A), image(B)
+    print('after the band was measured again: A', state(A), 'B', state(B))
+    assert state(A) == state(B) and state(A)[0]['n_rays'] == 4096
+    assert np.array_equal(img_a, img_b)
