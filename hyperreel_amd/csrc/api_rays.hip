@@ -1,12 +1,13 @@
 // C ABI, camera rays, light-field rays and the training feed: hr_generate_rays, hr_generate_rays_ndc, hr_generate_rays_fisheye (one set of checks, one
-// routine: generate_pixels), hr_generate_rays_lightfield, hr_generate_rays_epi, hr_rayset_* (kernels: rays_kernel.hip; arithmetic: hr_camera.h,
-// hr_lightfield.h, hr_sample_rng.h).
+// routine: generate_pixels), hr_generate_rays_lightfield, hr_generate_rays_epi, hr_rayset_* (kernels: rays_kernel.hip, importance_kernel.hip;
+// arithmetic: hr_camera.h, hr_lightfield.h, hr_sample_rng.h, hr_importance.h).
 // No model handle.  The set owns its device memory; hr_rayset_batch / hr_rayset_order / hr_rayset_sample enqueue one kernel and nothing else.
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
 #include "hr_camera.h"
+#include "hr_importance.h"
 #include "hr_lightfield.h"
 #include "hr_model.h"
 
@@ -21,6 +22,15 @@ struct HR_HIDDEN hr_rayset {
     DevMem<HrRayImage> images_dev;
     DevMem<int64_t> prefix_dev;
     DevMem<uint8_t> pixels;
+    // the importance rule (hr_rayset_set_image_importance): a listed image's pixel list and what it was made with
+    struct Listed {
+        DevMem<uint32_t> list;
+        int prev = -1;
+        int64_t num_take = 0;
+        float threshold = 0.0f, dir_z_below = 0.0f;
+    };
+    std::vector<Listed> listed;           // [n_images]; images[i].list points into listed[i].list
+    DevMem<uint32_t> importance_ws;       // hr_importance_workspace_words(width * height), allocated by the first such call
 };
 
 namespace {
@@ -157,6 +167,7 @@ static int rayset_alloc(hr_rayset* s, hr_rayset** out, const char* who)
 {
     const int n_images = s->n_images, width = s->width, height = s->height;
     s->images.assign((size_t)n_images, HrRayImage());
+    s->listed.resize((size_t)n_images);
     s->prefix.assign((size_t)n_images + 1, 0);
     hipError_t e = s->images_dev.alloc(sizeof(HrRayImage) * (size_t)n_images);
     if (e == hipSuccess) e = s->prefix_dev.alloc(sizeof(int64_t) * ((size_t)n_images + 1));
@@ -208,19 +219,53 @@ static int check_slot(const hr_rayset* set, int i, int every, int offset, const 
     return HR_OK;
 }
 
-// pixels and table entry of image i, then the prefix sums from i on
-static int rayset_commit(hr_rayset* set, int i, const HrRayImage& image, const uint8_t* rgb_host_or_dev)
+// A listed image's list holds the difference to its `prev` image as that one was when the list was made: replacing `prev` afterwards
+// would leave it stale
+static int check_not_a_prev(const hr_rayset* set, int i, const char* who)
 {
-    const size_t bytes = (size_t)set->height * set->width * 3;
-    HR_HIP(hipMemcpy(set->pixels + (size_t)i * bytes, rgb_host_or_dev, bytes, hipMemcpyDefault));
+    for (int j = 0; j < set->n_images; ++j)
+        if (set->images[j].list && set->listed[j].prev == i)
+            return fail(HR_E_INVALID, "%s: image %d is the previous frame of image %d, whose importance list was made from it and would be stale: "
+                        "set images in load order", who, i, j);
+    return HR_OK;
+}
+
+// table entry of image i (its pixels are in the store), then the prefix sums from i on
+static int rayset_commit_tables(hr_rayset* set, int i, const HrRayImage& image)
+{
     set->images[i] = image;
+    if (!image.list) set->listed[i] = hr_rayset::Listed();             // a list the slot held before goes
     for (int j = i; j < set->n_images; ++j) {
         const HrRayImage& im = set->images[j];
-        set->prefix[j + 1] = set->prefix[j] + (im.every > 0 ? hr_subsample_count(set->width, set->height, im.every, im.offset) : 0);
+        const int64_t kept = im.every < 1 ? 0 : im.list ? im.count : hr_subsample_count(set->width, set->height, im.every, im.offset);
+        set->prefix[j + 1] = set->prefix[j] + kept;
     }
     HR_HIP(hipMemcpy(set->images_dev + i, &set->images[i], sizeof(HrRayImage), hipMemcpyHostToDevice));
     HR_HIP(hipMemcpy(set->prefix_dev + i, &set->prefix[i], sizeof(int64_t) * (size_t)(set->n_images + 1 - i), hipMemcpyHostToDevice));
     return HR_OK;
+}
+
+static int rayset_store_pixels(hr_rayset* set, int i, const uint8_t* rgb_host_or_dev)
+{
+    const size_t bytes = (size_t)set->height * set->width * 3;
+    HR_HIP(hipMemcpy(set->pixels + (size_t)i * bytes, rgb_host_or_dev, bytes, hipMemcpyDefault));
+    return HR_OK;
+}
+
+// pixels and table entry of image i, then the prefix sums from i on
+static int rayset_commit(hr_rayset* set, int i, const HrRayImage& image, const uint8_t* rgb_host_or_dev)
+{
+    if (int rc = rayset_store_pixels(set, i, rgb_host_or_dev)) return rc;
+    return rayset_commit_tables(set, i, image);
+}
+
+// the checks hr_rayset_set_image_fisheye makes of its camera and distortion (messages name hr_rayset_set_image)
+static int check_set_camera(const hr_rayset* set, const hr_camera* cam, const hr_fisheye* fisheye)
+{
+    if (cam->width != set->width || cam->height != set->height || cam->fx == 0.0f || cam->fy == 0.0f)
+        return fail(HR_E_INVALID, "hr_rayset_set_image: bad camera (%d x %d in a set of %d x %d, fx %g, fy %g)", (int)cam->width, (int)cam->height,
+                    set->width, set->height, (double)cam->fx, (double)cam->fy);
+    return check_fisheye(fisheye, "hr_rayset_set_image_fisheye");
 }
 
 int hr_rayset_set_image(hr_rayset* set, int32_t i, const hr_camera* cam, int32_t every, int32_t offset, const uint8_t* rgb_host_or_dev)
@@ -235,15 +280,101 @@ int hr_rayset_set_image_fisheye(hr_rayset* set, int32_t i, const hr_camera* cam,
     if (!set || !cam || !rgb_host_or_dev) return fail(HR_E_INVALID, "hr_rayset_set_image: null argument");
     if (set->lightfield) return fail(HR_E_INVALID, "hr_rayset_set_image: the set holds light-field views (hr_rayset_create_lightfield): use hr_rayset_set_view");
     if (int rc = check_slot(set, i, every, offset, "hr_rayset_set_image", "image")) return rc;
-    if (cam->width != set->width || cam->height != set->height || cam->fx == 0.0f || cam->fy == 0.0f)
-        return fail(HR_E_INVALID, "hr_rayset_set_image: bad camera (%d x %d in a set of %d x %d, fx %g, fy %g)", (int)cam->width, (int)cam->height,
-                    set->width, set->height, (double)cam->fx, (double)cam->fy);
-    if (int rc = check_fisheye(fisheye, "hr_rayset_set_image_fisheye")) return rc;
+    if (int rc = check_set_camera(set, cam, fisheye)) return rc;
+    if (int rc = check_not_a_prev(set, i, "hr_rayset_set_image")) return rc;
     HrRayImage im = HrRayImage();
     im.cam = *cam;
     if (!undistorted(fisheye)) { im.fe = *fisheye; im.has_fe = 1; }
     im.every = every; im.offset = offset;
     return rayset_commit(set, i, im, rgb_host_or_dev);
+}
+
+int hr_rayset_set_image_importance(hr_rayset* set, int32_t i, const hr_camera* cam, const hr_fisheye* fisheye, int32_t prev, int64_t num_take,
+                                   float dir_z_below, const uint8_t* rgb_host_or_dev)
+{
+    const char* who = "hr_rayset_set_image_importance";
+    if (!set || !cam || !rgb_host_or_dev) return fail(HR_E_INVALID, "%s: null argument", who);
+    if (set->lightfield)
+        return fail(HR_E_INVALID, "%s: the set holds light-field views (hr_rayset_create_lightfield): the importance rule is for posed video frames", who);
+    if (int rc = check_slot(set, i, 1, 0, who, "image")) return rc;
+    const int64_t n_pixels = (int64_t)set->width * set->height;
+    if (n_pixels >= ((int64_t)1 << 31)) return fail(HR_E_INVALID, "%s: %lld pixels per image: pixel indices are 31-bit", who, (long long)n_pixels);
+    if (prev == i) return fail(HR_E_INVALID, "%s: prev == i (%d): an image is not its own previous frame", who, (int)i);
+    if (prev < 0 || prev >= set->n_images) return fail(HR_E_INVALID, "%s: prev %d outside the set's %d images", who, (int)prev, set->n_images);
+    if (set->images[prev].every < 1)
+        return fail(HR_E_INVALID, "%s: prev image %d is not set yet: set images in load order, the previous frame first", who, (int)prev);
+    if (num_take < 1)
+        return fail(HR_E_INVALID, "%s: num_take %lld < 1 (with 0 the reference's diff_sorted[-0] is the MINIMUM difference and its rule silently keeps "
+                    "nearly every pixel: refused, not reproduced)", who, (long long)num_take);
+    if (num_take > n_pixels) return fail(HR_E_INVALID, "%s: num_take %lld > the image's %lld pixels", who, (long long)num_take, (long long)n_pixels);
+    if (int rc = check_set_camera(set, cam, fisheye)) return rc;
+    if (int rc = check_not_a_prev(set, i, who)) return rc;
+
+    // built aside: the list and, once per set, the workspace
+    hr_rayset::Listed made;
+    made.prev = prev; made.num_take = num_take; made.dir_z_below = dir_z_below;
+    const uint32_t cap = (uint32_t)(num_take > 1 ? num_take - 1 : 1);
+    HR_HIP(made.list.alloc(sizeof(uint32_t) * (size_t)cap));
+    if (!set->importance_ws) HR_HIP(set->importance_ws.alloc(sizeof(uint32_t) * hr_importance_workspace_words(n_pixels)));
+    if (int rc = rayset_store_pixels(set, i, rgb_host_or_dev)) return rc;
+
+    HrRayImage im = HrRayImage();
+    im.cam = *cam;
+    if (!undistorted(fisheye)) { im.fe = *fisheye; im.has_fe = 1; }
+    im.every = 1; im.offset = 0;
+    HrImportanceArgs a = HrImportanceArgs();
+    a.image = im;
+    a.cur = set->pixels + (size_t)i * (size_t)n_pixels * 3;
+    a.prev = set->pixels + (size_t)prev * (size_t)n_pixels * 3;
+    a.width = set->width; a.height = set->height;
+    a.has_ndc = set->has_ndc ? 1 : 0;
+    a.ndc = set->ndc;
+    a.rank = (uint32_t)hr_importance_rank(n_pixels, num_take);
+    a.has_dir = isnan(dir_z_below) ? 0 : 1;
+    a.dir_z_below = dir_z_below;
+    a.list = made.list; a.list_cap = cap;
+    a.workspace = set->importance_ws;
+    HR_HIP(hr_launch_importance_select(a, nullptr));
+    uint32_t back[4] = {};               // threshold key, pad, the 64-bit kept count: one copy, which also waits for the kernels
+    HR_HIP(hipMemcpy(back, set->importance_ws + HR_IMP_WS_THRESHOLD, sizeof(back), hipMemcpyDeviceToHost));
+    made.threshold = hr_importance_key_value(back[0]);
+    im.count = (int64_t)(((uint64_t)back[3] << 32) | back[2]);
+    if (im.count > (int64_t)cap) return fail(HR_E_HIP, "%s: %lld pixels kept where %u fit", who, (long long)im.count, cap);
+    im.list = made.list;
+    set->listed[i] = std::move(made);
+    return rayset_commit_tables(set, i, im);
+}
+
+int hr_rayset_image_pixels(const hr_rayset* set, int32_t i, int64_t first, int64_t n, int32_t* out_dev, void* stream)
+{
+    if (!set) return fail(HR_E_INVALID, "hr_rayset_image_pixels: null set");
+    if (i < 0 || i >= set->n_images) return fail(HR_E_INVALID, "hr_rayset_image_pixels: image %d of %d", (int)i, set->n_images);
+    const int64_t kept = set->prefix[i + 1] - set->prefix[i];
+    if (first < 0 || n < 0 || first > kept || n > kept - first)
+        return fail(HR_E_INVALID, "hr_rayset_image_pixels: pixels [%lld, %lld + %lld) outside the image's %lld kept", (long long)first, (long long)first,
+                    (long long)n, (long long)kept);
+    if (n > 0 && !out_dev) return fail(HR_E_INVALID, "hr_rayset_image_pixels: null output");
+    if (n == 0) return HR_OK;
+    const HrRayImage& im = set->images[i];
+    hr_launch_image_pixels(im.list, set->width, set->height, im.every, im.offset, first, n, out_dev, (hipStream_t)stream);
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}
+
+int hr_rayset_image_info(const hr_rayset* set, int32_t i, struct hr_rayset_image_info* out)
+{
+    if (!set || !out) return fail(HR_E_INVALID, "hr_rayset_image_info: null argument");
+    if (i < 0 || i >= set->n_images) return fail(HR_E_INVALID, "hr_rayset_image_info: image %d of %d", (int)i, set->n_images);
+    const HrRayImage& im = set->images[i];
+    const hr_rayset::Listed& l = set->listed[i];
+    out->count = set->prefix[i + 1] - set->prefix[i];
+    out->every = im.every; out->offset = im.offset;
+    out->is_list = im.list ? 1 : 0;
+    out->prev = im.list ? l.prev : -1;
+    out->num_take = im.list ? l.num_take : 0;
+    out->threshold = im.list ? l.threshold : 0.0f;
+    out->dir_z_below = im.list ? l.dir_z_below : __builtin_nanf("");
+    return HR_OK;
 }
 
 int hr_rayset_set_view(hr_rayset* set, int32_t i, float s, float t, int32_t every, int32_t offset, const uint8_t* rgb_host_or_dev)

@@ -219,13 +219,15 @@ void hr_launch_generate_rays(const hr_camera& cam, const hr_fisheye* fe, const h
 // two-plane light-field rays.  epi: (a, b) = (v, t) of get_epi_rays, else (s, t) of the view
 void hr_launch_generate_rays_lightfield(const hr_lightfield& lf, bool epi, float a, float b, int64_t first, int64_t n, float* rays, hipStream_t stream);
 // one image of a device-resident training set: its camera -- or, in a light-field set, its position (s, t) on the camera plane -- and
-// its subsample rule (x + y + offset) % every == 0
+// its subsample rule: (x + y + offset) % every == 0, or with `list` the pixels listed there (the importance rule's, importance_kernel.hip)
 struct HrRayImage {
     hr_camera cam;
     hr_fisheye fe;               // the camera's distortion, read when has_fe (set for a pair that is not all zero)
     int32_t has_fe;
     int32_t every, offset;
     float s, t;
+    const uint32_t* list;        // NULL: the checkerboard rule.  Else the kept pixels' row-major indices y * width + x, ascending
+    int64_t count;               // entries of `list`
 };
 struct HrRaySetArgs {
     const HrRayImage* images;    // [n_images]
@@ -248,6 +250,33 @@ struct HrRaySetArgs {
 void hr_launch_rayset_batch(const HrRaySetArgs& a, hipStream_t stream);
 // rows [0, a.n) drawn with replacement (hr_sample_rng.h): first / key / indices of `a` are not read
 void hr_launch_rayset_sample(const HrRaySetArgs& a, uint64_t seed, uint64_t step, const uint64_t* step_dev, hipStream_t stream);
+
+// the importance subsample rule of one image against the image before it (importance_kernel.hip; arithmetic: hr_importance.h).  The
+// workspace is the set's: hr_importance_workspace_words(width * height) words -- four 256-bin digit histograms, the select state, the
+// kept total, one count per workgroup tile -- whose first HR_IMP_WS_COUNTS words the launcher clears on `stream` before its kernels.
+constexpr int HR_IMP_TILE = 1024;                 // consecutive pixels one workgroup compacts
+enum { HR_IMP_WS_HIST = 0, HR_IMP_WS_PREFIX = 1024, HR_IMP_WS_RANK = 1025, HR_IMP_WS_THRESHOLD = 1026,
+       HR_IMP_WS_TOTAL = 1028,                    // 64-bit, 8-byte aligned: the kept count, what the host copies back
+       HR_IMP_WS_COUNTS = 1032 };
+struct HrImportanceArgs {
+    HrRayImage image;            // the image's camera and lens (list / count are not read)
+    const uint8_t* cur;          // [h][w][3] the image's pixels ...
+    const uint8_t* prev;         // ... and the previous image's, both in the set's pixel store
+    int width, height;           // width * height < 2^31
+    int has_ndc;
+    hr_ndc ndc;
+    uint32_t rank;               // hr_importance_rank(width * height, num_take)
+    int has_dir;                 // keep only pixels whose ray has v[5] < dir_z_below
+    float dir_z_below;
+    uint32_t* list;              // out: the kept pixels, ascending
+    uint32_t list_cap;           // entries `list` holds: num_take - 1 suffice
+    uint32_t* workspace;
+};
+size_t hr_importance_workspace_words(int64_t n_pixels);
+hipError_t hr_launch_importance_select(const HrImportanceArgs& a, hipStream_t stream);
+// out[k] = row-major index of kept pixel first + k of an image, k < n: list[first + k], or with list == NULL the checkerboard rule's
+void hr_launch_image_pixels(const uint32_t* list, int width, int height, int every, int offset, int64_t first, int64_t n, int32_t* out,
+                            hipStream_t stream);
 
 // layout kernels (pack_kernels.hip)
 // dst[y][x][c_off + c] = src[c][y][x] for c < C  (dst texel stride = tex floats)

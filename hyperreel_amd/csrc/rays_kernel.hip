@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void hr_generate_rays_kernel(const Gen gen, in
     }
 }
 
-// set element -> image (binary search in the prefix sums) -> pixel (closed form) -> ray, colour, weight: output row t of a call.  Shared by
+// set element -> image (binary search in the prefix sums) -> pixel (closed form, or the image's list) -> ray, colour, weight: output row t of a call.  Shared by
 // hr_rayset_batch (the epoch's order, or the caller's indices) and hr_rayset_sample (draws with replacement): the same bits for the same element
 template <bool LF>
 __device__ __forceinline__ void rayset_write_row(const HrRaySetArgs& a, int64_t t, int64_t e)
@@ -84,7 +84,12 @@ __device__ __forceinline__ void rayset_write_row(const HrRaySetArgs& a, int64_t 
         }
         const HrRayImage& im = a.images[lo];
         int x, y;
-        hr_subsample_pixel(a.width, a.height, im.every, im.offset, e - a.prefix[lo], &x, &y);
+        if (im.list) {                                   // the importance rule's list (importance_kernel.hip)
+            const uint32_t p = im.list[e - a.prefix[lo]];
+            x = (int)(p % (uint32_t)a.width); y = (int)(p / (uint32_t)a.width);
+        } else {
+            hr_subsample_pixel(a.width, a.height, im.every, im.offset, e - a.prefix[lo], &x, &y);
+        }
         if (LF) {
             hr_lightfield_ray(a.lf, im.s, im.t, x, y, v);
         } else {

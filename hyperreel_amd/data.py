@@ -7,10 +7,13 @@ one camera and one subsample rule per image, and computes a batch's rays when th
 files: decoding images stays with the caller.  No CPU path: a missing library or a failing call raises.
 
 Immersive's fisheye cameras (datasets/immersive.py:43-48, 514-523) pass `distortions=`: each image's (k1, k2), undistorted per ray on the
-device.
+device.  Its subsample rule, importance_subsample (immersive.py:295-310), depends on the pixels: `subsample=` takes one
+Importance(...) per such image (DeviceRaySet.importance_rule) and the device selects, masks and compacts the kept pixels into a list
+(hr_rayset_set_image_importance).
 
 DeviceRaySet.from_lightfield does the same for the two-plane light-field datasets (datasets/lightfield.py,
 datasets/stanford.py): a position (s, t) on the camera plane per view instead of a camera."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -22,10 +25,44 @@ from .plan import hr_camera, hr_fisheye, hr_lightfield, hr_ndc
 # subsample rules of the reference's datasets that are not the checkerboard: named so that the refusal can say which
 UNSUPPORTED_RULES = {
     'random_subsample': 'datasets/neural_3d.py:152-166 draws np.random.permutation per image',
-    'importance_subsample': 'datasets/neural_3d.py:191-204 thresholds the difference to the previous frame',
+    'importance_subsample': 'datasets/immersive.py:295-310, datasets/neural_3d.py:191-204: it depends on the pixels, so it has no name-only form '
+                            '-- pass one Importance(num_take, prev, dir_z_below) per image, as DeviceRaySet.importance_rule builds them',
     'test_subsample': 'datasets/neural_3d.py:187-189 masks on a ray coordinate',
     'fisheye': 'a camera model, not a subsample rule: pass distortions= (datasets/immersive.py:43-48,514-523; DESIGN 3h)',
 }
+
+
+class Importance(collections.namedtuple('Importance', ['num_take', 'prev', 'dir_z_below'], defaults=(None, None))):
+    """One image's importance rule in DeviceRaySet(subsample=[...]) (importance_subsample, datasets/immersive.py:295-310): keep the pixels
+    whose mean absolute difference to image `prev` (default: the image before this one) is strictly greater than the num_take-th largest
+    of the image, and whose ray has coords[..., 5] < dir_z_below (None: no direction test, datasets/neural_3d.py:191-204)."""
+    __slots__ = ()
+
+
+def _parse_rules(subsample, n, n_pixels, lightfield=False):
+    """None | a rule name | one (every, offset) or Importance per image -> the per-image list, checked before any library call."""
+    if isinstance(subsample, str):
+        _refuse_rule(subsample)
+    if subsample is None:
+        return [(1, 0)] * n
+    rules = []
+    for i, r in enumerate(subsample):
+        if isinstance(r, Importance):
+            if lightfield:
+                raise ValueError(f'view {i}: the importance rule compares video frames of posed cameras; a light-field set takes (every, offset) pairs only')
+            take, prev = int(r.num_take), (i - 1 if r.prev is None else int(r.prev))
+            if take < 1:
+                raise ValueError(f'image {i}: Importance num_take {take} < 1 (with 0 the reference\'s diff_sorted[-0] is the minimum and its rule '
+                                 'silently keeps nearly every pixel: refused)')
+            if take > n_pixels:
+                raise ValueError(f'image {i}: Importance num_take {take} > the image\'s {n_pixels} pixels')
+            if prev == i or not 0 <= prev < n:
+                raise ValueError(f'image {i}: Importance prev {prev} must be another image of the set\'s {n}')
+            rules.append(Importance(take, prev, None if r.dir_z_below is None else float(r.dir_z_below)))
+        else:
+            every, offset = r
+            rules.append((int(every), int(offset)))
+    return rules
 
 
 def current_stream(device):
@@ -122,17 +159,18 @@ def _as_u8_image(img, i, H, W):
 class DeviceRaySet:
     """images_u8: (n, H, W, 3) uint8 (numpy, or a torch tensor on the host or the device), RGB as Image.convert("RGB") holds
     them; poses (n, 3, 4); intrinsics (n, 3, 3) or one (3, 3); times, cam_ids: (n) or None (6-column rays); img_wh = (W, H);
-    ndc: None | dict(fx, fy, near, width, height) | hr_ndc; subsample: None (every pixel) or one (every, offset) per image
-    (DeviceRaySet.video_rule builds the reference's); distortions: None (pinhole cameras) or (n, 2), each image's fisheye (k1, k2)
+    ndc: None | dict(fx, fy, near, width, height) | hr_ndc; subsample: None (every pixel) or, per image, one (every, offset)
+    (DeviceRaySet.video_rule builds the reference's) or one Importance(...) (DeviceRaySet.importance_rule), mixed freely; distortions: None (pinhole cameras) or (n, 2), each image's fisheye (k1, k2)
     (ImmersiveDataset.distortions[idx][:2]).  Element e of the set is row e of the reference's all_inputs."""
 
     def __init__(self, images_u8, poses, intrinsics, times, cam_ids, img_wh, ndc=None, subsample=None, device=None, distortions=None):
         if isinstance(subsample, str):
             _refuse_rule(subsample)
-        L = _lib.load()
         W, H = int(img_wh[0]), int(img_wh[1])
         poses = np.asarray(poses, np.float32)
         n = poses.shape[0]
+        rules = _parse_rules(subsample, n, W * H)
+        L = _lib.load()
         Ks = np.asarray(intrinsics, np.float32)
         Ks = np.broadcast_to(Ks, (n, 3, 3)) if Ks.ndim == 2 else Ks
         self.ray_dim = 8 if times is not None else 6
@@ -156,8 +194,14 @@ class DeviceRaySet:
                 _lib.check(L.hr_rayset_set_image_fisheye(self._h, i, C.byref(cam), C.byref(distortions[i]), every, offset, pixels),
                            'hr_rayset_set_image_fisheye')
 
-        self._fill(images_u8, n, W, H, subsample, device, create, set_image, (Ks, times, cam_ids),
-                   'images, poses, intrinsics, times, cam_ids and subsample must describe the same number of images')
+        def set_importance(i, rule, pixels):
+            cam = make_camera(poses[i], Ks[i], W, H, cam_ids[i], times[i])
+            _lib.check(L.hr_rayset_set_image_importance(self._h, i, C.byref(cam), C.byref(distortions[i]) if distortions is not None else None,
+                                                        rule.prev, rule.num_take, float('nan') if rule.dir_z_below is None else rule.dir_z_below,
+                                                        pixels), 'hr_rayset_set_image_importance')
+
+        self._fill(images_u8, n, W, H, rules, device, create, set_image, (Ks, times, cam_ids),
+                   'images, poses, intrinsics, times, cam_ids and subsample must describe the same number of images', set_importance)
 
     @classmethod
     def from_lightfield(cls, images_u8, st, lightfield, subsample=None, device=None):
@@ -169,9 +213,10 @@ class DeviceRaySet:
             _refuse_rule(subsample)
         if not isinstance(lightfield, hr_lightfield):
             raise TypeError('lightfield must be an hr_lightfield (data.make_lightfield)')
-        L = _lib.load()
         st = np.asarray(st, np.float64).reshape(-1, 2)
         n = st.shape[0]
+        rules = _parse_rules(subsample, n, int(lightfield.width) * int(lightfield.height), lightfield=True)
+        L = _lib.load()
         self = cls.__new__(cls)
         self.ray_dim = 6
         self._ndc = None
@@ -183,15 +228,14 @@ class DeviceRaySet:
         def set_view(i, every, offset, pixels):
             _lib.check(L.hr_rayset_set_view(self._h, i, float(st[i, 0]), float(st[i, 1]), every, offset, pixels), 'hr_rayset_set_view')
 
-        self._fill(images_u8, n, int(lightfield.width), int(lightfield.height), subsample, device, create, set_view, (),
+        self._fill(images_u8, n, int(lightfield.width), int(lightfield.height), rules, device, create, set_view, (),
                    'images, st and subsample must describe the same number of views')
         return self
 
-    def _fill(self, images_u8, n, W, H, subsample, device, create, set_one, per_image, mismatch):
-        """The constructors' shared tail: one checkerboard rule per image, every per-image sequence n long (else ValueError(mismatch)),
-        the device, the handle -- create(pointer to it) -- then set_one(i, every, offset, pixels pointer) for each image in turn, and the
-        set's size.  Both callables check their own C call."""
-        rules = [(1, 0)] * n if subsample is None else [(int(e), int(o)) for e, o in subsample]
+    def _fill(self, images_u8, n, W, H, rules, device, create, set_one, per_image, mismatch, set_importance=None):
+        """The constructors' shared tail: one rule per image (_parse_rules), every per-image sequence n long (else ValueError(mismatch)),
+        the device, the handle -- create(pointer to it) -- then for each image in turn set_one(i, every, offset, pixels pointer), or
+        set_importance(i, rule, pixels pointer) under an Importance rule, and the set's size.  The callables check their own C call."""
         if not all(len(seq) == n for seq in (images_u8, rules, *per_image)):
             raise ValueError(mismatch)
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
@@ -201,7 +245,10 @@ class DeviceRaySet:
             create(C.byref(self._h))
             for i in range(n):
                 img = _as_u8_image(images_u8[i], i, H, W)
-                set_one(i, rules[i][0], rules[i][1], C.c_void_p(img.data_ptr()))
+                if isinstance(rules[i], Importance):
+                    set_importance(i, rules[i], C.c_void_p(img.data_ptr()))
+                else:
+                    set_one(i, rules[i][0], rules[i][1], C.c_void_p(img.data_ptr()))
         self._size = int(_lib.load().hr_rayset_size(self._h))
 
     def __len__(self):
@@ -299,6 +346,45 @@ class DeviceRaySet:
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().hr_rayset_order(self._h, int(first), int(n), int(seed), int(epoch), C.c_void_p(out.data_ptr()), self._stream()),
                        'hr_rayset_order')
+        return out
+
+    def kept_pixels(self, i):
+        """The row-major pixel indices y * W + x of image i's rays in the set, in set order: (count) int32 on the device."""
+        n = self.image_info(i)['count']
+        out = torch.empty((n,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().hr_rayset_image_pixels(self._h, int(i), 0, n, C.c_void_p(out.data_ptr()), self._stream()), 'hr_rayset_image_pixels')
+        return out
+
+    def image_info(self, i):
+        """hr_rayset_image_info of image i as a dict: count, num_take, every, offset, is_list, prev, threshold, dir_z_below (None: no test)."""
+        info = _lib.hr_rayset_image_info()
+        _lib.check(_lib.load().hr_rayset_image_info(self._h, int(i), C.byref(info)), 'hr_rayset_image_info')
+        d = {k: getattr(info, k) for k, _ in info._fields_}
+        d['is_list'] = bool(d['is_list'])
+        d['dir_z_below'] = None if np.isnan(d['dir_z_below']) else d['dir_z_below']
+        return d
+
+    @staticmethod
+    def importance_rule(frames, n_pixels, load_full_step, subsample_keyframe_step, subsample_keyframe_frac, subsample_frac, first_of_video,
+                        dir_z_below=-0.05):
+        """Immersive's rule over images in its load order, video-major (prepare_train_data, datasets/immersive.py:330-389): `frames` holds
+        each image's frame number, `first_of_video` whether it is the first loaded frame of its video.  Such a frame, and one divisible by
+        load_full_step, keeps every pixel: (1, 0).  Any other compares with the image before it: Importance(round(n_pixels * frac), i - 1,
+        dir_z_below), frac = subsample_keyframe_frac for a frame divisible by subsample_keyframe_step, else subsample_frac
+        (importance_subsample, immersive.py:295-310).  dir_z_below=None: Neural 3D's variant without the direction test
+        (datasets/neural_3d.py:191-204).  Returns the list DeviceRaySet(subsample=) takes."""
+        frames = [int(f) for f in frames]
+        first = [bool(f) for f in first_of_video]
+        if len(first) != len(frames):
+            raise ValueError('frames and first_of_video must describe the same images')
+        out = []
+        for i, f in enumerate(frames):
+            if first[i] or f % load_full_step == 0:
+                out.append((1, 0))
+            else:
+                frac = subsample_keyframe_frac if f % subsample_keyframe_step == 0 else subsample_frac
+                out.append(Importance(int(np.round(n_pixels * frac)), i - 1, dir_z_below))
         return out
 
     @staticmethod

@@ -50,6 +50,12 @@ class hr_verify_info(C.Structure):
                 ('n_rays', C.c_int64), ('n_rays_used', C.c_int64), ('n_samples', C.c_int64), ('n_flipped', C.c_int64), ('n_shaky', C.c_int64)]
 
 
+class hr_rayset_image_info(C.Structure):
+    """Result of hr_rayset_image_info (include/hyperreel_hip.h)."""
+    _fields_ = [('count', C.c_int64), ('num_take', C.c_int64), ('every', C.c_int32), ('offset', C.c_int32), ('is_list', C.c_int32),
+                ('prev', C.c_int32), ('threshold', C.c_float), ('dir_z_below', C.c_float)]
+
+
 # every symbol include/hyperreel_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ('hr_abi_version', C.c_int, []),
@@ -91,6 +97,10 @@ SYMBOLS = [
     ('hr_rayset_order', C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     ('hr_rayset_sample', C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    ('hr_rayset_set_image_importance', C.c_int, [C.c_void_p, C.c_int32, C.POINTER(hr_camera), C.POINTER(hr_fisheye), C.c_int32, C.c_int64, C.c_float,
+                                                 C.c_void_p]),
+    ('hr_rayset_image_pixels', C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    ('hr_rayset_image_info', C.c_int, [C.c_void_p, C.c_int32, C.POINTER(hr_rayset_image_info)]),
     ('hr_upsample_plane', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ('hr_train_features', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ('hr_train_rows_forward', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

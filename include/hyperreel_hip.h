@@ -12,6 +12,13 @@
  * INTEGRATION.md, selected with `experiment.model.render.type: lightfield_hip`
  * through the reference's own registry (nlf/rendering.py:95-97).
  *
+ * Beside that path the header declares what surrounds it on the device: camera, fisheye and
+ * light-field rays, the training step, its loss and optimizer, image scores, and the
+ * training feed (hr_rayset_*): a device-resident training set under the datasets' subsample
+ * rules -- the checkerboard in closed form, and Immersive's data-dependent
+ * importance_subsample (datasets/immersive.py:295-310) as a per-image pixel list that
+ * hr_rayset_set_image_importance selects and compacts on the device.
+ *
  * Conventions: plain C types only; every pointer named *_dev is a device pointer
  * owned by the caller (e.g. torch tensor .data_ptr()); the library never frees
  * caller memory; `stream` is a hipStream_t passed as void*; all calls return 0 on
@@ -577,6 +584,38 @@ int hr_rayset_order(const hr_rayset* set, int64_t first, int64_t n, uint64_t see
  * (HR_ABI_VERSION stays). */
 int hr_rayset_sample(const hr_rayset* set, int64_t n, uint64_t seed, uint64_t step, const uint64_t* step_dev, float* coords_dev, float* rgb_dev,
                      float* weight_dev, int64_t* elements_dev_or_null, void* stream);
+
+/* ---- the importance subsample rule -- Immersive's, and Neural 3D's variant without the direction test
+ * (importance_subsample, datasets/immersive.py:295-310, datasets/neural_3d.py:191-204).  Image i keeps the pixels whose mean absolute
+ * difference to image `prev` (the frame before it in its video) is STRICTLY greater than the num_take-th largest such difference of the
+ * image, and, when dir_z_below is not NaN, whose ray -- the one hr_rayset_batch returns for the pixel -- has column 5 < dir_z_below
+ * (-0.05 in the reference).  The difference is torch.abs(rgb - last_rgb).mean(-1) on ToTensor's floats, bit for bit
+ * (csrc/hr_importance.h); which pixels are kept is therefore the reference's choice exactly, ties at the threshold included, and set
+ * element e stays row e of all_inputs: the kept pixels of an image follow in row-major order.  The rule depends on the pixels, so the
+ * set keeps a list per such image: a radix select of the threshold, the mask and a stable compaction run on the device
+ * (csrc/importance_kernel.hip), into at most (num_take - 1) * 4 bytes.  Images under either rule mix in one set.
+ * Stores the image like hr_rayset_set_image_fisheye (fisheye_or_null as there), runs the rule against image `prev` and commits.
+ * Synchronous.  HR_E_INVALID, naming the cause, before anything changes: a light-field set; prev == i, prev outside the set or not
+ * set yet; num_take < 1 (in the reference diff_sorted[-0] is the MINIMUM and the rule silently keeps nearly every pixel: refused, not
+ * reproduced) or num_take > width * height; a camera or distortion hr_rayset_set_image_fisheye refuses; width * height >= 2^31.
+ * Any hr_rayset_set_image* of an image that a listed image names as its `prev` is refused as well -- that list would be stale: set
+ * images in load order.  Additive: no existing struct or signature moved (HR_ABI_VERSION stays). */
+int hr_rayset_set_image_importance(hr_rayset* set, int32_t i, const hr_camera* cam, const hr_fisheye* fisheye_or_null, int32_t prev,
+                                   int64_t num_take, float dir_z_below, const uint8_t* rgb_host_or_dev);
+/* out_dev[k] (n int32, device memory) = the row-major pixel index y * width + x of kept pixel first + k of image i, under either rule
+ * (and for a light-field view).  [first, first + n) outside the image's kept pixels is HR_E_INVALID.  One kernel on `stream`. */
+int hr_rayset_image_pixels(const hr_rayset* set, int32_t i, int64_t first, int64_t n, int32_t* out_dev, void* stream);
+/* (a struct tag, not a typedef: the call below bears the same name) */
+struct hr_rayset_image_info {
+    int64_t count;            /* kept pixels: the image's rays in the set (0: not set yet, or nothing kept) */
+    int64_t num_take;         /* importance rule: its num_take, else 0 */
+    int32_t every, offset;    /* checkerboard rule (every == 0: not set yet); 1, 0 for a listed image */
+    int32_t is_list;          /* 1: the importance rule's list */
+    int32_t prev;             /* importance rule: the image the difference was taken to, else -1 */
+    float threshold;          /* importance rule: the num_take-th largest difference, else 0 */
+    float dir_z_below;        /* importance rule: the direction limit, NaN for none; else NaN */
+};
+int hr_rayset_image_info(const hr_rayset* set, int32_t i, struct hr_rayset_image_info* out);
 
 /* Grid management: F.interpolate(plane, size=(h2, w2), mode='bilinear', align_corners=True) of one
  * (1, C, H, W) float32 plane or line, as TensorVMSplit.up_sampling_VM / TensorVMKeyframeTime.up_sampling_VM apply it
