@@ -278,6 +278,24 @@ hipError_t hr_launch_importance_select(const HrImportanceArgs& a, hipStream_t st
 void hr_launch_image_pixels(const uint32_t* list, int width, int height, int every, int offset, int64_t first, int64_t n, int32_t* out,
                             hipStream_t stream);
 
+// one axis of PIL's 8-bit resize over a batch of same-sized RGB images (resize_kernel.hip; arithmetic and the kernel choice:
+// hr_resize.h).  Horizontal pass: `lines` image rows of 3-byte pixels become `out` pixels wide.  Vertical pass: `lines` is the BYTES of a
+// row, and `out` the output rows.  bounds (out, 2) and k (out, ksize) are hr_resize_coeffs' tables in device memory; staged, tile,
+// row_pitch, lds_bytes an hr_resize_axis_plan's; mad24 whether hr_resize_check found every |k| < 2^23.
+struct HrResizePass {
+    const uint8_t* src;
+    uint8_t* dst;
+    const uint8_t *src_lo, *src_hi;          // the source buffer [src_lo, src_hi): the staged kernels read nothing outside it
+    int64_t src_pitch, src_image;            // bytes between rows and between images
+    int64_t dst_pitch, dst_image;
+    const int32_t* bounds;
+    const int32_t* k;
+    int ksize, out, lines;
+    int staged, tile, row_pitch, lds_bytes, mad24;
+};
+int64_t hr_resize_pass_blocks(const HrResizePass& p, bool vertical, int n_images);      // workgroups of the launch: must stay below 2^31
+hipError_t hr_launch_resize_pass(const HrResizePass& p, bool vertical, int n_images, hipStream_t stream);
+
 // layout kernels (pack_kernels.hip)
 // dst[y][x][c_off + c] = src[c][y][x] for c < C  (dst texel stride = tex floats)
 // diagnostics export of the raw head in the user's (n, Z*P) layout; pruned columns read as 0

@@ -12,7 +12,10 @@ Importance(...) per such image (DeviceRaySet.importance_rule) and the device sel
 (hr_rayset_set_image_importance).
 
 DeviceRaySet.from_lightfield does the same for the two-plane light-field datasets (datasets/lightfield.py,
-datasets/stanford.py): a position (s, t) on the camera plane per view instead of a camera."""
+datasets/stanford.py): a position (s, t) on the camera plane per view instead of a camera.
+
+DeviceResize / reference_resize are the stage in front of the set: the resize every PIL-based dataset applies to a decoded image in
+get_rgb (datasets/llff.py:145-163), on the device and byte for byte as PIL computes it (hr_image_resize)."""
 import collections
 import ctypes as C
 
@@ -409,3 +412,120 @@ class DeviceRaySet:
                 out.append((int(np.round(1.0 / subsample_frac)), frame_offset))
                 frame_offset += 1
         return out
+
+
+# ---- the resize in front of the set (hr_image_resize) --------------------------------------------------------------------
+# filter names -> PIL's Image.Resampling numbers, which the C ABI takes
+RESIZE_FILTERS = {'lanczos': 1, 'bilinear': 2, 'bicubic': 3, 'box': 4}
+
+
+def _resize_filter(name):
+    if name not in RESIZE_FILTERS:
+        raise ValueError(f'resize filter {name!r} is not one of {sorted(RESIZE_FILTERS)} (PIL\'s NEAREST and HAMMING are not provided)')
+    return RESIZE_FILTERS[name]
+
+
+def _resize_wh(wh, what):
+    try:
+        w, h = wh
+        ok = int(w) == w and int(h) == h and int(w) >= 1 and int(h) >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f'{what} must be (width, height), two integers of at least 1; got {wh!r}')
+    return int(w), int(h)
+
+
+def _as_u8_batch(images_u8, wh=None):
+    """(n, H, W, 3) or (H, W, 3) uint8 as numpy, a host tensor or a device tensor -> a contiguous (n, H, W, 3) tensor where it lives"""
+    if not isinstance(images_u8, torch.Tensor):
+        a = np.ascontiguousarray(images_u8)
+        images_u8 = torch.from_numpy(a if a.flags.writeable else a.copy())        # (torch refuses to wrap a read-only array silently)
+    t = images_u8
+    if t.ndim == 3:
+        t = t[None]
+    if t.dtype != torch.uint8 or t.ndim != 4 or t.shape[-1] != 3 or t.shape[0] < 1:
+        raise ValueError(f'images must be uint8 (n, H, W, 3) or (H, W, 3), 8-bit RGB; got {t.dtype} {tuple(t.shape)}')
+    if wh is not None and (t.shape[2], t.shape[1]) != tuple(wh):
+        raise ValueError(f'images are {t.shape[2]} x {t.shape[1]} (W x H), the resize was made for {wh[0]} x {wh[1]}')
+    return t.contiguous()
+
+
+class DeviceResize:
+    """PIL's Image.resize of 8-bit RGB images on the device, byte for byte: src_wh = (W, H) -> dst_wh = (W2, H2) with filter 'lanczos' |
+    'bicubic' | 'bilinear' | 'box' (Image.LANCZOS, BICUBIC -- Image.resize's default -- BILINEAR, BOX), up to max_images images a launch.
+    Calling it with images_u8 takes (n, H, W, 3) or (H, W, 3) uint8 as numpy, a host tensor or a device tensor and returns a device uint8 tensor
+    (n, H2, W2, 3), which DeviceRaySet accepts as images_u8; it runs on torch's current stream, and more than max_images images go in
+    chunks.  The plan (coefficients computed on the host, the 8-bit image between the horizontal and the vertical pass) lives until
+    close().  No CPU path: a missing library or a failing call raises.
+
+    Out of scope: cv2.resize, which datasets/immersive.py:579, neural_3d.py:416 and donerf.py:242 call (another arithmetic, and two of
+    those calls pass the filter where cv2 takes dst); decoding image files; modes other than 8-bit RGB; Image.resize's box= and
+    reducing_gap=."""
+
+    def __init__(self, src_wh, dst_wh, filter='lanczos', max_images=1, device=None):
+        self.src_wh, self.dst_wh = _resize_wh(src_wh, 'src_wh'), _resize_wh(dst_wh, 'dst_wh')
+        self.filter = filter
+        number = _resize_filter(filter)
+        self.max_images = int(max_images)
+        if self.max_images < 1:
+            raise ValueError(f'max_images {max_images} < 1')
+        L = _lib.load()
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(L.hr_resize_plan_create(self.src_wh[0], self.src_wh[1], self.dst_wh[0], self.dst_wh[1], number, self.max_images,
+                                               C.byref(self._h)), 'hr_resize_plan_create')
+
+    def close(self):
+        if getattr(self, '_h', None):
+            _lib.load().hr_resize_plan_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __call__(self, images_u8, out=None):
+        """out: None (a fresh tensor) or a contiguous uint8 (n, H2, W2, 3) tensor on the plan's device (a fixed buffer for a captured graph)"""
+        if not getattr(self, '_h', None):
+            raise RuntimeError('DeviceResize is closed')
+        src = _as_u8_batch(images_u8, self.src_wh).to(self.device)
+        n, (W2, H2) = src.shape[0], self.dst_wh
+        if out is None:
+            out = torch.empty((n, H2, W2, 3), dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous() or tuple(out.shape) != (n, H2, W2, 3):
+            raise ValueError(f'out must be a contiguous uint8 ({n}, {H2}, {W2}, 3) tensor on {self.device}')
+        per_src, per_dst = src.shape[1] * src.shape[2] * 3, H2 * W2 * 3
+        with torch.cuda.device(self.device):
+            for first in range(0, n, self.max_images):
+                _lib.check(_lib.load().hr_image_resize(self._h, C.c_void_p(src.data_ptr() + first * per_src), min(self.max_images, n - first),
+                                                       C.c_void_p(out.data_ptr() + first * per_dst), current_stream(self.device)), 'hr_image_resize')
+        return out
+
+
+def reference_resize(images_u8, _img_wh, img_wh=None, first='lanczos', device=None):
+    """get_rgb's two steps (datasets/llff.py:145-163): img.resize(_img_wh, Image.LANCZOS), then img.resize(img_wh, Image.BOX) when
+    img_wh differs from _img_wh.  A step at equal size is no operation (Image.resize returns a copy).  first='bicubic' is
+    datasets/catacaustics.py:298, whose img.resize(wh) takes PIL's default.  images_u8 as for DeviceResize; returns a device uint8
+    tensor (n, H, W, 3) of the last size.  Out of scope: see DeviceResize."""
+    wh1 = _resize_wh(_img_wh, '_img_wh')
+    wh2 = wh1 if img_wh is None else _resize_wh(img_wh, 'img_wh')
+    _resize_filter(first)
+    x = _as_u8_batch(images_u8)
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    for wh, name in ((wh1, first), (wh2, 'box')):
+        if (x.shape[2], x.shape[1]) != wh:
+            step = DeviceResize((x.shape[2], x.shape[1]), wh, name, max_images=min(x.shape[0], 8), device=device)
+            try:
+                x = step(x)
+            finally:
+                torch.cuda.current_stream(device).synchronize()      # the plan's memory goes with it
+                step.close()
+    return x.to(device)
+
+
+def as_float(images_u8_dev):
+    """(n, H, W, 3) uint8 -> (n * H * W, 3) float32, x / 255: ToTensor followed by view(3, -1).permute(1, 0), the ground truth get_rgb
+    hands model.evaluate.  A plain torch op: no kernel of the library is involved."""
+    if images_u8_dev.dtype != torch.uint8 or images_u8_dev.shape[-1] != 3:
+        raise ValueError(f'as_float takes uint8 (..., 3) images, got {images_u8_dev.dtype} {tuple(images_u8_dev.shape)}')
+    return images_u8_dev.reshape(-1, 3).float().div(255)

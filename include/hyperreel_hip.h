@@ -617,6 +617,25 @@ struct hr_rayset_image_info {
 };
 int hr_rayset_image_info(const hr_rayset* set, int32_t i, struct hr_rayset_image_info* out);
 
+/* The resize in front of the training feed: what every PIL-based dataset of the reference does to a decoded image in get_rgb
+ * (datasets/llff.py:145-163: img.resize(_img_wh, Image.LANCZOS), then img.resize(img_wh, Image.BOX) when they differ), on the device and
+ * byte for byte as PIL computes it for an 8-bit RGB image (csrc/hr_resize.h states the arithmetic; PIL's output is the authority).
+ * Images are (h, w, 3) bytes, rows dense.  filter: PIL's Image.Resampling number -- 1 LANCZOS, 2 BILINEAR, 3 BICUBIC, 4 BOX.
+ * A plan serves one (w, h) -> (w2, h2) and filter, for up to max_images images a call: it owns both axes' coefficient tables, computed
+ * on the host and checked there (every row: 255 * sum|k| + 2^21 < 2^31, so that the int32 sums cannot overflow), and the 8-bit image
+ * between the horizontal and the vertical pass, in the memory of the device that is current at creation.  Create, resize and destroy
+ * on that device.  HR_E_INVALID, naming the argument: a size below 1 or beyond 2^20, an unknown filter, max_images < 1, a NULL `out`,
+ * a coefficient row that fails the accumulator check. */
+typedef struct hr_resize_plan hr_resize_plan;
+int hr_resize_plan_create(int32_t w, int32_t h, int32_t w2, int32_t h2, int32_t filter, int32_t max_images, hr_resize_plan** out);
+/* src_dev: n_images images (h, w, 3) -> dst_dev: n_images images (h2, w2, 3), both dense in device memory and not overlapping; exactly
+ * n_images * h2 * w2 * 3 bytes are written.  Only kernels (same size on both axes: one device-to-device copy) on `stream`: no
+ * host-to-device copy, no allocation, no synchronisation; capturable in a hipGraph.  Calls on one plan share its intermediate image:
+ * order them on one stream.  HR_E_INVALID: a NULL plan, src_dev or dst_dev; n_images outside 1..max_images.
+ * Additive: no existing struct or signature moved (HR_ABI_VERSION stays). */
+int hr_image_resize(const hr_resize_plan* p, const uint8_t* src_dev, int32_t n_images, uint8_t* dst_dev, void* stream);
+void hr_resize_plan_destroy(hr_resize_plan* p);
+
 /* Grid management: F.interpolate(plane, size=(h2, w2), mode='bilinear', align_corners=True) of one
  * (1, C, H, W) float32 plane or line, as TensorVMSplit.up_sampling_VM / TensorVMKeyframeTime.up_sampling_VM apply it
  * when the reference grows its grids (nlf/nets/tensorf_base.py:1152-1176, tensorf_dynamic.py:395-427).  Both buffers
