@@ -261,6 +261,10 @@ static void fill_train_args(const hr_model* m, HrTrainArgs& a, const float* rays
     a.n_basis_cols = m->n_basis_cols;
     a.ca_total = m->ca_total;
     a.white_bg = white_bg ? 1 : 0;
+    if (m->bg_source == 1) {          // hr_train_set_background: a white_bg configuration is white at every step, any other one flips the coin
+        a.white_bg = m->cfg.white_bg ? 1 : 0;
+        if (!m->cfg.white_bg) { a.bg_step = m->bg_step_dev; a.bg_seed = m->bg_seed; }
+    }
     a.color_table = nullptr;
     if (m->cfg.color_table_views > 0) {
         auto it = m->raw.find("color_embedding");
@@ -270,6 +274,19 @@ static void fill_train_args(const hr_model* m, HrTrainArgs& a, const float* rays
 
 static int train_forward(hr_model* m, const hr_train_tensors* params, const float* rays_dev, const float* head_dev, int64_t n_rays,
                          int32_t white_bg, float* rgb_dev, const hr_fields* fields, void* stream);
+
+int32_t hr_train_background_coin(uint64_t seed, uint64_t step) { return hr_background_coin(seed, step); }
+
+int hr_train_set_background(hr_model* m, int32_t source, uint64_t seed, const int64_t* step_dev)
+{
+    if (!m) return fail(HR_E_INVALID, "hr_train_set_background: null model");
+    if (source != 0 && source != 1) return fail(HR_E_INVALID, "hr_train_set_background: source %d (0: the white_bg argument, 1: the coin of the device step count)", (int)source);
+    if (source == 1 && !step_dev) return fail(HR_E_INVALID, "hr_train_set_background: source 1 needs the device step count (step_dev)");
+    m->bg_source = source;
+    m->bg_seed = source == 1 ? seed : 0;
+    m->bg_step_dev = source == 1 ? step_dev : nullptr;
+    return HR_OK;
+}
 
 int hr_train_forward(hr_model* m, const hr_train_tensors* params, const float* rays_dev, const float* head_dev, int64_t n_rays,
                      int32_t white_bg, float* rgb_dev, void* stream)

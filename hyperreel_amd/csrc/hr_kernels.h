@@ -306,6 +306,22 @@ void hr_launch_upsample_plane(const float* src, int C, int H, int W, float* dst,
 void hr_launch_pack_display(const float* rgb, int h, int w, int transpose, int flip, int rgba8, void* out, hipStream_t stream);
 void hr_launch_plane_reg_forward(const float* p, int C, int H, int W, float* sums, hipStream_t stream);
 void hr_launch_plane_reg_backward(const float* p, int C, int H, int W, const float* coef, float* grad, hipStream_t stream);
+// the whole TensoRF regulariser in one launch (reg_kernel.hip, hr_tensorf_reg): a workgroup owns HR_REG_BLOCK consecutive elements of one
+// tensor; first_block[] is the prefix sum of the tensors' workgroup counts, as in HrAdamBatch
+constexpr int HR_REG_BLOCK = 4096;
+struct HrRegBatch {
+    const float* p[HR_REG_MAX_TENSORS];
+    float* g[HR_REG_MAX_TENSORS];
+    int64_t n[HR_REG_MAX_TENSORS];             // C * H * W
+    int H[HR_REG_MAX_TENSORS], W[HR_REG_MAX_TENSORS];
+    float kh[HR_REG_MAX_TENSORS], kw[HR_REG_MAX_TENSORS], kl[HR_REG_MAX_TENSORS];
+    int sh[HR_REG_MAX_TENSORS], sw[HR_REG_MAX_TENSORS], sl[HR_REG_MAX_TENSORS];      // weight slots, -1: absent
+    int vec4[HR_REG_MAX_TENSORS];              // W % 4 == 0 and both buffers 16-byte aligned
+    int first_block[HR_REG_MAX_TENSORS + 1];
+    int count;
+};
+// partials: 3 floats per workgroup (first_block[count] workgroups), every one written by the first launch and read by the second
+void hr_launch_tensorf_reg(const HrRegBatch& b, const float* weights, float* partials, float* loss, int add_grad, hipStream_t stream);
 // optimizer step of the training loop (utils/__init__.py:49-76 get_optimizer -> torch.optim.Adam(betas=(0.9, 0.99), eps=1e-8)): every parameter
 // tensor of a step in ONE launch.  A block owns 4096 consecutive elements of one tensor; first_block[] is the prefix sum of the tensors' block counts
 constexpr int HR_ADAM_MAX_TENSORS = 40;

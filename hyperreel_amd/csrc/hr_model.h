@@ -151,6 +151,10 @@ struct HR_HIDDEN hr_model {
     size_t grad_fx_elems = 0;
     DevMem<HrFxUnit> fx_unit;            // ... and THIS model's fixed-point unit of the step (hr_train.h)
     int opt_train_det = 0;
+    // hr_train_set_background: 0 the white_bg argument of the training calls decides; 1 the coin of (bg_seed, *bg_step_dev) does
+    int bg_source = 0;
+    uint64_t bg_seed = 0;
+    const int64_t* bg_step_dev = nullptr;
     DevMem<float> tape;                  // per-sample values between the backward's phases: HR_TAPE_WORDS x tape_samples (hr_tape_bind)
     int64_t tape_samples = 0;
     // occupancy early-reject (hr_model_set_occupancy)

@@ -64,4 +64,15 @@ HR_RNG_FN uint64_t hr_sample_element(uint64_t size, uint64_t seed, uint64_t step
     return hr_mulhi64(hr_sample_draw(seed, step, row), size);
 }
 
+// The background coin of training step `step` (the reference composites a training step over white with probability 1/2,
+// tensorf_no_sample.py:236: `white_bg or (training and rand() < 0.5)`): one Philox word of (seed, step), white iff its top bit is set.
+// The sampler's rows of the same (seed, step) use counters (row, step) with row < 2^63; the coin's counter carries a constant no row
+// reaches in that place, so the coin is independent of every ray the step draws.
+#define HR_BG_COIN_DOMAIN 0xB6C01DC01DB6C01Dull
+
+HR_RNG_FN int hr_background_coin(uint64_t seed, uint64_t step)
+{
+    return (int)(hr_philox4x32_10(seed, HR_BG_COIN_DOMAIN, step).w[0] >> 31);
+}
+
 #endif  // HR_SAMPLE_RNG_H

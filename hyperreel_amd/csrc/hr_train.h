@@ -28,6 +28,7 @@
 
 #include "hr_grid.h"
 #include "hr_math.h"
+#include "hr_sample_rng.h"
 
 // Gradient accumulators (texel gradients, basis_mat's, the colour table's, the per-ray decode-matrix gradient in LDS) are `hr_acc_t`.
 // Default build: float, hardware fp32 atomics -- fast, and the sum depends on the order the memory system retires them in (two runs of
@@ -176,7 +177,17 @@ struct HrTrainArgs {
     float* f_points;            // (n, Z, 3)
     float* f_weights;           // (n, Z) render weights
     HrFxUnit* fx;               // deterministic build: this model's fixed-point unit for the step (NULL in the default build)
+    // hr_train_set_background(source 1): the background is the coin of (bg_seed, *bg_step), read when the kernel runs -- a replayed
+    // graph composites every step over its own background.  NULL: white_bg above decides
+    const int64_t* bg_step;
+    uint64_t bg_seed;
 };
+
+// this step's background, the same in every lane of every wavefront of the step's forward and backward
+HR_FN bool hr_train_white(const HrTrainArgs& a)
+{
+    return a.bg_step ? hr_background_coin(a.bg_seed, (uint64_t)*a.bg_step) != 0 : a.white_bg != 0;
+}
 
 // d/dx of hr_apply_act
 HR_FN float hr_act_grad(const hr_act& a, float x)
@@ -1010,7 +1021,8 @@ HR_FN void hr_ray_train(const hr_config& c, const HrTrainArgs& a, int64_t ray)
         c0 += wgt[k] * rr[0]; c1 += wgt[k] * rr[1]; c2 += wgt[k] * rr[2];
         acc_w += wgt[k];
     }
-    if (a.white_bg) { const float bg = 1.0f - acc_w; c0 += bg; c1 += bg; c2 += bg; }
+    const bool white = hr_train_white(a);
+    if (white) { const float bg = 1.0f - acc_w; c0 += bg; c1 += bg; c2 += bg; }
     const float cpre[3] = {c0, c1, c2};          // the composited colour before the per-ray transform
     float col[3];
     HrRayColor rc;
@@ -1023,7 +1035,7 @@ HR_FN void hr_ray_train(const hr_config& c, const HrTrainArgs& a, int64_t ray)
     float* dhead = a.d_head + ray * (int64_t)Z * P;
     for (int i = 0; i < Z * P; ++i) dhead[i] = 0.0f;
     hr_ray_color_bwd(c, a, head, rc, cpre, true, dhead, g);
-    const float gsum = a.white_bg ? (g[0] + g[1] + g[2]) : 0.0f;
+    const float gsum = white ? (g[0] + g[1] + g[2]) : 0.0f;
     float ddc[ZP];                // dL / d final distance
     float dfeat[ZP];
     for (int k = 0; k < Z; ++k) ddc[k] = 0.0f;

@@ -17,6 +17,7 @@
 #include "hr_mask.h"
 #define HR_GATHER_FENCED 1        // (the lane-per-sample forward: 90 registers instead of 102, sample_core.inc)
 #include "sample_core.inc"      // the render kernels' lane-per-sample building blocks (sort, cooperative gather)
+#include "hr_sample_rng.h"      // (before the deterministic build's namespace opens: hr_train.h reads the background coin)
 // The deterministic build of the sample-stage training kernels (train_det_kernel.hip: HR_TRAIN_DET, hr_acc_t = 64-bit fixed point, see
 // hr_train.h) compiles this file a second time: everything that depends on hr_acc_t lives in its own namespace there, the exports that
 // do not (rows, features, occupancy) are compiled once, in the default build.
@@ -178,7 +179,8 @@ __global__ __launch_bounds__(256) void hr_train_lanes_kernel(const hr_config* __
         c2 += __shfl_xor(c2, d, 64);
         acc_w += __shfl_xor(acc_w, d, 64);
     }
-    if (a.white_bg) { const float bg = 1.0f - acc_w; c0 += bg; c1 += bg; c2 += bg; }
+    const bool white = hr_train_white(a);
+    if (white) { const float bg = 1.0f - acc_w; c0 += bg; c1 += bg; c2 += bg; }
     const float cpre[3] = {c0, c1, c2};            // the composited colour before the per-ray transform
     float col[3];
     HrRayColor rc;
@@ -195,7 +197,7 @@ __global__ __launch_bounds__(256) void hr_train_lanes_kernel(const hr_config* __
         for (int i = 0; i < P; ++i) dhk[i] = 0.0f;
     // sample 0's row is lane 0's own; the colour table's adds come from lane 0 of every ray of the batch
     hr_ray_color_bwd(c, a, head, rc, cpre, k == 0 && (rc.form == HR_RAY_COLOR_TABLE ? ray_ok : lane_ok), dhk, g);
-    const float gsum = a.white_bg ? (g[0] + g[1] + g[2]) : 0.0f;
+    const float gsum = white ? (g[0] + g[1] + g[2]) : 0.0f;
     float dpre[3] = {0.f, 0.f, 0.f};
     if (lane_ok) hr_sample_color_bwd(c, wgt, g, raw, sc, pre, app, hk, dhk, dpre);
     const float dw = lane_ok ? ((g[0] * rr[0] + g[1] * rr[1] + g[2] * rr[2]) - gsum) : 0.0f;

@@ -38,6 +38,15 @@ class hr_loss_out(C.Structure):
     _fields_ = [('loss_sum', C.c_double), ('sse', C.c_double), ('loss', C.c_float), ('pad', C.c_float)]
 
 
+class hr_reg_tensor(C.Structure):
+    """One plane or line of hr_tensorf_reg's descriptor table (include/hyperreel_hip.h)."""
+    _fields_ = [('plane_dev', C.c_void_p), ('grad_dev', C.c_void_p), ('channels', C.c_int32), ('h', C.c_int32), ('w', C.c_int32),
+                ('kh', C.c_float), ('kw', C.c_float), ('kl', C.c_float), ('slot_h', C.c_int32), ('slot_w', C.c_int32), ('slot_l', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
+HR_REG_MAX_TENSORS, HR_REG_SLOTS = 12, 3
+HR_E_INVALID = -1
 HR_LOSS_MSE, HR_LOSS_WEIGHTED_MSE, HR_LOSS_MAE, HR_LOSS_WEIGHTED_MAE, HR_LOSS_HUBER = 0, 1, 2, 3, 4
 HR_LOSS_PREMULTIPLIED = 0x100
 
@@ -124,6 +133,12 @@ SYMBOLS = [
                                 C.c_void_p]),
     ('hr_plane_reg_forward', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     ('hr_plane_reg_backward', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('hr_train_background_coin', C.c_int32, [C.c_uint64, C.c_uint64]),
+    ('hr_train_set_background', C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p]),
+    ('hr_reg_plan_create', C.c_int, [C.POINTER(hr_reg_tensor), C.c_int32, C.POINTER(C.c_void_p)]),
+    ('hr_reg_plan_update', C.c_int, [C.c_void_p, C.POINTER(hr_reg_tensor), C.c_int32]),
+    ('hr_tensorf_reg', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ('hr_reg_plan_destroy', None, [C.c_void_p]),
     ('hr_adam_step', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ('hr_adam_step_dev', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_int32, C.c_void_p]),

@@ -598,6 +598,30 @@ class HipLightfieldModel(nn.Module):
         if self.sample_waves is not None:
             _lib.check(L.hr_model_set_option(self._native, _lib.HR_OPT_SAMPLE_WAVES, int(self.sample_waves)), 'hr_model_set_option')
         _lib.check(L.hr_model_set_option(self._native, _lib.HR_OPT_TRAIN_DETERMINISTIC, int(self.train_deterministic)), 'hr_model_set_option')
+        bg = getattr(self, '_bg_coin', None)
+        if bg is not None and not self._black_bg():
+            _lib.check(L.hr_train_set_background(self._native, 1, bg[0], C.c_void_p(bg[1].data_ptr())), 'hr_train_set_background')
+        else:
+            _lib.check(L.hr_train_set_background(self._native, 0, 0, None), 'hr_train_set_background')
+
+    def _black_bg(self):
+        return bool(self.cfg['color']['net'].get('black_bg', False))
+
+    def set_background_coin(self, seed=0, step_tensor=None):
+        """Binds the training step's background to the device (hr_train_set_background): with `step_tensor` -- one int64 on the HIP device,
+        HipAdam(capturable=True).step_tensor -- forward_train and its backward ignore their white_bg argument and composite step s =
+        step_tensor's value over white iff hyperreel_amd.train.background_coin(seed, s), read when the kernels run: the reference's
+        per-step draw (tensorf_no_sample.py:236) in a form a replayed graph follows.  As there, a white_bg configuration is white at
+        every step and a black_bg one black.  step_tensor=None unbinds: the white_bg argument decides again.  The binding survives a
+        re-created native model."""
+        if step_tensor is None:
+            self._bg_coin = None
+        else:
+            if step_tensor.dtype != torch.int64 or step_tensor.numel() != 1 or step_tensor.device.type != 'cuda':
+                raise TypeError('set_background_coin: step_tensor must be one int64 on the HIP device (HipAdam(capturable=True).step_tensor)')
+            self._bg_coin = (int(seed) & 0xFFFFFFFFFFFFFFFF, step_tensor)
+        if self._native is not None:
+            self._apply_options()
 
     @staticmethod
     def _frame_mode(v):
@@ -955,7 +979,9 @@ class HipLightfieldModel(nn.Module):
         h, hc = self._native, self._hc
         rays = self._check_rays(rays)
         net_cfg = self.cfg['color']['net']
-        if white_bg is None:
+        if getattr(self, '_bg_coin', None) is not None:         # set_background_coin: the device decides (a black_bg configuration stays black)
+            white_bg = False
+        elif white_bg is None:
             white_bg = (bool(net_cfg.get('white_bg', False)) or bool(torch.rand(()) < 0.5)) and not bool(net_cfg.get('black_bg', False))
         types = [e['type'] for e in self.cfg['embedding']['embeddings'].values()]
         pred = self.embedding_model.embeddings[types.index('ray_prediction')]

@@ -375,6 +375,193 @@ def l1_mean(plane):
     return PlaneReg.apply(plane)[2] / plane.numel()
 
 
+def background_coin(seed, step):
+    """True when training step `step` of `seed` composites over white under Model.set_background_coin / GraphedStep(white_bg='coin'): the
+    library's own hr_background_coin (csrc/hr_sample_rng.h), evaluated on the host."""
+    m = 0xFFFFFFFFFFFFFFFF
+    return bool(_lib.load().hr_train_background_coin(int(seed) & m, int(step) & m))
+
+
+class HipTensoRFRegularizer:
+    """The reference's TensoRF regulariser (nlf/regularizers/tensorf.py:35-96 on BaseRegularizer, nlf/regularizers/base.py:146-168) as ONE
+    device call per step (hr_tensorf_reg): value and gradient of density_L1, TV_loss_density and TV_loss_app over every plane and line
+    `net._reg_planes()` names, the gradient added into the parameters' .grad.
+
+        reg = HipTensoRFRegularizer(model, cfg, steps_per_epoch)
+        reg.set_iter(i); reg.sync()         # host: this iteration's three weights; device: written when they changed
+        loss.backward(); value = reg.accumulate()
+
+    cfg: the reference's regulariser group (conf/experiment/regularizers/tensorf/*.yaml: update_AlphaMask_list, lr_decay_target_ratio,
+    n_iters, total_num_tv_iters, L1_weight_initial, L1_weight_rest, TV_weight_density, TV_weight_app; optional wait_iters, stop_iters,
+    warmup_iters, and `weight`: a float or {type: exponential_decay, start, decay, num_epochs}).  steps_per_epoch: the reference's
+    len(train_dataset) // cur_batch_size.
+
+    What changes with the iteration lives in three floats on the device -- what the step multiplies L1, density TV and appearance TV by,
+    loss_weight() included -- so a recorded step that calls accumulate() follows set_iter() / sync() on every replay.  As the reference:
+    TV is weighted by the CONSTANT cfg.TV_weight_* (the decayed copies only gate `> 0`, which they stay); with both TV weights positive
+    the density TV term counts TWICE (`loss_tv = loss_tv + ...; total_loss += loss_tv`, tensorf.py:79-87); the L1 weight switches when
+    set_iter sees cur_iter == update_AlphaMask_list[0], and stays.  TV_weight_density <= 0 < TV_weight_app, where the reference raises
+    NameError (loss_tv is unbound), is refused here."""
+
+    SLOT_L1, SLOT_TV_DENSITY, SLOT_TV_APP = 0, 1, 2
+
+    def __init__(self, model, cfg, steps_per_epoch):
+        import numpy as np
+        get = lambda k, d: cfg[k] if k in cfg else d
+        self.model, self.cfg, self.steps_per_epoch = model, cfg, int(steps_per_epoch)
+        self.weight = get('weight', 0.0)
+        self.wait_iters, self.warmup_iters, self.stop_iters = get('wait_iters', 0), get('warmup_iters', 0), get('stop_iters', float('inf'))
+        self.update_AlphaMask_list = list(cfg['update_AlphaMask_list'])
+        self.total_num_tv_iters = cfg['total_num_tv_iters'] if 'total_num_tv_iters' in cfg else \
+            int(np.round((np.log(1e-4) / np.log(cfg['lr_decay_target_ratio'])) * cfg['n_iters']))
+        self.L1_reg_weight = cfg['L1_weight_initial']
+        self.TV_weight_density, self.TV_weight_app = cfg['TV_weight_density'], cfg['TV_weight_app']
+        if self.TV_weight_app > 0 and not self.TV_weight_density > 0:
+            raise ValueError('HipTensoRFRegularizer: TV_weight_density <= 0 with TV_weight_app > 0 -- the reference raises NameError on this '
+                             'combination (tensorf.py:86 reads loss_tv, which only the density branch binds); set TV_weight_density > 0 or TV_weight_app to 0')
+        if not isinstance(self.weight, float) and not (hasattr(self.weight, 'keys') and self.weight['type'] == 'exponential_decay'):
+            raise ValueError(f'HipTensoRFRegularizer: weight must be a float or an exponential_decay group, not {self.weight!r}')
+        self.cur_iter = 0 - self.wait_iters
+        self.weights = self._weights()
+        self._dev = self._synced = self._plan = self._plan_key = self._grad_key = None
+
+    # -- host: the reference's schedule, expression for expression
+    def loss_weight(self):
+        """base.py:154-165."""
+        import numpy as np
+        if isinstance(self.weight, float):
+            return self.weight
+        weight_num_iters = self.weight['num_epochs'] * self.steps_per_epoch
+        exponent = self.cur_iter / weight_num_iters
+        return self.weight['start'] * np.power(self.weight['decay'], exponent)
+
+    def warming_up(self):
+        return self.cur_iter < self.warmup_iters
+
+    def _weights(self):
+        """(L1, density TV, appearance TV): what multiplies the three unweighted terms in `loss(...) * loss_weight()` (base.py:146-152,
+        tensorf.py:57-89), as Python floats (doubles)."""
+        if self.cur_iter < 0 or self.cur_iter >= self.stop_iters:
+            return (0.0, 0.0, 0.0)
+        lw = float(self.loss_weight())
+        l1 = self.L1_reg_weight if self.L1_reg_weight > 0 else 0.0
+        tvd = tva = 0.0
+        if not self.cur_iter > self.total_num_tv_iters:
+            if self.TV_weight_density > 0:
+                tvd = self.TV_weight_density
+            if self.TV_weight_app > 0:
+                tva = self.TV_weight_app
+                tvd = tvd + tvd                    # loss_tv carries the density term into the second `total_loss + loss_tv`
+        return (l1 * lw, tvd * lw, tva * lw)
+
+    def set_iter(self, i):
+        self.cur_iter = i - self.wait_iters
+        if len(self.update_AlphaMask_list) > 0 and self.cur_iter == self.update_AlphaMask_list[0]:
+            self.L1_reg_weight = self.cfg['L1_weight_rest']
+        self.weights = self._weights()
+
+    def terms(self):
+        """The descriptor table without pointers: [(parameter, kh, kw, kl, slot_h, slot_w, slot_l)] over net._reg_planes(), with the skip
+        rules of density_L1 / TV_loss_density / TV_loss_app (models.py) and the reference's static factors formed in double."""
+        net = self.model.color_model.net
+        da, db, aa = net._reg_planes()
+        out = []
+        for i in range(3):
+            has_l1 = da[i].shape[1] != 0
+            tv_d = not (da[i].shape[1] == 0 or (net.video and db[i].shape[1] == 0))
+            tv_a = not ((aa[i].shape[1] == 0) if not net.video else (da[i].shape[1] == 0 or db[i].shape[1] == 0))
+            for p, l1, tv in ((da[i], has_l1, self.SLOT_TV_DENSITY if tv_d else -1), (db[i], has_l1, -1), (aa[i], False, self.SLOT_TV_APP if tv_a else -1)):
+                if not l1 and tv < 0:
+                    continue
+                b, c, h, w = p.shape
+                if b != 1:
+                    raise ValueError(f'HipTensoRFRegularizer: a plane of batch size {b}')
+                if tv >= 0 and c > 0 and (h < 2 or w < 2):
+                    raise ValueError(f'HipTensoRFRegularizer: total variation of a {h} x {w} plane (the reference divides by a zero count)')
+                kh = 1e-2 * 2 / (c * (h - 1) * w) if tv >= 0 and c > 0 else 0.0
+                kw = 1e-2 * 2 / (c * h * (w - 1)) if tv >= 0 and c > 0 else 0.0
+                kl = 1.0 / (c * h * w) if l1 and c > 0 else 0.0
+                out.append((p, kh, kw, kl, tv, tv, self.SLOT_L1 if l1 else -1))
+        return out
+
+    # -- device
+    def sync(self):
+        """Writes the three weights to the device floats accumulate() reads, ordered on the current stream, when they changed since the
+        last call.  Not inside a capture (a recorded copy would replay one value).  The device holds float32."""
+        w = tuple(float(v) for v in self.weights)
+        if self._dev is not None and w == self._synced:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('HipTensoRFRegularizer.sync inside a graph capture: call it before each replay instead')
+        if self._dev is None:
+            dev = next(self.model.parameters()).device
+            if dev.type != 'cuda':
+                raise RuntimeError('HipTensoRFRegularizer runs on the HIP device; there is no CPU path')
+            self._dev = torch.zeros(_lib.HR_REG_SLOTS, dtype=torch.float32, device=dev)
+            self._loss = torch.zeros(1 + _lib.HR_REG_SLOTS, dtype=torch.float32, device=dev)
+        self._dev.copy_(torch.tensor(w, dtype=torch.float32))
+        self._synced = w
+
+    def _table(self, terms):
+        arr = (_lib.hr_reg_tensor * max(len(terms), 1))()
+        for e, (p, kh, kw, kl, sh, sw, sl) in zip(arr, terms):
+            e.plane_dev, e.grad_dev = p.data_ptr() or None, p.grad.data_ptr() or None
+            e.channels, e.h, e.w = p.shape[1], p.shape[2], p.shape[3]
+            e.kh, e.kw, e.kl, e.slot_h, e.slot_w, e.slot_l = kh, kw, kl, sh, sw, sl
+        return arr
+
+    def accumulate(self):
+        """The one hr_tensorf_reg call, on the current stream: adds the regulariser's gradient into every listed parameter's .grad (a
+        zero gradient first where it is None; nothing is added while warming_up(), as the reference leaves the term out of `loss`) and
+        returns the weighted value `loss(...) * loss_weight()` as a detached device scalar -- the same tensor every call.  `terms_value`
+        holds the three unweighted terms of the last call.  The descriptor table is rebuilt when the model's parameters were replaced
+        (shrink, upsample_volume_grid, load_state_dict)."""
+        L = _lib.load()
+        if self._dev is None:
+            self.sync()
+        terms = self.terms()
+        for p, *_ in terms:
+            if not p.is_contiguous() or p.dtype != torch.float32:
+                raise RuntimeError('HipTensoRFRegularizer: planes must be contiguous float32')
+            if p.grad is None:
+                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            elif not p.grad.is_contiguous():
+                p.grad = p.grad.contiguous()
+        key = tuple((id(p), p.data_ptr(), tuple(p.shape)) for p, *_ in terms)
+        gkey = tuple(p.grad.data_ptr() for p, *_ in terms)
+        dev = self._dev.device
+        with torch.cuda.device(dev):
+            if self._plan is None or key != self._plan_key:
+                self.close()
+                h = C.c_void_p()
+                _lib.check(L.hr_reg_plan_create(self._table(terms), len(terms), C.byref(h)), 'hr_reg_plan_create')
+                self._plan, self._plan_key, self._grad_key = h, key, gkey
+            elif gkey != self._grad_key:
+                _lib.check(L.hr_reg_plan_update(self._plan, self._table(terms), len(terms)), 'hr_reg_plan_update')
+                self._grad_key = gkey
+            _lib.check(L.hr_tensorf_reg(self._plan, _ptr(self._dev), _ptr(self._loss), 0 if self.warming_up() else 1, _stream(dev)), 'hr_tensorf_reg')
+        return self._loss[0]
+
+    @property
+    def terms_value(self):
+        """(density_L1, TV_loss_density, TV_loss_app) of the last accumulate(), unweighted: a view of the device result."""
+        return self._loss[1:]
+
+    def close(self):
+        if self._plan is not None:
+            _lib.load().hr_reg_plan_destroy(self._plan)
+            self._plan = self._plan_key = self._grad_key = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+KEEP = object()         # GraphedStep.recapture: leave the setting as it is
+
+
 class GraphedStep:
     """The whole training step as ONE replayed graph (torch.cuda.graph over the library's launches):
 
@@ -387,13 +574,20 @@ class GraphedStep:
     optimizer's step count, which is also the sampler's step, and the learning rates (`optimizer.sync_hyperparameters()`, called by
     step() before the replay).
 
+    regularizer: a callable of the model whose result is added to the loss before backward() -- recorded with the Python floats it
+    used -- or a HipTensoRFRegularizer: its accumulate() runs after backward() and its value is added to the returned `loss`; step()
+    calls its set_iter(iteration) and sync() before the replay, so every replay trains with the reference's weights of its own iteration.
+    The iteration is the optimizer's count, read from the device when the step is (re)recorded and counted on the host from there.
+
     Construction runs `warmup` (>= 1) iterations eagerly on a side stream -- GENUINE training steps: they update the parameters and
     advance the count, and they are what sizes the library's lazily grown workspaces and allocates the moments -- and then records one
     iteration on a single stream (no parallel branches), which is not executed.  After construction `warmup` steps have been taken.
 
-    optimizer: HipAdam(capturable=True) holding every trainable parameter of the model.  white_bg: the background of every step; None
-    takes the configuration's `white_bg and not black_bg` -- a recorded step cannot redraw the reference's per-step coin
-    (tensorf_no_sample.py:236), so a model that trains with the coin needs one GraphedStep per background, or the eager loop.
+    optimizer: HipAdam(capturable=True) holding every trainable parameter of the model.  white_bg: True / False -- the background of
+    every step; None -- the configuration's `white_bg and not black_bg`; 'coin' -- the reference's per-step draw
+    (tensorf_no_sample.py:236), taken on the device from the optimizer's step count: step s is white iff background_coin(bg_seed, s)
+    (or always / never for a white_bg / black_bg configuration).  'coin' binds the model (Model.set_background_coin) until close() or
+    a recapture(white_bg=...) with another setting.
     step() returns the SAME two tensors every time (the graph's outputs: `loss` is the differentiated total, `sse` the squared-error
     sum of train/psnr); clone what must outlive the next replay.
 
@@ -401,7 +595,7 @@ class GraphedStep:
     growth, upsample_volume_grid, load_state_dict, a new optimizer state -- makes the recording stale: step() raises and names
     recapture().  Cascade models (point_prediction) are refused."""
 
-    def __init__(self, model, optimizer, rayset, batch_size, loss, seed=0, white_bg=None, regularizer=None, warmup=3):
+    def __init__(self, model, optimizer, rayset, batch_size, loss, seed=0, white_bg=None, regularizer=None, warmup=3, bg_seed=0):
         from .optim import HipAdam
         if not isinstance(optimizer, HipAdam) or not optimizer.capturable:
             raise TypeError('GraphedStep needs a HipAdam(capturable=True) optimizer: the step count and the learning rates of any other one live on '
@@ -414,8 +608,8 @@ class GraphedStep:
             raise NotImplementedError('GraphedStep: point_prediction cascades re-create their native model when a schedule moves; use the eager loop')
         self.model, self.optimizer, self.rayset, self.loss = model, optimizer, rayset, loss
         self.batch_size, self.seed, self.regularizer = int(batch_size), int(seed), regularizer
-        net_cfg = model.cfg['color']['net']
-        self.white_bg = (bool(net_cfg.get('white_bg', False)) and not bool(net_cfg.get('black_bg', False))) if white_bg is None else bool(white_bg)
+        self.bg_seed = int(bg_seed)
+        self.white_bg = self._background(white_bg)
         dev = rayset.device
         self.batch = {'coords': torch.empty((self.batch_size, rayset.ray_dim), dtype=torch.float32, device=dev),
                       'rgb': torch.empty((self.batch_size, 3), dtype=torch.float32, device=dev),
@@ -423,16 +617,43 @@ class GraphedStep:
         self.graph = None
         self.recapture(warmup=warmup)
 
+    def _background(self, white_bg):
+        if isinstance(white_bg, str):
+            if white_bg != 'coin':
+                raise ValueError(f"GraphedStep: white_bg must be True, False, None or 'coin', not {white_bg!r}")
+            return 'coin'
+        net_cfg = self.model.cfg['color']['net']
+        return (bool(net_cfg.get('white_bg', False)) and not bool(net_cfg.get('black_bg', False))) if white_bg is None else bool(white_bg)
+
+    def close(self):
+        """Drops the recording and, for white_bg='coin', unbinds the model's background from the step count."""
+        self.graph = self._out = None
+        if self.white_bg == 'coin':
+            self.model.set_background_coin(step_tensor=None)
+
     def _iteration(self):
         b = self.rayset.sample(self.batch_size, step_tensor=self.optimizer.step_tensor, seed=self.seed, out=self.batch)
-        rgb = self.model.forward_train(b['coords'], white_bg=self.white_bg)
+        rgb = self.model.forward_train(b['coords'], white_bg=False if self.white_bg == 'coin' else self.white_bg)
         loss, sse = self.loss.step_loss(rgb, b['rgb'], b['weight'])
-        if self.regularizer is not None:
+        device_reg = isinstance(self.regularizer, HipTensoRFRegularizer)
+        if self.regularizer is not None and not device_reg:
             loss = loss + self.regularizer(self.model)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
+        total = loss.detach()
+        if device_reg:                                       # value and gradient in one call, behind autograd's gradients
+            value = self.regularizer.accumulate()
+            if not self.regularizer.warming_up():            # (the reference logs a warming-up term and leaves it out of `loss`)
+                total = total + value
         self.optimizer.step()
-        return loss.detach(), sse
+        return total, sse
+
+    def _before_step(self):
+        """What the host owes the device before iteration `self._host_step` runs: the learning rates and the regulariser's weights."""
+        self.optimizer.sync_hyperparameters()
+        if isinstance(self.regularizer, HipTensoRFRegularizer):
+            self.regularizer.set_iter(self._host_step)
+            self.regularizer.sync()
 
     def _fingerprint(self):
         """What the recording holds pointers to: the parameters, their moments, and the compiled configuration."""
@@ -442,10 +663,10 @@ class GraphedStep:
                    for g in self.optimizer.param_groups for p in g['params'])
         return ps, ms, self.model._native_cfg
 
-    def recapture(self, optimizer=None, warmup=1):
+    def recapture(self, optimizer=None, warmup=1, white_bg=KEEP, bg_seed=None):
         """Runs `warmup` eager iterations (genuine steps; >= 1 whenever parameters were replaced: the native model and the moments are
         rebuilt by an eager step) and records the iteration again.  optimizer: the new HipAdam(capturable=True) when the parameters were
-        replaced (its count starts where its state says: 0 for a fresh one)."""
+        replaced (its count starts where its state says: 0 for a fresh one).  white_bg / bg_seed: another background setting."""
         from .optim import HipAdam
         if optimizer is not None:
             if not isinstance(optimizer, HipAdam) or not optimizer.capturable:
@@ -458,16 +679,26 @@ class GraphedStep:
                              'replaced, build a new HipAdam(capturable=True) over model.parameters() and pass it to recapture(optimizer=...)')
         self.graph = None
         self._out = None
+        if white_bg is not KEEP:
+            self.white_bg = self._background(white_bg)
+        if bg_seed is not None:
+            self.bg_seed = int(bg_seed)
+        # (binds to the optimizer this recording steps; any other setting leaves the white_bg argument in charge)
+        self.model.set_background_coin(self.bg_seed, self.optimizer.step_tensor if self.white_bg == 'coin' else None)
         dev = self.rayset.device
-        self.optimizer.sync_hyperparameters()
+        self._host_step = self.optimizer.steps_done()        # the host's mirror of the device count: the regulariser's iteration
         with torch.cuda.device(dev):
             side = torch.cuda.Stream(dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
                 for _ in range(int(warmup)):
+                    self._before_step()
                     self._iteration()
+                    self._host_step += 1
             torch.cuda.current_stream(dev).wait_stream(side)
             self.optimizer.zero_grad(set_to_none=True)
+            self._before_step()
+            self._reg_warming_up = self.regularizer.warming_up() if isinstance(self.regularizer, HipTensoRFRegularizer) else None
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):                   # one stream: the recording has no parallel branches
                 loss, sse = self._iteration()
@@ -487,6 +718,10 @@ class GraphedStep:
         if self.graph is None or self._fingerprint() != self._key:
             raise RuntimeError('GraphedStep: parameters, optimizer state or the native model were replaced since the step was recorded (grid '
                                'growth, upsample_volume_grid, load_state_dict ...); call gs.recapture() -- with a new optimizer over the new parameters')
-        self.optimizer.sync_hyperparameters()
+        self._before_step()
+        if self._reg_warming_up is not None and self.regularizer.warming_up() != self._reg_warming_up:
+            raise RuntimeError(f'GraphedStep: the regulariser left its warm-up at iteration {self._host_step}: the recorded step adds no '
+                               'regulariser gradient; call gs.recapture()')
         self.graph.replay()
+        self._host_step += 1
         return self._out

@@ -806,6 +806,21 @@ size_t hr_image_loss_workspace(int64_t n_rays);
 int hr_image_loss(const float* pred_dev, const float* gt_dev, const float* weight_dev, int64_t n_rays, int32_t type, float delta,
                   const float* upstream_dev, hr_loss_out* out_dev, float* d_pred_dev, void* workspace_dev, void* stream);
 
+/* The reference's per-step background coin (`white_bg or (training and rand() < 0.5)`, tensorf_no_sample.py:236) where a replayed
+ * graph can flip it: on the device.  hr_train_background_coin (host): 1 when training step `step` of `seed` composites over white --
+ * one Philox4x32-10 word of (seed, step), its top bit, drawn with a counter no sampled row of that step uses (csrc/hr_sample_rng.h:
+ * hr_background_coin, the same function the kernels call).  It does not reproduce torch's stream: the contract is "a fair coin, fixed by
+ * (seed, step), independent of the step's rays".
+ * hr_train_set_background: source 0 (the default) -- the white_bg argument of hr_train_forward* / hr_train_backward decides, as before;
+ * source 1 -- those calls ignore their white_bg argument: a model whose configuration has white_bg set is white at every step, any other
+ * one takes hr_train_background_coin(seed, *step_dev), with *step_dev (int64, device memory, e.g. hr_adam_step_dev's count) read when
+ * the kernels run.  The forward and the backward of one step see the same count when it advances after the backward, as
+ * hr_adam_step_dev does.  (hr_config.white_bg is already `white_bg and not black_bg`; a black_bg configuration is not bound to the
+ * coin by the Python layer.)  step_dev must stay valid while source is 1.  Additive: no existing struct or signature moved
+ * (HR_ABI_VERSION stays). */
+int32_t hr_train_background_coin(uint64_t seed, uint64_t step);
+int hr_train_set_background(hr_model* m, int32_t source, uint64_t seed, const int64_t* step_dev);
+
 /* TensoRF regularisers of one (1, C, H, W) float32 plane (TVLoss, nlf/regularizers/tensorf.py:14-34; density_L1,
  * nlf/nets/tensorf_base.py:1024-1035), no model involved.  Forward ADDS to sums_dev[3] =
  *   { sum (x[:, 1:, :] - x[:, :-1, :])^2,  sum (x[:, :, 1:] - x[:, :, :-1])^2,  sum |x| };
@@ -813,6 +828,44 @@ int hr_image_loss(const float* pred_dev, const float* gt_dev, const float* weigh
  * three upstream coefficients read from device memory (no host synchronisation inside a training step). */
 int hr_plane_reg_forward(const float* plane_dev, int32_t channels, int32_t h, int32_t w, float* sums_dev, void* stream);
 int hr_plane_reg_backward(const float* plane_dev, int32_t channels, int32_t h, int32_t w, const float* coef_dev, float* grad_dev, void* stream);
+
+/* The reference's whole TensoRF regulariser (nlf/regularizers/tensorf.py:57-89: density_L1, TV_loss_density, TV_loss_app) over up to
+ * HR_REG_MAX_TENSORS planes and lines in ONE pass: the value, and the gradient ADDED into the parameters' gradient buffers.  The gradient of
+ * these terms is linear in the step's weights and independent of the sums, so each plane is read once and its gradient read-modify-written
+ * once.  Per tensor t with sums Sh = sum (x[:, 1:, :] - x[:, :-1, :])^2, Sw = sum (x[:, :, 1:] - x[:, :, :-1])^2, Sl = sum |x|:
+ *   value_t = w[slot_h] * kh * Sh + w[slot_w] * kw * Sw + w[slot_l] * kl * Sl
+ *   grad   += w[slot_h] * kh * dSh/dx + w[slot_w] * kw * dSw/dx + w[slot_l] * kl * sign(x)
+ * with w = weights_dev (HR_REG_SLOTS floats in DEVICE memory, read when the kernel runs: a replayed graph sees what the host last wrote)
+ * and kh, kw, kl the static factors the reference's expressions put in front of the sums (TVLoss: 1e-2 * 2 / (C (H - 1) W) and
+ * 1e-2 * 2 / (C H (W - 1)); density_L1: 1 / (C H W)), formed in double by the caller.  A slot of -1 leaves its term out. */
+#define HR_REG_MAX_TENSORS 12
+#define HR_REG_SLOTS 3          /* by convention of the Python layer: 0 L1, 1 density TV, 2 appearance TV */
+typedef struct hr_reg_tensor {
+    const float* plane_dev;     /* (1, channels, h, w) float32, contiguous */
+    float* grad_dev;            /* same shape: added to */
+    int32_t channels, h, w;
+    float kh, kw, kl;
+    int32_t slot_h, slot_w, slot_l;    /* 0 .. HR_REG_SLOTS - 1, or -1: the term is absent */
+    int32_t reserved;
+} hr_reg_tensor;
+typedef struct hr_reg_plan hr_reg_plan;
+/* Checks the table and allocates the per-workgroup partial sums the call reduces through.  HR_E_INVALID, naming the tensor, before
+ * anything is allocated or launched: more than HR_REG_MAX_TENSORS tensors, channels < 0, h < 1 or w < 1, a NULL plane or gradient of
+ * a tensor that has elements, a slot outside -1 .. HR_REG_SLOTS - 1, a tensor with a TV term (slot_h or slot_w >= 0) and h < 2 or
+ * w < 2 (the reference divides by a zero count there).  Tensors with channels == 0 are skipped, as the reference skips its
+ * n_comp == 0 planes.  The plan holds the pointers: build a new one when a tensor or its gradient buffer is replaced. */
+int hr_reg_plan_create(const hr_reg_tensor* tensors, int32_t n_tensors, hr_reg_plan** out);
+/* The same table with other pointers (autograd hands out a new gradient buffer after zero_grad(set_to_none=True)): checked as above, and
+ * every tensor must keep its shape.  Host work only -- no allocation; launches already enqueued or recorded keep the pointers they had. */
+int hr_reg_plan_update(hr_reg_plan* plan, const hr_reg_tensor* tensors, int32_t n_tensors);
+/* One launch over every tensor (a workgroup owns 4096 consecutive elements of one tensor; 16-byte loads and stores where w % 4 == 0
+ * and both buffers are 16-byte aligned), then a one-workgroup finishing launch that adds the partial sums in a fixed order:
+ *   loss_dev[0] = sum over slots of w[s] * loss_dev[1 + s];   loss_dev[1 + s] = sum over the terms of slot s of k * S   (unweighted)
+ * No float atomics, no memset, no allocation, no synchronisation: calls on the same inputs give the same bits, and the call is capturable
+ * in a hipGraph.  add_grad == 0 computes the value only (the reference's warm-up: the term is logged, not trained on).
+ * Additive: no existing struct or signature moved (HR_ABI_VERSION stays). */
+int hr_tensorf_reg(const hr_reg_plan* plan, const float* weights_dev, float* loss_dev, int32_t add_grad, void* stream);
+void hr_reg_plan_destroy(hr_reg_plan* plan);
 
 /* The optimizer of the training loop (utils/__init__.py:49-76: torch.optim.Adam(params, lr, eps=1e-8, weight_decay, betas=(0.9, 0.99)); stepped by
  * Lightning after INRSystem.training_step, nlf/__init__.py:634-709): one Adam step over any number of parameter tensors in ONE pass over memory
