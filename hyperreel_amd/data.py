@@ -68,9 +68,7 @@ def _parse_rules(subsample, n, n_pixels, lightfield=False):
     return rules
 
 
-def current_stream(device):
-    """The stream argument of the C ABI's calls: torch's current stream on `device`."""
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+current_stream = _lib.stream            # (the name callers outside the package know it by)
 
 
 def _refuse_rule(rule):
@@ -173,7 +171,6 @@ class DeviceRaySet:
         poses = np.asarray(poses, np.float32)
         n = poses.shape[0]
         rules = _parse_rules(subsample, n, W * H)
-        L = _lib.load()
         Ks = np.asarray(intrinsics, np.float32)
         Ks = np.broadcast_to(Ks, (n, 3, 3)) if Ks.ndim == 2 else Ks
         self.ray_dim = 8 if times is not None else 6
@@ -187,21 +184,19 @@ class DeviceRaySet:
         self._ndc = make_ndc(ndc)
 
         def create(handle):
-            _lib.check(L.hr_rayset_create(n, W, H, self.ray_dim, C.byref(self._ndc) if self._ndc is not None else None, handle), 'hr_rayset_create')
+            _lib.call('hr_rayset_create', n, W, H, self.ray_dim, C.byref(self._ndc) if self._ndc is not None else None, handle)
 
         def set_image(i, every, offset, pixels):
             cam = make_camera(poses[i], Ks[i], W, H, cam_ids[i], times[i])
             if distortions is None:
-                _lib.check(L.hr_rayset_set_image(self._h, i, C.byref(cam), every, offset, pixels), 'hr_rayset_set_image')
+                _lib.call('hr_rayset_set_image', self._h, i, C.byref(cam), every, offset, pixels)
             else:
-                _lib.check(L.hr_rayset_set_image_fisheye(self._h, i, C.byref(cam), C.byref(distortions[i]), every, offset, pixels),
-                           'hr_rayset_set_image_fisheye')
+                _lib.call('hr_rayset_set_image_fisheye', self._h, i, C.byref(cam), C.byref(distortions[i]), every, offset, pixels)
 
         def set_importance(i, rule, pixels):
             cam = make_camera(poses[i], Ks[i], W, H, cam_ids[i], times[i])
-            _lib.check(L.hr_rayset_set_image_importance(self._h, i, C.byref(cam), C.byref(distortions[i]) if distortions is not None else None,
-                                                        rule.prev, rule.num_take, float('nan') if rule.dir_z_below is None else rule.dir_z_below,
-                                                        pixels), 'hr_rayset_set_image_importance')
+            _lib.call('hr_rayset_set_image_importance', self._h, i, C.byref(cam), C.byref(distortions[i]) if distortions is not None else None,
+                      rule.prev, rule.num_take, float('nan') if rule.dir_z_below is None else rule.dir_z_below, pixels)
 
         self._fill(images_u8, n, W, H, rules, device, create, set_image, (Ks, times, cam_ids),
                    'images, poses, intrinsics, times, cam_ids and subsample must describe the same number of images', set_importance)
@@ -219,17 +214,16 @@ class DeviceRaySet:
         st = np.asarray(st, np.float64).reshape(-1, 2)
         n = st.shape[0]
         rules = _parse_rules(subsample, n, int(lightfield.width) * int(lightfield.height), lightfield=True)
-        L = _lib.load()
         self = cls.__new__(cls)
         self.ray_dim = 6
         self._ndc = None
         self._lightfield = lightfield
 
         def create(handle):
-            _lib.check(L.hr_rayset_create_lightfield(n, C.byref(lightfield), handle), 'hr_rayset_create_lightfield')
+            _lib.call('hr_rayset_create_lightfield', n, C.byref(lightfield), handle)
 
         def set_view(i, every, offset, pixels):
-            _lib.check(L.hr_rayset_set_view(self._h, i, float(st[i, 0]), float(st[i, 1]), every, offset, pixels), 'hr_rayset_set_view')
+            _lib.call('hr_rayset_set_view', self._h, i, float(st[i, 0]), float(st[i, 1]), every, offset, pixels)
 
         self._fill(images_u8, n, int(lightfield.width), int(lightfield.height), rules, device, create, set_view, (),
                    'images, st and subsample must describe the same number of views')
@@ -237,8 +231,8 @@ class DeviceRaySet:
 
     def _fill(self, images_u8, n, W, H, rules, device, create, set_one, per_image, mismatch, set_importance=None):
         """The constructors' shared tail: one rule per image (_parse_rules), every per-image sequence n long (else ValueError(mismatch)),
-        the device, the handle -- create(pointer to it) -- then for each image in turn set_one(i, every, offset, pixels pointer), or
-        set_importance(i, rule, pixels pointer) under an Importance rule, and the set's size.  The callables check their own C call."""
+        the device, the handle -- create(pointer to it) -- then for each image in turn set_one(i, every, offset, pixels), or
+        set_importance(i, rule, pixels) under an Importance rule, and the set's size.  The callables check their own C call."""
         if not all(len(seq) == n for seq in (images_u8, rules, *per_image)):
             raise ValueError(mismatch)
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
@@ -249,23 +243,20 @@ class DeviceRaySet:
             for i in range(n):
                 img = _as_u8_image(images_u8[i], i, H, W)
                 if isinstance(rules[i], Importance):
-                    set_importance(i, rules[i], C.c_void_p(img.data_ptr()))
+                    set_importance(i, rules[i], img)
                 else:
-                    set_one(i, rules[i][0], rules[i][1], C.c_void_p(img.data_ptr()))
-        self._size = int(_lib.load().hr_rayset_size(self._h))
+                    set_one(i, rules[i][0], rules[i][1], img)
+        self._size = int(_lib.call('hr_rayset_size', self._h))
 
     def __len__(self):
         return self._size
 
     def close(self):
         if getattr(self, '_h', None):
-            _lib.load().hr_rayset_destroy(self._h)
+            _lib.call('hr_rayset_destroy', self._h)
             self._h = None
 
     __del__ = close
-
-    def _stream(self):
-        return current_stream(self.device)
 
     def batch(self, batch_idx, batch_size, epoch=0, seed=0, indices=None, out=None):
         """Rows [batch_idx * batch_size, + batch_size) of the epoch's order (the last batch of an epoch is short), or the set
@@ -281,11 +272,8 @@ class DeviceRaySet:
             if n <= 0:
                 raise IndexError(f'batch {batch_idx} of {batch_size} starts beyond the set\'s {self._size} rays')
         out = self._outputs(n, out)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().hr_rayset_batch(self._h, first, n, int(seed), int(epoch),
-                                                   C.c_void_p(indices.data_ptr()) if indices is not None else None,
-                                                   C.c_void_p(out['coords'].data_ptr()), C.c_void_p(out['rgb'].data_ptr()),
-                                                   C.c_void_p(out['weight'].data_ptr()), self._stream()), 'hr_rayset_batch')
+        _lib.call('hr_rayset_batch', self._h, first, n, int(seed), int(epoch), indices, out['coords'], out['rgb'], out['weight'],
+                  _lib.stream(self.device), device=self.device)
         return out
 
     def _outputs(self, n, out):
@@ -335,34 +323,27 @@ class DeviceRaySet:
             elif elements.dtype != torch.int64 or elements.device != self.device or not elements.is_contiguous() or tuple(elements.shape) != (n,):
                 raise ValueError(f"out['elements'] must be a contiguous int64 ({n},) tensor on the set's device")
             out = dict(out, elements=elements)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().hr_rayset_sample(self._h, n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF,
-                                                    C.c_void_p(step_tensor.data_ptr()) if step_tensor is not None else None,
-                                                    C.c_void_p(out['coords'].data_ptr()), C.c_void_p(out['rgb'].data_ptr()),
-                                                    C.c_void_p(out['weight'].data_ptr()),
-                                                    C.c_void_p(elements.data_ptr()) if elements is not None else None, self._stream()), 'hr_rayset_sample')
+        _lib.call('hr_rayset_sample', self._h, n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, step_tensor,
+                  out['coords'], out['rgb'], out['weight'], elements, _lib.stream(self.device), device=self.device)
         return out
 
     def order(self, first, n, epoch=0, seed=0):
         """The set elements of rows [first, first + n) of the epoch's order: (n) int64 on the device."""
         out = torch.empty((int(n),), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().hr_rayset_order(self._h, int(first), int(n), int(seed), int(epoch), C.c_void_p(out.data_ptr()), self._stream()),
-                       'hr_rayset_order')
+        _lib.call('hr_rayset_order', self._h, int(first), int(n), int(seed), int(epoch), out, _lib.stream(self.device), device=self.device)
         return out
 
     def kept_pixels(self, i):
         """The row-major pixel indices y * W + x of image i's rays in the set, in set order: (count) int32 on the device."""
         n = self.image_info(i)['count']
         out = torch.empty((n,), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().hr_rayset_image_pixels(self._h, int(i), 0, n, C.c_void_p(out.data_ptr()), self._stream()), 'hr_rayset_image_pixels')
+        _lib.call('hr_rayset_image_pixels', self._h, int(i), 0, n, out, _lib.stream(self.device), device=self.device)
         return out
 
     def image_info(self, i):
         """hr_rayset_image_info of image i as a dict: count, num_take, every, offset, is_list, prev, threshold, dir_z_below (None: no test)."""
         info = _lib.hr_rayset_image_info()
-        _lib.check(_lib.load().hr_rayset_image_info(self._h, int(i), C.byref(info)), 'hr_rayset_image_info')
+        _lib.call('hr_rayset_image_info', self._h, int(i), C.byref(info))
         d = {k: getattr(info, k) for k, _ in info._fields_}
         d['is_list'] = bool(d['is_list'])
         d['dir_z_below'] = None if np.isnan(d['dir_z_below']) else d['dir_z_below']
@@ -470,16 +451,14 @@ class DeviceResize:
         self.max_images = int(max_images)
         if self.max_images < 1:
             raise ValueError(f'max_images {max_images} < 1')
-        L = _lib.load()
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(L.hr_resize_plan_create(self.src_wh[0], self.src_wh[1], self.dst_wh[0], self.dst_wh[1], number, self.max_images,
-                                               C.byref(self._h)), 'hr_resize_plan_create')
+        _lib.call('hr_resize_plan_create', self.src_wh[0], self.src_wh[1], self.dst_wh[0], self.dst_wh[1], number, self.max_images,
+                  C.byref(self._h), device=self.device)
 
     def close(self):
         if getattr(self, '_h', None):
-            _lib.load().hr_resize_plan_destroy(self._h)
+            _lib.call('hr_resize_plan_destroy', self._h)
             self._h = None
 
     __del__ = close
@@ -497,8 +476,8 @@ class DeviceResize:
         per_src, per_dst = src.shape[1] * src.shape[2] * 3, H2 * W2 * 3
         with torch.cuda.device(self.device):
             for first in range(0, n, self.max_images):
-                _lib.check(_lib.load().hr_image_resize(self._h, C.c_void_p(src.data_ptr() + first * per_src), min(self.max_images, n - first),
-                                                       C.c_void_p(out.data_ptr() + first * per_dst), current_stream(self.device)), 'hr_image_resize')
+                _lib.call('hr_image_resize', self._h, C.c_void_p(src.data_ptr() + first * per_src), min(self.max_images, n - first),
+                          C.c_void_p(out.data_ptr() + first * per_dst), _lib.stream(self.device))
         return out
 
 

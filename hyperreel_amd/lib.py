@@ -202,3 +202,32 @@ def check(rc, what):
         msg = load().hr_last_error()
         cls = HipRangeError if rc == HR_E_RANGE else RuntimeError
         raise cls(f'{what} failed (code {rc}): {msg.decode() if msg else "?"}')
+
+
+# symbols whose C int is the answer, not a status (c_int32 IS c_int here, so restype alone cannot tell hr_train_background_coin's 1 from an error)
+VALUE_RETURNS = frozenset(('hr_abi_version', 'hr_sizeof_config', 'hr_train_background_coin'))
+
+
+def stream(device):
+    """The stream argument of the C ABI's calls: torch's current stream on `device`."""
+    import torch
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def call(name, *args, device=None):
+    """The one way the package calls the library: symbol `name` of load() with `args`, under torch.cuda.device(device) when one is given.
+    An argument with a data_ptr (a tensor) travels as that pointer -- NULL for None and for an empty tensor; it is neither copied, cast
+    nor checked for strides (row-strided views and outputs pass through here), so callers hand in what the ABI documents.  A status
+    return is checked as check() does and nothing is returned; a symbol that returns a value returns it."""
+    fn = getattr(_lib or load(), name)
+    args = [(a.data_ptr() if a.numel() else None) if hasattr(a, 'data_ptr') else a for a in args]
+    if device is None:
+        rc = fn(*args)
+    else:
+        import torch
+        with torch.cuda.device(device):
+            rc = fn(*args)
+    if fn.restype is not C.c_int or name in VALUE_RETURNS:
+        return rc
+    if rc != 0:
+        check(rc, name)

@@ -25,7 +25,7 @@ OUT_DOUBLES = C.sizeof(_lib.hr_loss_out) // 8           # hr_loss_out as a float
 
 def workspace_doubles(n_rays):
     """Length of the float64 workspace tensor a call on n_rays rays needs."""
-    return max(int(_lib.load().hr_image_loss_workspace(int(n_rays))) // 8, 1)
+    return max(int(_lib.call('hr_image_loss_workspace', int(n_rays))) // 8, 1)
 
 
 def _check(name, t, numel, device=None):
@@ -65,11 +65,7 @@ class ImageLoss(torch.autograd.Function):
         elif workspace.dtype != torch.float64 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
             raise ValueError(f'workspace must be a contiguous float64 tensor of at least {need} elements on the prediction\'s device')
         d_pred = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().hr_image_loss(
-                C.c_void_p(pred.data_ptr()), C.c_void_p(gt.data_ptr()), C.c_void_p(weight.data_ptr() if weight is not None else 0), n, int(kind),
-                float(delta), C.c_void_p(0), C.c_void_p(out.data_ptr()), C.c_void_p(d_pred.data_ptr() if d_pred is not None else 0),
-                C.c_void_p(workspace.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_image_loss')
+        _lib.call('hr_image_loss', pred, gt, weight, n, int(kind), float(delta), None, out, d_pred, workspace, _lib.stream(dev), device=dev)
         ctx.d_pred = d_pred
         loss, sse = out.view(torch.float32)[4], out[1]
         ctx.mark_non_differentiable(sse)

@@ -9,7 +9,6 @@ data_range=1.0) after `.cpu().numpy()`) and its per-step psnr_gpu (metrics.py:37
 
 There is no CPU path: tensors that are not on the HIP device raise.
 """
-import ctypes as C
 import math
 
 import torch
@@ -21,7 +20,7 @@ SSIM_RADIUS = 5          # the 11-tap Gaussian window; scores are means over the
 
 def workspace_doubles(h, w):
     """Length of the float64 workspace tensor a call on an h x w frame needs."""
-    return max(int(_lib.load().hr_image_metrics_workspace(int(h), int(w))) // 8, 1)
+    return max(int(_lib.call('hr_image_metrics_workspace', int(h), int(w))) // 8, 1)
 
 
 def _check_image(name, t, h, w, device=None):
@@ -44,7 +43,6 @@ def image_scores(pred, gt, h, w, ssim=True, out=None, workspace=None):
         raise ValueError(f'bad image shape {h} x {w}')
     pred = _check_image('pred', pred, h, w)
     gt = _check_image('gt', gt, h, w, pred.device)
-    L = _lib.load()
     dev = pred.device
     if out is None:
         out = torch.empty((4,), dtype=torch.float64, device=dev)
@@ -55,9 +53,7 @@ def image_scores(pred, gt, h, w, ssim=True, out=None, workspace=None):
         workspace = torch.empty((need,), dtype=torch.float64, device=dev)
     elif workspace.dtype != torch.float64 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
         raise ValueError(f'workspace must be a contiguous float64 tensor of at least {need} elements on the images\' device')
-    with torch.cuda.device(dev):
-        _lib.check(L.hr_image_metrics(C.c_void_p(pred.data_ptr()), C.c_void_p(gt.data_ptr()), h, w, int(bool(ssim)), C.c_void_p(out.data_ptr()),
-                                      C.c_void_p(workspace.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_image_metrics')
+    _lib.call('hr_image_metrics', pred, gt, h, w, int(bool(ssim)), out, workspace, _lib.stream(dev), device=dev)
     return out
 
 

@@ -8,15 +8,17 @@ nn.Parameters under exactly the reference's state_dict keys (SURVEY.md section 5
 reference checkpoints load by name.  The modules hold weights only -- all arithmetic
 happens in libhyperreel_hip.so, which receives the tensors through hr_model_upload.
 """
+import collections
 import ctypes as C
 import math
+import weakref
 
 import torch
 from torch import nn
 
 from . import lib as _lib
 from .config import n_to_reso, to_plain
-from .data import current_stream, make_camera, make_fisheye, make_ndc
+from .data import make_camera, make_fisheye, make_ndc
 from .plan import MLP_PRECISION, compile_model, hr_fields, hr_lightfield, hr_maps, upload_names
 
 _MLP_PRECISION_NAME = {code: name for name, code in MLP_PRECISION.items()}      # HR_OPT_MLP_PRECISION_ACTIVE -> 'f16x3' ...
@@ -192,22 +194,18 @@ class HostTensorVM(nn.Module):
         """TensorBase.getDenseAlpha (tensorf_base.py:381-401) / TensorVMKeyframeTime.getDenseAlpha (tensorf_dynamic.py:499-536):
         alpha = 1 - exp(-sigma * 0.01) on a dense (n0, n1, n2) lattice of the box (keyframe nets: the maximum over the
         frames), points the current mask rejects get 0.  One HIP launch (hr_dense_alpha) on the owner's native model."""
-        owner = self._owner() if getattr(self, '_owner', None) is not None else None
+        owner = self._owner() if self._owner is not None else None
         if owner is None:
             raise RuntimeError('getDenseAlpha needs the owning HipLightfieldModel (its native handle)')
         h = owner.native()
         n = [int(v) for v in grid_size]
         dev = self.aabb.device
         out = torch.empty(n, dtype=torch.float32, device=dev)
-        L = _lib.load()
         vol = getattr(self, 'alpha_volume', None)
         box = self.alpha_aabb.detach().cpu().reshape(-1).tolist() if vol is not None else [0.0] * 6
         pn = [vol.shape[2], vol.shape[1], vol.shape[0]] if vol is not None else [0, 0, 0]
-        with torch.cuda.device(dev):
-            _lib.check(L.hr_dense_alpha(h, (C.c_int32 * 3)(*n), C.c_float(0.01), int(owner.dataset.get('num_frames', 1)),
-                                        C.c_void_p(vol.contiguous().data_ptr()) if vol is not None else C.c_void_p(0),
-                                        (C.c_int32 * 3)(*pn), (C.c_float * 6)(*box), C.c_void_p(out.data_ptr()),
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_dense_alpha')
+        _lib.call('hr_dense_alpha', h, (C.c_int32 * 3)(*n), 0.01, int(owner.dataset.get('num_frames', 1)), None if vol is None else vol.contiguous(),
+                  (C.c_int32 * 3)(*pn), (C.c_float * 6)(*box), out, _lib.stream(dev), device=dev)
         return out
 
     @torch.no_grad()
@@ -311,7 +309,6 @@ class HostTensorVM(nn.Module):
         TensorVMKeyframeTime.upsample_volume_grid (nlf/nets/tensorf_dynamic.py:395-441): every plane and line is
         resized bilinearly (align_corners=True) to the new grid by hr_upsample_plane; planes of a video net whose density
         plane has no components are re-created as zeros, as in the reference.  Parameters must live on the HIP device."""
-        L = _lib.load()
         N = [int(v) for v in res_target]
 
         def resize(p, h2, w2):
@@ -320,9 +317,7 @@ class HostTensorVM(nn.Module):
                 raise RuntimeError('upsample_volume_grid runs on the HIP device; there is no CPU path')
             _, c, h, w = src.shape
             dst = torch.empty((1, c, h2, w2), dtype=torch.float32, device=src.device)
-            with torch.cuda.device(src.device):
-                _lib.check(L.hr_upsample_plane(C.c_void_p(src.data_ptr()), c, h, w, C.c_void_p(dst.data_ptr()), h2, w2,
-                                               C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)), 'hr_upsample_plane')
+            _lib.call('hr_upsample_plane', src, c, h, w, dst, h2, w2, _lib.stream(src.device), device=src.device)
             return nn.Parameter(dst)
 
         for i in range(3):
@@ -355,6 +350,49 @@ class HostColorModel(nn.Module):
         self.net.set_iter(i)
 
 
+KEEP, CONFIG, UPLOAD, CREATE = 'keep', 'config', 'upload', 'create'        # what native_action asks for, weakest first
+
+# What an hr_model was made from (held) or would be made from now (want).  param_key: HipLightfieldModel._param_key(), None = stale;
+# box_key: (data_ptr, version) of the net's aabb buffer; made: (mlp_precision code, grid_dtype code, compiled aabb), which with the grid
+# is fixed at creation; blob: config_blob of the compiled configuration; cascade: whether it has a coarse level.
+NativeKey = collections.namedtuple('NativeKey', ['param_key', 'grid', 'box_key', 'made', 'blob', 'cascade'])
+
+
+def config_blob(coarse, hc):
+    """The bytes of a compiled configuration: what tells two of them apart."""
+    return bytes(hc) + (bytes(coarse) if coarse is not None else b'')
+
+
+def native_action(held, want, values_travel=False):
+    """The rule for an hr_model's life: held (None: no handle) against want -> KEEP | CONFIG (hr_model_update_config) | UPLOAD (every
+    tensor again, then finalize; the configuration after it where that moved too) | CREATE (a new handle, then the upload).
+    values_travel: a training step hands the parameter values to the kernels itself -- the parameter key is not looked at, a new grid
+    or box is what makes the handle stale."""
+    if held is None:
+        return CREATE
+    if values_travel:
+        stale = (held.grid, held.box_key) != (want.grid, want.box_key)
+    else:
+        stale = held.param_key != want.param_key
+    moved = held.blob != want.blob                         # cur_iter moved a schedule, or what was uploaded compiles differently
+    if (stale and (held.grid, held.made) != (want.grid, want.made)) or (moved and want.cascade):
+        return CREATE                                      # (hr_model_update_config does not take cascades: two nested configurations)
+    if stale:
+        return UPLOAD
+    return CONFIG if moved else KEEP
+
+
+class _Native:
+    """Everything a HipLightfieldModel knows about its hr_model."""
+
+    def __init__(self):
+        self.handle = None
+        self.key = None            # NativeKey of what the handle holds
+        self.hc = self.coarse = None   # the compiled configuration behind key.blob (coarse: a cascade's first level)
+        self.iter = None           # cur_iter that configuration was compiled at
+        self.occ_key = None        # the occupancy volume handed to it (_sync_occupancy)
+
+
 class HipLightfieldModel(nn.Module):
     """Drop-in for model_dict['lightfield'] (nlf/models/models.py:141-143)."""
 
@@ -371,7 +409,6 @@ class HipLightfieldModel(nn.Module):
         # opt-in occupancy early-reject (hr_model_set_occupancy): samples the colour net's AlphaGridMask rejects are neither
         # gathered nor composited -- the reference's own test at tensorf_no_sample.py:171-177, which it ships disabled
         self.use_occupancy = bool(kwargs.get('use_occupancy', False))
-        self._occ_key = None
         self.frame_kernel = self._frame_mode(kwargs.get('frame_kernel', False))
         self.sample_waves = kwargs.get('sample_waves')
         self.train_deterministic = bool(kwargs.get('train_deterministic', False))
@@ -389,15 +426,15 @@ class HipLightfieldModel(nn.Module):
         self.param = _Dummy()
         self.embedding_model = HostEmbedding(cfg, mlp_layer_shapes(cfg), self.dataset)
         self.color_model = HostColorModel(net, grid, self.dataset['num_keyframes'])
-        import weakref
         self.color_model.net._owner = weakref.ref(self)
         self.cur_iter = None           # training iteration of the activation / PE schedules; None = converged (see set_iter)
-        self._native = None
-        self._native_key = None
-        self._native_cfg = None        # bytes of the hr_config the native handle currently holds
-        self._sched_built = None       # cur_iter that configuration was compiled at
-        self._native_box = None        # (data_ptr, version) of the net's aabb buffer the handle was created for
-        self._coarse_hc = None         # hr_config of a cascade's coarse level (None for single-level models)
+        self._n = _Native()
+        self._render_calls = 0         # render() calls of this handle's overflow guard (_overflow_guard)
+        self._reserve = None           # rays per chunk asked for by reserve()
+        self._bg_coin = None           # (seed, step tensor) of set_background_coin
+        self._box_host = (None, None)  # (box key, the aabb buffer on the host)
+        self._grid_size_host = None    # (gridSize tensor, its version, its values)
+        self._f8_cannot_calibrate = self._warned_detached_fields = False
         # fail on configurations outside the supported path now, not at the first render
         self._compile(grid)
 
@@ -405,15 +442,28 @@ class HipLightfieldModel(nn.Module):
         """Grows the feature grids like the reference's training loop does (nlf/__init__.py upsampling hooks ->
         color_model.net.upsample_volume_grid); the native model is rebuilt for the new size at the next render."""
         self.color_model.net.upsample_volume_grid(res_target)
-        self._native_key = None
+        self.invalidate()
+
+    # the names the state went by (tests and tools read them)
+    _native = property(lambda self: self._n.handle)
+    _hc = property(lambda self: self._n.hc)
+    _coarse_hc = property(lambda self: self._n.coarse)
+
+    def invalidate(self):
+        """The next native() uploads every tensor again, whatever their versions say."""
+        if self._n.key is not None:
+            self._n.key = self._n.key._replace(param_key=None)
+
+    def _box_key(self):
+        box = self.color_model.net.aabb
+        return (box.data_ptr(), box._version)
 
     def _compile(self, grid):
         """-> (coarse hr_config or None, hr_config of the level that renders), schedules evaluated at cur_iter."""
         # the box is the net's buffer, not the YAML's value: `shrink` replaces it during training and checkpoints carry it
-        box = self.color_model.net.aabb
-        key = (box.data_ptr(), box._version)
-        if getattr(self, '_box_host', (None, None))[0] != key:        # one device->host copy per change of the box, not per call
-            self._box_host = (key, box.detach().cpu().numpy())
+        key = self._box_key()
+        if self._box_host[0] != key:        # one device->host copy per change of the box, not per call
+            self._box_host = (key, self.color_model.net.aabb.detach().cpu().numpy())
         aabb = self._box_host[1]
         return compile_model(self.cfg, self.dataset, grid, self.mlp_precision, self.grid_dtype, iteration=self.cur_iter, aabb=aabb)
 
@@ -434,7 +484,7 @@ class HipLightfieldModel(nn.Module):
         # The cache holds the TENSOR it read (shrink / upsample_volume_grid / load_state_dict replace gridSize by fresh tensors whose _version is 0
         # again and whose storage the allocator may hand out at a freed tensor's address: identity, not data_ptr, is the key -- ADVICE r4)
         gs = self.color_model.net.gridSize
-        cached = getattr(self, '_grid_size_host', None)
+        cached = self._grid_size_host
         if cached is None or cached[0] is not gs or cached[1] != gs._version:
             cached = self._grid_size_host = (gs, gs._version, [int(v) for v in gs.tolist()])
         return list(cached[2])
@@ -475,18 +525,17 @@ class HipLightfieldModel(nn.Module):
         for k in list(sd.keys()):
             if k in own and torch.is_tensor(sd[k]) and sd[k].shape != own[k].shape and sd[k].numel() == own[k].numel():
                 sd[k] = sd[k].view(own[k].shape)
-        self._native_key = None
+        self.invalidate()
         return super().load_state_dict(sd, strict=strict)
 
     # -- native side -------------------------------------------------------------------
-    def _tensors(self):
+    def _tensors(self, coarse, hc):
         own = dict(self.named_parameters())
-        coarse, hc = self._compile(self.grid_size)
         types = [e['type'] for e in self.cfg['embedding']['embeddings'].values()]
         idx = {'idx': types.index('ray_prediction'),
                'pp_idx': types.index('point_prediction') if 'point_prediction' in types else -1,
                'ct_idx': types.index('color_transform') if 'color_transform' in types else -1}
-        return coarse, hc, [(abi, own[key.format(**idx)]) for abi, key in upload_names(hc, coarse)]
+        return [(abi, own[key.format(**idx)]) for abi, key in upload_names(hc, coarse)]
 
     def _param_key(self):
         # cheap fingerprint of everything the native model was built from: in-place
@@ -495,94 +544,88 @@ class HipLightfieldModel(nn.Module):
         return (self.mlp_precision, self.grid_dtype, net.aabb.data_ptr(), net.aabb._version) + \
             tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in self.parameters())
 
-    def _sync_schedule(self, hc=None, coarse=None):
-        """Hands the configuration compiled at cur_iter to an existing native handle if it differs from what it holds."""
-        if hc is None:
-            coarse, hc = self._compile(self.grid_size)
-        blob = bytes(hc) + (bytes(coarse) if coarse is not None else b'')
-        if blob != self._native_cfg:
-            if coarse is not None:
-                # hr_model_update_config does not take cascades (two nested configurations): re-create the handle with
-                # the constants of this iteration and upload again
-                _lib.load().hr_model_destroy(self._native)
-                self._native = None
-                self._render_calls = 0
-                self._native_key = None
-                self.native()
-                return
+    def _want(self, values_travel):
+        """-> (NativeKey of what the model is now, coarse, hc).  The configuration is compiled only when something it is compiled from
+        moved: while native_action keeps the handle on the cheap keys alone and cur_iter stands, it compiles to what is held."""
+        n = self._n
+        grid, box_key = self.grid_size, self._box_key()
+        param_key = None if values_travel else self._param_key()
+        if n.key is not None and n.iter == self.cur_iter:
+            same = n.key._replace(param_key=param_key, grid=grid, box_key=box_key)
+            if native_action(n.key, same, values_travel) is KEEP:
+                return same, n.coarse, n.hc
+        coarse, hc = self._compile(grid)
+        made = (hc.mlp_precision, hc.grid_dtype, tuple(hc.aabb))
+        return NativeKey(param_key, grid, box_key, made, config_blob(coarse, hc), coarse is not None), coarse, hc
+
+    def held_config(self):
+        """The bytes of the configuration the native handle holds (None: no handle yet)."""
+        return None if self._n.key is None else self._n.key.blob
+
+    def wanted_config(self):
+        """The bytes cur_iter compiles to now."""
+        return config_blob(*self._compile(self.grid_size))
+
+    def native(self, values_travel=False):
+        """Returns the hr_model handle, brought to what native_action asks for: created, its weights (re)uploaded if any parameter
+        changed, the constants of cur_iter's schedules swapped in.  values_travel: forward_train's call (see native_action)."""
+        n = self._n
+        want, coarse, hc = self._want(values_travel)
+        action = native_action(n.key if n.handle is not None else None, want, values_travel)
+        if action is not KEEP:
             dev = next(self.parameters()).device
+            if dev.type != 'cuda':
+                raise RuntimeError('HipLightfieldModel must live on a HIP device (model.cuda()); there is no CPU path')
             with torch.cuda.device(dev):
-                _lib.check(_lib.load().hr_model_update_config(self._native, C.byref(hc), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                           'hr_model_update_config')
-            self._native_cfg = blob
-        self._hc = hc
-        self._sched_built = self.cur_iter
+                if action is CREATE:
+                    self._create(want, coarse, hc, values_travel)
+                if action is not CONFIG:
+                    torch.cuda.current_stream().synchronize()
+                    for abi, t in self._tensors(coarse, hc):
+                        t = t.detach().contiguous().float()
+                        _lib.call('hr_model_upload', n.handle, abi.encode(), t, t.numel() * 4)
+                    _lib.call('hr_model_finalize', n.handle)
+                    n.key = want._replace(param_key=self._param_key(), blob=n.key.blob)
+                if n.key.blob != want.blob:          # CONFIG, or an upload into a handle that still held another iteration's constants
+                    _lib.call('hr_model_update_config', n.handle, C.byref(hc), _lib.stream(dev))
+                    n.key = n.key._replace(blob=want.blob)
+        n.hc, n.coarse, n.iter = hc, coarse, self.cur_iter
+        return n.handle
 
-    def native(self):
-        """Returns the hr_model handle, (re)uploading weights if any parameter changed."""
-        key = self._param_key()
-        if self._native is not None and key == self._native_key:
-            if self._sched_built != self.cur_iter:
-                self._sync_schedule()
-            return self._native
-        coarse, hc, tensors = self._tensors()
-        L = _lib.load()
-        dev = tensors[0][1].device
-        if dev.type != 'cuda':
-            raise RuntimeError('HipLightfieldModel must live on a HIP device (model.cuda()); there is no CPU path')
-        def create():
-            h = C.c_void_p()
-            if coarse is None:
-                _lib.check(L.hr_model_create(C.byref(hc), C.byref(h)), 'hr_model_create')
-            else:
-                _lib.check(L.hr_model_create_cascade(C.byref(coarse), C.byref(hc), C.byref(h)), 'hr_model_create_cascade')
-            self._native = h
-            self._occ_key = None                   # a fresh handle holds no occupancy volume
-            self._apply_options()
-            if getattr(self, '_reserve', None):
-                _lib.check(L.hr_model_reserve(h, self._reserve), 'hr_model_reserve')
-            self._native_grid = self.grid_size
-            self._native_box = (self.color_model.net.aabb.data_ptr(), self.color_model.net.aabb._version)
-            self._native_cfg = bytes(hc) + (bytes(coarse) if coarse is not None else b'')
-
-        with torch.cuda.device(dev):
-            if self._native is None:
-                create()
-            elif self._native_grid != self.grid_size or self._hc.mlp_precision != hc.mlp_precision \
-                    or self._hc.grid_dtype != hc.grid_dtype or list(self._hc.aabb) != list(hc.aabb):
-                L.hr_model_destroy(self._native)
-                create()
-            torch.cuda.current_stream().synchronize()
-            for abi, t in tensors:
-                t = t.detach().contiguous().float()
-                _lib.check(L.hr_model_upload(self._native, abi.encode(), C.c_void_p(t.data_ptr()),
-                                             t.numel() * 4), f'hr_model_upload({abi})')
-            _lib.check(L.hr_model_finalize(self._native), 'hr_model_finalize')
-        self._native_key = key
-        self._hc = hc
-        self._coarse_hc = coarse
-        self._sync_schedule(hc, coarse)          # an existing handle may still hold another iteration's constants
-        return self._native
+    def _create(self, want, coarse, hc, values_travel):
+        n = self._n
+        if n.handle is not None:
+            _lib.call('hr_model_destroy', n.handle)
+            if native_action(n.key, want._replace(blob=n.key.blob), values_travel) is not CREATE:
+                self._render_calls = 0                 # re-created for a cascade's schedule alone: its overflow guard polls from the start
+            n.handle = n.key = None
+        h = C.c_void_p()
+        if coarse is None:
+            _lib.call('hr_model_create', C.byref(hc), C.byref(h))
+        else:
+            _lib.call('hr_model_create_cascade', C.byref(coarse), C.byref(hc), C.byref(h))
+        n.handle, n.key = h, want._replace(param_key=None)
+        n.occ_key = None                       # a fresh handle holds no occupancy volume
+        self._apply_options()
+        if self._reserve:
+            _lib.call('hr_model_reserve', h, self._reserve)
 
     def _sync_occupancy(self):
         """Hands the colour net's current mask volume to the native model (or clears it)."""
         net = self.color_model.net
         vol = getattr(net, 'alpha_volume', None) if self.use_occupancy else None
         key = None if vol is None else (vol.data_ptr(), vol._version, tuple(vol.shape), net.alpha_aabb.data_ptr(), net.alpha_aabb._version)
-        if key == self._occ_key or self._native is None:
+        if key == self._n.occ_key or self._native is None:
             return
-        L = _lib.load()
         dev = next(self.parameters()).device
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            if vol is None:
-                _lib.check(L.hr_model_set_occupancy(self._native, C.c_void_p(0), None, None, stream), 'hr_model_set_occupancy')
-            else:
-                v = vol.detach().contiguous().float().to(dev)
-                n = (C.c_int32 * 3)(v.shape[2], v.shape[1], v.shape[0])
-                box = (C.c_float * 6)(*net.alpha_aabb.detach().cpu().reshape(-1).tolist())
-                _lib.check(L.hr_model_set_occupancy(self._native, C.c_void_p(v.data_ptr()), n, box, stream), 'hr_model_set_occupancy')
-        self._occ_key = key
+        if vol is None:
+            _lib.call('hr_model_set_occupancy', self._native, None, None, None, _lib.stream(dev), device=dev)
+        else:
+            v = vol.detach().contiguous().float().to(dev)
+            n = (C.c_int32 * 3)(v.shape[2], v.shape[1], v.shape[0])
+            box = (C.c_float * 6)(*net.alpha_aabb.detach().cpu().reshape(-1).tolist())
+            _lib.call('hr_model_set_occupancy', self._native, v, n, box, _lib.stream(dev), device=dev)
+        self._n.occ_key = key
 
     def set_occupancy(self, enable=True):
         """Turns the occupancy early-reject of render() on or off (needs a mask: updateAlphaMask or a checkpoint's)."""
@@ -593,16 +636,15 @@ class HipLightfieldModel(nn.Module):
             self._sync_occupancy()
 
     def _apply_options(self):
-        L = _lib.load()
-        _lib.check(L.hr_model_set_option(self._native, _lib.HR_OPT_FRAME_KERNEL, int(self.frame_kernel)), 'hr_model_set_option')
+        _lib.call('hr_model_set_option', self._native, _lib.HR_OPT_FRAME_KERNEL, int(self.frame_kernel))
         if self.sample_waves is not None:
-            _lib.check(L.hr_model_set_option(self._native, _lib.HR_OPT_SAMPLE_WAVES, int(self.sample_waves)), 'hr_model_set_option')
-        _lib.check(L.hr_model_set_option(self._native, _lib.HR_OPT_TRAIN_DETERMINISTIC, int(self.train_deterministic)), 'hr_model_set_option')
-        bg = getattr(self, '_bg_coin', None)
+            _lib.call('hr_model_set_option', self._native, _lib.HR_OPT_SAMPLE_WAVES, int(self.sample_waves))
+        _lib.call('hr_model_set_option', self._native, _lib.HR_OPT_TRAIN_DETERMINISTIC, int(self.train_deterministic))
+        bg = self._bg_coin
         if bg is not None and not self._black_bg():
-            _lib.check(L.hr_train_set_background(self._native, 1, bg[0], C.c_void_p(bg[1].data_ptr())), 'hr_train_set_background')
+            _lib.call('hr_train_set_background', self._native, 1, bg[0], bg[1])
         else:
-            _lib.check(L.hr_train_set_background(self._native, 0, 0, None), 'hr_train_set_background')
+            _lib.call('hr_train_set_background', self._native, 0, 0, None)
 
     def _black_bg(self):
         return bool(self.cfg['color']['net'].get('black_bg', False))
@@ -655,9 +697,7 @@ class HipLightfieldModel(nn.Module):
 
     def frame_kernel_active(self):
         """True when render() of this model runs as the single persistent frame kernel (head tile in LDS)."""
-        v = C.c_int32(0)
-        _lib.check(_lib.load().hr_model_get_option(self.native(), _lib.HR_OPT_FRAME_KERNEL_ACTIVE, C.byref(v)), 'hr_model_get_option')
-        return bool(v.value)
+        return bool(self._get_option(_lib.HR_OPT_FRAME_KERNEL_ACTIVE))
 
     def chunk_rays(self):
         """Rays per launch of the head workspace (hr_model_reserve / the finalize default): the most hr_stage_* accept."""
@@ -665,7 +705,7 @@ class HipLightfieldModel(nn.Module):
 
     def _get_option(self, opt):
         v = C.c_int32(0)
-        _lib.check(_lib.load().hr_model_get_option(self.native(), opt, C.byref(v)), 'hr_model_get_option')
+        _lib.call('hr_model_get_option', self.native(), opt, C.byref(v))
         return int(v.value)
 
     def mlp_precision_active(self):
@@ -694,7 +734,7 @@ class HipLightfieldModel(nn.Module):
         """hr_model_verify_info as a dict: the band of the verified fast path for THIS model and the f16f8-vs-f16x3 measurement on the
         calibration rays it was derived from (band = max(floor, 4 x the largest difference of a distance / length / point))."""
         v = _lib.hr_verify_info()
-        _lib.check(_lib.load().hr_model_verify_info(self.native(), C.byref(v)), 'hr_model_verify_info')
+        _lib.call('hr_model_verify_info', self.native(), C.byref(v))
         return {k: getattr(v, k) for k, _ in v._fields_}
 
     def mlp_overflowed(self):
@@ -711,25 +751,22 @@ class HipLightfieldModel(nn.Module):
         self.native()
         rays = self._check_rays(rays)
         out = (C.c_float * 8)()
-        with torch.cuda.device(rays.device):
-            stream = C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream)
-            _lib.check(_lib.load().hr_model_calibrate(self.native(), C.c_void_p(rays.data_ptr()), rays.shape[0], out, stream), 'hr_model_calibrate')
+        _lib.call('hr_model_calibrate', self.native(), rays, rays.shape[0], out, _lib.stream(rays.device), device=rays.device)
         return [float(v) for v in out[:int(self._hc.mlp_layers)]]
 
     def reserve(self, rays_per_chunk):
         """Sizes the native workspace; remembered, so that a handle that is re-created (grid growth, cascade schedules) gets it again."""
         self._reserve = int(rays_per_chunk)
-        L = _lib.load()
-        _lib.check(L.hr_model_reserve(self.native(), self._reserve), 'hr_model_reserve')
+        _lib.call('hr_model_reserve', self.native(), self._reserve)
 
     def device_bytes(self):
-        return int(_lib.load().hr_model_device_bytes(self.native()))
+        return int(_lib.call('hr_model_device_bytes', self.native()))
 
     def __del__(self):
         try:
             if self._native is not None:
-                _lib.load().hr_model_destroy(self._native)
-                self._native = None
+                _lib.call('hr_model_destroy', self._native)
+                self._n.handle = None
                 self._render_calls = 0
         except Exception:
             pass
@@ -758,7 +795,6 @@ class HipLightfieldModel(nn.Module):
         render those maps into (a captured graph's fixed buffers).  `want` and `maps` are exclusive."""
         h = self.native()
         self._sync_occupancy()
-        L = _lib.load()
         rays = self._check_rays(rays)
         B = rays.shape[0]
         hc = self._hc
@@ -787,21 +823,18 @@ class HipLightfieldModel(nn.Module):
                     raise ValueError(f'maps_out[{k!r}] must be a contiguous {shape} float32 tensor on the rays\' device')
                 out[k] = t
                 setattr(mp, slots[k], t.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream)
+        stream, rgb = _lib.stream(rays.device), out['rgb']
         with torch.cuda.device(rays.device):
             if not want:
                 for attempt in (0, 1):
                     if frame_time is not None and mp is not None:
-                        _lib.check(L.hr_render_frame_maps(h, C.c_void_p(rays.data_ptr()), B, float(frame_time), C.c_void_p(out['rgb'].data_ptr()),
-                                                          C.byref(mp), stream), 'hr_render_frame_maps')
+                        _lib.call('hr_render_frame_maps', h, rays, B, float(frame_time), rgb, C.byref(mp), stream)
                     elif frame_time is not None:
-                        _lib.check(L.hr_render_frame(h, C.c_void_p(rays.data_ptr()), B, float(frame_time), C.c_void_p(out['rgb'].data_ptr()), stream),
-                                   'hr_render_frame')
+                        _lib.call('hr_render_frame', h, rays, B, float(frame_time), rgb, stream)
                     elif mp is not None:
-                        _lib.check(L.hr_render_maps(h, C.c_void_p(rays.data_ptr()), B, C.c_void_p(out['rgb'].data_ptr()), C.byref(mp), stream),
-                                   'hr_render_maps')
+                        _lib.call('hr_render_maps', h, rays, B, rgb, C.byref(mp), stream)
                     else:
-                        _lib.check(L.hr_render(h, C.c_void_p(rays.data_ptr()), B, C.c_void_p(out['rgb'].data_ptr()), stream), 'hr_render')
+                        _lib.call('hr_render', h, rays, B, rgb, stream)
                     if attempt == 1 or not self._overflow_guard(rays):
                         break
                 return out
@@ -813,8 +846,7 @@ class HipLightfieldModel(nn.Module):
             for k in want:
                 out[k] = torch.zeros(shapes[k], dtype=torch.float32, device=rays.device)
                 setattr(f, slots[k], out[k].data_ptr())
-            _lib.check(L.hr_render_fields(h, C.c_void_p(rays.data_ptr()), B, C.c_void_p(out['rgb'].data_ptr()),
-                                          C.byref(f), stream), 'hr_render_fields')
+            _lib.call('hr_render_fields', h, rays, B, rgb, C.byref(f), stream)
         return out
 
     def _overflow_guard(self, rays):
@@ -824,7 +856,7 @@ class HipLightfieldModel(nn.Module):
         on the model's first 16 render calls and every 256th after (one 4-byte read behind a synchronise; never inside a stream
         capture).  If set: the arithmetic is re-decided on the offending rays -- 'auto' re-packs as bf16x3 (fp32 exponent range), a forced
         fp16 mode raises HipRangeError -- and the caller renders the batch again.  Returns True when it did so."""
-        n = self._render_calls = getattr(self, '_render_calls', 0) + 1
+        n = self._render_calls = self._render_calls + 1
         if not (n <= 16 or n % 256 == 0) or torch.cuda.is_current_stream_capturing():
             return False
         active = self.mlp_precision_active()
@@ -845,7 +877,7 @@ class HipLightfieldModel(nn.Module):
                     raise _lib.HipRangeError(f'mlp_precision {self.mlp_precision!r} overflowed the IEEE-half range on rendered rays of a point_prediction '
                                              'cascade; use mlp_precision="auto" or "bf16x3"') from e
                 self.mlp_precision = 'bf16x3'
-                self._native_key = None
+                self.invalidate()
                 self.native()
             return True
         if active == 'f16f8' and self.mlp_verified() and self.redo_overflowed():
@@ -856,14 +888,14 @@ class HipLightfieldModel(nn.Module):
             self.calibrate(rays)
             if self.mlp_verified() and self.verify_info()['listed_frac'] > 0.05:
                 self.mlp_precision = 'f16x3'
-                self._native_key = None
+                self.invalidate()
                 self.native()
             return True
         if active == 'f16f8' and self.mlp_f8_saturated():
             # f16f8: the fp8 images of a layer's output are scaled from the calibration's largest activation of that layer.  Beyond 16x that they
             # saturate (finite, less accurate).  Where the model can be calibrated on the caller's rays, do so and render again; a cascade's
             # point MLP sees internal rows (hr_model_calibrate refuses it): say so once and carry on
-            if getattr(self, '_f8_cannot_calibrate', False):
+            if self._f8_cannot_calibrate:
                 return False
             try:
                 self.calibrate(rays)
@@ -894,10 +926,9 @@ class HipLightfieldModel(nn.Module):
         fe, nd = make_fisheye(fisheye), make_ndc(ndc)
         rd = self._hc.ray_dim
         rays = torch.empty((hi - lo, rd), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):                    # NULL for both optional pointers: hr_generate_rays itself
-            _lib.check(_lib.load().hr_generate_rays_fisheye(C.byref(cam), C.byref(fe) if fe is not None else None,
-                                                            C.byref(nd) if nd is not None else None, rd, lo, hi - lo,
-                                                            C.c_void_p(rays.data_ptr()), current_stream(dev)), 'hr_generate_rays_fisheye')
+        # NULL for both optional pointers: hr_generate_rays itself
+        _lib.call('hr_generate_rays_fisheye', C.byref(cam), C.byref(fe) if fe is not None else None, C.byref(nd) if nd is not None else None,
+                  rd, lo, hi - lo, rays, _lib.stream(dev), device=dev)
         return rays
 
     def render_camera(self, pose, K, width, height, time=None, cam_id=0.0, pixel_range=None, ndc=None, fisheye=None):
@@ -911,15 +942,13 @@ class HipLightfieldModel(nn.Module):
         self.native()
         if self._hc.ray_dim != 6:
             raise ValueError(f'two-plane light-field rays have 6 columns; this model takes {self._hc.ray_dim}')
-        L = _lib.load()
         dev = torch.device(device) if device is not None else next(self.parameters()).device
         lo, hi = (0, int(lightfield.width) * int(lightfield.height)) if pixel_range is None else (int(pixel_range[0]), int(pixel_range[1]))
         if hi < lo:
             raise ValueError(f'pixel_range {pixel_range} is reversed')
         rays = torch.empty((hi - lo, 6), dtype=torch.float32, device=dev)
-        fn, name = (L.hr_generate_rays_epi, 'hr_generate_rays_epi') if epi else (L.hr_generate_rays_lightfield, 'hr_generate_rays_lightfield')
-        with torch.cuda.device(dev):
-            _lib.check(fn(C.byref(lightfield), float(a), float(b), lo, hi - lo, C.c_void_p(rays.data_ptr()), current_stream(dev)), name)
+        _lib.call('hr_generate_rays_epi' if epi else 'hr_generate_rays_lightfield', C.byref(lightfield), float(a), float(b), lo, hi - lo, rays,
+                  _lib.stream(dev), device=dev)
         return rays
 
     def generate_lightfield_rays(self, s, t, lightfield, pixel_range=None, device=None):
@@ -958,10 +987,8 @@ class HipLightfieldModel(nn.Module):
             raise ValueError('rgb must be a (H*W, 3) tensor on the HIP device')
         out = torch.empty((oh, ow, 4), dtype=torch.uint8, device=rgb.device) if rgba8 else \
             torch.empty((oh, ow, 3), dtype=torch.float32, device=rgb.device)
-        with torch.cuda.device(rgb.device):
-            _lib.check(_lib.load().hr_pack_display(C.c_void_p(rgb.data_ptr()), int(height), int(width), int(bool(transpose)), int(bool(flip)),
-                                                   int(bool(rgba8)), C.c_void_p(out.data_ptr()),
-                                                   C.c_void_p(torch.cuda.current_stream(rgb.device).cuda_stream)), 'hr_pack_display')
+        _lib.call('hr_pack_display', rgb, int(height), int(width), int(bool(transpose)), int(bool(flip)), int(bool(rgba8)), out,
+                  _lib.stream(rgb.device), device=rgb.device)
         return out
 
     def forward_train(self, rays, white_bg=None, want_fields=False):
@@ -971,15 +998,10 @@ class HipLightfieldModel(nn.Module):
         (tensorf_no_sample.py:236).  The activation schedules are the converged ones (see set_iter).
         want_fields: also return {'distances', 'points', 'render_weights', 'head'} of THIS forward (detached; hr_train_forward_fields)."""
         from . import train as T
-        box = self.color_model.net.aabb
-        if self._native is None or self._native_grid != self.grid_size or self._native_box != (box.data_ptr(), box._version):
-            self.native()
-        elif self._sched_built != self.cur_iter:
-            self._sync_schedule()
-        h, hc = self._native, self._hc
+        h, hc = self.native(values_travel=True), self._hc
         rays = self._check_rays(rays)
         net_cfg = self.cfg['color']['net']
-        if getattr(self, '_bg_coin', None) is not None:         # set_background_coin: the device decides (a black_bg configuration stays black)
+        if self._bg_coin is not None:         # set_background_coin: the device decides (a black_bg configuration stays black)
             white_bg = False
         elif white_bg is None:
             white_bg = (bool(net_cfg.get('white_bg', False)) or bool(torch.rand(()) < 0.5)) and not bool(net_cfg.get('black_bg', False))
@@ -1006,22 +1028,11 @@ class HipLightfieldModel(nn.Module):
         extra = ()
         if hc.color_table_views > 0:                            # ColorTransformEmbedding's table (point.py:558-602)
             extra = (self.embedding_model.embeddings[types.index('color_transform')].color_embedding,)
-        # (the request travels as a class attribute: autograd.Function.apply takes tensors.  Whatever happens inside, neither the request nor a
-        #  previous call's fields may outlive this call -- ADVICE r4)
-        T.SampleStage.fields_out = None
-        T.SampleStage.want_fields = hc.z_channels if want_fields else None
-        try:
-            rgb = T.SampleStage.apply(h, rays, head, white_bg, vm.basis_mat.weight, *T.grid_parameters(vm), *extra)
-            f = T.SampleStage.fields_out
-        finally:
-            T.SampleStage.want_fields = None
-            T.SampleStage.fields_out = None
+        args = (h, rays, head, white_bg, vm.basis_mat.weight, *T.grid_parameters(vm), *extra)
         if want_fields:
-            if f is None:
-                raise RuntimeError('forward_train(want_fields=True): the sample stage returned no fields')
-            f['head'] = head.detach()
-            return rgb, f
-        return rgb
+            rgb, distances, points, weights = T.SampleStageFields.apply(hc.z_channels, *args)
+            return rgb, {'distances': distances, 'points': points, 'render_weights': weights, 'head': head.detach()}
+        return T.SampleStage.apply(*args)
 
     def forward(self, rays, render_kwargs=None):
         """LightfieldModel.forward (models.py:135-138).  In train mode with autograd enabled this is the
@@ -1045,15 +1056,9 @@ class HipLightfieldModel(nn.Module):
             # covers the colour loss and the plane regularisers).
             rgb, r = self.forward_train(rays, want_fields=True)
             r['rgb'] = rgb.detach()
-            out = {k: v.detach() for k, v in self._forward_fields(rays, render_kwargs, r).items()}
-            if not getattr(self, '_warned_detached_fields', False):
-                import warnings
-                self._warned_detached_fields = True
-                warnings.warn('HipLightfieldModel.forward in train mode: the fields ' + ', '.join(sorted(k for k in out if k != 'rgb')) +
-                              ' are DETACHED values of the training forward -- a regulariser that needs their gradient contributes none '
-                              '(differentiable: rgb, and the plane regularisers of hyperreel_amd.train)', RuntimeWarning, stacklevel=2)
-            out['rgb'] = rgb
-            return out
+            return self._detached_fields(self._forward_fields(rays, render_kwargs, r), rgb,
+                                         ' are DETACHED values of the training forward -- a regulariser that needs their gradient contributes none '
+                                         '(differentiable: rgb, and the plane regularisers of hyperreel_amd.train)')
         out = self._forward_fields(rays, render_kwargs)
         if self.training and torch.is_grad_enabled():
             # INRSystem.training_step passes the regularizers' field list on the main forward (nlf/__init__.py:634-709):
@@ -1061,15 +1066,22 @@ class HipLightfieldModel(nn.Module):
             # per-step background draw); the requested fields are the inference kernel's values, detached -- a
             # regulariser that needs d(field)/d(parameters) is outside the training path (SURVEY 8f-4 covers the colour loss
             # and the plane regularisers).
-            out = {k: v.detach() for k, v in out.items()}
-            if not getattr(self, '_warned_detached_fields', False):
-                import warnings
-                self._warned_detached_fields = True
-                warnings.warn('HipLightfieldModel.forward in train mode: the fields ' + ', '.join(sorted(k for k in out if k != 'rgb')) +
-                              ' come from the inference kernels and are DETACHED -- a regulariser that needs their gradient contributes none '
-                              '(differentiable: rgb, and the plane regularisers of hyperreel_amd.train); every such step also re-uploads the '
-                              'weights for the inference pass', RuntimeWarning, stacklevel=2)
-            out['rgb'] = self.forward_train(rays)
+            return self._detached_fields(out, self.forward_train(rays),
+                                         ' come from the inference kernels and are DETACHED -- a regulariser that needs their gradient contributes none '
+                                         '(differentiable: rgb, and the plane regularisers of hyperreel_amd.train); every such step also re-uploads the '
+                                         'weights for the inference pass')
+        return out
+
+    def _detached_fields(self, out, rgb, how):
+        """forward's train-mode answer to a field list: the fields detached, `rgb` the differentiable colour; warns once, `how` saying
+        where the fields come from."""
+        out = {k: v.detach() for k, v in out.items()}
+        if not self._warned_detached_fields:
+            import warnings
+            self._warned_detached_fields = True
+            warnings.warn('HipLightfieldModel.forward in train mode: the fields ' + ', '.join(sorted(k for k in out if k != 'rgb')) + how,
+                          RuntimeWarning, stacklevel=3)
+        out['rgb'] = rgb
         return out
 
     # -- diagnostics surface (visualizers only) ------------------------------------------
@@ -1115,7 +1127,7 @@ class HipLightfieldModel(nn.Module):
 
     def _field_names(self):
         """The keys _forward_fields can produce for this model (others are skipped, as the reference's loop over x skips them)."""
-        hc = getattr(self, '_hc', None)
+        hc = self._hc
         if hc is None:                                  # no native model yet: the configuration it will be built from
             hc = self._compile(self.grid_size)[1]
         names = {'render_weights', 'points', 'distances', 'viewdirs', 'weights'}

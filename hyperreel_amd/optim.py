@@ -79,49 +79,13 @@ class HipAdam(torch.optim.Optimizer):
             self._lr_host = None
             self.sync_hyperparameters()
 
-    def _step_dev(self):
-        """One launch sequence of hr_adam_step_dev over every parameter that has a gradient (validated by step())."""
-        ps, gs, ms, vs, ns, hp, li = [], [], [], [], [], [], []
-        keep = []
-        dev = self.step_tensor.device
-        for gi, group in enumerate(self.param_groups):
-            b1, b2 = group['betas']
-            for p in group['params']:
-                if p.grad is None:
-                    continue
-                if p.device != dev:
-                    raise RuntimeError('HipAdam: all parameters of one optimizer on one device')
-                st = self.state[p]
-                if len(st) == 0:
-                    if torch.cuda.is_current_stream_capturing():
-                        raise RuntimeError('HipAdam(capturable=True): take one eager step before the capture (the first step allocates the moments)')
-                    st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                keep.append(g)
-                ps.append(p.data_ptr()); gs.append(g.data_ptr()); ms.append(st['exp_avg'].data_ptr()); vs.append(st['exp_avg_sq'].data_ptr())
-                ns.append(p.numel())
-                hp += [float(b1), float(b2), float(group['eps']), float(group['weight_decay'])]
-                li.append(gi)
-        if not ps:
-            return
-        k = len(ps)
-        PV, NV, HV, IV = C.c_void_p * k, C.c_int64 * k, C.c_double * (4 * k), C.c_int32 * k
-        L = _lib.load()
-        with torch.cuda.device(dev):
-            _lib.check(L.hr_adam_step_dev(PV(*ps), PV(*gs), PV(*ms), PV(*vs), NV(*ns), HV(*hp), IV(*li), len(self.param_groups),
-                                          C.c_void_p(self._lr_dev.data_ptr()), C.c_void_p(self.step_tensor.data_ptr()), k,
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_adam_step_dev')
-
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        ps, gs, ms, vs, ns, hp = [], [], [], [], [], []
-        keep = []
-        dev = None
+        dev = self.step_tensor.device if self.capturable else None
         # validate EVERYTHING before any state is touched: a raise must not leave some parameters' step counts advanced (ADVICE r4)
         for group in self.param_groups:
             if group.get('amsgrad', False) or group.get('maximize', False):
@@ -137,39 +101,35 @@ class HipAdam(torch.optim.Optimizer):
                     dev = p.device
                 elif p.device != dev:
                     raise RuntimeError('HipAdam: all parameters of one optimizer on one device')
-        if self.capturable:
-            self._step_dev()
-            return loss
-        for group in self.param_groups:
-            b1, b2 = group['betas']
+        # one row per parameter that has a gradient: (p, gradient, its state, group index); the capturable form keeps no host count
+        rows = []
+        for gi, group in enumerate(self.param_groups):
             for p in group['params']:
                 if p.grad is None:
                     continue
-                if p.device.type != 'cuda':
-                    raise RuntimeError('HipAdam steps parameters on the HIP device; there is no CPU path')
-                if p.dtype != torch.float32 or p.grad.dtype != torch.float32 or p.grad.is_sparse or not p.is_contiguous():
-                    raise RuntimeError('HipAdam: contiguous float32 parameters with dense float32 gradients')
-                if dev is None:
-                    dev = p.device
-                elif p.device != dev:
-                    raise RuntimeError('HipAdam: all parameters of one optimizer on one device')
                 st = self.state[p]
                 if len(st) == 0:
-                    st['step'] = torch.tensor(0.0, dtype=torch.float32)               # (host, as torch.optim.Adam keeps it when not capturable)
+                    if not self.capturable:
+                        st['step'] = torch.tensor(0.0, dtype=torch.float32)               # (host, as torch.optim.Adam keeps it when not capturable)
+                    elif torch.cuda.is_current_stream_capturing():
+                        raise RuntimeError('HipAdam(capturable=True): take one eager step before the capture (the first step allocates the moments)')
                     st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st['step'] += 1
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                keep.append(g)
-                ps.append(p.data_ptr()); gs.append(g.data_ptr()); ms.append(st['exp_avg'].data_ptr()); vs.append(st['exp_avg_sq'].data_ptr())
-                ns.append(p.numel())
-                hp += [float(group['lr']), float(b1), float(b2), float(group['eps']), float(group['weight_decay']), float(st['step'])]
-        if not ps:
+                if not self.capturable:
+                    st['step'] += 1
+                rows.append((p, p.grad if p.grad.is_contiguous() else p.grad.contiguous(), st, gi))
+        if not rows:
             return loss
-        k = len(ps)
-        PV, NV, HV = C.c_void_p * k, C.c_int64 * k, C.c_double * (6 * k)
-        L = _lib.load()
-        with torch.cuda.device(dev):
-            _lib.check(L.hr_adam_step(PV(*ps), PV(*gs), PV(*ms), PV(*vs), NV(*ns), HV(*hp), k,
-                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'hr_adam_step')
+        k, groups = len(rows), self.param_groups
+        ptrs = [(C.c_void_p * k)(*(t.data_ptr() for t in col)) for col in zip(*((p, g, st['exp_avg'], st['exp_avg_sq']) for p, g, st, _ in rows))]
+        ns = (C.c_int64 * k)(*(p.numel() for p, *_ in rows))
+        if self.capturable:     # betas, eps, weight_decay per row; lr and the count are read on the device
+            hp = [float(v) for *_, gi in rows for v in (*groups[gi]['betas'], groups[gi]['eps'], groups[gi]['weight_decay'])]
+            _lib.call('hr_adam_step_dev', *ptrs, ns, (C.c_double * len(hp))(*hp), (C.c_int32 * k)(*(gi for *_, gi in rows)), len(groups),
+                      self._lr_dev, self.step_tensor, k, _lib.stream(dev), device=dev)
+        else:
+            hp = [float(v) for _, _, st, gi in rows for v in (groups[gi]['lr'], *groups[gi]['betas'], groups[gi]['eps'], groups[gi]['weight_decay'], st['step'])]
+            _lib.call('hr_adam_step', *ptrs, ns, (C.c_double * len(hp))(*hp), k, _lib.stream(dev), device=dev)
+        # the launch wrote the parameters behind torch's back: whoever keys on their versions (the model's native handle) must see a step
+        torch.autograd.graph.increment_version([p for p, *_ in rows])
         return loss

@@ -21,14 +21,6 @@ import torch
 from . import lib as _lib
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else C.c_void_p(0)
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _tensors_struct(groups, basis, table=None):
     """groups: 4 lists of 3 tensors (density a, density b, app a, app b) -> hr_train_tensors."""
     t = _lib.hr_train_tensors()
@@ -47,12 +39,13 @@ class SampleStage(torch.autograd.Function):
     app a[0..2], app b[0..2] (a = plane | plane_space, b = line | plane_time), then -- only for models with a per-camera
     colour table (ColorTransformEmbedding, read with dataset.val_all) -- its `color_embedding`."""
 
-    fields_out = None      # set by forward() when `want_fields` was given: {'distances', 'points', 'render_weights'} of that call, detached
+    poison_outputs = False # tests: gradient buffers start as NaN instead of uninitialised memory
 
     @staticmethod
-    def forward(ctx, handle, rays, head, white_bg, basis, *tensors):
+    def run(ctx, fields_z, handle, rays, head, white_bg, basis, tensors):
+        """The forward of both stages -> (rgb, fields): fields is None, or with fields_z = z_channels the forward's own per-sample
+        (distances, points, render_weights) (hr_train_forward_fields)."""
         grids, table = tensors[:12], (tensors[12] if len(tensors) > 12 else None)
-        L = _lib.load()
         dev = rays.device
         if dev.type != 'cuda' or head.device != dev:
             raise RuntimeError('SampleStage runs on the HIP device; there is no CPU path')
@@ -60,36 +53,30 @@ class SampleStage(torch.autograd.Function):
         vals = [g.detach().contiguous() for g in grids]
         groups = [vals[0:3], vals[3:6], vals[6:9], vals[9:12]]
         params = _tensors_struct(groups, basis.detach().contiguous(), None if table is None else table.detach().contiguous())
-        rgb = torch.empty((rays.shape[0], 3), dtype=torch.float32, device=dev)
-        want = SampleStage.want_fields
-        SampleStage.want_fields = None
-        with torch.cuda.device(dev):
-            if want:
-                # the forward's own per-sample values (hr_train_forward_fields): what a field-consuming regulariser reads, without a
-                # second pass through the inference kernels
-                from .plan import hr_fields
-                B, Z = rays.shape[0], int(want)
-                f = hr_fields()
-                out = {'distances': torch.zeros((B, Z), dtype=torch.float32, device=dev), 'points': torch.zeros((B, Z, 3), dtype=torch.float32, device=dev),
-                       'render_weights': torch.zeros((B, Z), dtype=torch.float32, device=dev)}
-                f.distances_dev, f.points_dev, f.weights_dev = out['distances'].data_ptr(), out['points'].data_ptr(), out['render_weights'].data_ptr()
-                _lib.check(L.hr_train_forward_fields(handle, C.byref(params), _ptr(rays), _ptr(head), B, int(bool(white_bg)), _ptr(rgb), C.byref(f),
-                                                     _stream(dev)), 'hr_train_forward_fields')
-                SampleStage.fields_out = out
-            else:
-                _lib.check(L.hr_train_forward(handle, C.byref(params), _ptr(rays), _ptr(head), rays.shape[0], int(bool(white_bg)), _ptr(rgb),
-                                              _stream(dev)), 'hr_train_forward')
+        B = rays.shape[0]
+        rgb = torch.empty((B, 3), dtype=torch.float32, device=dev)
+        fields = None
+        if fields_z:
+            # the forward's own per-sample values: what a field-consuming regulariser reads, without a second pass through the inference kernels
+            from .plan import hr_fields
+            Z = int(fields_z)
+            f = hr_fields()
+            fields = tuple(torch.zeros(shape, dtype=torch.float32, device=dev) for shape in ((B, Z), (B, Z, 3), (B, Z)))
+            f.distances_dev, f.points_dev, f.weights_dev = (t.data_ptr() for t in fields)
+            _lib.call('hr_train_forward_fields', handle, C.byref(params), rays, head, B, int(bool(white_bg)), rgb, C.byref(f), _lib.stream(dev), device=dev)
+        else:
+            _lib.call('hr_train_forward', handle, C.byref(params), rays, head, B, int(bool(white_bg)), rgb, _lib.stream(dev), device=dev)
         ctx.handle, ctx.white_bg = handle, int(bool(white_bg))
         ctx.has_table = table is not None
         ctx.save_for_backward(rays, head, basis, *tensors)
-        return rgb
+        return rgb, fields
 
-    poison_outputs = False # tests: gradient buffers start as NaN instead of uninitialised memory
-    want_fields = None     # set to z_channels right before apply() to make that call produce fields_out (single-threaded host code)
+    @staticmethod
+    def forward(ctx, handle, rays, head, white_bg, basis, *tensors):
+        return SampleStage.run(ctx, None, handle, rays, head, white_bg, basis, tensors)[0]
 
     @staticmethod
     def backward(ctx, d_rgb):
-        L = _lib.load()
         rays, head, basis, *tensors = ctx.saved_tensors
         grids, table = tensors[:12], (tensors[12] if ctx.has_table else None)
         dev = rays.device
@@ -106,10 +93,23 @@ class SampleStage(torch.autograd.Function):
         gt = _tensors_struct([g_grids[0:3], g_grids[3:6], g_grids[6:9], g_grids[9:12]], g_basis, g_table)
         if g_basis.numel() == 0:
             raise RuntimeError('basis_mat has no columns')
-        with torch.cuda.device(dev):
-            _lib.check(L.hr_train_backward(ctx.handle, _ptr(rays), _ptr(head), _ptr(d_rgb), rays.shape[0], ctx.white_bg, _ptr(d_head),
-                                           C.byref(gt), _stream(dev)), 'hr_train_backward')
+        _lib.call('hr_train_backward', ctx.handle, rays, head, d_rgb, rays.shape[0], ctx.white_bg, d_head, C.byref(gt), _lib.stream(dev), device=dev)
         return (None, None, d_head, None, g_basis, *g_grids) + (() if table is None else (g_table,))
+
+
+class SampleStageFields(torch.autograd.Function):
+    """SampleStage that also returns its forward's per-sample fields: apply(z_channels, <SampleStage's arguments>) ->
+    (rgb, distances (B, Z), points (B, Z, 3), render_weights (B, Z)); the three fields carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, z_channels, *args):
+        rgb, fields = SampleStage.run(ctx, z_channels, *args[:5], args[5:])
+        ctx.mark_non_differentiable(*fields)
+        return (rgb, *fields)
+
+    @staticmethod
+    def backward(ctx, d_rgb, *_):
+        return (None, *SampleStage.backward(ctx, d_rgb))
 
 
 class CoarseRows(torch.autograd.Function):
@@ -118,14 +118,12 @@ class CoarseRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, handle, rays, head, n_rows_per_ray, row_dim):
-        L = _lib.load()
         dev = rays.device
         if dev.type != 'cuda' or head.device != dev:
             raise RuntimeError('CoarseRows runs on the HIP device; there is no CPU path')
         rays, head = rays.contiguous().float(), head.contiguous().float()
         rows = torch.empty((rays.shape[0] * int(n_rows_per_ray), int(row_dim)), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.hr_train_rows_forward(handle, _ptr(rays), _ptr(head), rays.shape[0], _ptr(rows), _stream(dev)), 'hr_train_rows_forward')
+        _lib.call('hr_train_rows_forward', handle, rays, head, rays.shape[0], rows, _lib.stream(dev), device=dev)
         ctx.handle = handle
         ctx.save_for_backward(rays, head)
         ctx.shape = tuple(rows.shape)
@@ -133,15 +131,12 @@ class CoarseRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_rows):
-        L = _lib.load()
         rays, head = ctx.saved_tensors
         dev = rays.device
         d_rows = d_rows.contiguous().float()
         scratch = torch.empty(ctx.shape, dtype=torch.float32, device=dev)
         d_head = torch.empty_like(head)
-        with torch.cuda.device(dev):
-            _lib.check(L.hr_train_rows_backward(ctx.handle, _ptr(rays), _ptr(head), _ptr(d_rows), rays.shape[0], _ptr(scratch), _ptr(d_head),
-                                                _stream(dev)), 'hr_train_rows_backward')
+        _lib.call('hr_train_rows_backward', ctx.handle, rays, head, d_rows, rays.shape[0], scratch, d_head, _lib.stream(dev), device=dev)
         return None, None, d_head, None, None
 
 
@@ -171,11 +166,9 @@ def row_features(hc, rows):
 
 def ray_features(handle, rays, mlp_in):
     """rays (B, ray_dim) -> MLP input (B, mlp_in): RayParam + positional encoding on the device."""
-    L = _lib.load()
     rays = rays.contiguous().float()
     out = torch.empty((rays.shape[0], int(mlp_in)), dtype=torch.float32, device=rays.device)
-    with torch.cuda.device(rays.device):
-        _lib.check(L.hr_train_features(handle, _ptr(rays), rays.shape[0], _ptr(out), _stream(rays.device)), 'hr_train_features')
+    _lib.call('hr_train_features', handle, rays, rays.shape[0], out, _lib.stream(rays.device), device=rays.device)
     return out
 
 
@@ -185,7 +178,6 @@ class HipLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, slope):
-        L = _lib.load()
         dev = x.device
         if dev.type != 'cuda' or weight.device != dev:
             raise RuntimeError('HipLinear runs on the HIP device; there is no CPU path')
@@ -195,16 +187,13 @@ class HipLinear(torch.autograd.Function):
         w, b = weight.detach().contiguous().float(), bias.detach().contiguous().float()
         rows, fin, fout = x.shape[0], x.shape[1], w.shape[0]
         y = torch.empty((rows, fout), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.hr_linear_forward(_ptr(x), x.stride(0), rows, fin, _ptr(w), _ptr(b), fout, float(slope), _ptr(y), fout, _stream(dev)),
-                       'hr_linear_forward')
+        _lib.call('hr_linear_forward', x, x.stride(0), rows, fin, w, b, fout, float(slope), y, fout, _lib.stream(dev), device=dev)
         ctx.slope = float(slope)
         ctx.save_for_backward(x, w, y)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        L = _lib.load()
         x, w, y = ctx.saved_tensors
         dev = x.device
         dy = dy.contiguous().float()
@@ -212,11 +201,9 @@ class HipLinear(torch.autograd.Function):
         dx = torch.empty((rows, fin), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(w)
         db = torch.empty((fout,), dtype=torch.float32, device=dev)
-        ws = torch.empty((max(int(L.hr_linear_workspace(rows, fin, fout)) // 4, 1),), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.hr_linear_backward(_ptr(x), x.stride(0), _ptr(w), _ptr(y) if ctx.slope >= 0 else C.c_void_p(0), fout, _ptr(dy), fout,
-                                            rows, fin, fout, ctx.slope, _ptr(dx) if dx is not None else C.c_void_p(0), fin, _ptr(dw), _ptr(db),
-                                            _ptr(ws), _stream(dev)), 'hr_linear_backward')
+        ws = torch.empty((max(int(_lib.call('hr_linear_workspace', rows, fin, fout)) // 4, 1),), dtype=torch.float32, device=dev)
+        _lib.call('hr_linear_backward', x, x.stride(0), w, y if ctx.slope >= 0 else None, fout, dy, fout, rows, fin, fout, ctx.slope, dx, fin, dw, db,
+                  ws, _lib.stream(dev), device=dev)
         return dx, dw, db, None
 
 
@@ -228,7 +215,6 @@ class HipMLP(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, handle, rays, feats, skip_mask, n_out, *params):
-        L = _lib.load()
         dev = rays.device
         nl = len(params) // 2
         ws = [p.detach().contiguous().float() for p in params[0::2]]
@@ -255,15 +241,13 @@ class HipMLP(torch.autograd.Function):
         av = PV(*([a.data_ptr() for a in acts] + [0]))
         ldv = (C.c_int64 * nl)(*(lds + [0]))
         offv = (C.c_int32 * nl)(*(offs + [0]))
-        with torch.cuda.device(dev):
-            _lib.check(L.hr_mlp_train_forward(handle, wv, bv, _ptr(rays), n, av, ldv, offv, _ptr(head), _stream(dev)), 'hr_mlp_train_forward')
+        _lib.call('hr_mlp_train_forward', handle, wv, bv, rays, n, av, ldv, offv, head, _lib.stream(dev), device=dev)
         ctx.skip_mask, ctx.nl, ctx.fin, ctx.hidden = int(skip_mask), nl, fin, hidden
         ctx.save_for_backward(*xs, *ws)
         return head
 
     @staticmethod
     def backward(ctx, dhead):
-        L = _lib.load()
         nl, fin, hidden = ctx.nl, ctx.fin, ctx.hidden
         xs, ws = ctx.saved_tensors[:nl], ctx.saved_tensors[nl:]
         dev = dhead.device
@@ -290,11 +274,9 @@ class HipMLP(torch.autograd.Function):
                     dx = dxb[:, lead + hidden - fin_l:]
                 dw = torch.empty_like(w)
                 db = torch.empty((fout,), dtype=torch.float32, device=dev)
-                wsb = torch.empty((max(int(L.hr_linear_workspace(rows, fin_l, fout)) // 4, 1),), dtype=torch.float32, device=dev)
-                _lib.check(L.hr_linear_backward(_ptr(x), x.stride(0), _ptr(w), C.c_void_p(y_ptr), ldy, C.c_void_p(dy_ptr), ld_dy, rows, fin_l, fout,
-                                                -1.0 if last else 0.01, _ptr(dx) if dx is not None else C.c_void_p(0),
-                                                dx.stride(0) if dx is not None else fin_l, _ptr(dw), _ptr(db), _ptr(wsb), _stream(dev)),
-                           'hr_linear_backward')
+                wsb = torch.empty((max(int(_lib.call('hr_linear_workspace', rows, fin_l, fout)) // 4, 1),), dtype=torch.float32, device=dev)
+                _lib.call('hr_linear_backward', x, x.stride(0), w, C.c_void_p(y_ptr), ldy, C.c_void_p(dy_ptr), ld_dy, rows, fin_l, fout,
+                          -1.0 if last else 0.01, dx, dx.stride(0) if dx is not None else fin_l, dw, db, wsb, _lib.stream(dev))
                 grads[2 * l], grads[2 * l + 1] = dw, db
                 keep.append((dx, wsb))
                 if dx is not None:                      # upstream of layer l - 1: the hidden columns of dx (a skip layer's first fin columns belong to the input)
@@ -340,26 +322,22 @@ class PlaneReg(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plane):
-        L = _lib.load()
         if plane.device.type != 'cuda':
             raise RuntimeError('PlaneReg runs on the HIP device; there is no CPU path')
         x = plane.detach().contiguous().float()
         _, c, h, w = x.shape
         sums = torch.zeros(3, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.hr_plane_reg_forward(_ptr(x), c, h, w, _ptr(sums), _stream(x.device)), 'hr_plane_reg_forward')
+        _lib.call('hr_plane_reg_forward', x, c, h, w, sums, _lib.stream(x.device), device=x.device)
         ctx.save_for_backward(x)
         return sums
 
     @staticmethod
     def backward(ctx, d_sums):
-        L = _lib.load()
         (x,) = ctx.saved_tensors
         _, c, h, w = x.shape
         coef = d_sums.contiguous().float()
         grad = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(L.hr_plane_reg_backward(_ptr(x), c, h, w, _ptr(coef), _ptr(grad), _stream(x.device)), 'hr_plane_reg_backward')
+        _lib.call('hr_plane_reg_backward', x, c, h, w, coef, grad, _lib.stream(x.device), device=x.device)
         return grad
 
 
@@ -379,7 +357,7 @@ def background_coin(seed, step):
     """True when training step `step` of `seed` composites over white under Model.set_background_coin / GraphedStep(white_bg='coin'): the
     library's own hr_background_coin (csrc/hr_sample_rng.h), evaluated on the host."""
     m = 0xFFFFFFFFFFFFFFFF
-    return bool(_lib.load().hr_train_background_coin(int(seed) & m, int(step) & m))
+    return bool(_lib.call('hr_train_background_coin', int(seed) & m, int(step) & m))
 
 
 class HipTensoRFRegularizer:
@@ -516,7 +494,6 @@ class HipTensoRFRegularizer:
         returns the weighted value `loss(...) * loss_weight()` as a detached device scalar -- the same tensor every call.  `terms_value`
         holds the three unweighted terms of the last call.  The descriptor table is rebuilt when the model's parameters were replaced
         (shrink, upsample_volume_grid, load_state_dict)."""
-        L = _lib.load()
         if self._dev is None:
             self.sync()
         terms = self.terms()
@@ -534,12 +511,12 @@ class HipTensoRFRegularizer:
             if self._plan is None or key != self._plan_key:
                 self.close()
                 h = C.c_void_p()
-                _lib.check(L.hr_reg_plan_create(self._table(terms), len(terms), C.byref(h)), 'hr_reg_plan_create')
+                _lib.call('hr_reg_plan_create', self._table(terms), len(terms), C.byref(h))
                 self._plan, self._plan_key, self._grad_key = h, key, gkey
             elif gkey != self._grad_key:
-                _lib.check(L.hr_reg_plan_update(self._plan, self._table(terms), len(terms)), 'hr_reg_plan_update')
+                _lib.call('hr_reg_plan_update', self._plan, self._table(terms), len(terms))
                 self._grad_key = gkey
-            _lib.check(L.hr_tensorf_reg(self._plan, _ptr(self._dev), _ptr(self._loss), 0 if self.warming_up() else 1, _stream(dev)), 'hr_tensorf_reg')
+            _lib.call('hr_tensorf_reg', self._plan, self._dev, self._loss, 0 if self.warming_up() else 1, _lib.stream(dev))
         return self._loss[0]
 
     @property
@@ -549,7 +526,7 @@ class HipTensoRFRegularizer:
 
     def close(self):
         if self._plan is not None:
-            _lib.load().hr_reg_plan_destroy(self._plan)
+            _lib.call('hr_reg_plan_destroy', self._plan)
             self._plan = self._plan_key = self._grad_key = None
 
     def __del__(self):
@@ -661,7 +638,7 @@ class GraphedStep:
         st = self.optimizer.state
         ms = tuple((st[p]['exp_avg'].data_ptr(), st[p]['exp_avg_sq'].data_ptr()) if p in st and 'exp_avg' in st[p] else None
                    for g in self.optimizer.param_groups for p in g['params'])
-        return ps, ms, self.model._native_cfg
+        return ps, ms, self.model.held_config()
 
     def recapture(self, optimizer=None, warmup=1, white_bg=KEEP, bg_seed=None):
         """Runs `warmup` eager iterations (genuine steps; >= 1 whenever parameters were replaced: the native model and the moments are
@@ -710,8 +687,7 @@ class GraphedStep:
         """One replay.  Returns {'loss', 'sse'}: device tensors, overwritten by the next replay."""
         m = self.model
         if m.cur_iter != self._cur_iter:                     # set_iter since the recording: do the compiled constants still hold?
-            coarse, hc = m._compile(m.grid_size)
-            if bytes(hc) + (bytes(coarse) if coarse is not None else b'') != m._native_cfg:
+            if m.wanted_config() != m.held_config():
                 raise RuntimeError(f'GraphedStep: set_iter({m.cur_iter}) changed the compiled configuration the recorded step was built from '
                                    f'(recorded at {self._cur_iter}); call gs.recapture()')
             self._cur_iter = m.cur_iter
@@ -723,5 +699,6 @@ class GraphedStep:
             raise RuntimeError(f'GraphedStep: the regulariser left its warm-up at iteration {self._host_step}: the recorded step adds no '
                                'regulariser gradient; call gs.recapture()')
         self.graph.replay()
+        self.model.invalidate()                              # the replay stepped the parameters without moving their versions
         self._host_step += 1
         return self._out
