@@ -22,6 +22,8 @@ struct HR_HIDDEN hr_rayset {
     DevMem<HrRayImage> images_dev;
     DevMem<int64_t> prefix_dev;
     DevMem<uint8_t> pixels;
+    int bpp = 3;                          // bytes of a stored pixel: 3 (HR_PIXELS_RGB8) or 4 (HR_PIXELS_RGBA8_WHITE)
+    bool stored = false;                  // an image's pixels are in the store: the format is fixed
     // the importance rule (hr_rayset_set_image_importance): a listed image's pixel list and what it was made with
     struct Listed {
         DevMem<uint32_t> list;
@@ -122,6 +124,7 @@ HrRaySetArgs set_args(const hr_rayset* s, int64_t first, int64_t n, uint64_t see
     a.images = s->images_dev;
     a.prefix = s->prefix_dev;
     a.pixels = s->pixels;
+    a.rgba = s->bpp == 4;
     a.n_images = s->n_images; a.width = s->width; a.height = s->height; a.ray_dim = s->ray_dim;
     a.has_ndc = s->has_ndc ? 1 : 0;
     a.ndc = s->ndc;
@@ -211,6 +214,24 @@ int hr_rayset_create_lightfield(int32_t n_views, const hr_lightfield* lf, hr_ray
 
 void hr_rayset_destroy(hr_rayset* set) { delete set; }
 
+int hr_rayset_set_pixel_format(hr_rayset* set, int32_t format)
+{
+    if (!set) return fail(HR_E_INVALID, "hr_rayset_set_pixel_format: null set");
+    if (format != HR_PIXELS_RGB8 && format != HR_PIXELS_RGBA8_WHITE)
+        return fail(HR_E_INVALID, "hr_rayset_set_pixel_format: unknown format %d (HR_PIXELS_RGB8 = %d, HR_PIXELS_RGBA8_WHITE = %d)", (int)format,
+                    (int)HR_PIXELS_RGB8, (int)HR_PIXELS_RGBA8_WHITE);
+    if (set->stored)
+        return fail(HR_E_STATE, "hr_rayset_set_pixel_format: the set already holds an image: a set is RGB or RGBA as a whole, choose before the first "
+                    "hr_rayset_set_image / hr_rayset_set_view");
+    const int bpp = format == HR_PIXELS_RGBA8_WHITE ? 4 : 3;
+    if (bpp == set->bpp) return HR_OK;
+    DevMem<uint8_t> store;                 // built aside: the set keeps its store when this fails
+    HR_HIP(store.alloc((size_t)set->n_images * set->height * set->width * (size_t)bpp));
+    set->pixels = std::move(store);
+    set->bpp = bpp;
+    return HR_OK;
+}
+
 // slot i of the set (`what`: "image" / "view") and its subsample rule
 static int check_slot(const hr_rayset* set, int i, int every, int offset, const char* who, const char* what)
 {
@@ -247,8 +268,9 @@ static int rayset_commit_tables(hr_rayset* set, int i, const HrRayImage& image)
 
 static int rayset_store_pixels(hr_rayset* set, int i, const uint8_t* rgb_host_or_dev)
 {
-    const size_t bytes = (size_t)set->height * set->width * 3;
+    const size_t bytes = (size_t)set->height * set->width * (size_t)set->bpp;
     HR_HIP(hipMemcpy(set->pixels + (size_t)i * bytes, rgb_host_or_dev, bytes, hipMemcpyDefault));
+    set->stored = true;
     return HR_OK;
 }
 
@@ -296,6 +318,9 @@ int hr_rayset_set_image_importance(hr_rayset* set, int32_t i, const hr_camera* c
     if (!set || !cam || !rgb_host_or_dev) return fail(HR_E_INVALID, "%s: null argument", who);
     if (set->lightfield)
         return fail(HR_E_INVALID, "%s: the set holds light-field views (hr_rayset_create_lightfield): the importance rule is for posed video frames", who);
+    if (set->bpp != 3)
+        return fail(HR_E_INVALID, "%s: the set holds RGBA pixels (hr_rayset_set_pixel_format): the importance rule compares 8-bit RGB frames, as the "
+                    "reference's importance datasets load them", who);
     if (int rc = check_slot(set, i, 1, 0, who, "image")) return rc;
     const int64_t n_pixels = (int64_t)set->width * set->height;
     if (n_pixels >= ((int64_t)1 << 31)) return fail(HR_E_INVALID, "%s: %lld pixels per image: pixel indices are 31-bit", who, (long long)n_pixels);

@@ -232,7 +232,8 @@ struct HrRayImage {
 struct HrRaySetArgs {
     const HrRayImage* images;    // [n_images]
     const int64_t* prefix;       // [n_images + 1]: kept pixels of the images before i; prefix[n_images] = size
-    const uint8_t* pixels;       // [n_images][h][w][3], 8-bit RGB
+    const uint8_t* pixels;       // [n_images][h][w][3], 8-bit RGB; with rgba [n_images][h][w][4], 8-bit RGBA
+    int rgba;                    // the colour of a row is the pixel composited over white: rgb * alpha + (1 - alpha)
     int n_images, width, height, ray_dim;
     int has_ndc;
     hr_ndc ndc;
@@ -278,8 +279,8 @@ hipError_t hr_launch_importance_select(const HrImportanceArgs& a, hipStream_t st
 void hr_launch_image_pixels(const uint32_t* list, int width, int height, int every, int offset, int64_t first, int64_t n, int32_t* out,
                             hipStream_t stream);
 
-// one axis of PIL's 8-bit resize over a batch of same-sized RGB images (resize_kernel.hip; arithmetic and the kernel choice:
-// hr_resize.h).  Horizontal pass: `lines` image rows of 3-byte pixels become `out` pixels wide.  Vertical pass: `lines` is the BYTES of a
+// one axis of PIL's 8-bit resize over a batch of same-sized RGB or RGBA images (resize_kernel.hip; arithmetic and the kernel choice:
+// hr_resize.h).  Horizontal pass: `lines` image rows of `channels`-byte pixels become `out` pixels wide.  Vertical pass: `lines` is the BYTES of a
 // row, and `out` the output rows.  bounds (out, 2) and k (out, ksize) are hr_resize_coeffs' tables in device memory; staged, tile,
 // row_pitch, lds_bytes an hr_resize_axis_plan's; mad24 whether hr_resize_check found every |k| < 2^23.
 struct HrResizePass {
@@ -292,6 +293,8 @@ struct HrResizePass {
     const int32_t* k;
     int ksize, out, lines;
     int staged, tile, row_pitch, lds_bytes, mad24;
+    int channels;                            // bytes of a pixel: 3, or 4 for RGBA (src, dst and both pitches are then multiples of 4)
+    int premultiply, unpremultiply;          // RGBA: this pass is the first that runs (converts what it reads) / the last (what it writes)
 };
 int64_t hr_resize_pass_blocks(const HrResizePass& p, bool vertical, int n_images);      // workgroups of the launch: must stay below 2^31
 hipError_t hr_launch_resize_pass(const HrResizePass& p, bool vertical, int n_images, hipStream_t stream);

@@ -151,13 +151,39 @@ HR_RSZ_FN uint8_t hr_resize_finish(int32_t acc)
     return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
 }
 
-// one output byte: n taps, pixel bytes `stride` apart (3: along a row of RGB pixels; the row pitch: down a column)
+// one output byte: n taps, pixel bytes `stride` apart (3 or 4: along a row of RGB or RGBA pixels; the row pitch: down a column)
 template <bool MAD24>
 HR_RSZ_FN uint8_t hr_resize_dot(const uint8_t* px, int64_t stride, const int32_t* k, int32_t n)
 {
     int32_t acc = hr_resize_acc0();
     for (int32_t x = 0; x < n; ++x) acc = hr_resize_mad<MAD24>(acc, px[x * stride], k[x]);
     return hr_resize_finish(acc);
+}
+
+// ---- RGBA: PIL resamples premultiplied bytes (Image.resize of an RGBA image: RGBA -> RGBa, the resize above on all four channels,
+// RGBa -> RGBA; libImaging/Convert.c).  Both conversions are integer rules of their own; alpha passes through both unchanged.
+// colour byte c under alpha a -> premultiplied: PIL's MULDIV255, the rounded c * a / 255 without a division
+HR_RSZ_FN uint8_t hr_premultiply(uint8_t c, uint8_t a)
+{
+    const uint32_t t = (uint32_t)c * a + 128;
+    return (uint8_t)(((t >> 8) + t) >> 8);
+}
+
+// premultiplied byte c under alpha a -> colour: copied at a == 0 and a == 255, else min(255, 255 * c / a), the division truncating
+// (after a Lanczos or bicubic pass c > a occurs: the clamp is live)
+HR_RSZ_FN uint8_t hr_unpremultiply(uint8_t c, uint8_t a)
+{
+    if (a == 0 || a == 255) return c;
+    const uint32_t q = (255u * c) / a;                // exact: an integer division of 16-bit by 8-bit values
+    return (uint8_t)(q > 255 ? 255 : q);
+}
+
+// a whole pixel, alpha in the top byte (little-endian R, G, B, A)
+HR_RSZ_FN uint32_t hr_premultiply_pixel(uint32_t px)
+{
+    const uint8_t a = (uint8_t)(px >> 24);
+    return (uint32_t)hr_premultiply((uint8_t)px, a) | (uint32_t)hr_premultiply((uint8_t)(px >> 8), a) << 8
+           | (uint32_t)hr_premultiply((uint8_t)(px >> 16), a) << 16 | (px & 0xff000000u);
 }
 
 // ---- which kernel serves an axis (resize_kernel.hip) ------------------------------------------------------------------------------
@@ -192,10 +218,11 @@ static inline int32_t hr_resize_span(const int32_t* bounds, int32_t out, int32_t
     return span;
 }
 
-static inline hr_resize_axis_plan hr_resize_plan_horizontal(const int32_t* bounds, int32_t out, int64_t ksize)
+// bpp: the bytes of a pixel, 3 (RGB) or 4 (RGBA)
+static inline hr_resize_axis_plan hr_resize_plan_horizontal(const int32_t* bounds, int32_t out, int64_t ksize, int32_t bpp = 3)
 {
     hr_resize_axis_plan p = {0, HR_RESIZE_H_TILE, hr_resize_span(bounds, out, HR_RESIZE_H_TILE), 0, 0};
-    const int64_t pitch = ((int64_t)p.span * 3 + 15 + 15) / 16 * 16;               // the span, wherever its first byte falls in a 16-byte chunk
+    const int64_t pitch = ((int64_t)p.span * bpp + 15 + 15) / 16 * 16;               // the span, wherever its first byte falls in a 16-byte chunk
     const int64_t lds = (int64_t)HR_RESIZE_H_TILE * ksize * 4 + HR_RESIZE_H_ROWS * pitch;
     if (lds <= HR_RESIZE_LDS_BUDGET) {
         p.staged = 1;
@@ -205,9 +232,11 @@ static inline hr_resize_axis_plan hr_resize_plan_horizontal(const int32_t* bound
     return p;
 }
 
-static inline hr_resize_axis_plan hr_resize_plan_vertical(const int32_t* bounds, int32_t out, int64_t ksize)
+// (a vertical tile spans bytes, whatever pixel they belong to: bpp changes nothing here)
+static inline hr_resize_axis_plan hr_resize_plan_vertical(const int32_t* bounds, int32_t out, int64_t ksize, int32_t bpp = 3)
 {
     (void)ksize;
+    (void)bpp;
     hr_resize_axis_plan p = {0, 1, 0, HR_RESIZE_V_PITCH, 0};
     for (int32_t tile = 8; tile >= 1; tile >>= 1) {
         p.tile = tile;

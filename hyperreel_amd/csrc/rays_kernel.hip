@@ -96,7 +96,14 @@ __device__ __forceinline__ void rayset_write_row(const HrRaySetArgs& a, int64_t 
             hr_pixel_ray_fisheye(im.cam, im.has_fe ? &im.fe : nullptr, a.has_ndc ? &a.ndc : nullptr, x, y, v);
             v[6] = im.cam.cam_id; v[7] = im.cam.time;
         }
-        if (a.rgb) {
+        if (a.rgb && a.rgba) {
+            // RGBA over white (datasets/blender.py:61-70): ToTensor, then rgb * alpha + (1 - alpha), one float32 rounding per
+            // operation as torch computes it -- no multiply-add is contracted out of these
+            const uint32_t px = reinterpret_cast<const uint32_t*>(a.pixels)[((int64_t)lo * a.height + y) * a.width + x];
+            const float al = (float)(px >> 24) / 255.0f, rest = __fsub_rn(1.0f, al);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) c[k] = __fadd_rn(__fmul_rn((float)((px >> (8 * k)) & 255u) / 255.0f, al), rest);
+        } else if (a.rgb) {
             const uint8_t* px = a.pixels + (((int64_t)lo * a.height + y) * a.width + x) * 3;
             c[0] = (float)px[0] / 255.0f; c[1] = (float)px[1] / 255.0f; c[2] = (float)px[2] / 255.0f;   // ToTensor
         }

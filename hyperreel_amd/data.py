@@ -42,7 +42,7 @@ class Importance(collections.namedtuple('Importance', ['num_take', 'prev', 'dir_
     __slots__ = ()
 
 
-def _parse_rules(subsample, n, n_pixels, lightfield=False):
+def _parse_rules(subsample, n, n_pixels, lightfield=False, alpha=None):
     """None | a rule name | one (every, offset) or Importance per image -> the per-image list, checked before any library call."""
     if isinstance(subsample, str):
         _refuse_rule(subsample)
@@ -53,6 +53,9 @@ def _parse_rules(subsample, n, n_pixels, lightfield=False):
         if isinstance(r, Importance):
             if lightfield:
                 raise ValueError(f'view {i}: the importance rule compares video frames of posed cameras; a light-field set takes (every, offset) pairs only')
+            if alpha is not None:
+                raise ValueError(f'image {i}: the importance rule compares 8-bit RGB frames (the reference\'s importance datasets load RGB); '
+                                 f'a set with alpha={alpha!r} takes (every, offset) pairs only')
             take, prev = int(r.num_take), (i - 1 if r.prev is None else int(r.prev))
             if take < 1:
                 raise ValueError(f'image {i}: Importance num_take {take} < 1 (with 0 the reference\'s diff_sorted[-0] is the minimum and its rule '
@@ -150,27 +153,39 @@ def stanford_normalize_coord(coord, camera_coords):
     return (norm_x, norm_y)
 
 
-def _as_u8_image(img, i, H, W):
+def _as_u8_image(img, i, H, W, channels=3):
     img = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
-    if img.dtype != torch.uint8 or tuple(img.shape) != (H, W, 3):
-        raise ValueError(f'image {i}: expected uint8 ({H}, {W}, 3), got {img.dtype} {tuple(img.shape)}')
+    if img.dtype != torch.uint8 or tuple(img.shape) != (H, W, channels):
+        raise ValueError(f'image {i}: expected uint8 ({H}, {W}, {channels}), got {img.dtype} {tuple(img.shape)}')
     return img.contiguous()
+
+
+def _alpha_channels(alpha):
+    """alpha=None: 8-bit RGB, 3 bytes a pixel; 'white': 8-bit RGBA composited over white, 4."""
+    if alpha is None:
+        return 3
+    if alpha != 'white':
+        raise ValueError(f"alpha must be None (8-bit RGB images) or 'white' (8-bit RGBA images over white, the reference's only background); got {alpha!r}")
+    return 4
 
 
 class DeviceRaySet:
     """images_u8: (n, H, W, 3) uint8 (numpy, or a torch tensor on the host or the device), RGB as Image.convert("RGB") holds
     them; poses (n, 3, 4); intrinsics (n, 3, 3) or one (3, 3); times, cam_ids: (n) or None (6-column rays); img_wh = (W, H);
-    ndc: None | dict(fx, fy, near, width, height) | hr_ndc; subsample: None (every pixel) or, per image, one (every, offset)
+    ndc: None | dict(fx, fy, near, width, height) | hr_ndc; alpha: None, or 'white' -- images_u8 is then (n, H, W, 4) uint8, RGBA as
+    Image.convert("RGBA") holds them, and a row's rgb is the pixel over white, rgb * a + (1 - a) on bytes / 255, bit for bit what the
+    reference's RGBA datasets train on (datasets/blender.py:61-70, donerf.py:240-249); subsample: None (every pixel) or, per image, one (every, offset)
     (DeviceRaySet.video_rule builds the reference's) or one Importance(...) (DeviceRaySet.importance_rule), mixed freely; distortions: None (pinhole cameras) or (n, 2), each image's fisheye (k1, k2)
     (ImmersiveDataset.distortions[idx][:2]).  Element e of the set is row e of the reference's all_inputs."""
 
-    def __init__(self, images_u8, poses, intrinsics, times, cam_ids, img_wh, ndc=None, subsample=None, device=None, distortions=None):
+    def __init__(self, images_u8, poses, intrinsics, times, cam_ids, img_wh, ndc=None, subsample=None, device=None, distortions=None, alpha=None):
         if isinstance(subsample, str):
             _refuse_rule(subsample)
+        self._channels = _alpha_channels(alpha)
         W, H = int(img_wh[0]), int(img_wh[1])
         poses = np.asarray(poses, np.float32)
         n = poses.shape[0]
-        rules = _parse_rules(subsample, n, W * H)
+        rules = _parse_rules(subsample, n, W * H, alpha=alpha)
         Ks = np.asarray(intrinsics, np.float32)
         Ks = np.broadcast_to(Ks, (n, 3, 3)) if Ks.ndim == 2 else Ks
         self.ray_dim = 8 if times is not None else 6
@@ -202,8 +217,9 @@ class DeviceRaySet:
                    'images, poses, intrinsics, times, cam_ids and subsample must describe the same number of images', set_importance)
 
     @classmethod
-    def from_lightfield(cls, images_u8, st, lightfield, subsample=None, device=None):
-        """A set of two-plane light-field views (hr_rayset_create_lightfield): images_u8 (n, V, U, 3) uint8 as for the constructor,
+    def from_lightfield(cls, images_u8, st, lightfield, subsample=None, device=None, alpha=None):
+        """A set of two-plane light-field views (hr_rayset_create_lightfield): images_u8 (n, V, U, 3) uint8 as for the constructor
+        ((n, V, U, 4) with alpha='white'),
         st: (n, 2) the views' (s, t) -- lightfield_coord or stanford_normalize_coord of each -- in the order the reference's
         prepare_train_data visits them, t outer and s inner (datasets/lightfield.py:106-141); lightfield: make_lightfield(...).
         Element e is row e of that order's concatenated get_lightfield_rays; rays have 6 columns."""
@@ -213,8 +229,10 @@ class DeviceRaySet:
             raise TypeError('lightfield must be an hr_lightfield (data.make_lightfield)')
         st = np.asarray(st, np.float64).reshape(-1, 2)
         n = st.shape[0]
-        rules = _parse_rules(subsample, n, int(lightfield.width) * int(lightfield.height), lightfield=True)
+        channels = _alpha_channels(alpha)
+        rules = _parse_rules(subsample, n, int(lightfield.width) * int(lightfield.height), lightfield=True, alpha=alpha)
         self = cls.__new__(cls)
+        self._channels = channels
         self.ray_dim = 6
         self._ndc = None
         self._lightfield = lightfield
@@ -235,13 +253,18 @@ class DeviceRaySet:
         set_importance(i, rule, pixels) under an Importance rule, and the set's size.  The callables check their own C call."""
         if not all(len(seq) == n for seq in (images_u8, rules, *per_image)):
             raise ValueError(mismatch)
+        channels = self._channels
+        if channels == 4:                      # an RGBA set checks its images before any device work: RGB bytes would be read as RGBA
+            images_u8 = [_as_u8_image(images_u8[i], i, H, W, 4) for i in range(n)]
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.width, self.height, self.n_images = W, H, n
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             create(C.byref(self._h))
+            if channels == 4:
+                _lib.call('hr_rayset_set_pixel_format', self._h, _lib.HR_PIXELS_RGBA8_WHITE)
             for i in range(n):
-                img = _as_u8_image(images_u8[i], i, H, W)
+                img = _as_u8_image(images_u8[i], i, H, W, channels)
                 if isinstance(rules[i], Importance):
                     set_importance(i, rules[i], img)
                 else:
@@ -417,23 +440,35 @@ def _resize_wh(wh, what):
     return int(w), int(h)
 
 
-def _as_u8_batch(images_u8, wh=None):
-    """(n, H, W, 3) or (H, W, 3) uint8 as numpy, a host tensor or a device tensor -> a contiguous (n, H, W, 3) tensor where it lives"""
+RESIZE_MODES = {'RGB': 3, 'RGBA': 4}          # PIL's mode names -> bytes of a pixel
+
+
+def _resize_mode(mode):
+    if mode not in RESIZE_MODES:
+        raise ValueError(f'resize mode {mode!r} is not one of {sorted(RESIZE_MODES)} (PIL\'s other modes, LA among them, are not provided)')
+    return RESIZE_MODES[mode]
+
+
+def _as_u8_batch(images_u8, wh=None, channels=3):
+    """(n, H, W, 3) or (H, W, 3) uint8 as numpy, a host tensor or a device tensor -> a contiguous (n, H, W, 3) tensor where it lives
+    (channels=4: the same of RGBA images)"""
     if not isinstance(images_u8, torch.Tensor):
         a = np.ascontiguousarray(images_u8)
         images_u8 = torch.from_numpy(a if a.flags.writeable else a.copy())        # (torch refuses to wrap a read-only array silently)
     t = images_u8
     if t.ndim == 3:
         t = t[None]
-    if t.dtype != torch.uint8 or t.ndim != 4 or t.shape[-1] != 3 or t.shape[0] < 1:
-        raise ValueError(f'images must be uint8 (n, H, W, 3) or (H, W, 3), 8-bit RGB; got {t.dtype} {tuple(t.shape)}')
+    if t.dtype != torch.uint8 or t.ndim != 4 or t.shape[-1] != channels or t.shape[0] < 1:
+        raise ValueError(f'images must be uint8 (n, H, W, {channels}) or (H, W, {channels}), 8-bit {"RGBA" if channels == 4 else "RGB"}; '
+                         f'got {t.dtype} {tuple(t.shape)}')
     if wh is not None and (t.shape[2], t.shape[1]) != tuple(wh):
         raise ValueError(f'images are {t.shape[2]} x {t.shape[1]} (W x H), the resize was made for {wh[0]} x {wh[1]}')
     return t.contiguous()
 
 
 class DeviceResize:
-    """PIL's Image.resize of 8-bit RGB images on the device, byte for byte: src_wh = (W, H) -> dst_wh = (W2, H2) with filter 'lanczos' |
+    """PIL's Image.resize of 8-bit RGB images -- or, with mode='RGBA', of 8-bit RGBA images, (.., 4) wherever (.., 3) stands below:
+    PIL resamples them premultiplied and converts back -- on the device, byte for byte: src_wh = (W, H) -> dst_wh = (W2, H2) with filter 'lanczos' |
     'bicubic' | 'bilinear' | 'box' (Image.LANCZOS, BICUBIC -- Image.resize's default -- BILINEAR, BOX), up to max_images images a launch.
     Calling it with images_u8 takes (n, H, W, 3) or (H, W, 3) uint8 as numpy, a host tensor or a device tensor and returns a device uint8 tensor
     (n, H2, W2, 3), which DeviceRaySet accepts as images_u8; it runs on torch's current stream, and more than max_images images go in
@@ -441,10 +476,11 @@ class DeviceResize:
     close().  No CPU path: a missing library or a failing call raises.
 
     Out of scope: cv2.resize, which datasets/immersive.py:579, neural_3d.py:416 and donerf.py:242 call (another arithmetic, and two of
-    those calls pass the filter where cv2 takes dst); decoding image files; modes other than 8-bit RGB; Image.resize's box= and
-    reducing_gap=."""
+    those calls pass the filter where cv2 takes dst); decoding image files; modes other than 8-bit RGB and RGBA (LA among them);
+    Image.resize's box= and reducing_gap=."""
 
-    def __init__(self, src_wh, dst_wh, filter='lanczos', max_images=1, device=None):
+    def __init__(self, src_wh, dst_wh, filter='lanczos', max_images=1, device=None, mode='RGB'):
+        self.mode, self._channels = mode, _resize_mode(mode)
         self.src_wh, self.dst_wh = _resize_wh(src_wh, 'src_wh'), _resize_wh(dst_wh, 'dst_wh')
         self.filter = filter
         number = _resize_filter(filter)
@@ -453,7 +489,7 @@ class DeviceResize:
             raise ValueError(f'max_images {max_images} < 1')
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self._h = C.c_void_p()
-        _lib.call('hr_resize_plan_create', self.src_wh[0], self.src_wh[1], self.dst_wh[0], self.dst_wh[1], number, self.max_images,
+        _lib.call('hr_resize_plan_create_rgba' if self._channels == 4 else 'hr_resize_plan_create', self.src_wh[0], self.src_wh[1], self.dst_wh[0], self.dst_wh[1], number, self.max_images,
                   C.byref(self._h), device=self.device)
 
     def close(self):
@@ -467,13 +503,14 @@ class DeviceResize:
         """out: None (a fresh tensor) or a contiguous uint8 (n, H2, W2, 3) tensor on the plan's device (a fixed buffer for a captured graph)"""
         if not getattr(self, '_h', None):
             raise RuntimeError('DeviceResize is closed')
-        src = _as_u8_batch(images_u8, self.src_wh).to(self.device)
+        ch = self._channels
+        src = _as_u8_batch(images_u8, self.src_wh, ch).to(self.device)
         n, (W2, H2) = src.shape[0], self.dst_wh
         if out is None:
-            out = torch.empty((n, H2, W2, 3), dtype=torch.uint8, device=self.device)
-        elif out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous() or tuple(out.shape) != (n, H2, W2, 3):
-            raise ValueError(f'out must be a contiguous uint8 ({n}, {H2}, {W2}, 3) tensor on {self.device}')
-        per_src, per_dst = src.shape[1] * src.shape[2] * 3, H2 * W2 * 3
+            out = torch.empty((n, H2, W2, ch), dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous() or tuple(out.shape) != (n, H2, W2, ch):
+            raise ValueError(f'out must be a contiguous uint8 ({n}, {H2}, {W2}, {ch}) tensor on {self.device}')
+        per_src, per_dst = src.shape[1] * src.shape[2] * ch, H2 * W2 * ch
         with torch.cuda.device(self.device):
             for first in range(0, n, self.max_images):
                 _lib.call('hr_image_resize', self._h, C.c_void_p(src.data_ptr() + first * per_src), min(self.max_images, n - first),
@@ -481,19 +518,22 @@ class DeviceResize:
         return out
 
 
-def reference_resize(images_u8, _img_wh, img_wh=None, first='lanczos', device=None):
+def reference_resize(images_u8, _img_wh, img_wh=None, first='lanczos', device=None, mode='RGB'):
     """get_rgb's two steps (datasets/llff.py:145-163): img.resize(_img_wh, Image.LANCZOS), then img.resize(img_wh, Image.BOX) when
     img_wh differs from _img_wh.  A step at equal size is no operation (Image.resize returns a copy).  first='bicubic' is
     datasets/catacaustics.py:298, whose img.resize(wh) takes PIL's default.  images_u8 as for DeviceResize; returns a device uint8
-    tensor (n, H, W, 3) of the last size.  Out of scope: see DeviceResize."""
+    tensor (n, H, W, 3) of the last size.  mode='RGBA': (.., 4) images as Image.convert('RGBA') holds them (datasets/blender.py:61-70,
+    donerf.py:240-249); each step is then a full RGBA resize, the image between the two un-premultiplied 8-bit RGBA.  Out of scope: see
+    DeviceResize."""
+    channels = _resize_mode(mode)
     wh1 = _resize_wh(_img_wh, '_img_wh')
     wh2 = wh1 if img_wh is None else _resize_wh(img_wh, 'img_wh')
     _resize_filter(first)
-    x = _as_u8_batch(images_u8)
+    x = _as_u8_batch(images_u8, channels=channels)
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     for wh, name in ((wh1, first), (wh2, 'box')):
         if (x.shape[2], x.shape[1]) != wh:
-            step = DeviceResize((x.shape[2], x.shape[1]), wh, name, max_images=min(x.shape[0], 8), device=device)
+            step = DeviceResize((x.shape[2], x.shape[1]), wh, name, max_images=min(x.shape[0], 8), device=device, mode=mode)
             try:
                 x = step(x)
             finally:
@@ -508,3 +548,17 @@ def as_float(images_u8_dev):
     if images_u8_dev.dtype != torch.uint8 or images_u8_dev.shape[-1] != 3:
         raise ValueError(f'as_float takes uint8 (..., 3) images, got {images_u8_dev.dtype} {tuple(images_u8_dev.shape)}')
     return images_u8_dev.reshape(-1, 3).float().div(255)
+
+
+def composite_white(images_rgba_u8_dev):
+    """(n, H, W, 4) uint8 RGBA -> (n * H * W, 3) float32 over white: ToTensor, view(4, -1).permute(1, 0), then
+    img[:, :3] * img[:, -1:] + (1 - img[:, -1:]) (datasets/blender.py:61-70), as_float's counterpart for an RGBA dataset: the ground
+    truth get_rgb hands model.evaluate, and bit for bit the rgb a DeviceRaySet(alpha='white') row holds.  Plain torch ops, each one
+    float32 rounding and the division a true one: no kernel of the library is involved."""
+    if images_rgba_u8_dev.dtype != torch.uint8 or images_rgba_u8_dev.shape[-1] != 4:
+        raise ValueError(f'composite_white takes uint8 (..., 4) images, got {images_rgba_u8_dev.dtype} {tuple(images_rgba_u8_dev.shape)}')
+    # a device tensor as the divisor: torch's device kernels divide by a host scalar as a multiplication by 1 / 255, which differs on 126 bytes
+    x = images_rgba_u8_dev.reshape(-1, 4).float() / torch.full((), 255.0, dtype=torch.float32, device=images_rgba_u8_dev.device)
+    a = x[:, 3:]
+    prod = x[:, :3] * a
+    return prod + (1 - a)

@@ -59,6 +59,10 @@ class hr_verify_info(C.Structure):
                 ('n_rays', C.c_int64), ('n_rays_used', C.c_int64), ('n_samples', C.c_int64), ('n_flipped', C.c_int64), ('n_shaky', C.c_int64)]
 
 
+# hr_rayset_set_pixel_format's formats (include/hyperreel_hip.h)
+HR_PIXELS_RGB8, HR_PIXELS_RGBA8_WHITE = 0, 1
+
+
 class hr_rayset_image_info(C.Structure):
     """Result of hr_rayset_image_info (include/hyperreel_hip.h)."""
     _fields_ = [('count', C.c_int64), ('num_take', C.c_int64), ('every', C.c_int32), ('offset', C.c_int32), ('is_list', C.c_int32),
@@ -113,6 +117,8 @@ SYMBOLS = [
     ('hr_resize_plan_create', C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     ('hr_image_resize', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     ('hr_resize_plan_destroy', None, [C.c_void_p]),
+    ('hr_resize_plan_create_rgba', C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    ('hr_rayset_set_pixel_format', C.c_int, [C.c_void_p, C.c_int32]),
     ('hr_upsample_plane', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ('hr_train_features', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ('hr_train_rows_forward', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -535,6 +535,17 @@ int hr_generate_rays_epi(const hr_lightfield* lf, float v, float t, int64_t firs
  * NULL: world-space rays).  The library owns the pixel store (n_images * height * width * 3 bytes) and the per-image table. */
 int hr_rayset_create(int32_t n_images, int32_t width, int32_t height, int32_t ray_dim, const hr_ndc* ndc, hr_rayset** out);
 void hr_rayset_destroy(hr_rayset* set);
+/* What the set's pixels are: a set is one format as a whole, HR_PIXELS_RGB8 when this is never called.
+ *   HR_PIXELS_RGBA8_WHITE  every hr_rayset_set_image* / hr_rayset_set_view then takes height * width * 4 bytes of RGBA, what
+ *     Image.convert("RGBA") holds, and a row's colour is the pixel over white as the reference's RGBA datasets compute it
+ *     (datasets/blender.py:61-70, donerf.py:240-249): C = byte / 255, rgb = C * A + (1 - A) in float32, one rounding per operation --
+ *     bit for bit torch's.  Coordinates, weights, elements and the order are those of the RGB set of the same cameras.
+ * Valid on a set of either kind (hr_rayset_create, hr_rayset_create_lightfield) before its first image is stored: afterwards
+ * HR_E_STATE and nothing changes.  Replaces the pixel store (n_images * height * width * 4 bytes).  HR_E_INVALID: a NULL set, an unknown
+ * format.  hr_rayset_set_image_importance on an RGBA set is HR_E_INVALID: the reference's importance datasets are RGB.
+ * Additive: no existing struct or signature moved (HR_ABI_VERSION stays). */
+enum { HR_PIXELS_RGB8 = 0, HR_PIXELS_RGBA8_WHITE = 1 };
+int hr_rayset_set_pixel_format(hr_rayset* set, int32_t format);
 /* Image i: pose, intrinsics, cam_id and time in `cam` (its width / height must be the set's), the subsample rule (every >= 1,
  * offset >= 0) and height * width * 3 bytes of RGB, row-major, host or device memory -- what Image.convert("RGB") holds before ToTensor
  * (get_rgb, technicolor.py:398-417).  Synchronous (set-up, not the training loop).  Images not yet set hold no rays. */
@@ -628,6 +639,13 @@ int hr_rayset_image_info(const hr_rayset* set, int32_t i, struct hr_rayset_image
  * a coefficient row that fails the accumulator check. */
 typedef struct hr_resize_plan hr_resize_plan;
 int hr_resize_plan_create(int32_t w, int32_t h, int32_t w2, int32_t h2, int32_t filter, int32_t max_images, hr_resize_plan** out);
+/* The same for 8-bit RGBA images, (h, w, 4) bytes: Image.resize of an RGBA image, which is not the RGB resize on four channels -- PIL
+ * converts to premultiplied RGBa (c * a / 255, rounded), resamples the four channels by the rule above and converts back (copied at
+ * alpha 0 and 255, else min(255, 255 * c / a), truncated); csrc/hr_resize.h states both.  Same size on both axes: a copy, nothing is
+ * converted (a pixel of alpha 0 keeps its colour bytes).  hr_image_resize on such a plan reads and writes 4 bytes per pixel and wants
+ * src_dev and dst_dev 4-byte aligned (HR_E_INVALID otherwise).  Refusals as hr_resize_plan_create, under its name.
+ * Additive: no existing struct or signature moved (HR_ABI_VERSION stays). */
+int hr_resize_plan_create_rgba(int32_t w, int32_t h, int32_t w2, int32_t h2, int32_t filter, int32_t max_images, hr_resize_plan** out);
 /* src_dev: n_images images (h, w, 3) -> dst_dev: n_images images (h2, w2, 3), both dense in device memory and not overlapping; exactly
  * n_images * h2 * w2 * 3 bytes are written.  Only kernels (same size on both axes: one device-to-device copy) on `stream`: no
  * host-to-device copy, no allocation, no synchronisation; capturable in a hipGraph.  Calls on one plan share its intermediate image:

@@ -3,7 +3,10 @@ hipGraph, for the technicolor-shaped set with real pixels (800 images of 2048 x 
 small fixture set (tests/golden/camera/video_ndc.npz); beside it, from the same run, (a) the training step of
 tools/train_bench.py on the technicolor model and (b) the reference's form of the feed: slicing 16 384 rows of a pinned host
 all_inputs float tensor (12 floats per ray) and copying them to the device.
-python tools/batch_ab.py [--seconds S] [--rounds R] [--images N] [--out F]
+A Blender-shaped pair rides along (100 images of 800 x 800, world rays): the same cameras as an RGB set and as an RGBA set composited
+over white (DeviceRaySet(alpha='white')), and the donerf_sphere training step replayed from a GraphedStep fed by each.
+--rgba-only measures that pair alone.
+python tools/batch_ab.py [--seconds S] [--rounds R] [--images N] [--rgba-only] [--out F]
 Each timed window is preceded by a time-based warm-up of the same call and lasts --seconds; the variants alternate inside a round and
 the best window is quoted.  Nothing is asserted: the numbers are printed.  Measurement aid (GPU box)."""
 import argparse
@@ -25,6 +28,7 @@ ap.add_argument('--seconds', type=float, default=0.5, help='length of a timed wi
 ap.add_argument('--rounds', type=int, default=3)
 ap.add_argument('--images', type=int, default=800, help='images of 2048 x 1088 in the large set')
 ap.add_argument('--batch', type=int, default=16384)
+ap.add_argument('--rgba-only', action='store_true', help='only the Blender-shaped RGB / RGBA pair and the DoNeRF step fed by each')
 ap.add_argument('--out', default='')
 args = ap.parse_args()
 assert torch.cuda.is_available(), 'tools/batch_ab.py measures on the HIP device'
@@ -95,8 +99,35 @@ def large_set(n_images):
                         (W, H), ndc=dict(fx=2400.0, fy=2400.0, near=0.95, width=W, height=H))
 
 
+def blender_set(alpha, n_images=100):
+    """Blender's shape: 100 images of 800 x 800 on a circle about the origin looking inwards, every pixel kept; alpha=None takes the RGB
+    bytes of the same RGBA images (pixels from a seeded generator on the device, alpha 0 / 255 on half of the images, any byte on the rest)"""
+    W = H = 800
+    gen = torch.Generator(device='cuda').manual_seed(1)
+    poses = []
+    for i in range(n_images):
+        a = 2 * np.pi * i / n_images
+        z = np.array([np.sin(a), 0.0, np.cos(a)])                       # the camera looks down -z of its frame, at the origin
+        x = np.array([np.cos(a), 0.0, -np.sin(a)])
+        poses.append(np.stack([x, np.array([0.0, 1.0, 0.0]), z, 4.0 * z], 1))
+    K = np.array([[1111.0, 0, W / 2], [0, 1111.0, H / 2], [0, 0, 1]])
+
+    class Images:
+        def __len__(self):
+            return n_images
+
+        def __getitem__(self, i):
+            img = torch.randint(0, 256, (H, W, 4), dtype=torch.uint8, device='cuda', generator=gen)
+            if i % 2 == 0:
+                img[..., 3] = (img[..., 3] >> 7) * 255
+            return img if alpha else img[..., :3].contiguous()
+
+    return DeviceRaySet(Images(), np.asarray(poses), K, None, None, (W, H), alpha=alpha)
+
+
 res = {'batch': BS, 'threads': len(os.sched_getaffinity(0))}
-sets = {'small_fixture_set': small_set(), 'technicolor_shaped_set': large_set(args.images)}
+sets = {} if args.rgba_only else {'small_fixture_set': small_set(), 'technicolor_shaped_set': large_set(args.images)}
+sets.update({'blender_shaped_rgb_set': blender_set(None), 'blender_shaped_rgba_set': blender_set('white')})
 steps, graphs, keep = {}, {}, []
 for name, s in sets.items():
     out = {'coords': torch.empty((BS, s.ray_dim), device='cuda'), 'rgb': torch.empty((BS, 3), device='cuda'), 'weight': torch.empty((BS, 1), device='cuda')}
@@ -110,7 +141,7 @@ for name, s in sets.items():
 
     steps[name] = eager
     graphs[name] = graph_of(lambda s=s, out=out: s.batch(1, BS, epoch=0, seed=0, out=out))
-    res[name] = {'rays': len(s), 'images': s.n_images, 'pixel_store_gb': round(s.n_images * s.width * s.height * 3 / 1e9, 3)}
+    res[name] = {'rays': len(s), 'images': s.n_images, 'pixel_store_gb': round(s.n_images * s.width * s.height * s._channels / 1e9, 3)}
 
 # (b) the reference's feed: rows [i * BS, (i + 1) * BS) of a pinned host all_inputs (the epoch's shuffle already applied), to the device
 rows = 64 * BS
@@ -133,6 +164,35 @@ for _ in range(args.rounds):
     ms.setdefault('host_slice_copy', []).append(timed(host_feed, args.seconds))
 res['ms_best'] = {k: round(min(v), 5) for k, v in ms.items()}
 res['ms_all'] = {k: [round(x, 5) for x in v] for k, v in ms.items()}
+# the DoNeRF training step, replayed from one graph, fed by the RGB and by the RGBA set of the same cameras
+from hyperreel_amd import config as HC, scenes  # noqa: E402
+from hyperreel_amd.losses import HipImageLoss  # noqa: E402
+from hyperreel_amd.optim import HipAdam  # noqa: E402
+from hyperreel_amd.render import build_render_fn  # noqa: E402
+from hyperreel_amd.train import GraphedStep  # noqa: E402
+
+
+def donerf_step(rayset):
+    cfg, ds = HC.model_config('donerf_sphere'), HC.dataset_scalars('donerf_sphere')
+    sd = scenes.make_state_dict(cfg, ds, None, seed=7, density='dense', app_scale=1.0)
+    fn = build_render_fn(cfg, dataset=ds, grid_size=[int(v) for v in sd['model.color_model.net.gridSize']])
+    fn.model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=False)
+    fn.train()
+    opt = HipAdam([p for p in fn.model.parameters() if p.requires_grad], lr=1e-3, betas=(0.9, 0.99), eps=1e-8, capturable=True)
+    return GraphedStep(fn.model, opt, rayset, BS, loss=HipImageLoss('mse'), seed=0, white_bg=True, warmup=3)
+
+
+fed = {name: donerf_step(sets[name]) for name in ('blender_shaped_rgb_set', 'blender_shaped_rgba_set')}
+step_ms = {}
+for _ in range(args.rounds):
+    for name, gs in fed.items():
+        step_ms.setdefault('donerf_step_fed_by_' + name, []).append(timed(gs.step, args.seconds))
+ms.update(step_ms)
+res['ms_best'] = {k: round(min(v), 5) for k, v in ms.items()}
+res['ms_all'] = {k: [round(x, 5) for x in v] for k, v in ms.items()}
+best = res['ms_best']
+res['rgba_over_rgb'] = {k: round(best[f'{k}_blender_shaped_rgba_set'] / best[f'{k}_blender_shaped_rgb_set'], 4) for k in ('eager', 'graph', 'donerf_step_fed_by')}
+del fed
 print(json.dumps(res), flush=True)
 for s in sets.values():
     s.close()
@@ -140,10 +200,11 @@ del sets, steps, graphs, keep
 torch.cuda.empty_cache()
 
 # (a) the training step the batch feeds
-from train_bench import train_step_figures  # noqa: E402
-fig = train_step_figures('technicolor_z_plane', BS, steps=30)
-res['train_step'] = {k: v for k, v in fig.items() if isinstance(v, (int, float, str))}
-print(json.dumps(res['train_step']), flush=True)
+if not args.rgba_only:
+    from train_bench import train_step_figures  # noqa: E402
+    fig = train_step_figures('technicolor_z_plane', BS, steps=30)
+    res['train_step'] = {k: v for k, v in fig.items() if isinstance(v, (int, float, str))}
+    print(json.dumps(res['train_step']), flush=True)
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
