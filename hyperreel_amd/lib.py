@@ -61,6 +61,9 @@ class hr_verify_info(C.Structure):
 
 # hr_rayset_set_pixel_format's formats (include/hyperreel_hip.h)
 HR_PIXELS_RGB8, HR_PIXELS_RGBA8_WHITE = 0, 1
+# hr_png_encode's pixel types and its adaptive filter mode (the fixed ones are the PNG filter numbers 0..4)
+HR_PNG_U8, HR_PNG_F32_TO8B = 0, 1
+HR_PNG_FILTER_ADAPTIVE = 5
 
 
 class hr_rayset_image_info(C.Structure):
@@ -118,6 +121,10 @@ SYMBOLS = [
     ('hr_image_resize', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     ('hr_resize_plan_destroy', None, [C.c_void_p]),
     ('hr_resize_plan_create_rgba', C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    ('hr_png_bound', C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    ('hr_png_encoder_create', C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    ('hr_png_encode', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ('hr_png_encoder_destroy', None, [C.c_void_p]),
     ('hr_rayset_set_pixel_format', C.c_int, [C.c_void_p, C.c_int32]),
     ('hr_upsample_plane', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ('hr_train_features', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -654,6 +654,31 @@ int hr_resize_plan_create_rgba(int32_t w, int32_t h, int32_t w2, int32_t h2, int
 int hr_image_resize(const hr_resize_plan* p, const uint8_t* src_dev, int32_t n_images, uint8_t* dst_dev, void* stream);
 void hr_resize_plan_destroy(hr_resize_plan* p);
 
+/* ---- PNG files on the device (csrc/hr_png.h states the format arithmetic once) ----
+ * A frame that is already in device memory becomes a complete, standard PNG file in device memory: signature, IHDR, one IDAT chunk
+ * per strip of rows, IEND; 8 bits a sample, non-interlaced, `channels` 1 (grey), 3 (RGB) or 4 (RGBA).  The host copies `*file_bytes_dev`
+ * bytes and writes them.  pixels_dev is row-major (h, w, channels), contiguous: HR_PNG_U8 bytes, or HR_PNG_F32_TO8B floats that go
+ * through the display pack's to8b as they are read -- (uint8)(255 * clip(x, 0, 1)), NaN giving 0 (numpy's own cast of NaN is
+ * undefined).  filter_mode: HR_PNG_FILTER_ADAPTIVE (per row, the filter with the smallest sum of min(v, 256 - v); lowest index on a
+ * tie) or a fixed PNG filter 0..4.  Integer arithmetic and integer LDS atomics only: the same frame gives the same file on every run,
+ * and the host build of hr_png.h (hr_png_encode_host) gives the same bytes.
+ * hr_png_bound: a capacity that always suffices (every strip falls back to stored blocks when its Huffman block is not smaller).
+ * hr_png_encoder_create: the encoder owns its workspace in device memory (current device).  hr_png_encode: three kernels and a
+ * one-workgroup scan on `stream`; no allocation, no synchronisation, no host read-back, no memset; capturable in a hipGraph.  Nothing
+ * beyond *file_bytes_dev bytes of file_dev is written.  One encode at a time per encoder (the workspace is its own).
+ * HR_E_INVALID before anything is launched or written: w or h below 1 (or a row beyond 2^27 bytes, an image beyond 2^30 filtered bytes), channels not in
+ * {1, 3, 4}, capacity below hr_png_bound, a NULL pointer, an unknown pixel_type or filter_mode.
+ * Additive: no existing struct or signature moved (HR_ABI_VERSION stays). */
+#define HR_PNG_U8 0
+#define HR_PNG_F32_TO8B 1
+#define HR_PNG_FILTER_ADAPTIVE 5
+typedef struct hr_png_encoder hr_png_encoder;
+int hr_png_bound(int32_t w, int32_t h, int32_t channels, int64_t* bytes);
+int hr_png_encoder_create(int32_t w, int32_t h, int32_t channels, hr_png_encoder** out);
+int hr_png_encode(hr_png_encoder* e, const void* pixels_dev, int32_t pixel_type, int32_t filter_mode, void* file_dev, int64_t capacity,
+                  int64_t* file_bytes_dev, void* stream);
+void hr_png_encoder_destroy(hr_png_encoder* e);
+
 /* Grid management: F.interpolate(plane, size=(h2, w2), mode='bilinear', align_corners=True) of one
  * (1, C, H, W) float32 plane or line, as TensorVMSplit.up_sampling_VM / TensorVMKeyframeTime.up_sampling_VM apply it
  * when the reference grows its grids (nlf/nets/tensorf_base.py:1152-1176, tensorf_dynamic.py:395-427).  Both buffers
