@@ -476,7 +476,7 @@ class DeviceResize:
     close().  No CPU path: a missing library or a failing call raises.
 
     Out of scope: cv2.resize, which datasets/immersive.py:579, neural_3d.py:416 and donerf.py:242 call (another arithmetic, and two of
-    those calls pass the filter where cv2 takes dst); decoding image files; modes other than 8-bit RGB and RGBA (LA among them);
+    those calls pass the filter where cv2 takes dst); decoding image files (PNG: hyperreel_amd.png.load_png); modes other than 8-bit RGB and RGBA (LA among them);
     Image.resize's box= and reducing_gap=."""
 
     def __init__(self, src_wh, dst_wh, filter='lanczos', max_images=1, device=None, mode='RGB'):

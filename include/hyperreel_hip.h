@@ -679,6 +679,52 @@ int hr_png_encode(hr_png_encoder* e, const void* pixels_dev, int32_t pixel_type,
                   int64_t* file_bytes_dev, void* stream);
 void hr_png_encoder_destroy(hr_png_encoder* e);
 
+/* ---- PNG files decoded on the device (csrc/hr_png_decode.h states the decoder once for host and device) ----
+ * A batch of PNG files in device memory becomes (n, h, w, out_channels) bytes in device memory: the container with every chunk's CRC-32,
+ * the zlib stream across IDAT boundaries (stored, fixed and dynamic blocks; code-length sets taken and refused as zlib's inflate does),
+ * the Adler-32, PNG filters 0..4, and PIL's convert('L' | 'RGB' | 'RGBA').  Accepted: 8 bits a sample, colour type 0 / 2 / 4 / 6, no
+ * interlace; everything else is HR_PNG_E_UNSUPPORTED (hr_png_probe says so beforehand, a caller keeps its own decoder for those).
+ * status_dev holds one int32 per image: HR_PNG_OK or one of the codes below; an image whose status is not HR_PNG_OK is all zeros.
+ * hr_png_probe: host only, reads the signature and IHDR of file_host[0..n) (no checksum); HR_E_INVALID when they are not there.
+ * hr_png_decoder_create: every image of a call is w x h; the decoder owns its workspace in device memory (current device): the filtered
+ * bytes of max_images images and one row of pixels each, nothing that grows with a file's chunk count.  max_file_bytes_total bounds
+ * offsets_dev's values: files_dev holds at least that many bytes, and an image whose offsets leave [0, max_file_bytes_total] or decrease
+ * is HR_PNG_E_OFFSETS and not read.
+ * hr_png_decode: files_dev the files one after another, offsets_dev[n_images + 1] their bounds, out_dev (n_images, h, w, out_channels)
+ * with out_channels 1, 3 or 4.  Three kernels on `stream`, one workgroup per image; no allocation, no synchronisation, no read-back,
+ * no memset; capturable in a hipGraph.  One decode at a time per decoder.  n_images == 0 launches nothing.
+ * HR_E_INVALID before anything is launched: a NULL pointer, n_images outside [0, max_images], out_channels not 1, 3 or 4.
+ * Additive: no existing struct or signature moved (HR_ABI_VERSION stays). */
+#define HR_PNG_OK 0
+#define HR_PNG_E_SIGNATURE 1     /* not a PNG signature */
+#define HR_PNG_E_CHUNK 2         /* IHDR not first or not 13 bytes, zero size, IDAT chunks apart, none at all, a length beyond 2^31 - 1 */
+#define HR_PNG_E_CRC 3
+#define HR_PNG_E_UNSUPPORTED 4   /* palette, 1 / 2 / 4 / 16 bits, Adam7, unknown compression or filter method */
+#define HR_PNG_E_SIZE 5          /* not the decoder's w x h */
+#define HR_PNG_E_ZLIB_HEADER 6
+#define HR_PNG_E_BLOCK 7         /* block type 3, LEN / NLEN, more than 286 / 30 symbols */
+#define HR_PNG_E_CODE 8          /* a refused set of code lengths, an unassigned code, length symbol 286 / 287, distance symbol 30 / 31 */
+#define HR_PNG_E_DISTANCE 9      /* a distance reaching before the first byte produced */
+#define HR_PNG_E_TRUNCATED 10    /* the file, or the zlib stream inside its IDAT chunks, ends early; no IEND */
+#define HR_PNG_E_TOO_LONG 11     /* more than h * (1 + w * channels) bytes */
+#define HR_PNG_E_TOO_SHORT 12
+#define HR_PNG_E_ADLER 13
+#define HR_PNG_E_FILTER 14       /* a row's filter byte above 4 */
+#define HR_PNG_E_OFFSETS 15
+typedef struct hr_png_info {
+    int32_t width, height, bit_depth, color_type;
+    int32_t channels;            /* samples a pixel in the file: 1, 2 (grey + alpha), 3 or 4; 1 for a palette */
+    int32_t interlace;
+    int32_t supported;           /* 1: hr_png_decode takes it */
+    int32_t reserved;
+} hr_png_info;
+typedef struct hr_png_decoder hr_png_decoder;
+int hr_png_probe(const void* file_host, int64_t n, hr_png_info* info);
+int hr_png_decoder_create(int32_t w, int32_t h, int32_t max_images, int64_t max_file_bytes_total, hr_png_decoder** out);
+int hr_png_decode(hr_png_decoder* dec, const void* files_dev, const int64_t* offsets_dev, int32_t n_images, int32_t out_channels, void* out_dev,
+                  int32_t* status_dev, void* stream);
+void hr_png_decoder_destroy(hr_png_decoder* dec);
+
 /* Grid management: F.interpolate(plane, size=(h2, w2), mode='bilinear', align_corners=True) of one
  * (1, C, H, W) float32 plane or line, as TensorVMSplit.up_sampling_VM / TensorVMKeyframeTime.up_sampling_VM apply it
  * when the reference grows its grids (nlf/nets/tensorf_base.py:1152-1176, tensorf_dynamic.py:395-427).  Both buffers
