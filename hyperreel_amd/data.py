@@ -476,7 +476,7 @@ class DeviceResize:
     close().  No CPU path: a missing library or a failing call raises.
 
     Out of scope: cv2.resize, which datasets/immersive.py:579, neural_3d.py:416 and donerf.py:242 call (another arithmetic, and two of
-    those calls pass the filter where cv2 takes dst); decoding image files (PNG: hyperreel_amd.png.load_png); modes other than 8-bit RGB and RGBA (LA among them);
+    those calls pass the filter where cv2 takes dst); decoding image files (load_images below: hyperreel_amd.png.load_png, hyperreel_amd.jpeg.load_jpeg); modes other than 8-bit RGB and RGBA (LA among them);
     Image.resize's box= and reducing_gap=."""
 
     def __init__(self, src_wh, dst_wh, filter='lanczos', max_images=1, device=None, mode='RGB'):
@@ -540,6 +540,27 @@ def reference_resize(images_u8, _img_wh, img_wh=None, first='lanczos', device=No
                 torch.cuda.current_stream(device).synchronize()      # the plan's memory goes with it
                 step.close()
     return x.to(device)
+
+
+def load_images(paths, mode='RGB', device=None):
+    """uint8 (n, H, W, C) on the device from image files of one format, PNG or JPEG, told by each file's first bytes (a directory such
+    as LLFF's images/ may hold either): png.load_png or jpeg.load_jpeg.  A list that mixes the two is refused, naming the first file
+    that differs; so is a file that is neither."""
+    from . import jpeg, png
+    paths = list(paths)
+    if not paths:
+        raise ValueError('load_images: no paths')
+    kinds = []
+    for p in paths:
+        with open(p, 'rb') as f:
+            head = f.read(8)
+        kind = 'PNG' if head == b'\x89PNG\r\n\x1a\n' else 'JPEG' if head[:2] == b'\xff\xd8' else None
+        if kind is None:
+            raise ValueError(f'{p}: neither a PNG signature nor a JPEG SOI marker')
+        if kinds and kind != kinds[0]:
+            raise ValueError(f'{p} is a {kind} file, {paths[0]} a {kinds[0]} file: load_images takes one format a call')
+        kinds.append(kind)
+    return (png.load_png if kinds[0] == 'PNG' else jpeg.load_jpeg)(paths, mode, device)
 
 
 def as_float(images_u8_dev):

@@ -69,6 +69,17 @@ PNG_STATUS_NAMES = ('OK', 'BAD_SIGNATURE', 'BAD_CHUNK', 'BAD_CRC', 'UNSUPPORTED'
                     'BAD_DISTANCE', 'TRUNCATED', 'TOO_LONG', 'TOO_SHORT', 'BAD_ADLER', 'BAD_FILTER', 'BAD_OFFSETS')
 
 
+# hr_jpeg_decode's per-image status codes, by value
+JPEG_STATUS_NAMES = ('OK', 'NO_SOI', 'BAD_MARKER', 'UNSUPPORTED', 'SIZE_MISMATCH', 'BAD_TABLE', 'BAD_CODE', 'BAD_COEF', 'BAD_RESTART', 'TRUNCATED',
+                     'TOO_LONG', 'BAD_OFFSETS')
+
+
+class hr_jpeg_info(C.Structure):
+    """Result of hr_jpeg_probe (include/hyperreel_hip.h)."""
+    _fields_ = [('width', C.c_int32), ('height', C.c_int32), ('components', C.c_int32), ('h_samp', C.c_int32), ('v_samp', C.c_int32),
+                ('restart_interval', C.c_int32), ('supported', C.c_int32), ('status', C.c_int32)]
+
+
 class hr_png_info(C.Structure):
     """Result of hr_png_probe (include/hyperreel_hip.h)."""
     _fields_ = [('width', C.c_int32), ('height', C.c_int32), ('bit_depth', C.c_int32), ('color_type', C.c_int32), ('channels', C.c_int32),
@@ -138,6 +149,10 @@ SYMBOLS = [
     ('hr_png_decoder_create', C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     ('hr_png_decode', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('hr_png_decoder_destroy', None, [C.c_void_p]),
+    ('hr_jpeg_probe', C.c_int, [C.c_void_p, C.c_int64, C.POINTER(hr_jpeg_info)]),
+    ('hr_jpeg_decoder_create', C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
+    ('hr_jpeg_decode', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('hr_jpeg_decoder_destroy', None, [C.c_void_p]),
     ('hr_rayset_set_pixel_format', C.c_int, [C.c_void_p, C.c_int32]),
     ('hr_upsample_plane', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ('hr_train_features', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

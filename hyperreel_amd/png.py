@@ -15,7 +15,8 @@ and the host copies the file's bytes, nothing else.  A float frame goes through 
 
 replaces  np.stack([np.asarray(Image.open(p).convert('RGB')) for p in paths])  and its upload: the host reads the files' bytes and copies
 them to the device once; the container's checksums, inflate, the PNG filters and PIL's convert run there, one image per workgroup.  8 bits a
-sample, colour type 0 / 2 / 4 / 6, no interlace; probe() tells beforehand, and a caller keeps PIL for the rest.
+sample, colour type 0 / 2 / 4 / 6, no interlace; probe() tells beforehand; JPEG files go to hyperreel_amd.jpeg (data.load_images picks by signature), and a caller keeps PIL for
+palette, 16-bit and interlaced PNGs.
 """
 import collections
 import ctypes as C

@@ -725,6 +725,45 @@ int hr_png_decode(hr_png_decoder* dec, const void* files_dev, const int64_t* off
                   int32_t* status_dev, void* stream);
 void hr_png_decoder_destroy(hr_png_decoder* dec);
 
+/* ---- JPEG files decoded on the device (csrc/hr_jpeg_decode.h states the decoder once for host and device) ----
+ * A batch of baseline JPEG files in device memory becomes (n, h, w, out_channels) bytes in device memory, byte for byte what PIL's
+ * Image.open(f).convert('L' | 'RGB' | 'RGBA') gives: Huffman decoding parallel inside a stream (subsequences of subseq_bits bits that
+ * synchronise themselves over rounds), libjpeg's jpeg_idct_islow, fancy upsampling and fixed-point YCbCr -> RGB.  Accepted: SOF0 / SOF1 at
+ * 8 bits, one component or three as YCbCr with luma 1x1 / 2x1 / 2x2 and chroma 1x1, one scan, restart markers; everything else is
+ * HR_JPEG_E_UNSUPPORTED (hr_jpeg_probe says so beforehand).  The decoder is strict: a damaged file gets a status below and an all-zero
+ * image, libjpeg's recovery is not reproduced.
+ * hr_jpeg_probe: host only, reads the markers of file_host[0..n) up to the scan; HR_E_INVALID when there is no SOI or no frame header.
+ * hr_jpeg_decoder_create: every image of a call is w x h; subseq_bits 0 for the default, else a multiple of 32 from 128 up.  The decoder
+ * owns its workspace in device memory (current device).
+ * hr_jpeg_decode: as hr_png_decode; rounds_dev (may be NULL) gets per image the most rounds a restart interval took.  Only enqueues
+ * kernels on `stream`: no allocation, no synchronisation, no read-back; capturable in a graph.  One decode at a time per decoder. */
+#define HR_JPEG_OK 0
+#define HR_JPEG_E_SOI 1          /* no SOI at the start of the file */
+#define HR_JPEG_E_MARKER 2       /* bad or overlong segment, truncated header, no SOF / SOS, an unknown marker */
+#define HR_JPEG_E_UNSUPPORTED 3
+#define HR_JPEG_E_SIZE 4         /* not the decoder's w x h */
+#define HR_JPEG_E_TABLE 5        /* missing or invalid DQT / DHT */
+#define HR_JPEG_E_CODE 6         /* a bit pattern that is no code, a size above 11 (DC) or 10 (AC), a run symbol baseline does not have */
+#define HR_JPEG_E_COEF 7         /* a run past coefficient 63; values beyond what libjpeg's 16-bit arithmetic holds */
+#define HR_JPEG_E_RESTART 8      /* missing, surplus or out-of-order RSTn */
+#define HR_JPEG_E_TRUNCATED 9    /* the entropy data or the file ends early; no EOI */
+#define HR_JPEG_E_TOO_LONG 10    /* a byte or more of entropy data left over after a restart interval's last MCU */
+#define HR_JPEG_E_OFFSETS 11
+typedef struct hr_jpeg_info {
+    int32_t width, height;
+    int32_t components;          /* 1 or 3 (4 in a file that is not taken) */
+    int32_t h_samp, v_samp;      /* luma sampling; 0 when the file is not taken */
+    int32_t restart_interval;
+    int32_t supported;           /* 1: hr_jpeg_decode takes it */
+    int32_t status;              /* the HR_JPEG_* code the head of the file gives */
+} hr_jpeg_info;
+typedef struct hr_jpeg_decoder hr_jpeg_decoder;
+int hr_jpeg_probe(const void* file_host, int64_t n, hr_jpeg_info* info);
+int hr_jpeg_decoder_create(int32_t w, int32_t h, int32_t max_images, int64_t max_file_bytes_total, int32_t subseq_bits, hr_jpeg_decoder** out);
+int hr_jpeg_decode(hr_jpeg_decoder* dec, const void* files_dev, const int64_t* offsets_dev, int32_t n_images, int32_t out_channels, void* out_dev,
+                   int32_t* status_dev, int32_t* rounds_dev, void* stream);
+void hr_jpeg_decoder_destroy(hr_jpeg_decoder* dec);
+
 /* Grid management: F.interpolate(plane, size=(h2, w2), mode='bilinear', align_corners=True) of one
  * (1, C, H, W) float32 plane or line, as TensorVMSplit.up_sampling_VM / TensorVMKeyframeTime.up_sampling_VM apply it
  * when the reference grows its grids (nlf/nets/tensorf_base.py:1152-1176, tensorf_dynamic.py:395-427).  Both buffers
