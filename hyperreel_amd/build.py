@@ -4,6 +4,7 @@
 
 The library links only against the HIP runtime; it has no torch dependency.
 """
+import functools
 import os
 import subprocess
 import sys
@@ -12,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB_DIR = os.path.join(HERE, '_build')
 LIB_PATH = os.path.join(LIB_DIR, 'libhyperreel_hip.so')
-SOURCES = ['api.hip', 'api_model.hip', 'api_mlp.hip', 'api_render.hip', 'api_train.hip', 'api_metrics.hip', 'api_rays.hip', 'api_resize.hip', 'api_loss.hip', 'api_reg.hip', 'api_png.hip', 'api_png_decode.hip', 'api_jpeg_decode.hip', 'mlp_kernel.hip', 'mlp_bf16x3_kernel.hip', 'mlp_f16x3_kernel.hip', 'mlp_f16x2_kernel.hip', 'mlp_f16f8_kernel.hip', 'fused_bf16x3_kernel.hip', 'fused_f16x3_kernel.hip', 'fused_f16x2_kernel.hip', 'fused_f16f8_kernel.hip',
+SOURCES = ['api.hip', 'api_model.hip', 'api_mlp.hip', 'api_render.hip', 'api_train.hip', 'api_metrics.hip', 'api_rays.hip', 'api_resize.hip', 'api_loss.hip', 'api_reg.hip', 'api_png.hip', 'api_image_decode.hip', 'mlp_kernel.hip', 'mlp_bf16x3_kernel.hip', 'mlp_f16x3_kernel.hip', 'mlp_f16x2_kernel.hip', 'mlp_f16f8_kernel.hip', 'fused_bf16x3_kernel.hip', 'fused_f16x3_kernel.hip', 'fused_f16x2_kernel.hip', 'fused_f16f8_kernel.hip',
            'sample_kernel.hip', 'sample_maps_kernel.hip', 'range_kernel.hip', 'band_kernel.hip', 'pack_kernels.hip', 'train_kernel.hip', 'train_det_kernel.hip', 'train_gemm_kernel.hip', 'metrics_kernel.hip', 'rays_kernel.hip', 'importance_kernel.hip', 'resize_kernel.hip', 'loss_kernel.hip', 'reg_kernel.hip', 'png_kernel.hip', 'png_decode_kernel.hip', 'jpeg_decode_kernel.hip']
 HEADERS = ['hr_model.h', 'hr_kernels.h', 'hr_math.h', 'hr_grid.h', 'hr_plan.h', 'hr_train.h', 'hr_mask.h', 'hr_metrics.h', 'hr_camera.h', 'hr_lightfield.h', 'hr_loss.h', 'hr_sample_rng.h', 'hr_importance.h', 'hr_resize.h', 'hr_mlp_pack.h', 'hr_png.h', 'hr_png_decode.h', 'hr_jpeg_decode.h', 'mlp_split_impl.inc', 'mlp_split_core.inc', 'sample_core.inc', 'sample_kernel.inc', 'sample_kernel_body.inc', 'fused_impl.inc', 'train_kernel.hip', os.path.join('..', '..', 'include', 'hyperreel_hip.h')]
 
@@ -126,6 +127,40 @@ def build(force=False, verbose=False, extra_flags=()):
         print(' '.join(cmd), flush=True)
     subprocess.run(cmd, check=True)
     return LIB_PATH
+
+
+def build_host_library(out, src, deps, opt='-O2'):
+    """g++ -shared of a plain C++ restatement of csrc's headers (the product's *_host.cpp at -O2, the tests' at -O1), rebuilt when a
+    dep is newer.  Safe under pytest-xdist: one builder at a time (flock), built aside and renamed, so the library appears atomically."""
+    import fcntl
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out + '.lock', 'w') as lk:
+        fcntl.flock(lk, fcntl.LOCK_EX)
+        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+            tmp = f'{out}.{os.getpid()}.tmp'
+            subprocess.run(['g++', opt, '-ffp-contract=off', '-fno-fast-math', '-shared', '-fPIC', '-o', tmp, src], check=True)
+            os.replace(tmp, out)
+    return out
+
+
+def host_library(name, headers, signatures):
+    """(build, load) of csrc/<name>.cpp, which includes csrc's `headers`: build() is build_host_library into _build/libhr_<name>.so and
+    returns the path; load() is that library as a ctypes.CDLL, loaded once, with {symbol: (restype, argtypes)} bound."""
+    src = os.path.join(CSRC, name + '.cpp')
+    deps = [src, *[os.path.join(CSRC, h) for h in headers], os.path.join(HERE, '..', 'include', 'hyperreel_hip.h')]
+
+    def build():
+        return build_host_library(os.path.join(LIB_DIR, f'libhr_{name}.so'), src, deps)
+
+    @functools.lru_cache(maxsize=None)
+    def load():
+        import ctypes
+        lib = ctypes.CDLL(build())
+        for symbol, (restype, argtypes) in signatures.items():
+            getattr(lib, symbol).restype, getattr(lib, symbol).argtypes = restype, argtypes
+        return lib
+
+    return build, load
 
 
 if __name__ == '__main__':

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from ._codec import HandleOwner
 from .plan import hr_camera, hr_fisheye, hr_lightfield, hr_ndc
 
 # subsample rules of the reference's datasets that are not the checkerboard: named so that the refusal can say which
@@ -169,7 +170,7 @@ def _alpha_channels(alpha):
     return 4
 
 
-class DeviceRaySet:
+class DeviceRaySet(HandleOwner):
     """images_u8: (n, H, W, 3) uint8 (numpy, or a torch tensor on the host or the device), RGB as Image.convert("RGB") holds
     them; poses (n, 3, 4); intrinsics (n, 3, 3) or one (3, 3); times, cam_ids: (n) or None (6-column rays); img_wh = (W, H);
     ndc: None | dict(fx, fy, near, width, height) | hr_ndc; alpha: None, or 'white' -- images_u8 is then (n, H, W, 4) uint8, RGBA as
@@ -274,12 +275,7 @@ class DeviceRaySet:
     def __len__(self):
         return self._size
 
-    def close(self):
-        if getattr(self, '_h', None):
-            _lib.call('hr_rayset_destroy', self._h)
-            self._h = None
-
-    __del__ = close
+    DESTROY = 'hr_rayset_destroy'          # HandleOwner: close(), and a __del__ that survives interpreter teardown
 
     def batch(self, batch_idx, batch_size, epoch=0, seed=0, indices=None, out=None):
         """Rows [batch_idx * batch_size, + batch_size) of the epoch's order (the last batch of an epoch is short), or the set
@@ -466,7 +462,7 @@ def _as_u8_batch(images_u8, wh=None, channels=3):
     return t.contiguous()
 
 
-class DeviceResize:
+class DeviceResize(HandleOwner):
     """PIL's Image.resize of 8-bit RGB images -- or, with mode='RGBA', of 8-bit RGBA images, (.., 4) wherever (.., 3) stands below:
     PIL resamples them premultiplied and converts back -- on the device, byte for byte: src_wh = (W, H) -> dst_wh = (W2, H2) with filter 'lanczos' |
     'bicubic' | 'bilinear' | 'box' (Image.LANCZOS, BICUBIC -- Image.resize's default -- BILINEAR, BOX), up to max_images images a launch.
@@ -492,12 +488,7 @@ class DeviceResize:
         _lib.call('hr_resize_plan_create_rgba' if self._channels == 4 else 'hr_resize_plan_create', self.src_wh[0], self.src_wh[1], self.dst_wh[0], self.dst_wh[1], number, self.max_images,
                   C.byref(self._h), device=self.device)
 
-    def close(self):
-        if getattr(self, '_h', None):
-            _lib.call('hr_resize_plan_destroy', self._h)
-            self._h = None
-
-    __del__ = close
+    DESTROY = 'hr_resize_plan_destroy'          # HandleOwner: close(), and a __del__ that survives interpreter teardown
 
     def __call__(self, images_u8, out=None):
         """out: None (a fresh tensor) or a contiguous uint8 (n, H2, W2, 3) tensor on the plan's device (a fixed buffer for a captured graph)"""

@@ -9,6 +9,7 @@ import numpy as np
 
 from hyperreel_amd import config as C
 from hyperreel_amd import scenes
+from hyperreel_amd.build import build_host_library
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
@@ -354,13 +355,5 @@ def train_branch(hc, n_rays=96, deterministic=False):
 
 
 def build_host_lib(out, src, deps):
-    """g++ -shared of a host restatement, safe under pytest-xdist: one builder at a time (flock), the library appears atomically."""
-    import fcntl, subprocess
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    with open(out + '.lock', 'w') as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-            tmp = f'{out}.{os.getpid()}.tmp'
-            subprocess.run(['g++', '-O1', '-ffp-contract=off', '-fno-fast-math', '-shared', '-fPIC', '-o', tmp, src], check=True)
-            os.replace(tmp, out)
-    return out
+    """g++ -shared of a host restatement: the package's own builder (flock, atomic rename), at the -O1 the tests' restatements are held to"""
+    return build_host_library(out, src, deps, opt='-O1')
