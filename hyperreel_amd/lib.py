@@ -33,6 +33,14 @@ class hr_image_scores(C.Structure):
     _fields_ = [('sse', C.c_double), ('ssim_sum', C.c_double * 3)]
 
 
+class hr_lpips_scores(C.Structure):
+    """Result of hr_lpips, written on the device (include/hyperreel_hip.h)."""
+    _fields_ = [('layer', C.c_double * 5), ('total', C.c_double)]
+
+
+HR_LPIPS_ALEX, HR_LPIPS_VGG = 0, 1
+
+
 class hr_loss_out(C.Structure):
     """Result of hr_image_loss, written on the device (include/hyperreel_hip.h)."""
     _fields_ = [('loss_sum', C.c_double), ('sse', C.c_double), ('loss', C.c_float), ('pad', C.c_float)]
@@ -169,6 +177,10 @@ SYMBOLS = [
     ('hr_pack_display', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     ('hr_image_metrics_workspace', C.c_size_t, [C.c_int32, C.c_int32]),
     ('hr_image_metrics', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('hr_lpips_create', C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ('hr_lpips_destroy', None, [C.c_void_p]),
+    ('hr_lpips_workspace', C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    ('hr_lpips', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('hr_image_loss_workspace', C.c_size_t, [C.c_int64]),
     ('hr_image_loss', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p]),

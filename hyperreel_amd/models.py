@@ -970,13 +970,22 @@ class HipLightfieldModel(nn.Module):
         """render(generate_epi_rays(...))['rgb'], bit for bit."""
         return self.render(self.generate_epi_rays(v, t, lightfield, pixel_range))['rgb']
 
-    def evaluate(self, rays, gt, h, w, frame_time=None, ssim=True):
+    def evaluate(self, rays, gt, h, w, frame_time=None, ssim=True, lpips=None):
         """Render a frame and score it against its ground truth without leaving the device until the four sums are read: what
         validation_image does on the host (nlf/__init__.py:976-980, metrics.py:25-35).  rays: the frame's h*w rays; gt: (h*w, 3)
-        on the HIP device.  Returns (rgb, {'mse', 'psnr', 'ssim'}); rgb is the unchanged render() call's, bit for bit."""
+        on the HIP device.  Returns (rgb, {'mse', 'psnr', 'ssim'}); rgb is the unchanged render() call's, bit for bit.
+        lpips: an hyperreel_amd.lpips.Lpips; the result gains 'lpips', the distance of the same frame (metrics.py:54-58), enqueued
+        before the first read-back.  LPIPS does not add across image tiles (receptive fields cross the cuts): on image-parallel ranks
+        gather the frame and score it on one rank."""
         from . import metrics
         rgb = self.render(rays, frame_time=frame_time)['rgb']
-        return rgb, metrics.scores_to_metrics(metrics.image_scores(rgb, gt, h, w, ssim=ssim), h, w)
+        sums = metrics.image_scores(rgb, gt, h, w, ssim=ssim)
+        if lpips is None:
+            return rgb, metrics.scores_to_metrics(sums, h, w)
+        dist = lpips.lpips_scores(rgb, gt, h, w)
+        m = metrics.scores_to_metrics(sums, h, w)
+        m['lpips'] = float(dist[5])
+        return rgb, m
 
     def pack_display(self, rgb, height, width, transpose=False, flip=False, rgba8=True):
         """The viewer's hand-over (utils/gui_utils.py:174-205) on the device: rgb (H*W, 3) as rendered -> the displayed

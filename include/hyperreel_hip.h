@@ -894,6 +894,42 @@ size_t hr_image_metrics_workspace(int32_t h, int32_t w);
 int hr_image_metrics(const float* pred_dev, const float* gt_dev, int32_t h, int32_t w, int32_t want_ssim, hr_image_scores* out_dev,
                      void* workspace_dev, void* stream);
 
+/* LPIPS: the third score of the reference's results tables, which it computes on the host after a copy of the frame
+ * (metrics.py:54-58 compute_lpips; utils/tensorf_utils.py:76-88 rgb_lpips with the nets 'alex' and 'vgg', version '0.1',
+ * normalize=True).  LPIPS v0.1 in eval mode; the definition is stated once in csrc/hr_lpips.h: images * 2 - 1, the scaling layer,
+ * the backbone on both images, five taps, channel-unit-normalised squared differences weighted by the non-negative `lin` layers,
+ * spatial means, summed.  The pretrained weights are the CALLER's (torchvision's backbone, the lpips package's lin layers): nothing
+ * is shipped, and agreement with published numbers rests on them.  Additive: no existing struct or signature moved
+ * (HR_ABI_VERSION stays). */
+enum { HR_LPIPS_ALEX = 0, HR_LPIPS_VGG = 1 };
+struct hr_lpips;                /* (no typedef: the call below has the name; say `struct hr_lpips`) */
+typedef struct hr_lpips_scores {
+    double layer[5];            /* per tap: mean over its pixels of sum_c lin[c] (n_pred[c] - n_gt[c])^2 */
+    double total;               /* layer[0] + ... + layer[4] in that order: the LPIPS distance */
+} hr_lpips_scores;
+
+/* conv_w[i], conv_b[i]: the i-th convolution's weight (cout, cin, k, k) and bias (cout) as torch holds them (OIHW, float32,
+ * contiguous), 5 of them for HR_LPIPS_ALEX and 13 for HR_LPIPS_VGG; lin_w[k]: the C_k weights of tap k's 1x1 convolution (C_k = 64,
+ * 192, 384, 256, 256 for alex, 64, 128, 256, 512, 512 for vgg).  Each pointer may be host or device memory.  The object owns its
+ * copies: the weights packed into the matrix instructions' operand order, on the current device.  Synchronises the device once.
+ * HR_E_INVALID for a NULL pointer or an unknown net. */
+int hr_lpips_create(int32_t net, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w,
+                    struct hr_lpips** out);
+void hr_lpips_destroy(struct hr_lpips* p);
+
+/* bytes of workspace_dev that a call on an h x w frame needs; 0 for an unknown net, a frame below the minimum (31 x 31 for alex,
+ * 16 x 16 for vgg: every tap is at least 1 x 1) or one whose layers pass 2^31 pixels */
+size_t hr_lpips_workspace(int32_t net, int32_t h, int32_t w);
+
+/* pred_dev, gt_dev: (h * w, 3) float32 in [0, 1], as hr_render writes a frame -> *out_dev (device memory).  workspace_dev: at least
+ * hr_lpips_workspace(net, h, w) bytes, 16-byte aligned.  Only kernels on `stream`: no allocation, no synchronisation, no memset;
+ * every byte of *out_dev and of the workspace that is read is written first by the same call; capturable in a hipGraph.  The sums
+ * are added in a fixed order without atomics: calls on the same inputs give the same bits, (pred, gt) and (gt, pred) too.
+ * HR_E_INVALID, before anything is launched, for a NULL pointer, a frame below the minimum or too large, a misaligned workspace.
+ * The distance of a frame is not the sum of its tiles' (receptive fields cross the cut): score whole frames. */
+int hr_lpips(const struct hr_lpips* p, const float* pred_dev, const float* gt_dev, int32_t h, int32_t w, hr_lpips_scores* out_dev,
+             void* workspace_dev, void* stream);
+
 /* Training image loss: INRSystem.training_step's
  *     image_loss = self.loss(results['rgb'] * weight, rgb * weight, **batch)            (nlf/__init__.py:665)
  * for the modules of losses.py's loss_dict that accept that call, with the squared error train/psnr needs (psnr_gpu, :668) from the
