@@ -1,4 +1,5 @@
-"""JPEG training images decoded on the device (csrc/hr_jpeg_decode.h, jpeg_decode_kernel.hip), png.py's sibling.
+"""JPEG files on the device, png.py's sibling: training images decoded (csrc/hr_jpeg_decode.h, jpeg_decode_kernel.hip) and
+rendered frames encoded (csrc/hr_jpeg_encode.h, jpeg_encode_kernel.hip).
 
     images_u8 = load_jpeg(paths, 'RGB')         # (n, H, W, 3) uint8 on the device
     dec = JpegDecoder(4032, 3024, max_images=8)
@@ -9,6 +10,13 @@ full-size JPEGs): the host reads the files' bytes and copies them to the device 
 stream -- libjpeg's IDCT, chroma upsampling, colour conversion and PIL's convert run there, byte for byte as PIL 12.2 / libjpeg-turbo 3.1
 give them.  Baseline and extended sequential Huffman files at 8 bits, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, one scan, with or without
 restart markers; probe() tells beforehand.  Progressive, arithmetic, CMYK and other samplings are refused by name: decode those with PIL.
+
+    enc = JpegEncoder(800, 800, quality=90, subsampling='4:2:0')      # RGB; channels=4 for pack_display's RGBA8, 1 for a map
+    data = enc.encode(rgb)                      # bytes of a complete baseline JPEG file
+    save_jpeg('frame.jpg', rgb)
+
+replaces  Image.fromarray(to8b(rgb.cpu().numpy())).save(f, 'JPEG', quality=90, subsampling=2) : the frame stays on the device, to8b is
+fused into the encoder's first read, and the host copies the file's bytes -- PIL 12.2's own, byte for byte -- and nothing else.
 """
 import collections
 import ctypes as C
@@ -25,6 +33,18 @@ build_decode_host, decode_host_lib = host_library('jpeg_decode_host', ('hr_jpeg_
     'hr_jpeg_host_probe': (C.c_int32, [C.c_char_p, C.c_int64, C.POINTER(_lib.hr_jpeg_info)]),
     'hr_jpeg_host_decode': (C.c_int32, [C.c_char_p, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p, C.POINTER(_lib.hr_jpeg_info), C.POINTER(C.c_int32)]),
     'hr_jpeg_host_idct': (C.c_int32, [C.c_void_p] * 3)})
+
+
+class hr_jpeg_enc_stats(C.Structure):
+    """What hr_jpeg_host_encode reports of a scan (csrc/hr_jpeg_encode.h)."""
+    _fields_ = [('stuffed', C.c_int64), ('zrl', C.c_int64), ('max_dc_cat', C.c_int32), ('max_ac_cat', C.c_int32)]
+
+
+# ... and of csrc/hr_jpeg_encode.h (csrc/jpeg_encode_host.cpp)
+build_host, host_lib = host_library('jpeg_encode_host', ('hr_jpeg_encode.h', 'hr_jpeg_decode.h', 'hr_png_decode.h', 'hr_png.h', 'hr_math.h'), {
+    'hr_jpeg_host_bound': (C.c_int64, [C.c_int32] * 5),
+    'hr_jpeg_host_encode': (C.c_int64, [C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_int64, C.POINTER(hr_jpeg_enc_stats)])})
+SUBSAMPLINGS = {'4:4:4': _lib.HR_JPEG_444, '4:2:2': _lib.HR_JPEG_422, '4:2:0': _lib.HR_JPEG_420}
 
 
 class JpegDecodeError(_codec.DecodeError):
@@ -109,3 +129,123 @@ def decode_host(data, mode='RGB', size=None, with_status=False, subseq_bits=0, w
     if st:
         raise JpegDecodeError(0, st)
     return (out, int(rounds.value)) if with_rounds else out
+
+
+# ---- encoding ---------------------------------------------------------------------------------------------------------------------------
+def _subsampling(subsampling):
+    """the C ABI's number of '4:4:4' | '4:2:2' | '4:2:0' or of PIL's 0 | 1 | 2"""
+    if isinstance(subsampling, str):
+        if subsampling not in SUBSAMPLINGS:
+            raise ValueError(f'subsampling {subsampling!r}: one of {sorted(SUBSAMPLINGS)} or PIL\'s number 0, 1, 2')
+        subsampling = SUBSAMPLINGS[subsampling]
+    return int(subsampling)
+
+
+def bound(width, height, channels=3, subsampling='4:2:0', restart_rows=0):
+    """hr_jpeg_bound: a capacity in bytes that always holds the file"""
+    n = C.c_int64()
+    _lib.call('hr_jpeg_bound', int(width), int(height), int(channels), _subsampling(subsampling), int(restart_rows), C.byref(n))
+    return int(n.value)
+
+
+class JpegEncoder(_codec.HandleOwner):
+    """Encodes (height, width, channels) frames on the device as baseline JPEG files: channels 1 (grey, subsampling '4:4:4'), 3 (RGB) or 4
+    (RGBA, the alpha byte ignored).  quality 1..100 and subsampling '4:4:4' | '4:2:2' | '4:2:0' as PIL's save; restart_rows > 0 puts a
+    restart marker after every so many MCU rows.  A frame is a device tensor as PngEncoder's: float32 (H, W, C), (H * W, C) or (H, W),
+    turned into bytes by to8b as it is read, or uint8 of the same shapes; one that is not contiguous is copied first.  The encoder owns
+    its device workspace: one encode at a time per encoder."""
+    DESTROY = 'hr_jpeg_encoder_destroy'
+
+    def __init__(self, width, height, channels=3, quality=90, subsampling='4:2:0', restart_rows=0, device=None):
+        import torch
+        self.width, self.height, self.channels = int(width), int(height), int(channels)
+        self.quality, self.restart_rows = int(quality), int(restart_rows)
+        self.subsampling = _subsampling(subsampling)
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self._h = C.c_void_p()
+        _lib.call('hr_jpeg_encoder_create', self.width, self.height, self.channels, self.quality, self.subsampling, self.restart_rows, C.byref(self._h),
+                  device=self.device)
+        self.bound = bound(self.width, self.height, self.channels, self.subsampling, self.restart_rows)
+
+    def _frame(self, frame):
+        import torch
+        if not isinstance(frame, torch.Tensor) or frame.device != self.device:
+            raise ValueError(f'frame must be a tensor on {self.device}')
+        if frame.dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f'frame must be float32 or uint8, got {frame.dtype}')
+        if frame.numel() != self.height * self.width * self.channels or (frame.dim() > 1 and self.channels > 1 and frame.shape[-1] != self.channels):
+            raise ValueError(f'frame {tuple(frame.shape)} is not ({self.height}, {self.width}, {self.channels}) or ({self.height * self.width}, {self.channels})')
+        return frame.contiguous()
+
+    def encode_device(self, frame, out=None, length=None):
+        """Enqueues the encode on torch's current stream and returns (uint8 buffer of `bound` bytes, int64 length tensor of one element):
+        the file is buffer[:length], and no byte past it is written.  No allocation when `out` and `length` are given, no
+        synchronisation: capturable in a graph, with `frame` a contiguous buffer that is refilled between replays."""
+        import torch
+        frame = self._frame(frame)
+        if out is None:
+            out = torch.empty(self.bound, dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous() or out.numel() < self.bound:
+            raise ValueError(f'out must be a contiguous uint8 tensor of at least {self.bound} bytes on {self.device}')
+        if length is None:
+            length = torch.empty(1, dtype=torch.int64, device=self.device)
+        elif length.dtype != torch.int64 or length.device != self.device or length.numel() != 1:
+            raise ValueError(f'length must be an int64 tensor of one element on {self.device}')
+        _lib.call('hr_jpeg_encode', self._h, frame, _lib.HR_PNG_U8 if frame.dtype == torch.uint8 else _lib.HR_PNG_F32_TO8B, out, out.numel(), length,
+                  _lib.stream(self.device), device=self.device)
+        return out, length
+
+    def encode(self, frame):
+        """The file's bytes: one device-to-host copy of the length, one of that many bytes"""
+        out, length = self.encode_device(frame)
+        n = int(length.item())
+        return out[:n].cpu().numpy().tobytes()
+
+
+def save_jpeg(path, frame, width=None, height=None, **options):
+    """Writes a device frame (H, W, C) or (H, W) -- or (H * W, C) with width and height given -- as a JPEG file; options: JpegEncoder's
+    quality, subsampling, restart_rows.  A grey frame is written 4:4:4 unless a subsampling is asked for."""
+    if frame.dim() == 3 or (frame.dim() == 2 and width is None):
+        height, width = frame.shape[:2]
+        channels = 1 if frame.dim() == 2 else frame.shape[2]
+    else:
+        if width is None or height is None:
+            raise ValueError('a flat (H * W, C) frame needs width and height')
+        channels = frame.shape[-1] if frame.dim() == 2 else 1
+    if channels == 1:
+        options.setdefault('subsampling', '4:4:4')
+    enc = JpegEncoder(width, height, channels, device=frame.device, **options)
+    try:
+        data = enc.encode(frame)
+    finally:
+        enc.close()
+    with open(path, 'wb') as f:
+        f.write(data)
+    return len(data)
+
+
+def encode_host(array, channels=None, quality=90, subsampling='4:2:0', restart_rows=0, with_stats=False):
+    """The same file from a numpy array (H, W, C) or (H, W), uint8 or float32, encoded on the host by the header the kernels are built
+    from: byte for byte what the device writes.  Needs no GPU.  A grey array takes subsampling '4:4:4' only, as the device does.
+    with_stats: (bytes, {'stuffed', 'zrl', 'max_dc_cat', 'max_ac_cat'}) of the scan."""
+    host = host_lib()
+    array = np.ascontiguousarray(array)
+    if array.dtype not in (np.uint8, np.float32) or array.ndim not in (2, 3):
+        raise ValueError(f'array must be uint8 or float32 of shape (H, W, C) or (H, W), got {array.dtype} {array.shape}')
+    channels = int(channels) if channels is not None else (1 if array.ndim == 2 else int(array.shape[-1]))
+    sub = _subsampling(subsampling)
+    h, w = array.shape[:2]
+    cap = host.hr_jpeg_host_bound(w, h, channels, sub, int(restart_rows)) if array.size == h * w * channels and 1 <= int(quality) <= 100 else -1
+    if cap < 0:
+        raise ValueError(f'array {array.shape}, quality {quality}, subsampling {subsampling}, restart_rows {restart_rows}: not an image and options '
+                         f'the encoder takes (channels 1, 3 or 4; 1 x 1 to 65535 x 65535; quality 1..100; grey only 4:4:4)')
+    file = np.empty(cap, np.uint8)
+    stats = hr_jpeg_enc_stats()
+    n = host.hr_jpeg_host_encode(array.ctypes.data_as(C.c_void_p), _lib.HR_PNG_U8 if array.dtype == np.uint8 else _lib.HR_PNG_F32_TO8B, w, h, channels,
+                                 int(quality), sub, int(restart_rows), file.ctypes.data_as(C.c_void_p), file.size, C.byref(stats))
+    if n < 0:
+        raise RuntimeError('hr_jpeg_encode_host refused the image')
+    data = file[:n].tobytes()
+    if with_stats:
+        return data, {'stuffed': stats.stuffed, 'zrl': stats.zrl, 'max_dc_cat': stats.max_dc_cat, 'max_ac_cat': stats.max_ac_cat}
+    return data

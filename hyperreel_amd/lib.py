@@ -72,6 +72,8 @@ HR_PIXELS_RGB8, HR_PIXELS_RGBA8_WHITE = 0, 1
 # hr_png_encode's pixel types and its adaptive filter mode (the fixed ones are the PNG filter numbers 0..4)
 HR_PNG_U8, HR_PNG_F32_TO8B = 0, 1
 HR_PNG_FILTER_ADAPTIVE = 5
+# hr_jpeg_encoder_create's subsampling (PIL's numbers)
+HR_JPEG_444, HR_JPEG_422, HR_JPEG_420 = 0, 1, 2
 # hr_png_decode's per-image status codes, by value
 PNG_STATUS_NAMES = ('OK', 'BAD_SIGNATURE', 'BAD_CHUNK', 'BAD_CRC', 'UNSUPPORTED', 'SIZE_MISMATCH', 'BAD_ZLIB_HEADER', 'BAD_BLOCK', 'BAD_CODE',
                     'BAD_DISTANCE', 'TRUNCATED', 'TOO_LONG', 'TOO_SHORT', 'BAD_ADLER', 'BAD_FILTER', 'BAD_OFFSETS')
@@ -153,6 +155,10 @@ SYMBOLS = [
     ('hr_png_encoder_create', C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     ('hr_png_encode', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ('hr_png_encoder_destroy', None, [C.c_void_p]),
+    ('hr_jpeg_bound', C.c_int, [C.c_int32] * 5 + [C.POINTER(C.c_int64)]),
+    ('hr_jpeg_encoder_create', C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_void_p)]),
+    ('hr_jpeg_encode', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ('hr_jpeg_encoder_destroy', None, [C.c_void_p]),
     ('hr_png_probe', C.c_int, [C.c_void_p, C.c_int64, C.POINTER(hr_png_info)]),
     ('hr_png_decoder_create', C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     ('hr_png_decode', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -679,6 +679,33 @@ int hr_png_encode(hr_png_encoder* e, const void* pixels_dev, int32_t pixel_type,
                   int64_t* file_bytes_dev, void* stream);
 void hr_png_encoder_destroy(hr_png_encoder* e);
 
+/* ---- JPEG files written on the device (csrc/hr_jpeg_encode.h states the encoder once for host and device) ----
+ * A frame that is already in device memory becomes a complete baseline JPEG file in device memory, byte for byte the file PIL 12.2 /
+ * libjpeg-turbo writes for Image.save(f, 'JPEG', quality=q, subsampling=s[, restart_marker_rows=r]) with the standard Huffman tables:
+ * JFIF header, jpeg_set_quality's tables, libjpeg's fixed-point colour conversion, edge replication and h2v1 / h2v2 downsampling,
+ * jpeg_fdct_islow, quantisation, interleaved MCUs, Huffman coding with byte stuffing, optional restart markers every restart_rows MCU rows.
+ * pixels_dev is row-major (h, w, channels), contiguous, with hr_png_encode's pixel types: HR_PNG_U8 bytes, or HR_PNG_F32_TO8B floats that
+ * go through to8b as they are read (NaN gives 0).  channels 1: grey; 3: RGB; 4: RGBA with the alpha byte ignored (hr_pack_display's).
+ * subsampling: HR_JPEG_444 / HR_JPEG_422 / HR_JPEG_420 (PIL's numbers); a grey image takes HR_JPEG_444 only.
+ * hr_jpeg_bound: a capacity that always holds the file.  hr_jpeg_encoder_create: the encoder owns its workspace in device memory (current
+ * device), with the tables and the header built on the host.  hr_jpeg_encode: eight kernels on `stream` (a hipStream_t passed as void*),
+ * no allocation, no synchronisation, capturable; file_dev[0 .. *length_dev) is the file, nothing is written past it; one encode at a time
+ * per encoder.  Integer arithmetic and integer atomic OR only: the same frame gives the same file on every run, and the host build of
+ * hr_jpeg_encode.h (hr_jpeg_encode_host) gives the same bytes.
+ * HR_E_INVALID: a size below 1 or above 65535, channels outside {1, 3, 4}, quality outside 1..100, an unknown subsampling, grey with a
+ * subsampling other than 4:4:4, negative restart_rows or more than 65535 MCUs per interval, an image of more blocks than 32-bit bit
+ * offsets address (about 2.5 million), capacity below hr_jpeg_bound, a NULL pointer, an unknown pixel_type.
+ * Additive: no existing struct or signature moved (HR_ABI_VERSION stays). */
+#define HR_JPEG_444 0
+#define HR_JPEG_422 1
+#define HR_JPEG_420 2
+typedef struct hr_jpeg_encoder hr_jpeg_encoder;
+int hr_jpeg_bound(int32_t w, int32_t h, int32_t channels, int32_t subsampling, int32_t restart_rows, int64_t* bytes);
+int hr_jpeg_encoder_create(int32_t w, int32_t h, int32_t channels, int32_t quality, int32_t subsampling, int32_t restart_rows, hr_jpeg_encoder** out);
+int hr_jpeg_encode(hr_jpeg_encoder* e, const void* pixels_dev, int32_t pixel_type, void* file_dev, int64_t capacity, int64_t* length_dev,
+                   void* stream);
+void hr_jpeg_encoder_destroy(hr_jpeg_encoder* e);
+
 /* ---- PNG files decoded on the device (csrc/hr_png_decode.h states the decoder once for host and device) ----
  * A batch of PNG files in device memory becomes (n, h, w, out_channels) bytes in device memory: the container with every chunk's CRC-32,
  * the zlib stream across IDAT boundaries (stored, fixed and dynamic blocks; code-length sets taken and refused as zlib's inflate does),
