@@ -527,12 +527,33 @@ static inline bool hr_mlp_can_verify(const hr_config& c, bool cascade_level)
     return !cascade_level && c.z_channels <= 64 && c.mlp_layers >= 2 && c.mlp_hidden == 256 && isect_ok && c.contract_type != HR_CONTRACT_DONERF;
 }
 
+// The f16f8 kernels evaluate the windowed positional encoding with v_sin_f32 / v_cos_f32 of x / 2pi formed in fp32 (HR_FAST_SINCOS,
+// hr_math.h): the phase error of that product grows as ~6e-8 |x| rad, and beyond 512 pi the instructions return 0 and 1.  The largest
+// argument of a group is pe_base_mult * freq_mult^n_freqs times the parameterised ray coordinate (hr_ray_features forms it by the same
+// repeated product); up to HR_FAST_SINCOS_MAX_FREQ = 16 the phase error of a coordinate of order one stays at the ~1e-6 HR_SINCOS grants
+// the instructions anyway (6e-8 x 16).  The five benchmark families have at most 4.  Beyond it f16f8 is not run (hr_mlp_choice).
+static const float HR_FAST_SINCOS_MAX_FREQ = 16.0f;
+static inline bool hr_mlp_fast_sincos_ok(const hr_config& c)
+{
+    for (int g = 0; g < c.n_groups && g < HR_MAX_GROUPS; ++g) {
+        const hr_param_group& pg = c.groups[g];
+        if (pg.pe_type != HR_PE_WINDOWED || pg.pe_n_freqs <= 0) continue;
+        float f = 1.0f;
+        for (int j = 0; j < pg.pe_n_freqs; ++j) f = f * pg.pe_freq_mult;
+        if (!(fabsf(pg.pe_base_mult * f) <= HR_FAST_SINCOS_MAX_FREQ)) return false;
+    }
+    return true;
+}
+
 // Which arithmetic a model's MLP runs.  act_max[l]: the calibration's largest |input feature| (l = 0) and |pre-activation| of hidden
 // Linear l - 1; all zero before a measurement, and read only when needs_calibration comes back set -- the caller then measures and asks
 // again.  HR_MLP_AUTO becomes the verified fast path (f16f8, verified) when every one of them is finite and below
 // HR_F16_CALIBRATION_LIMIT and the model can be verified, f16x3 when it cannot, and bf16x3 (fp32 exponent range) when they are not;
 // a FORCED fp16 mode that fails the test is HR_E_RANGE, a forced f16f8v on a model that cannot be verified (or a width the range
-// kernel does not cover: range_supported) HR_E_INVALID.
+// kernel does not cover: range_supported) HR_E_INVALID.  A windowed encoding beyond HR_FAST_SINCOS_MAX_FREQ (hr_mlp_fast_sincos_ok)
+// takes f16f8 away: HR_MLP_AUTO and a forced f16f8 / f16f8v are f16x3 there (IEEE sincosf, nothing verified; HR_E_RANGE as for a forced
+// f16x3) -- a fall-back that HR_OPT_MLP_PRECISION_ACTIVE reports, not a refusal: shipped nets are beyond the limit (stanford_z_plane_mem:
+// two-plane coordinates at 2^6) and render under a forced f16f8.
 struct HrMlpChoice {
     int active_precision, verified;
     bool needs_calibration;
@@ -547,11 +568,12 @@ static inline HrMlpChoice hr_mlp_choice(const hr_config& c, bool cascade_level, 
     if (!range_supported) return {want, 0, true, HR_E_INVALID};
     bool fits = true;
     for (int l = 0; l < c.mlp_layers; ++l) fits = fits && isfinite(act_max[l]) && act_max[l] < HR_F16_CALIBRATION_LIMIT;
-    const bool can_verify = hr_mlp_can_verify(c, cascade_level);
+    const bool f8_ok = hr_mlp_fast_sincos_ok(c), can_verify = f8_ok && hr_mlp_can_verify(c, cascade_level);
     if (want == HR_MLP_AUTO) {
         if (!fits) return {HR_MLP_BF16X3, 0, true, HR_OK};
         return {can_verify ? HR_MLP_F16F8 : HR_MLP_F16X3, can_verify ? 1 : 0, true, HR_OK};
     }
+    if ((want == HR_MLP_F16F8 || want == HR_MLP_F16F8V) && !f8_ok) return {HR_MLP_F16X3, 0, true, fits ? HR_OK : HR_E_RANGE};
     if (want == HR_MLP_F16F8V && !can_verify) return {want, 0, true, HR_E_INVALID};
     if (!fits) return {want, 0, true, HR_E_RANGE};
     return {want == HR_MLP_F16F8V ? HR_MLP_F16F8 : want, want == HR_MLP_F16F8V ? 1 : 0, true, HR_OK};

@@ -19,7 +19,7 @@ from torch import nn
 from . import lib as _lib
 from .config import n_to_reso, to_plain
 from .data import make_camera, make_fisheye, make_ndc
-from .plan import MLP_PRECISION, compile_model, hr_fields, hr_lightfield, hr_maps, upload_names
+from .plan import MLP_PRECISION, compile_model, fast_sincos_ok, hr_fields, hr_lightfield, hr_maps, upload_names
 
 _MLP_PRECISION_NAME = {code: name for name, code in MLP_PRECISION.items()}      # HR_OPT_MLP_PRECISION_ACTIVE -> 'f16x3' ...
 
@@ -436,7 +436,12 @@ class HipLightfieldModel(nn.Module):
         self._grid_size_host = None    # (gridSize tensor, its version, its values)
         self._f8_cannot_calibrate = self._warned_detached_fields = False
         # fail on configurations outside the supported path now, not at the first render
-        self._compile(grid)
+        coarse, hc = self._compile(grid)
+        if self.mlp_precision in ('f16f8', 'f16f8v') and not all(fast_sincos_ok(c) for c in (coarse, hc) if c is not None):
+            import warnings
+            warnings.warn(f"hyperreel_amd: mlp_precision {self.mlp_precision!r} was requested, but a windowed positional encoding of this model reaches "
+                          "base_multiplier * freq_multiplier ** n_freqs > 16, beyond what the f16f8 kernels' v_sin / v_cos hold: the MLP runs f16x3 "
+                          "(mlp_precision_active() reports it)")
 
     def upsample_volume_grid(self, res_target):
         """Grows the feature grids like the reference's training loop does (nlf/__init__.py upsampling hooks ->

@@ -340,6 +340,24 @@ MLP_PRECISION = {'fp32': 0, 'bf16x3': 1, 'f16x3': 2, 'f16x2': 3, 'auto': 4, 'f16
 
 GRID_DTYPE = {'fp32': 0, 'fp16': 1}
 
+FAST_SINCOS_MAX_FREQ = 16.0     # HR_FAST_SINCOS_MAX_FREQ (csrc/hr_plan.h)
+
+
+def fast_sincos_ok(hc):
+    """hr_mlp_fast_sincos_ok (csrc/hr_plan.h): no windowed group's largest frequency, pe_base_mult * pe_freq_mult ** pe_n_freqs formed in
+    float32 as the kernels form it, is beyond what the f16f8 kernels' v_sin / v_cos encoding holds.  Where it is, 'auto' resolves to
+    f16x3 in the library and so does a forced 'f16f8' / 'f16f8v' (HipLightfieldModel warns by name; mlp_precision_active() reports it)."""
+    for i in range(hc.n_groups):
+        pg = hc.groups[i]
+        if pg.pe_type != PE['windowed'] or pg.pe_n_freqs <= 0:
+            continue
+        f = F32(1.0)
+        for _ in range(pg.pe_n_freqs):
+            f = F32(f * F32(pg.pe_freq_mult))
+        if not abs(F32(pg.pe_base_mult) * f) <= F32(FAST_SINCOS_MAX_FREQ):
+            return False
+    return True
+
 
 def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp32', _coarse=False, iteration='inherit'):
     """cfg: `experiment.model` group (dict/Cfg); dataset: {near, far, depth_range,

@@ -62,7 +62,9 @@ def _stage_layer_shapes(stage, n_out):
         if i == 0:
             shapes.append((W, n_in))
         elif i == D + 1:
-            shapes.append((n_out, W))
+            # (a skip into the last Linear: the reference sizes it (n_out, W) and then fails in forward on cat([input, x]); the
+            #  kernels and the packer define it like every other skip layer, hr_mlp_pack.h: layer_in)
+            shapes.append((n_out, W + (n_in if i in skips else 0)))
         elif i in skips:
             shapes.append((W, W + n_in))
         else:

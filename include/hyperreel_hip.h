@@ -118,7 +118,9 @@ enum { HR_MLP_FP32 = 0, HR_MLP_BF16X3 = 1, HR_MLP_F16X3 = 2, HR_MLP_F16X2 = 3,
        /* fp16 halves like F16X3, but only the leading product x_hi*w_hi is an f16 MFMA: the two correction products (2^-11 of it) are ONE
         * fp8 (OCP e4m3) K=64 MFMA per 32 k with power-of-two block scales -- two thirds of F16X3's matrix-pipe time at ~2^-16 relative
         * per product (F16X3 2^-22, F16X2 2^-12).  Same range rule as F16X3, plus a per-layer exponent for the fp8 images taken from the
-        * calibration (16x headroom); an activation beyond either range sets HR_OPT_MLP_OVERFLOW.  gfx950 (v_mfma_scale_f32_32x32x64_f8f6f4). */
+        * calibration (16x headroom); an activation beyond either range sets HR_OPT_MLP_OVERFLOW.  gfx950 (v_mfma_scale_f32_32x32x64_f8f6f4).
+        * Its kernels evaluate the windowed positional encoding with v_sin / v_cos, which holds up to pe_base_mult * pe_freq_mult^pe_n_freqs
+        * = 16 per windowed group: beyond that F16F8, F16F8V and HR_MLP_AUTO all resolve to F16X3 (HR_OPT_MLP_PRECISION_ACTIVE says so). */
        HR_MLP_F16F8 = 5,
        /* F16F8 with its discrete decisions VERIFIED (what HR_MLP_AUTO resolves to where it applies: a plain ray MLP of width 256, at most 64
         * samples per ray, activations inside the fp16 range).  The per-sample stage is continuous in the MLP's head except at a few

@@ -161,6 +161,80 @@ def test_width_128_defeats_it_too():
     assert mlp_choice(hc, FITS)[3] == E_INVALID
 
 
+def test_windowed_encoding_beyond_16_takes_f16f8_away():
+    """The f16f8 kernels' v_sin / v_cos encoding is held to pe_base_mult * freq_mult^n_freqs <= 16 per windowed group (6e-8 x 16 ~ 1e-6 of
+    phase on a coordinate of order one).  DoNeRF's net has one frequency (2); 2^4 = 16 is inside, the float above 16 (base 1 + 2^-23), 2^5
+    and 8 x 2^2 = 32 are beyond: auto and a forced f16f8 / f16f8v are then f16x3 without verification (HR_E_RANGE where the activations
+    do not fit, as for a forced f16x3; auto: bf16x3), the other arithmetics as asked.  BasicPE (IEEE sinf in every kernel), a group
+    without PE and one without frequencies do not count, a second group does.  A fall-back, not a refusal: shipped nets are beyond the
+    limit and are rendered under a forced f16f8 (tests/test_gpu_f16f8.py).  plan.py's mirror agrees case by case."""
+    up = float(np.nextafter(F32(1), F32(2)))
+    cases = [(1, 2.0, 1.0, True), (4, 2.0, 1.0, True), (2, 4.0, 1.0, True), (3, 2.0, 2.0, True), (4, 2.0, up, False), (5, 2.0, 1.0, False),
+             (2, 2.0, 8.0, False), (8, 2.0, 1.0, False), (0, 2.0, 16.0, True), (0, 2.0, 17.0, True), (4, -2.0, 1.0, True), (5, -2.0, 1.0, False)]
+    for n, mult, base, ok in cases:
+        for want in sorted(P, key=P.get):
+            hc = _config(mlp_precision=want)
+            g = hc.groups[0]
+            assert g.pe_type == plan.PE['windowed']
+            g.pe_n_freqs, g.pe_freq_mult, g.pe_base_mult = n, mult, base
+            assert plan.fast_sincos_ok(hc) == ok, (n, mult, base)
+            got = mlp_choice(hc, FITS)
+            if ok or want in ('fp32', 'bf16x3', 'f16x3', 'f16x2'):
+                _check(got, TABLE[want, True, True])
+                _check(mlp_choice(hc, TOO_LARGE), TABLE[want, False, True])
+            else:
+                assert got == (P['f16x3'], 0, True, OK), (want, n, mult, base)
+                far = mlp_choice(hc, TOO_LARGE)
+                assert far == (P['bf16x3'], 0, True, OK) if want == 'auto' else far[2:] == (True, E_RANGE), (want, far)
+    hc = _config(mlp_precision='f16f8')
+    hc.groups[0].pe_n_freqs = 8
+    hc.groups[0].pe_type = plan.PE['basic']
+    assert plan.fast_sincos_ok(hc) and mlp_choice(hc, FITS) == (P['f16f8'], 0, True, OK)
+    hc.groups[0].pe_type = plan.PE[None]
+    assert plan.fast_sincos_ok(hc) and mlp_choice(hc, FITS) == (P['f16f8'], 0, True, OK)
+    hc = _config('neural_3d_z_plane', mlp_precision='f16f8v')           # two groups: the rays' and the time column's
+    assert hc.n_groups == 2 and mlp_choice(hc, FITS) == (P['f16f8'], 1, True, OK)
+    hc.groups[1].pe_n_freqs = 5
+    assert not plan.fast_sincos_ok(hc) and mlp_choice(hc, FITS) == (P['f16x3'], 0, True, OK)
+    # the five benchmark families: at most 4
+    for model in C.MODEL_NAMES:
+        hc = _config(model)
+        for i in range(hc.n_groups):
+            assert hc.groups[i].pe_base_mult * hc.groups[i].pe_freq_mult ** hc.groups[i].pe_n_freqs <= 4.0
+    # every arithmetic still compiles beyond the limit (nothing is refused)
+    cfg = C.model_config('donerf_sphere')
+    cfg.embedding.embeddings.ray_prediction_0.params.ray.pe.update(n_freqs=5, exclude_identity=True)
+    ds = C.dataset_scalars('donerf_sphere')
+    for want in sorted(P, key=P.get):
+        hc = plan.compile_config(cfg, ds, [28, 24, 20], mlp_precision=want)
+        assert hc.mlp_in == 60 and hc.mlp_precision == P[want] and not plan.fast_sincos_ok(hc)
+
+
+def test_shipped_sweep_nets_beyond_the_limit_still_compile_under_f16f8():
+    """Why the rule falls back instead of refusing: of the shipped YAMLs' fixtures, stanford_z_plane_mem encodes its two-plane coordinates
+    with six frequencies (2^6 = 64) and two more nets sit at the limit itself (2^4).  All of them compile under a forced f16f8, and the
+    one beyond the limit resolves to f16x3."""
+    from helpers import Golden, sweep_cases
+    top = {}
+    for case in sweep_cases():
+        g = Golden(case)
+        if plan.is_cascade(g.cfg):
+            continue
+        try:
+            hc = plan.compile_config(g.cfg, g.dataset, g.grid, mlp_precision='f16f8')
+        except NotImplementedError as e:
+            assert 'hidden_channels == 256' in str(e), (case, e)          # (the 128-wide nets have the exact fp32 MLP only)
+            continue
+        freqs = [hc.groups[i].pe_base_mult * hc.groups[i].pe_freq_mult ** hc.groups[i].pe_n_freqs for i in range(hc.n_groups)
+                 if hc.groups[i].pe_type == plan.PE['windowed'] and hc.groups[i].pe_n_freqs > 0]
+        top[case] = max(freqs, default=0.0)
+        assert plan.fast_sincos_ok(hc) == (top[case] <= 16.0)
+        if top[case] > 16.0:
+            assert mlp_choice(hc, [1.0] * 8) == (P['f16x3'], 0, True, OK)
+    assert top['sweep/stanford_z_plane_mem'] == 64.0 and sorted(c for c, v in top.items() if v > 16.0) == ['sweep/stanford_z_plane_mem']
+    assert sum(v == 16.0 for v in top.values()) >= 2
+
+
 def test_intersections_the_margins_are_derived_for():
     """Axis planes (z_plane, voxel_grid), the euclidean distance, sphere and cylinder with fixed origins; not the resized sphere /
     cylinder (sphere_new, cylinder_new) nor the deformable voxel grid.  The shipped families: all five are verified under auto."""
