@@ -83,6 +83,10 @@ int validate(const hr_config& c, bool coarse = false)
     for (int i = 0; i < 3; ++i)
         if (c.grid[i] < 2) return fail(HR_E_INVALID, "grid size must be >= 2 on every axis");
     if (c.shading == HR_SHADING_RGB ? c.app_dim != 3 : c.app_dim != 27) return fail(HR_E_INVALID, "app_dim must be 3 (RGB) or 27 (SH)");
+    if (hr_shading_is_mlp(c.shading) && !coarse) {     // the colour network's kernels
+        if (c.casc_in_z > 0) return fail(HR_E_INVALID, "MLP shading modes do not support point_prediction cascades");
+        if (c.z_channels > HR_SHADE_MAX_Z) return fail(HR_E_INVALID, "MLP shading modes support at most %d samples per ray (got %d)", HR_SHADE_MAX_Z, c.z_channels);
+    }
     if (c.mlp_precision < HR_MLP_FP32 || c.mlp_precision > HR_MLP_F16F8V) return fail(HR_E_INVALID, "unknown mlp_precision");
     if (c.mlp_layers != 0 && c.mlp_precision != HR_MLP_FP32 && c.mlp_precision != HR_MLP_AUTO && c.mlp_hidden != 256)      // (AUTO resolves to fp32 there)
         return fail(HR_E_INVALID, "the split (bf16x3 / f16x3) MLP needs mlp_hidden == 256");
@@ -191,6 +195,48 @@ int hr_model_create_cascade(const hr_config* coarse, const hr_config* fine, hr_m
     return HR_OK;
 }
 
+static const char* const SHADE_TENSORS[6] = {"renderModule.mlp.0.weight", "renderModule.mlp.0.bias", "renderModule.mlp.2.weight",
+                                             "renderModule.mlp.2.bias",   "renderModule.mlp.4.weight", "renderModule.mlp.4.bias"};
+
+int hr_model_set_shading_mlp(hr_model* m, const hr_shading_mlp* d)
+{
+    if (!m || !d) return fail(HR_E_INVALID, "null argument");
+    if (m->is_coarse || !hr_shading_is_mlp(m->cfg.shading))
+        return fail(HR_E_INVALID, "hr_model_set_shading_mlp: the model's shading is not HR_SHADING_MLP_FEA / HR_SHADING_MLP");
+    if (d->view_pe < 0 || d->view_pe > HR_SHADE_MAX_PE) return fail(HR_E_INVALID, "view_pe must be in [0,%d] (got %d)", HR_SHADE_MAX_PE, d->view_pe);
+    if (m->cfg.shading == HR_SHADING_MLP_FEA && (d->fea_pe < 0 || d->fea_pe > HR_SHADE_MAX_PE))
+        return fail(HR_E_INVALID, "fea_pe must be in [0,%d] (got %d)", HR_SHADE_MAX_PE, d->fea_pe);
+    if (d->feature_c < 1 || d->feature_c > HR_SHADE_MAX_C) return fail(HR_E_INVALID, "feature_c must be in [1,%d] (got %d)", HR_SHADE_MAX_C, d->feature_c);
+    for (const char* name : SHADE_TENSORS) { m->expect.erase(name); m->raw.erase(name); }
+    m->shade_net = hr_shade_net(m->cfg.shading, *d);
+    for (int l = 0; l < 3; ++l) {
+        const HrShadeLayer L = hr_shade_layer(m->shade_net, l);
+        m->expect[SHADE_TENSORS[2 * l]] = sizeof(float) * (size_t)L.N * L.K;
+        m->expect[SHADE_TENSORS[2 * l + 1]] = sizeof(float) * (size_t)L.N;
+    }
+    m->shade_set = true;
+    m->finalized = false;
+    return HR_OK;
+}
+
+// the colour network's tensors -> the shading kernel's tiles (hr_shade.h), at finalize
+static int pack_shading(hr_model* m)
+{
+    for (int l = 0; l < 3; ++l) {
+        const HrShadeLayer L = hr_shade_layer(m->shade_net, l);
+        std::vector<float> w((size_t)L.N * L.K), b((size_t)L.N), tiles, bias;
+        HR_HIP(hipMemcpy(w.data(), m->raw[SHADE_TENSORS[2 * l]].p, w.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HR_HIP(hipMemcpy(b.data(), m->raw[SHADE_TENSORS[2 * l + 1]].p, b.size() * sizeof(float), hipMemcpyDeviceToHost));
+        hr_shade_pack_layer(L, w.data(), b.data(), tiles, bias);
+        HR_HIP(m->shade_w[l].alloc(tiles.size() * sizeof(float)));
+        HR_HIP(hipMemcpy(m->shade_w[l], tiles.data(), tiles.size() * sizeof(float), hipMemcpyHostToDevice));
+        HR_HIP(m->shade_b[l].alloc(bias.size() * sizeof(float)));
+        HR_HIP(hipMemcpy(m->shade_b[l], bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
+        m->packed_bytes += (int64_t)((tiles.size() + bias.size()) * sizeof(float));
+    }
+    return HR_OK;
+}
+
 int hr_model_upload(hr_model* m, const char* name, const void* ptr, size_t bytes)
 {
     if (!m || !name) return fail(HR_E_INVALID, "null argument");
@@ -225,7 +271,10 @@ static int finalize_end(hr_model* m, HrMlpState& mlp)
 {
     HR_HIP(hipGetLastError());
     if (m->chunk == 0 && !m->is_coarse) {
-        const int rc = hr_model_reserve(m, hr_default_chunk(hr_head_quads(m->cfg, m->p_live), rows_per_ray(m->cfg)));
+        int64_t chunk = hr_default_chunk(hr_head_quads(m->cfg, m->p_live), rows_per_ray(m->cfg));
+        if (hr_shading_is_mlp(m->cfg.shading))
+            chunk = hr_shade_default_chunk(chunk, hr_shade_plan(m->cfg.shading, m->shade_net.view_pe, m->shade_net.fea_pe, m->shade_net.feature_c, m->cfg.z_channels));
+        const int rc = hr_model_reserve(m, chunk);
         if (rc != HR_OK) return rc;
     }
     const int rc = set_mlp_state(m, mlp, nullptr);
@@ -242,6 +291,11 @@ int hr_model_finalize(hr_model* m)
         if (rc != HR_OK) return rc;
     }
     const hr_config& c = m->cfg;
+    if (hr_shading_is_mlp(c.shading) && !m->is_coarse) {
+        if (!m->shade_set) return fail(HR_E_STATE, "MLP shading mode: hr_model_set_shading_mlp has not been called");
+        for (const char* name : SHADE_TENSORS)
+            if (m->raw.find(name) == m->raw.end()) return fail(HR_E_STATE, "MLP shading mode: tensor '%s' was never uploaded", name);
+    }
     for (auto& kv : m->expect)
         if (m->raw.find(kv.first) == m->raw.end())
             return fail(HR_E_MISSING, "tensor '%s%s' was never uploaded", (m->coarse && kv.first.compare(0, 4, "mlp.") == 0) ? "mlp1." : "",
@@ -324,6 +378,10 @@ int hr_model_finalize(hr_model* m)
         HR_HIP(hipMemcpy(m->slot_col, sc.data(), sc.size() * sizeof(int), hipMemcpyHostToDevice));
         m->basis_ld = ld;
     }
+    if (hr_shading_is_mlp(c.shading)) {
+        const int rc = pack_shading(m);
+        if (rc != HR_OK) return rc;
+    }
     // hr_render_frame: one line per time plane for the frame's blended keyframe rows (float32 texels)
     for (int j = 0; j < 3; ++j) {
         m->frame_line[j].reset();
@@ -379,6 +437,13 @@ int hr_model_reserve(hr_model* m, int64_t rays_per_chunk)
     const size_t bytes = sizeof(float) * n_rows * nq * 4;                        // HQ layout over rows
     HR_HIP(m->head.alloc(bytes));
     if (m->cfg.mlp_layers == 0) HR_HIP(hipMemset(m->head, 0, bytes));   // ZeroMLP: written once, only ever read
+    m->shade_rows.reset();
+    m->shade_rgb.reset();
+    if (hr_shading_is_mlp(m->cfg.shading) && !m->is_coarse) {           // hr_shade_plan's ws_bytes_per_ray
+        const size_t samples = (size_t)rays_per_chunk * m->cfg.z_channels;
+        HR_HIP(m->shade_rows.alloc(sizeof(float) * samples * HR_SHADE_ROW));
+        HR_HIP(m->shade_rgb.alloc(sizeof(float) * samples * 3));
+    }
     if (m->coarse) {
         int rc = hr_model_reserve(m->coarse.get(), rays_per_chunk);
         if (rc != HR_OK) return rc;
@@ -510,7 +575,8 @@ int64_t hr_model_device_bytes(const hr_model* m)
     int64_t raw = 0;
     for (auto& kv : m->raw) raw += (int64_t)kv.second.bytes;
     return raw + m->packed_bytes + (m->mlp.pack ? m->mlp.pack->bytes : 0) + (int64_t)sizeof(float) * m->chunk * m->cfg.z_channels * m->p_live +
-           (m->rows ? (int64_t)sizeof(float) * m->chunk * m->cfg.casc_in_z * m->cfg.casc_row_dim : 0) + hr_model_device_bytes(m->coarse.get());
+           (m->rows ? (int64_t)sizeof(float) * m->chunk * m->cfg.casc_in_z * m->cfg.casc_row_dim : 0) +
+           (m->shade_rows ? (int64_t)sizeof(float) * m->chunk * m->cfg.z_channels * (HR_SHADE_ROW + 3) : 0) + hr_model_device_bytes(m->coarse.get());
 }
 
 void hr_model_destroy(hr_model* m)

@@ -101,6 +101,20 @@ void fill_sample_args(const hr_model* m, HrSampleArgs& a, const float* rays, int
     for (int i = 0; i < 4; ++i) a.row_kind[i] = a.row_len[i] = 0;
 }
 
+static void fill_shade_args(const hr_model* m, HrShadeArgs& a, const float* feat, int64_t feat_ld, const float* vdir, int64_t vdir_ld, int64_t n_rows,
+                            float* rgb)
+{
+    const HrShadeNet& g = m->shade_net;
+    a.net = g;
+    a.stride = hr_shade_plan(g.shading, g.view_pe, g.fea_pe, g.feature_c, 1).stride;
+    a.feat = feat; a.feat_ld = feat_ld;
+    a.vdir = vdir; a.vdir_ld = vdir_ld;
+    a.live_col = -1;
+    a.n_rows = n_rows;
+    a.rgb = rgb;
+    for (int l = 0; l < 3; ++l) { a.wpack[l] = m->shade_w[l]; a.bias[l] = m->shade_b[l]; }
+}
+
 // Cascade, everything before the final sample kernel: coarse MLP -> coarse intersect (emits the point MLP's input
 // rows, one per coarse sample) -> point MLP over n * casc_in_z rows.  Leaves the fine head in m->head.
 static void launch_cascade_front(hr_model* m, const float* rays, int64_t n, hipStream_t st)
@@ -145,6 +159,7 @@ void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int
 // The frame kernel (fused_impl.inc) for the whole ray list; false: hr_frame_plan says the call does not fit it (nothing launched)
 bool launch_frame(hr_model* m, const float* rays, int64_t n, float* rgb, bool probe, hipStream_t st)
 {
+    if (hr_shading_is_mlp(m->cfg.shading)) return false;      // the colour network is no part of the frame kernel: the chunked plan (launch_samples)
     const int prec = m->mlp.active_precision, L = m->cfg.mlp_layers;
     const bool split = prec == HR_MLP_BF16X3 || prec == HR_MLP_F16X3 || prec == HR_MLP_F16X2 || prec == HR_MLP_F16F8;      // their elements: 16 bits (HrMlpTiles::wsplit)
     const HrFramePlanIn in = {n, m->opt_frame_kernel, m->opt_sample_waves, m->coarse || m->is_coarse, m->mlp.verified != 0, split, sizeof(uint16_t),
@@ -175,17 +190,33 @@ static int check_render(const hr_model* m, const float* rays, int64_t n, const f
 // The sample stage of one launch: the plain kernel, or with `maps` (hr_render_maps: non-NULL, some pointer set) the kernel that also
 // writes the per-ray maps.  r0: the launch's first ray in the caller's buffers, as args.rgb is offset (0 for the list-driven passes,
 // whose rays are indices into the whole call)
-static void launch_samples(const hr_model* m, const HrSampleArgs& sa, const hr_maps* maps, int64_t r0, hipStream_t st)
+// false: the runtime refused a kernel's LDS request (an MLP shading mode's shading kernel; the launch's pixels are not written)
+static bool launch_samples(const hr_model* m, const HrSampleArgs& sa, const hr_maps* maps, int64_t r0, hipStream_t st)
 {
-    if (!maps) {
+    const bool shade = hr_shading_is_mlp(m->cfg.shading);
+    if (!maps && !shade) {
         hr_launch_samples(m->kcfg, sa, st);
-        return;
+        return true;
     }
-    hr_maps mp = *maps;
+    hr_maps mp = hr_maps();
+    if (maps) mp = *maps;
     if (mp.distances_dev) mp.distances_dev += r0;
     if (mp.points_dev) mp.points_dev += r0 * 3;
     if (mp.acc_dev) mp.acc_dev += r0;
-    hr_launch_samples_maps(m->kcfg, sa, mp, st);
+    if (!shade) {
+        hr_launch_samples_maps(m->kcfg, sa, mp, st);
+        return true;
+    }
+    // MLP shading modes: the chunk's samples exported, shaded by the colour network, composited by the import form
+    HrSampleArgs ex = sa;
+    ex.fields = hr_fields();                    // diagnostics are the import form's
+    hr_launch_samples_shade_export(m->kcfg, ex, m->shade_rows, st);
+    HrShadeArgs ha;
+    fill_shade_args(m, ha, m->shade_rows, HR_SHADE_ROW, m->shade_rows + HR_SHADE_FEAT, HR_SHADE_ROW, sa.n_rays * m->cfg.z_channels, m->shade_rgb);
+    ha.live_col = HR_SHADE_FEAT + 3;
+    if (!hr_launch_shade(ha, st)) return false;
+    hr_launch_samples_shade_import(m->kcfg, sa, mp, m->shade_rows, m->shade_rgb, st);
+    return true;
 }
 
 // The verified fast path over one call's rays: first pass in f16f8 with the rays at risk listed on the device, then the list
@@ -278,7 +309,7 @@ static int render_impl(hr_model* m, const float* rays_dev, int64_t n_rays, float
     // verified fast path.  With diagnostics requested every output comes from ONE arithmetic: the f16x3 tiles throughout.
     // So does a model with an occupancy volume (hr_occupancy_test decides per cell from a head-dependent point; the band does not cover it),
     // and a render inside a stream capture whose band is out of date (hr_model_update_config since the last measurement: measuring synchronises).
-    bool verify = m->mlp.verified && !fields && !m->occ && n_rays < ((int64_t)1 << 31);
+    bool verify = m->mlp.verified && !fields && !m->occ && n_rays < ((int64_t)1 << 31) && !hr_shading_is_mlp(c.shading);
     if (verify && m->mlp.band_stale) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
@@ -312,7 +343,7 @@ static int render_impl(hr_model* m, const float* rays_dev, int64_t n_rays, float
                 hr_launch_head_export(m->head, fields->head_dev + r0 * (int64_t)Z * c.preds_per_z, n, Z, c.preds_per_z, m->p_live,
                                       (m->mlp.pack->n_out + 3) / 4, rows_per_ray(c), m->col_map, st);
         }
-        launch_samples(m, sa, maps, r0, st);
+        if (!launch_samples(m, sa, maps, r0, st)) return fail(HR_E_HIP, "the shading kernel's LDS request was refused");
     }
     HR_HIP(hipGetLastError());
     return HR_OK;
@@ -377,7 +408,23 @@ int hr_stage_samples(hr_model* m, const float* rays_dev, int64_t n_rays, float* 
     if (n_rays > m->chunk) return fail(HR_E_INVALID, "n_rays exceeds the reserved chunk (%lld)", (long long)m->chunk);
     HrSampleArgs sa;
     fill_sample_args(m, sa, rays_dev, n_rays, rgb_dev);
-    hr_launch_samples(m->kcfg, sa, (hipStream_t)stream);
+    if (!launch_samples(m, sa, nullptr, 0, (hipStream_t)stream))    // (an MLP shading mode: export, colour network, import)
+        return fail(HR_E_HIP, "the shading kernel's LDS request was refused");
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}
+
+int hr_stage_shade(hr_model* m, const float* feat_dev, const float* viewdirs_dev, int64_t n, float* rgb_dev, void* stream)
+{
+    if (!m) return fail(HR_E_INVALID, "null model");
+    if (!m->finalized) return fail(HR_E_STATE, "hr_model_finalize has not been called");
+    if (!hr_shading_is_mlp(m->cfg.shading)) return fail(HR_E_INVALID, "hr_stage_shade: the model's shading is not HR_SHADING_MLP_FEA / HR_SHADING_MLP");
+    if (n < 0) return fail(HR_E_INVALID, "negative row count");
+    if (n > 0 && (!feat_dev || !viewdirs_dev || !rgb_dev)) return fail(HR_E_INVALID, "null feature / view direction / rgb buffer");
+    if (hr_shade_blocks(n) >= ((int64_t)1 << 31)) return fail(HR_E_INVALID, "hr_stage_shade: too many rows for one launch");
+    HrShadeArgs ha;
+    fill_shade_args(m, ha, feat_dev, HR_SHADE_FEAT, viewdirs_dev, 3, n, rgb_dev);
+    if (!hr_launch_shade(ha, (hipStream_t)stream)) return fail(HR_E_HIP, "the shading kernel's LDS request was refused");
     HR_HIP(hipGetLastError());
     return HR_OK;
 }

@@ -146,6 +146,34 @@ struct HrSampleArgs {
     unsigned* flags;        // the model's sticky status word (bit 2: the redo list overflowed)
 };
 
+// ---------------------------------------------------------------- MLP shading modes (shade_kernel.hip, sample_shade_kernel.hip)
+#include "hr_shade.h"
+
+// workspace pointers of the sample stage's export / import forms: an argument of those two kernels only (HrSampleArgs stays as it is)
+struct HrShadeIO {
+    float* rows;            // export (written) and import (the live flags read): (n_rays * Z, HR_SHADE_ROW) rows [f | v | live | 0] of the launch's sorted samples
+    const float* rgbk;      // import: (n_rays * Z, 3) colours of the shading kernel
+    int m_off;              // export: float offset in the dynamic LDS of the workgroup's 27 x ca_total copy of basis_mat
+};
+struct HrShadeArgs {
+    HrShadeNet net;
+    int stride;                  // hr_shade_plan's LDS row stride
+    const float* feat;           // row r's 27 features at feat + r * feat_ld
+    int64_t feat_ld;
+    const float* vdir;           // row r's view direction at vdir + r * vdir_ld
+    int64_t vdir_ld;
+    int live_col;                // >= 0: feat[r * feat_ld + live_col] != 0 marks a row whose colour is read (tiles without one are skipped); -1: every row
+    int64_t n_rows;
+    float* rgb;                  // (n_rows, 3)
+    const float4* wpack[3];      // hr_shade.h's tiles
+    const float* bias[3];
+};
+// false: the runtime refused the kernel's LDS (nothing launched)
+bool hr_launch_shade(const HrShadeArgs& a, hipStream_t stream);
+void hr_launch_samples_shade_export(const hr_config& cfg, const HrSampleArgs& args, float* rows, hipStream_t stream);
+// maps: ray-indexed like args.rgb; all pointers NULL when no map is asked for
+void hr_launch_samples_shade_import(const hr_config& cfg, const HrSampleArgs& args, const hr_maps& maps, float* rows, const float* rgbk, hipStream_t stream);
+
 // training forward (mlp_split_impl.inc, HR_SPLIT_TRAIN_KERNEL): where the output of hidden Linear l (after its LeakyReLU) goes besides LDS --
 // act[l] + ray * ld[l] + off[l] + feature, fp32 (NULL: not kept)
 struct HrMlpTaps {

@@ -169,6 +169,13 @@ struct HR_HIDDEN hr_model {
                                            // events, profiles/r05_headline_diag_*.json) and with the tighter tail (hardware block dispatch instead of a static tile deal)
     int opt_sample_waves = HR_DEFAULT_SAMPLE_WAVES;
     int n_cus = 0;
+    // MLP shading modes (hr_model_set_shading_mlp): the colour network's descriptor, its tiles (hr_shade.h) and the chunk's workspace
+    bool shade_set = false;
+    HrShadeNet shade_net = {};
+    DevMem<float4> shade_w[3];
+    DevMem<float> shade_b[3];
+    DevMem<float> shade_rows;            // (chunk * Z, HR_SHADE_ROW): the export form's rows
+    DevMem<float> shade_rgb;             // (chunk * Z, 3): the shading kernel's colours
 };
 
 // a ray with a live sample beyond it (60 degrees off a plane's normal; a sphere nearly tangent) is not what the margins of the verified fast

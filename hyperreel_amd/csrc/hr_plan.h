@@ -226,6 +226,8 @@ static inline bool hr_sample_lds_refused(const hr_config& c, int p_live, size_t*
     (void)hr_plane_geometry(c, pl, &ca_total, &n_basis_cols);      // (an inconsistent geometry is refused by hr_model_finalize)
     const int zp = hr_round_zp(c.z_channels);
     *bytes = hr_sample_lds_bytes(hr_head_quads(c, p_live), ca_total, zp, rows_per_ray(c));
+    // an MLP shading mode: the export form of the sample stage keeps all 27 rows of basis_mat behind it (sample_shade_kernel.hip)
+    if (c.shading == HR_SHADING_MLP_FEA || c.shading == HR_SHADING_MLP) *bytes += sizeof(float) * (size_t)27 * ca_total;
     return *bytes + 4096 + (zp > 64 ? 0 : 256 * sizeof(float)) > HR_LDS_PER_WORKGROUP;
 }
 
@@ -568,7 +570,9 @@ static inline HrMlpChoice hr_mlp_choice(const hr_config& c, bool cascade_level, 
     if (!range_supported) return {want, 0, true, HR_E_INVALID};
     bool fits = true;
     for (int l = 0; l < c.mlp_layers; ++l) fits = fits && isfinite(act_max[l]) && act_max[l] < HR_F16_CALIBRATION_LIMIT;
-    const bool f8_ok = hr_mlp_fast_sincos_ok(c), can_verify = f8_ok && hr_mlp_can_verify(c, cascade_level);
+    // (an MLP shading mode: the verified path's margins are not derived for the colour network -- f16f8 / f16f8v / auto run f16x3 there)
+    const bool shade_mlp = c.shading == HR_SHADING_MLP_FEA || c.shading == HR_SHADING_MLP;
+    const bool f8_ok = !shade_mlp && hr_mlp_fast_sincos_ok(c), can_verify = f8_ok && hr_mlp_can_verify(c, cascade_level);
     if (want == HR_MLP_AUTO) {
         if (!fits) return {HR_MLP_BF16X3, 0, true, HR_OK};
         return {can_verify ? HR_MLP_F16F8 : HR_MLP_F16X3, can_verify ? 1 : 0, true, HR_OK};
@@ -618,5 +622,65 @@ static inline int hr_verify_fallback(float listed_frac, float max_d_rgb)
     if (!(max_d_rgb <= HR_VERIFY_RGB_LIMIT)) return 2;
     return listed_frac > HR_VERIFY_LISTED_LIMIT ? 1 : 0;
 }
+
+// ---------------------------------------------------------------- MLP shading (shade_kernel.hip, sample_shade_kernel.hip; layout: hr_shade.h)
+// A model whose colour comes from TensoRF's per-sample network (HR_SHADING_MLP_FEA / HR_SHADING_MLP) renders a chunk in three launches
+// after the ray MLP: the sample stage in its export form (per sorted sample a 32-float row: 27 features, the view direction, a live
+// flag, a zero), the shading kernel over all rows of the chunk, and the sample stage in its import form, which composites the
+// network's colours exactly as it composites decoded ones.
+#define HR_SHADE_FEAT 27
+#define HR_SHADE_ROW 32           // floats of an exported row: [f 0..26 | v 27..29 | live 30 | 0]
+#define HR_SHADE_MAX_PE 6
+#define HR_SHADE_MAX_C 256
+#define HR_SHADE_MAX_Z 64
+#define HR_SHADE_TILE_M 64        // rows of one MFMA tile of the shading kernel
+#define HR_SHADE_SPAN 512         // consecutive rows a workgroup of the shading kernel owns: their live rows, compacted, fill its tiles
+
+static inline bool hr_shading_is_mlp(int shading) { return shading == HR_SHADING_MLP_FEA || shading == HR_SHADING_MLP; }
+// width of the network's input: tensorf_base.py:43 (MLPRender_Fea), :111 (MLPRender)
+static inline int hr_shade_width(int shading, int view_pe, int fea_pe)
+{
+    return HR_SHADE_FEAT + 3 + 2 * 3 * view_pe + (shading == HR_SHADING_MLP_FEA ? 2 * HR_SHADE_FEAT * fea_pe : 0);
+}
+
+struct HrShadePlan {
+    int k0, k0p;                // input width, padded to a multiple of 16 (the k-step of the fp32 tiles)
+    int hp, nt_h;               // hidden width padded to 16, its 16-column tiles
+    int nt_wave;                // column tiles per wavefront in the hidden layers: ceil(nt_h / 4), 1..4 (the kernel's template argument)
+    int rows_per_tile;          // HR_SHADE_TILE_M; a workgroup compacts the live rows of HR_SHADE_SPAN rows into such tiles
+    int stride;                 // LDS row stride in floats: max(k0p, hp) + 4 (the hidden activations overwrite the input rows in place)
+    size_t lds;                 // dynamic LDS of a workgroup
+    size_t ws_bytes_per_ray;    // workspace of a chunk per ray: the exported rows and the network's colours
+    int launches;               // launches per chunk besides the ray MLP's
+};
+static inline HrShadePlan hr_shade_plan(int shading, int view_pe, int fea_pe, int feature_c, int z_channels)
+{
+    HrShadePlan P = HrShadePlan();
+    P.k0 = hr_shade_width(shading, view_pe, fea_pe);
+    P.k0p = (P.k0 + 15) & ~15;
+    P.hp = (feature_c + 15) & ~15;
+    P.nt_h = P.hp / 16;
+    P.nt_wave = (P.nt_h + 3) / 4;
+    P.rows_per_tile = HR_SHADE_TILE_M;
+    P.stride = (P.k0p > P.hp ? P.k0p : P.hp) + 4;
+    P.lds = (size_t)HR_SHADE_TILE_M * P.stride * sizeof(float);
+    P.ws_bytes_per_ray = (size_t)z_channels * (HR_SHADE_ROW + 3) * sizeof(float);
+    P.launches = 3;
+    return P;
+}
+// workgroups of the shading kernel over n rows
+static inline int64_t hr_shade_blocks(int64_t n_rows) { return (n_rows + HR_SHADE_SPAN - 1) / HR_SHADE_SPAN; }
+// rays per launch of an MLP-shaded model when the caller reserves nothing: the chunk's shading workspace stays within 256 MB
+static inline int64_t hr_shade_default_chunk(int64_t head_chunk, const HrShadePlan& P)
+{
+    int64_t rays = ((int64_t)256 << 20) / (int64_t)P.ws_bytes_per_ray;
+    rays &= ~(int64_t)63;
+    if (rays < 64) rays = 64;
+    return rays < head_chunk ? rays : head_chunk;
+}
+// the export form's live flag: the reference's app_mask, weight > rm_weight_mask_thre (strict; tensorf_no_sample.py:201).  Tiles of the
+// shading kernel without a flagged row are skipped, and the import form masks by the flag, not by its own weight (the two forms sum
+// the density in different orders: their weights agree to rounding, not always in a comparison)
+static constexpr inline bool hr_shade_live(float weight, float thresh) { return weight > thresh; }
 
 #endif  // HR_PLAN_H

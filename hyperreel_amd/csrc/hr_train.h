@@ -383,6 +383,7 @@ static inline
 const char* hr_train_unsupported(const hr_config& c)
 {
     if (c.grid_dtype != HR_GRID_FP32) return "float16 grids";
+    if (c.shading == HR_SHADING_MLP_FEA || c.shading == HR_SHADING_MLP) return "the colour network of shadingMode MLP_Fea / MLP (inference only)";
     return nullptr;
 }
 

@@ -1129,10 +1129,14 @@ __device__ __forceinline__ void hr_fill_decode(const hr_config& cfg, const HrSam
 // scratch of the block for rays that span several wavefronts (ZP > 64, stand-alone kernel only).
 // MAPS (hr_sample_maps_kernel only): also the ray's weighted sums of distance and point and its sum of weights -- the reference's
 // fields=['distances', 'points'] and acc_map (tensorf_no_sample.py:232, 254-278) -- into `*maps`, which no other instantiation reads.
-template <int ZP, bool HALF, int PIPE, int NB, int PC, bool MAPS = false>
+// SHADE (sample_shade_kernel.hip only; MLP shading modes, DESIGN 3l): 1 = the export form -- `M` holds all 27 rows of basis_mat, the
+// sample's 27 appearance features, its view direction and its live flag go to `shade->rows` (hr_plan.h: HR_SHADE_ROW floats per sorted
+// sample) and nothing else is written; 2 = the import form -- the colour of a sample the export form found above the weight threshold
+// (the row's live flag) is read from `shade->rgbk` (the shading kernel's output) instead of being decoded, everything after it is unchanged.
+template <int ZP, bool HALF, int PIPE, int NB, int PC, bool MAPS = false, int SHADE = 0>
 __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSampleArgs& a, const HrRayLane& L, int64_t ray, bool ray_ok, int k,
                                                const float* hrow, int HS, const float* M, const float* ones, float* s_x,
-                                               const hr_maps* maps = nullptr)
+                                               const hr_maps* maps = nullptr, const HrShadeIO* shade = nullptr)
 {
     const int tid = threadIdx.x;
     const int Z = cfg.z_channels;
@@ -1202,7 +1206,28 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
     if (a.occ && valid) valid = hr_occupancy_test(a, p);     // opt-in occupancy early-reject: empty space is neither gathered nor composited (sigma = 0)
     float sig_feat = 0.0f;
     float pre0 = 0.0f, pre1 = 0.0f, pre2 = 0.0f;
-    if constexpr (PC != 0) {               // plane classes [8, 4, 4] / [8, 0, 0] (hr_gather_844 / hr_gather_844h)
+    if constexpr (SHADE == 1) {            // export form: the own-sample gather once per three rows of basis_mat, each triple stored at once
+        HrAxisTaps at = {};
+        if (valid) {
+            at.ax[0] = hr_make_tap(hr_normalize_coord(cfg, p[0], 0), cfg.grid[0]);
+            at.ax[1] = hr_make_tap(hr_normalize_coord(cfg, p[1], 1), cfg.grid[1]);
+            at.ax[2] = hr_make_tap(hr_normalize_coord(cfg, p[2], 2), cfg.grid[2]);
+            at.t = hr_make_tap(cfg.video ? hr_normalize_time(cfg, base_t) : 0.0f, cfg.video ? cfg.num_keyframes : 2);
+        }
+        float* row = shade->rows + (ray * Z + k) * HR_SHADE_ROW;
+#pragma unroll 1
+        for (int t3 = 0; t3 < HR_SHADE_FEAT / 3; ++t3) {
+            float sg = 0.0f, f0 = 0.0f, f1 = 0.0f, f2 = 0.0f;
+            if (valid) {
+                const float* Mt = M + 3 * t3 * CA;
+                hr_gather_plane<HALF, 1, 0>(a.planes[0], at, Mt, CA, sg, f0, f1, f2);
+                hr_gather_plane<HALF, 1, 1>(a.planes[1], at, Mt, CA, sg, f0, f1, f2);
+                hr_gather_plane<HALF, 1, 2>(a.planes[2], at, Mt, CA, sg, f0, f1, f2);
+            }
+            if (t3 == 0) sig_feat = sg;
+            if (lane_ok) { row[3 * t3 + 0] = f0; row[3 * t3 + 1] = f1; row[3 * t3 + 2] = f2; }
+        }
+    } else if constexpr (PC != 0) {        // plane classes [8, 4, 4] / [8, 0, 0] (hr_gather_844 / hr_gather_844h)
         float pn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (valid) {
             pn[0] = hr_normalize_coord(cfg, p[0], 0);
@@ -1288,13 +1313,30 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
     if (kw == 0) T = before;                       // == 1 for the ray's first sample
     const float weight = alpha * T;
     HR_SPH(7);
+    if constexpr (SHADE == 1) {                    // export form: the rest of the sample's row, and nothing else
+        if (lane_ok) {
+            float* row = shade->rows + (ray * Z + k) * HR_SHADE_ROW;
+            row[HR_SHADE_FEAT + 0] = L.vd[0]; row[HR_SHADE_FEAT + 1] = L.vd[1]; row[HR_SHADE_FEAT + 2] = L.vd[2];
+            row[HR_SHADE_FEAT + 3] = hr_shade_live(weight, cfg.weight_thresh) ? 1.0f : 0.0f;
+            row[HR_SHADE_FEAT + 4] = 0.0f;
+        }
+        return;
+    }
 
     // ---- colour decode (+ per-sample scale/shift) and front-to-back sum
     float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
     if (lane_ok) {
         float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
         if (cfg.weight_thresh > 0.0f) risk->hit = risk->hit || (fabsf(weight - cfg.weight_thresh) <= 1e-4f);
-        if (weight > cfg.weight_thresh) {          // app_mask, tensorf_no_sample.py:201
+        if constexpr (SHADE == 2) {
+            // import form: renderModule's colour (tensorf_no_sample.py:208-219) from the shading kernel.  The mask is the one the export form
+            // took from ITS weight (the same arithmetic, the density summed in another order) and the shading kernel's tiles were chosen
+            // by -- a colour is read exactly where one was computed
+            if (shade->rows[(ray * Z + k) * HR_SHADE_ROW + HR_SHADE_FEAT + 3] != 0.0f) {
+                const float* c = shade->rgbk + (ray * Z + k) * 3;
+                r0 = c[0]; r1 = c[1]; r2 = c[2];
+            }
+        } else if (weight > cfg.weight_thresh) {   // app_mask, tensorf_no_sample.py:201
             if (cfg.shading == HR_SHADING_SH) {    // SHRender, tensorf_utils.py:334-338
                 r0 = fmaxf(pre0 + 0.5f, 0.0f); r1 = fmaxf(pre1 + 0.5f, 0.0f); r2 = fmaxf(pre2 + 0.5f, 0.0f);
             } else {                               // RGBRender, tensorf_utils.py:341-343

@@ -2,6 +2,12 @@
 // hr_sample_maps_kernel (sample_maps_kernel.hip) -- textually, not as a function, so that hr_sample_kernel compiles to the
 // instructions it always had.  In scope: ZP, HALF, PC, NB, `cfg` (the configuration in device memory) and the argument block `a`;
 // HR_SAMPLE_MAPS (false | true) and HR_SAMPLE_MAPS_PTR (nullptr | the kernel's hr_maps) select hr_sample_body's per-ray maps.
+// HR_SAMPLE_SHADE (0 unless defined; 1 export | 2 import) and HR_SAMPLE_SHADE_PTR (the kernel's HrShadeIO) select hr_sample_body's
+// forms for the MLP shading modes (sample_shade_kernel.hip).
+#ifndef HR_SAMPLE_SHADE
+#define HR_SAMPLE_SHADE 0
+#define HR_SAMPLE_SHADE_PTR nullptr
+#endif
     constexpr int RPB = 256 / ZP;   // rays per block
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int CA = a.ca_total;                   // padded appearance slots (multiple of 4)
@@ -85,9 +91,17 @@
     } else if (rib == 0) {
         hr_fill_decode<ZP>(cfg, a, hr_load_ray(cfg, a, 0, false), k, M);
     }
+#if HR_SAMPLE_SHADE == 1                          // export form (sample_shade_kernel.hip): all 27 rows of basis_mat, one copy per workgroup, behind the plan's LDS
+    M = lds + HR_SAMPLE_SHADE_PTR->m_off;
+    for (int pos = tid; pos < CA; pos += 256) {
+        const int col = a.slot_col[pos];
+        for (int c = 0; c < HR_SHADE_FEAT; ++c) M[c * CA + pos] = col >= 0 ? a.basis_t[(size_t)col * a.basis_ld + c] : 0.0f;
+    }
+#endif
     __shared__ __attribute__((aligned(16))) float s_ones[HR_GATHER_ONES];
     hr_gather_ones_init(s_ones);
     __syncthreads();
     const HrRayLane L = hr_read_ray_record(s_ray + rib * HR_RAY_RECORD);
 
-    hr_sample_body<ZP, HALF, 1, NB, PC, HR_SAMPLE_MAPS>(cfg, a, L, ray, ray_ok, k, s_head + rib * RPR * HS, HS, M, s_ones, s_x, HR_SAMPLE_MAPS_PTR);
+    hr_sample_body<ZP, HALF, 1, NB, PC, HR_SAMPLE_MAPS, HR_SAMPLE_SHADE>(cfg, a, L, ray, ray_ok, k, s_head + rib * RPR * HS, HS, M, s_ones, s_x, HR_SAMPLE_MAPS_PTR,
+                                                                         HR_SAMPLE_SHADE_PTR);

@@ -19,7 +19,7 @@ from torch import nn
 from . import lib as _lib
 from .config import n_to_reso, to_plain
 from .data import make_camera, make_fisheye, make_ndc
-from .plan import MLP_PRECISION, compile_model, fast_sincos_ok, hr_fields, hr_lightfield, hr_maps, upload_names
+from .plan import MLP_PRECISION, compile_model, fast_sincos_ok, hr_fields, hr_lightfield, hr_maps, shading_mlp, shading_width, upload_names
 
 _MLP_PRECISION_NAME = {code: name for name, code in MLP_PRECISION.items()}      # HR_OPT_MLP_PRECISION_ACTIVE -> 'f16x3' ...
 
@@ -107,6 +107,18 @@ class HostEmbedding(nn.Module):
         self.embeddings = nn.ModuleList(mods)
 
 
+class HostRenderModule(nn.Module):
+    """Parameter container shaped like MLPRender_Fea / MLPRender (nlf/nets/tensorf_base.py:38-69, 106-135): `mlp` is a Sequential with
+    Linears at indices 0, 2 and 4, initialised as there (nn.Linear's default, the last bias 0).  The function runs in the library
+    (csrc/shade_kernel.hip)."""
+
+    def __init__(self, in_mlpC, featureC):
+        super().__init__()
+        self.mlp = nn.Sequential(nn.Linear(in_mlpC, featureC), nn.ReLU(inplace=True), nn.Linear(featureC, featureC), nn.ReLU(inplace=True),
+                                 nn.Linear(featureC, 3))
+        nn.init.constant_(self.mlp[-1].bias, 0)
+
+
 class HostTensorVM(nn.Module):
     """Parameter container shaped like TensorVMSplit (nlf/nets/tensorf_base.py:895-991) or
     TensorVMKeyframeTime (nlf/nets/tensorf_dynamic.py:108-244)."""
@@ -137,6 +149,9 @@ class HostTensorVM(nn.Module):
         self.register_buffer('aabb', torch.tensor(to_plain(net_cfg['aabb']), dtype=torch.float32))
         self.register_buffer('gridSize', torch.tensor([int(v) for v in grid_size], dtype=torch.long))
         self.basis_mat = nn.Linear(sum(self.n_app), self.app_dim, bias=False)
+        shade = shading_mlp(net_cfg)
+        if shade is not None:                    # MLP_Fea / MLP: the reference's renderModule (tensorf_base.py:38-69, 106-135, 252-262)
+            self.renderModule = HostRenderModule(shading_width(net_cfg['shadingMode'], shade), shade.feature_c)
         if self.video:
             self.basis_mat_density = nn.Linear(sum(self.n_den), 1, bias=False)
         self.init_svd_volume(grid_size)
@@ -611,6 +626,8 @@ class HipLightfieldModel(nn.Module):
             _lib.call('hr_model_create_cascade', C.byref(coarse), C.byref(hc), C.byref(h))
         n.handle, n.key = h, want._replace(param_key=None)
         n.occ_key = None                       # a fresh handle holds no occupancy volume
+        if getattr(hc, 'shade_mlp', None) is not None:         # MLP shading modes: the colour network's descriptor, before any upload
+            _lib.call('hr_model_set_shading_mlp', h, C.byref(hc.shade_mlp))
         self._apply_options()
         if self._reserve:
             _lib.call('hr_model_reserve', h, self._reserve)
@@ -1012,6 +1029,9 @@ class HipLightfieldModel(nn.Module):
         (tensorf_no_sample.py:236).  The activation schedules are the converged ones (see set_iter).
         want_fields: also return {'distances', 'points', 'render_weights', 'head'} of THIS forward (detached; hr_train_forward_fields)."""
         from . import train as T
+        mode = self.cfg['color']['net'].get('shadingMode', 'MLP_PE')
+        if shading_mlp(self.cfg['color']['net']) is not None:
+            raise NotImplementedError(f'training with shadingMode {mode}: the colour network is inference only')
         h, hc = self.native(values_travel=True), self._hc
         rays = self._check_rays(rays)
         net_cfg = self.cfg['color']['net']

@@ -38,7 +38,38 @@ ISECT = {'z_plane': 0, 'sphere': 1, 'cylinder': 2, 'sphere_new': 3, 'cylinder_ne
 ISECT_Z_CHANNELS = {0: 1, 1: 4, 2: 4, 3: 8, 4: 8, 5: 1, 6: 1, 7: 4}     # z_vals channels each type reads per sample
 CONTRACT = {'identity': 0, 'mipnerf': 1, 'bbox': 2, 'z_depth': 2, 'donerf': 3}   # bbox and z_depth share the affine kernel path
 DENSITY = {'relu': 0, 'softplus': 1, 'relu_abs': 2}
-SHADING = {'RGB': 0, 'SH': 1}
+SHADING = {'RGB': 0, 'SH': 1, 'MLP_Fea': 2, 'MLP': 3}
+MLP_SHADING = ('MLP_Fea', 'MLP')          # TensoRF's per-sample colour networks (tensorf_base.py:38-69, 106-135): inference only
+SHADE_MAX_PE, SHADE_MAX_C, SHADE_MAX_Z = 6, 256, 64        # csrc/hr_plan.h: HR_SHADE_MAX_*
+
+
+class hr_shading_mlp(C.Structure):
+    """The colour network of an MLP shading mode (include/hyperreel_hip.h); compile_config hands it on as hc.shade_mlp."""
+    _fields_ = [('view_pe', C.c_int32), ('fea_pe', C.c_int32), ('feature_c', C.c_int32)]
+
+
+def shading_mlp(net):
+    """-> hr_shading_mlp of a colour net's YAML group, or None (RGB / SH).  Defaults: tensorf_base.py:238-241.  Refuses by name what the
+    kernels do not cover."""
+    mode = net.get('shadingMode', 'MLP_PE')
+    if mode not in MLP_SHADING:
+        return None
+    dim = int(net.get('data_dim_color', 27))
+    if dim != 27:
+        raise NotImplementedError(f"shadingMode '{mode}' with data_dim_color {dim}: the colour network's kernels take 27 appearance features")
+    d = hr_shading_mlp(int(net.get('view_pe', 6)), int(net.get('fea_pe', 6)) if mode == 'MLP_Fea' else 0, int(net.get('featureC', 128)))
+    if not 0 <= d.view_pe <= SHADE_MAX_PE:
+        raise NotImplementedError(f"shadingMode '{mode}': view_pe {d.view_pe} outside 0..{SHADE_MAX_PE}")
+    if not 0 <= d.fea_pe <= SHADE_MAX_PE:
+        raise NotImplementedError(f"shadingMode '{mode}': fea_pe {d.fea_pe} outside 0..{SHADE_MAX_PE}")
+    if not 1 <= d.feature_c <= SHADE_MAX_C:
+        raise NotImplementedError(f"shadingMode '{mode}': featureC {d.feature_c} outside 1..{SHADE_MAX_C}")
+    return d
+
+
+def shading_width(mode, d):
+    """Input width of the colour network: tensorf_base.py:43 (MLPRender_Fea), :111 (MLPRender)."""
+    return 27 + 3 + 2 * 3 * d.view_pe + (2 * 27 * d.fea_pe if mode == 'MLP_Fea' else 0)
 
 
 class hr_act(C.Structure):
@@ -757,9 +788,19 @@ def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp
     for k in range(3):
         hc.n_den[k], hc.n_app[k] = int(nd[k]), int(na[k])
     shading = n.get('shadingMode', 'MLP_PE')
+    if shading == 'MLP_PE':
+        # in_mlpC counts 3 + 6 pos_pe position inputs that forward never concatenates for these nets (tensorf_base.py:77 vs 93-99)
+        raise NotImplementedError("shadingMode 'MLP_PE': the reference cannot run it (MLPRender_PE's first Linear expects more inputs than its "
+                                  "forward concatenates)")
     if shading not in SHADING:
-        raise NotImplementedError(f"shadingMode '{shading}' is outside the hot-path scope (RGB, SH)")
+        raise NotImplementedError(f"shadingMode '{shading}' is outside the hot-path scope (RGB, SH, MLP_Fea, MLP)")
     hc.shading = SHADING[shading]
+    hc.shade_mlp = shading_mlp(n)             # None for RGB / SH; not part of hr_config: hr_model_set_shading_mlp takes it
+    if hc.shade_mlp is not None and not _coarse:
+        if hc.z_channels > SHADE_MAX_Z:
+            raise NotImplementedError(f"shadingMode '{shading}' with z_channels {hc.z_channels} > {SHADE_MAX_Z}")
+        if mlp_precision in ('f16f8', 'f16f8v') and hc.mlp_hidden == 256:
+            mlp_precision = 'f16x3'           # the verified path's margins are not derived for this decoder ('auto': hr_mlp_choice decides the same)
     hc.app_dim = int(n.get('data_dim_color', 27))
     hc.distance_scale = float(n.get('distance_scale', 25))
     hc.weight_thresh = float(n.get('rm_weight_mask_thre', 0.0001))
@@ -811,6 +852,9 @@ def compile_cascade(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='f
     -> ray_intersect -> ...  Returns (coarse, fine) hr_configs for hr_model_create_cascade.  The point MLP is
     described to `compile_config` as a ray_prediction over the columns of its input row."""
     import copy
+    mode = cfg['color']['net'].get('shadingMode', 'MLP_PE')
+    if mode in MLP_SHADING:
+        raise NotImplementedError(f"shadingMode '{mode}' with a point_prediction cascade")
     items = list(cfg['embedding']['embeddings'].items())
     types = [e['type'] for _, e in items]
     ip = types.index('point_prediction')
@@ -901,6 +945,10 @@ def upload_names(hc, coarse=None):
             for j in range(3):
                 names.append((f'{what}_{kind}.{j}', f'color_model.net.{what}_{kind}.{j}'))
     names.append(('basis_mat.weight', 'color_model.net.basis_mat.weight'))
+    if getattr(hc, 'shade_mlp', None) is not None:          # MLPRender_Fea / MLPRender: Sequential indices 0, 2, 4
+        for i in (0, 2, 4):
+            for what in ('weight', 'bias'):
+                names.append((f'renderModule.mlp.{i}.{what}', f'color_model.net.renderModule.mlp.{i}.{what}'))
     if hc.color_table_views > 0:
         names.append(('color_embedding', 'embedding_model.embeddings.{ct_idx}.color_embedding'))
     return names

@@ -206,6 +206,17 @@ def make_state_dict(cfg, dataset, grid_size=None, seed=0, density='dense', app_s
     sd[NET + 'basis_mat.weight'] = _uniform(rng, (app_dim, sum(na)), 1.0 / math.sqrt(max(sum(na), 1)))
     if video:
         sd[NET + 'basis_mat_density.weight'] = _uniform(rng, (1, sum(nd)), 1.0 / math.sqrt(max(sum(nd), 1)))
+    # MLP shading modes: renderModule.mlp.{0,2,4} (tensorf_base.py:38-69, 106-135), drawn LAST so that every other tensor of a seed is
+    # what it was.  nn.Linear's default U(+-1/sqrt(fan_in)), last bias 0 as the reference sets it; the last weight x 4 spreads the
+    # colours over (0.1, 0.9) instead of hugging 0.5 without saturating the sigmoid
+    mode = net.get('shadingMode', 'MLP_PE')
+    if mode in ('MLP_Fea', 'MLP'):
+        view_pe, fea_pe, C_ = int(net.get('view_pe', 6)), int(net.get('fea_pe', 6)), int(net.get('featureC', 128))
+        width = app_dim + 3 + 2 * 3 * view_pe + (2 * app_dim * fea_pe if mode == 'MLP_Fea' else 0)
+        for i, (o, n_in) in zip((0, 2, 4), ((C_, width), (C_, C_), (3, C_))):
+            b = 1.0 / math.sqrt(n_in)
+            sd[f'{NET}renderModule.mlp.{i}.weight'] = _uniform(rng, (o, n_in), b * (4.0 if i == 4 else 1.0))
+            sd[f'{NET}renderModule.mlp.{i}.bias'] = _uniform(rng, (o,), b) if i != 4 else np.zeros((o,), np.float32)
     return sd
 
 
@@ -274,6 +285,32 @@ def benchmark_rays(model_name, H=800, W=800, frame=0, num_frames=50):
     else:
         pose = look_at_pose((0.3, 0.0, 0.0), (1.0, 0.1, 0.05))
     return pinhole_rays(H, W, 40.0, pose, cam_id=0 if video else None, time=t)
+
+
+def scale_density(sd, factor):
+    """The scene with every density plane (not the lines / time planes) multiplied by `factor`: a thinner medium, whose transmittance
+    decays over the whole ray instead of the first few samples.  Returns a new dict."""
+    return {k: ((v * np.float32(factor)).astype(np.float32) if 'density_plane' in k and 'time' not in k else v) for k, v in sd.items()}
+
+
+def carve_half_space(sd, frac=0.5):
+    """Empties the scene where x lies in the lower `frac` of its axis: every density factor that spans x (the planes of pairs 0 and
+    1, the line or time plane of pair 2) vanishes there, so with a relu density a ray that stays on that side has no sample with a
+    weight and a ray that stays on the other side keeps all of its own.  Returns a new dict."""
+    out = dict(sd)
+    for k, v in sd.items():
+        if 'density_' not in k:
+            continue
+        j, kind = int(k.rsplit('.', 1)[1]), k.split('.')[-2]
+        v = v.copy()
+        if j in (0, 1) and kind in ('density_plane', 'density_plane_space'):       # (1, C, N[m1], Nx)
+            v[..., :int(frac * v.shape[3])] = 0.0
+        elif j == 2 and kind == 'density_line':                                    # (1, C, Nx, 1)
+            v[:, :, :int(frac * v.shape[2])] = 0.0
+        elif j == 2 and kind == 'density_plane_time':                              # (1, C, K, Nx)
+            v[..., :int(frac * v.shape[3])] = 0.0
+        out[k] = v
+    return out
 
 
 def carve_density(sd, lo=(0.25, 0.3, 0.2), hi=(0.75, 0.8, 0.7)):

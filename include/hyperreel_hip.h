@@ -104,7 +104,10 @@ enum { HR_CONTRACT_IDENTITY = 0, HR_CONTRACT_MIPNERF = 1, HR_CONTRACT_AFFINE = 2
        /* DoNeRFContract (contract.py:195-240): p -> p / |p| * (|p| fac + 1e-8)^(1/power), d -> sign(d) (|d| + 1e-8)^power / fac */
        HR_CONTRACT_DONERF = 3 };
 enum { HR_DENSITY_RELU = 0, HR_DENSITY_SOFTPLUS = 1, HR_DENSITY_RELU_ABS = 2 };
-enum { HR_SHADING_RGB = 0, HR_SHADING_SH = 1 };
+enum { HR_SHADING_RGB = 0, HR_SHADING_SH = 1,
+       /* TensoRF's per-sample colour networks (nlf/nets/tensorf_base.py:38-69 MLPRender_Fea, :106-135 MLPRender): inference only; the
+        * network is described by hr_model_set_shading_mlp (below), app_dim is 27 */
+       HR_SHADING_MLP_FEA = 2, HR_SHADING_MLP = 3 };
 /* arithmetic of the MLP GEMMs: exact fp32 MFMA, or three 16-bit MFMA products of the hi/lo split operands with fp32
  * accumulation (needs mlp_hidden 256): bf16 halves (~2^-17 relative per product, fp32 range) or fp16 halves (~2^-22,
  * i.e. fp32-grade, but activations must stay below 65504); F16X2 additionally takes the weights as single halfs (two
@@ -1086,6 +1089,25 @@ int hr_adam_step_dev(float* const* param_dev, const float* const* grad_dev, floa
  * must not exceed the reserved chunk size. */
 int hr_stage_mlp(hr_model* m, const float* rays_dev, int64_t n_rays, void* stream);
 int hr_stage_samples(hr_model* m, const float* rays_dev, int64_t n_rays, float* rgb_dev, void* stream);
+
+/* The per-sample colour network of an HR_SHADING_MLP_FEA / HR_SHADING_MLP model (`renderModule`, nlf/nets/tensorf_base.py:38-69, 106-135;
+ * called at nlf/nets/tensorf_no_sample.py:208-219): three Linears of hidden width feature_c over
+ *   MLP_FEA: [f, v, PE(f, fea_pe), PE(v, view_pe)]      MLP: [f, v, PE(v, view_pe)]        (fea_pe is not read)
+ * with f the 27 appearance features after basis_mat, v the sample's view direction and PE utils/tensorf_utils.py:232-239's
+ * cat[sin(p_i 2^j), cos(p_i 2^j)] (index i * F + j; a PE of 0 frequencies is left out), ReLU between the Linears, sigmoid after the last.
+ * view_pe, fea_pe in 0..6, feature_c in 1..256.
+ * hr_model_set_shading_mlp: between hr_model_create and hr_model_finalize of a model with such a shading (HR_E_INVALID for another model,
+ * a cascade, more than 64 samples per ray or a value out of range).  hr_model_upload then takes `renderModule.mlp.{0,2,4}.weight|bias` in
+ * the reference's (out, in) layout; hr_model_finalize returns HR_E_STATE, naming it, while the descriptor or one of the six tensors is
+ * missing.  Such a model renders through every hr_render* entry point (its own three-launch sample stage: DESIGN 3l; never the frame
+ * kernel or the verified fast path); the hr_train_* entry points return HR_E_INVALID for it.
+ * hr_stage_shade: the network alone on n rows -- feat_dev (n, 27), viewdirs_dev (n, 3) -> rgb_dev (n, 3), one launch on `stream`, no
+ * allocation, no synchronisation.  Additive: no existing struct or signature moved (HR_ABI_VERSION stays). */
+typedef struct hr_shading_mlp {
+    int32_t view_pe, fea_pe, feature_c;
+} hr_shading_mlp;
+int hr_model_set_shading_mlp(hr_model* m, const hr_shading_mlp* desc);
+int hr_stage_shade(hr_model* m, const float* feat_dev, const float* viewdirs_dev, int64_t n, float* rgb_dev, void* stream);
 
 /* Profiling aid: runs the MLP stage with a per-wave phase timeline.  trace_dev receives 64
  * s_memtime stamps per wave (4 waves per workgroup, workgroups of 64 or 128 rays); only the
