@@ -1,5 +1,6 @@
-"""What the image decoders share (png.py, jpeg.py): the output modes, the error's base, the packing of a batch of files and the decoder
-front end around a native handle.  A format's module states its C symbols, its status names and its own arguments, nothing else."""
+"""What the image codecs share (png.py, jpeg.py): the output modes, the error's base, the packing of a batch of files, the geometry and
+the checks of a frame to encode, and the decoder and encoder front ends around a native handle.  A format's module states its C symbols,
+its status names and its own arguments, nothing else."""
 import ctypes as C
 
 import numpy as np
@@ -161,3 +162,106 @@ class Decoder(HandleOwner):
             raise cls.Error(e.index, e.status, what=f'{paths[e.index]}: image') from None
         finally:
             dec.close()
+
+
+# ---- encoding ---------------------------------------------------------------------------------------------------------------------------
+def frame_geometry(frame, width=None, height=None):
+    """(width, height, channels) of a frame (H, W, C) or (H, W) -- or, with width and height given, of a flat (H * W, C) or (H * W,) one"""
+    if frame.dim() == 3 or (frame.dim() == 2 and width is None):
+        height, width = frame.shape[:2]
+        channels = 1 if frame.dim() == 2 else frame.shape[2]
+    else:
+        if width is None or height is None:
+            raise ValueError('a flat (H * W, C) frame needs width and height')
+        channels = frame.shape[-1] if frame.dim() == 2 else 1
+    return int(width), int(height), int(channels)
+
+
+torch = None      # the module, from the first check of a tensor on: the checks run in every encode, and encode_host needs numpy alone
+
+
+def _bind_torch():
+    global torch
+    import torch
+
+
+def check_frame(frame, device, width, height, channels):
+    """The frame an encoder of width x height x channels on `device` takes, contiguous: float32 or uint8, (H, W, C), (H * W, C) or, for
+    channels 1, (H, W).  Anything else is refused."""
+    if torch is None:
+        _bind_torch()
+    if not isinstance(frame, torch.Tensor) or frame.device != device:
+        raise ValueError(f'frame must be a tensor on {device}')
+    if frame.dtype is not torch.float32 and frame.dtype is not torch.uint8:
+        raise ValueError(f'frame must be float32 or uint8, got {frame.dtype}')
+    if frame.numel() != height * width * channels or (frame.dim() > 1 and channels > 1 and frame.shape[-1] != channels):
+        raise ValueError(f'frame {tuple(frame.shape)} is not ({height}, {width}, {channels}) or ({height * width}, {channels})')
+    return frame.contiguous()
+
+
+def check_out(out, device, bound):
+    if torch is None:
+        _bind_torch()
+    if out.dtype is not torch.uint8 or out.device != device or not out.is_contiguous() or out.numel() < bound:
+        raise ValueError(f'out must be a contiguous uint8 tensor of at least {bound} bytes on {device}')
+    return out
+
+
+def check_length(length, device):
+    if torch is None:
+        _bind_torch()
+    if length.dtype is not torch.int64 or length.device != device or length.numel() != 1:
+        raise ValueError(f'length must be an int64 tensor of one element on {device}')
+    return length
+
+
+def array_geometry(array, channels=None):
+    """(the array made contiguous, channels, height, width) of a numpy image (H, W, C) or (H, W), uint8 or float32: the front of the
+    formats' encode_host.  channels: the caller's, else 1 for (H, W) and C otherwise."""
+    array = np.ascontiguousarray(array)
+    if array.dtype not in (np.uint8, np.float32) or array.ndim not in (2, 3):
+        raise ValueError(f'array must be uint8 or float32 of shape (H, W, C) or (H, W), got {array.dtype} {array.shape}')
+    if channels is None:
+        channels = 1 if array.ndim == 2 else array.shape[-1]
+    return array, int(channels), int(array.shape[0]), int(array.shape[1])
+
+
+class Encoder(HandleOwner):
+    """Encodes (height, width, channels) frames on the device: channels 1 (grey), 3 (RGB) or 4 (RGBA).  A frame is a device tensor:
+    float32 (H, W, C) or (H * W, C) -- what model.render* returns -- or (H, W) for channels 1, turned into bytes by to8b as it is read;
+    or uint8 of the same shapes (pack_display's RGBA8 with channels=4).  A frame that is not contiguous (a [..., :3] slice of a wider
+    buffer) is copied into a contiguous one first.  The encoder owns its device workspace: one encode at a time per encoder.  A subclass
+    states CREATE, ENCODE, DESTROY and BOUND (C symbols; create_args follow channels in CREATE, bound_args in BOUND) and, where ENCODE has
+    arguments of its own between pixel_type and file_dev, an encode_device that takes them after `out` and hands them to _encode."""
+    CREATE = ENCODE = BOUND = None
+
+    def __init__(self, width, height, channels=3, device=None, create_args=(), bound_args=()):
+        import torch
+        self.width, self.height, self.channels = int(width), int(height), int(channels)
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self._h = C.c_void_p()
+        _lib.call(self.CREATE, self.width, self.height, self.channels, *create_args, C.byref(self._h), device=self.device)
+        n = C.c_int64()
+        _lib.call(self.BOUND, self.width, self.height, self.channels, *bound_args, C.byref(n))
+        self.bound = int(n.value)
+
+    def _encode(self, frame, out, length, options):
+        """encode_device with the format's own arguments of ENCODE as a tuple"""
+        device = self.device
+        frame = check_frame(frame, device, self.width, self.height, self.channels)          # binds torch
+        out = torch.empty(self.bound, dtype=torch.uint8, device=device) if out is None else check_out(out, device, self.bound)
+        length = torch.empty(1, dtype=torch.int64, device=device) if length is None else check_length(length, device)
+        _lib.call(self.ENCODE, self._h, frame, _lib.HR_PNG_U8 if frame.dtype is torch.uint8 else _lib.HR_PNG_F32_TO8B, *options, out, out.numel(),
+                  length, _lib.stream(device), device=device)
+        return out, length
+
+    def encode_device(self, frame, out=None, length=None):
+        """Enqueues the encode on torch's current stream and returns (uint8 buffer of `bound` bytes, int64 length tensor of one element):
+        the file is buffer[:length], and no byte past it is written.  No allocation when `out` and `length` are given, no
+        synchronisation: capturable in a graph, with `frame` a contiguous buffer that is refilled between replays."""
+        return self._encode(frame, out, length, ())
+
+    def encode(self, frame, *options, **named):
+        """The file's bytes: one device-to-host copy of the length, one of that many bytes.  options: what follows `out` in encode_device."""
+        out, length = self.encode_device(frame, None, *options, **named)
+        return out[:int(length.item())].cpu().numpy().tobytes()

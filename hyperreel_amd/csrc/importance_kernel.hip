@@ -14,6 +14,7 @@
 #include "hr_camera.h"
 #include "hr_importance.h"
 #include "hr_kernels.h"
+#include "hr_scan.h"
 
 namespace {
 
@@ -23,21 +24,6 @@ constexpr int ITEMS = HR_IMP_TILE / THREADS;      // rounds of a workgroup over 
 __device__ __forceinline__ uint32_t pixel_key(const HrImportanceArgs& a, uint32_t p)
 {
     return hr_importance_key(a.cur + (size_t)p * 3, a.prev + (size_t)p * 3);
-}
-
-// inclusive sum over the workgroup's 256 threads (Hillis-Steele in LDS); s[255] holds the total on return
-__device__ __forceinline__ uint32_t block_scan_inclusive(uint32_t v, uint32_t* s)
-{
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-    for (int off = 1; off < THREADS; off <<= 1) {
-        const uint32_t add = t >= off ? s[t - off] : 0u;
-        __syncthreads();
-        s[t] += add;
-        __syncthreads();
-    }
-    return s[t];
 }
 
 // digit pass PASS (0: bits 31..24): histogram of the digit over the keys whose higher digits equal the prefix found so far
@@ -66,7 +52,7 @@ __global__ __launch_bounds__(THREADS) void importance_narrow_kernel(uint32_t* __
     const uint32_t c = ws[HR_IMP_WS_HIST + pass * 256 + threadIdx.x];
     const uint32_t rank = pass ? ws[HR_IMP_WS_RANK] : rank0;
     const uint32_t prefix = pass ? ws[HR_IMP_WS_PREFIX] : 0u;
-    const uint32_t incl = block_scan_inclusive(c, s);
+    const uint32_t incl = hr_block_scan_inclusive<THREADS>(c, s);
     if (incl - c <= rank && rank < incl) {               // exactly one thread: the counts sum to more than the rank
         ws[HR_IMP_WS_RANK] = rank - (incl - c);
         ws[HR_IMP_WS_PREFIX] = (prefix << 8) | threadIdx.x;
@@ -123,7 +109,7 @@ __global__ __launch_bounds__(THREADS) void importance_scan_kernel(uint32_t* __re
     for (uint32_t base = 0; base < n_counts; base += THREADS) {
         const uint32_t i = base + threadIdx.x;
         const uint32_t c = i < n_counts ? counts[i] : 0u;
-        const uint32_t incl = block_scan_inclusive(c, s);
+        const uint32_t incl = hr_block_scan_inclusive<THREADS>(c, s);
         if (i < n_counts) counts[i] = carry + incl - c;
         carry += s[THREADS - 1];
         __syncthreads();

@@ -16,6 +16,7 @@
 //                               an FF, the marker after an interval's last byte
 // Integer arithmetic and integer atomic OR only: the file is the same on every run.  Every word that is read has been written by the same call.
 #include "hr_jpeg_encode.h"
+#include "hr_scan.h"
 
 namespace {
 
@@ -24,22 +25,6 @@ constexpr int SCAN_THREADS = 1024;                  // kernels 3, 7
 constexpr int ROW = 9;                              // ints between two rows of a block in LDS: columns read without bank conflicts
 
 static_assert(HR_JPEG_ENC_CHUNK == 4 * THREADS, "a lane of the stuffing passes owns one word of its chunk");
-
-// inclusive sum over the workgroup's N threads (Hillis-Steele in LDS); s[N - 1] holds the total on return
-template <int N>
-__device__ __forceinline__ uint32_t block_scan_inclusive(uint32_t v, uint32_t* s)
-{
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-    for (int off = 1; off < N; off <<= 1) {
-        const uint32_t add = t >= off ? s[t - off] : 0u;
-        __syncthreads();
-        s[t] += add;
-        __syncthreads();
-    }
-    return s[t];
-}
 
 __device__ __forceinline__ const hr_jpeg_enc_tables* tables_of(const HrJpegEncArgs& a) { return (const hr_jpeg_enc_tables*)(a.workspace + a.plan.off_tables); }
 __device__ __forceinline__ int16_t* coef_of(const HrJpegEncArgs& a) { return (int16_t*)(a.workspace + a.plan.off_coef); }
@@ -112,7 +97,7 @@ __global__ __launch_bounds__(THREADS) void jpeg_enc_count_kernel(const HrJpegEnc
         hr_jpeg_enc_block_code(codes + 16 * ti, codes + 32 + 256 * ti, coef + (int64_t)b * 64, hr_jpeg_enc_dc_diff(p, coef, b, k), k.dummy != 0,
                                [&](uint32_t, int len, int, bool) { bits += (uint32_t)len; });
     }
-    const uint32_t incl = block_scan_inclusive<THREADS>(bits, sc);
+    const uint32_t incl = hr_block_scan_inclusive<THREADS>(bits, sc);
     if (b < p.n_blocks) words_at(a, p.off_local)[b] = incl - bits;
     if (t == THREADS - 1) words_at(a, p.off_wg)[blockIdx.x] = incl;
 }
@@ -128,7 +113,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void jpeg_enc_scan_kernel(const HrJpe
     for (int32_t base = 0; base < p.n_wg; base += SCAN_THREADS) {
         const int32_t i = base + t;
         const uint32_t v = i < p.n_wg ? wg[i] : 0u;
-        const uint32_t incl = block_scan_inclusive<SCAN_THREADS>(v, sc);
+        const uint32_t incl = hr_block_scan_inclusive<SCAN_THREADS>(v, sc);
         if (i < p.n_wg) wg[i] = carry + incl - v;
         carry += sc[SCAN_THREADS - 1];
         __syncthreads();
@@ -150,7 +135,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void jpeg_enc_scan_kernel(const HrJpe
             bytes = (s1 - s0 + 7u) >> 3;
             ibit[i] = s0;
         }
-        const uint32_t incl = block_scan_inclusive<SCAN_THREADS>(bytes, sc);
+        const uint32_t incl = hr_block_scan_inclusive<SCAN_THREADS>(bytes, sc);
         if (i < p.n_int) ibyte[i] = carry + incl - bytes;
         carry += sc[SCAN_THREADS - 1];
         __syncthreads();
@@ -210,7 +195,7 @@ __global__ __launch_bounds__(THREADS) void jpeg_enc_ffcount_kernel(const HrJpegE
     const int64_t first = ((int64_t)blockIdx.x * THREADS + threadIdx.x) * 4;
     if ((int64_t)blockIdx.x * HR_JPEG_ENC_CHUNK >= (int64_t)raw_bytes) return;      // (the whole workgroup)
     const uint32_t v = first < (int64_t)raw_bytes ? words_at(a, p.off_raw)[first >> 2] : 0u;
-    const uint32_t incl = block_scan_inclusive<THREADS>(ff_in_word(v, first, raw_bytes), sc);
+    const uint32_t incl = hr_block_scan_inclusive<THREADS>(ff_in_word(v, first, raw_bytes), sc);
     if (threadIdx.x == THREADS - 1) words_at(a, p.off_ff)[blockIdx.x] = incl;
 }
 
@@ -226,7 +211,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void jpeg_enc_ffscan_kernel(const HrJ
     for (int64_t base = 0; base < chunks; base += SCAN_THREADS) {
         const int64_t i = base + t;
         const uint32_t v = i < chunks ? ff[i] : 0u;
-        const uint32_t incl = block_scan_inclusive<SCAN_THREADS>(v, sc);
+        const uint32_t incl = hr_block_scan_inclusive<SCAN_THREADS>(v, sc);
         if (i < chunks) ff[i] = carry + incl - v;
         carry += sc[SCAN_THREADS - 1];
         __syncthreads();
@@ -250,7 +235,7 @@ __global__ __launch_bounds__(THREADS) void jpeg_enc_scatter_kernel(const HrJpegE
     if ((int64_t)blockIdx.x * HR_JPEG_ENC_CHUNK >= (int64_t)raw_bytes) return;      // (the whole workgroup)
     const uint32_t v = first < (int64_t)raw_bytes ? words_at(a, p.off_raw)[first >> 2] : 0u;
     const uint32_t mine = ff_in_word(v, first, raw_bytes);
-    uint32_t ff = words_at(a, p.off_ff)[blockIdx.x] + block_scan_inclusive<THREADS>(mine, sc) - mine;
+    uint32_t ff = words_at(a, p.off_ff)[blockIdx.x] + hr_block_scan_inclusive<THREADS>(mine, sc) - mine;
     if (first >= (int64_t)raw_bytes) return;
     // the restart interval of the lane's first byte: the last one that starts at or before it
     const uint32_t* ibyte = words_at(a, p.off_int_byte);

@@ -14,6 +14,7 @@
 // Integer arithmetic and integer LDS atomics only: the file is the same on every run.  No global atomics, no memset: every word of the
 // workspace that is read has been written by the same call.
 #include "hr_png.h"
+#include "hr_scan.h"
 
 namespace {
 
@@ -22,28 +23,6 @@ constexpr int SCAN_THREADS = 256;
 constexpr int WAVES = THREADS / 64;
 constexpr uint32_t OUT_BYTES = HR_PNG_STRIP_BYTES + 1024;      // the chunk window in LDS: a whole ordinary strip's chunk data
 constexpr uint32_t WIDE_SLICE = 8;                            // tokens per thread and window of a strip wider than the budget (21 bits at most each)
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// inclusive sum over the workgroup's N threads (Hillis-Steele in LDS); s[N - 1] holds the total on return
-template <int N>
-__device__ __forceinline__ uint32_t block_scan_inclusive(uint32_t v, uint32_t* s)
-{
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-    for (int off = 1; off < N; off <<= 1) {
-        const uint32_t add = t >= off ? s[t - off] : 0u;
-        __syncthreads();
-        s[t] += add;
-        __syncthreads();
-    }
-    return s[t];
-}
 
 __device__ __forceinline__ uint32_t* strip_meta(const HrPngArgs& a, int s)
 {
@@ -72,7 +51,7 @@ __global__ __launch_bounds__(THREADS) void png_filter_kernel(const HrPngArgs a)
             uint32_t sums[5] = {0, 0, 0, 0, 0};
             for (int32_t x = lane; x < row_len; x += 64) hr_png_filter_costs(a.pixels, a.pixel_type, y, x, row_len, pl.channels, sums);
             HR_UNROLL
-            for (int k = 0; k < 5; ++k) sums[k] = wave_sum(sums[k]);
+            for (int k = 0; k < 5; ++k) sums[k] = hr_wave_sum(sums[k]);
             f = hr_png_choose_filter(sums);
         }
         uint8_t* o = filt + (size_t)r * pl.row_bytes;
@@ -169,7 +148,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void png_scan_kernel(const HrPngArgs 
         uint32_t* m = strip_meta(a, i < n_strips ? i : 0);
         const uint32_t c = i < n_strips ? 12u + m[HR_PNG_M_DATA_LEN] : 0u;
         if (t < 2) ad[t] = 0;
-        const uint32_t incl = block_scan_inclusive<SCAN_THREADS>(c, sc);
+        const uint32_t incl = hr_block_scan_inclusive<SCAN_THREADS>(c, sc);
         if (i < n_strips) {
             m[HR_PNG_M_OFFSET] = carry + incl - c;
             atomicAdd(&ad[0], m[HR_PNG_M_ADLER_A]);
@@ -272,7 +251,7 @@ __global__ __launch_bounds__(THREADS) void png_pack_kernel(const HrPngArgs a)
                 hr_png_token_bits(codes, tok[i], &value, &count);
                 bits += count;
             }
-            const uint32_t incl = block_scan_inclusive<THREADS>(bits, sc);
+            const uint32_t incl = hr_block_scan_inclusive<THREADS>(bits, sc);
             uint32_t at = bit - flushed * 8u + (incl - bits);
             for (uint32_t i = beg; i < end; ++i) {
                 uint32_t value, count;

@@ -148,70 +148,22 @@ def bound(width, height, channels=3, subsampling='4:2:0', restart_rows=0):
     return int(n.value)
 
 
-class JpegEncoder(_codec.HandleOwner):
+class JpegEncoder(_codec.Encoder):
     """Encodes (height, width, channels) frames on the device as baseline JPEG files: channels 1 (grey, subsampling '4:4:4'), 3 (RGB) or 4
     (RGBA, the alpha byte ignored).  quality 1..100 and subsampling '4:4:4' | '4:2:2' | '4:2:0' as PIL's save; restart_rows > 0 puts a
-    restart marker after every so many MCU rows.  A frame is a device tensor as PngEncoder's: float32 (H, W, C), (H * W, C) or (H, W),
-    turned into bytes by to8b as it is read, or uint8 of the same shapes; one that is not contiguous is copied first.  The encoder owns
-    its device workspace: one encode at a time per encoder."""
-    DESTROY = 'hr_jpeg_encoder_destroy'
+    restart marker after every so many MCU rows.  _codec.Encoder says what a frame is."""
+    CREATE, ENCODE, DESTROY, BOUND = 'hr_jpeg_encoder_create', 'hr_jpeg_encode', 'hr_jpeg_encoder_destroy', 'hr_jpeg_bound'
 
     def __init__(self, width, height, channels=3, quality=90, subsampling='4:2:0', restart_rows=0, device=None):
-        import torch
-        self.width, self.height, self.channels = int(width), int(height), int(channels)
         self.quality, self.restart_rows = int(quality), int(restart_rows)
         self.subsampling = _subsampling(subsampling)
-        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        self._h = C.c_void_p()
-        _lib.call('hr_jpeg_encoder_create', self.width, self.height, self.channels, self.quality, self.subsampling, self.restart_rows, C.byref(self._h),
-                  device=self.device)
-        self.bound = bound(self.width, self.height, self.channels, self.subsampling, self.restart_rows)
-
-    def _frame(self, frame):
-        import torch
-        if not isinstance(frame, torch.Tensor) or frame.device != self.device:
-            raise ValueError(f'frame must be a tensor on {self.device}')
-        if frame.dtype not in (torch.float32, torch.uint8):
-            raise ValueError(f'frame must be float32 or uint8, got {frame.dtype}')
-        if frame.numel() != self.height * self.width * self.channels or (frame.dim() > 1 and self.channels > 1 and frame.shape[-1] != self.channels):
-            raise ValueError(f'frame {tuple(frame.shape)} is not ({self.height}, {self.width}, {self.channels}) or ({self.height * self.width}, {self.channels})')
-        return frame.contiguous()
-
-    def encode_device(self, frame, out=None, length=None):
-        """Enqueues the encode on torch's current stream and returns (uint8 buffer of `bound` bytes, int64 length tensor of one element):
-        the file is buffer[:length], and no byte past it is written.  No allocation when `out` and `length` are given, no
-        synchronisation: capturable in a graph, with `frame` a contiguous buffer that is refilled between replays."""
-        import torch
-        frame = self._frame(frame)
-        if out is None:
-            out = torch.empty(self.bound, dtype=torch.uint8, device=self.device)
-        elif out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous() or out.numel() < self.bound:
-            raise ValueError(f'out must be a contiguous uint8 tensor of at least {self.bound} bytes on {self.device}')
-        if length is None:
-            length = torch.empty(1, dtype=torch.int64, device=self.device)
-        elif length.dtype != torch.int64 or length.device != self.device or length.numel() != 1:
-            raise ValueError(f'length must be an int64 tensor of one element on {self.device}')
-        _lib.call('hr_jpeg_encode', self._h, frame, _lib.HR_PNG_U8 if frame.dtype == torch.uint8 else _lib.HR_PNG_F32_TO8B, out, out.numel(), length,
-                  _lib.stream(self.device), device=self.device)
-        return out, length
-
-    def encode(self, frame):
-        """The file's bytes: one device-to-host copy of the length, one of that many bytes"""
-        out, length = self.encode_device(frame)
-        n = int(length.item())
-        return out[:n].cpu().numpy().tobytes()
+        super().__init__(width, height, channels, device, (self.quality, self.subsampling, self.restart_rows), (self.subsampling, self.restart_rows))
 
 
 def save_jpeg(path, frame, width=None, height=None, **options):
     """Writes a device frame (H, W, C) or (H, W) -- or (H * W, C) with width and height given -- as a JPEG file; options: JpegEncoder's
     quality, subsampling, restart_rows.  A grey frame is written 4:4:4 unless a subsampling is asked for."""
-    if frame.dim() == 3 or (frame.dim() == 2 and width is None):
-        height, width = frame.shape[:2]
-        channels = 1 if frame.dim() == 2 else frame.shape[2]
-    else:
-        if width is None or height is None:
-            raise ValueError('a flat (H * W, C) frame needs width and height')
-        channels = frame.shape[-1] if frame.dim() == 2 else 1
+    width, height, channels = _codec.frame_geometry(frame, width, height)
     if channels == 1:
         options.setdefault('subsampling', '4:4:4')
     enc = JpegEncoder(width, height, channels, device=frame.device, **options)
@@ -229,12 +181,8 @@ def encode_host(array, channels=None, quality=90, subsampling='4:2:0', restart_r
     from: byte for byte what the device writes.  Needs no GPU.  A grey array takes subsampling '4:4:4' only, as the device does.
     with_stats: (bytes, {'stuffed', 'zrl', 'max_dc_cat', 'max_ac_cat'}) of the scan."""
     host = host_lib()
-    array = np.ascontiguousarray(array)
-    if array.dtype not in (np.uint8, np.float32) or array.ndim not in (2, 3):
-        raise ValueError(f'array must be uint8 or float32 of shape (H, W, C) or (H, W), got {array.dtype} {array.shape}')
-    channels = int(channels) if channels is not None else (1 if array.ndim == 2 else int(array.shape[-1]))
+    array, channels, h, w = _codec.array_geometry(array, channels)
     sub = _subsampling(subsampling)
-    h, w = array.shape[:2]
     cap = host.hr_jpeg_host_bound(w, h, channels, sub, int(restart_rows)) if array.size == h * w * channels and 1 <= int(quality) <= 100 else -1
     if cap < 0:
         raise ValueError(f'array {array.shape}, quality {quality}, subsampling {subsampling}, restart_rows {restart_rows}: not an image and options '

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import encoder_front_common as F
 import jpeg_encode_common as E
 from hyperreel_amd import jpeg
 from hyperreel_amd import lib as _lib
@@ -87,48 +88,15 @@ def test_two_encoders_on_two_streams():
     options = [{'quality': 90, 'subsampling': '4:2:0', 'restart_rows': 0}, {'quality': 50, 'subsampling': '4:4:4', 'restart_rows': 1}]
     expect = [jpeg.encode_host(a, **o) for a, o in zip(arrays, options)]
     frames = [torch.from_numpy(a).cuda() for a in arrays]
-    encs = [jpeg.JpegEncoder(w, h, 3, **o) for o in options]
-    assert encs[0].encode(frames[0]) == expect[0] and encs[0].encode(frames[0]) == expect[0]
-    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
-    torch.cuda.synchronize()
-    outs = []
-    for _ in range(3):
-        for e, f, s in zip(encs, frames, streams):
-            with torch.cuda.stream(s):
-                outs.append(e.encode_device(f))
-    torch.cuda.synchronize()
-    for i, (buf, length) in enumerate(outs):
-        assert buf[:int(length.item())].cpu().numpy().tobytes() == expect[i % 2]
-    for e in encs:
-        e.close()
+    F.two_encoders_on_two_streams([jpeg.JpegEncoder(w, h, 3, **o) for o in options], frames, expect)
 
 
 def test_graph_capture_replays_over_a_changing_frame():
     """one captured encode_device, three replays with the frame refilled between them: the eager bytes each time"""
     t = E.tool()
     w, h, c = 96, 80, 3
-    enc = jpeg.JpegEncoder(w, h, c, quality=90, subsampling='4:2:0', restart_rows=2)
-    frame = torch.zeros((h, w, c), dtype=torch.float32, device='cuda')
-    out = torch.empty(enc.bound, dtype=torch.uint8, device='cuda')
-    length = torch.zeros(1, dtype=torch.int64, device='cuda')
     inputs = [torch.from_numpy(t.as_float(t.content(k, w, h, c, 4), 5)).cuda() for k in ('noise', 'flat', 'binary')]
-    eager = [enc.encode(x) for x in inputs]
-    assert len(set(eager)) == 3
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        enc.encode_device(frame, out=out, length=length)          # warm-up outside the capture
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        enc.encode_device(frame, out=out, length=length)
-    for x, expect in zip(inputs, eager):
-        frame.copy_(x)
-        g.replay()
-        torch.cuda.synchronize()
-        assert out[:int(length.item())].cpu().numpy().tobytes() == expect
-    enc.close()
+    F.graph_capture_replays_over_a_changing_frame(jpeg.JpegEncoder(w, h, c, quality=90, subsampling='4:2:0', restart_rows=2), inputs)
 
 
 def test_device_decoder_reads_the_devices_file_as_pil_does():
@@ -161,10 +129,7 @@ def test_flat_frame_sliced_frame_grey_map_and_save_jpeg(tmp_path):
     n = jpeg.save_jpeg(path, torch.from_numpy(grey).cuda(), quality=75)
     data = open(path, 'rb').read()
     assert n == len(data) and data == jpeg.encode_host(grey, quality=75, subsampling='4:4:4')
-    with pytest.raises(ValueError):
-        enc.encode(torch.zeros((h, w, 4), device='cuda'))
-    with pytest.raises(ValueError):
-        enc.encode(torch.zeros((h, w, 3), dtype=torch.float64, device='cuda'))
+    F.front_end_refusals(enc)
     enc.close()
 
 

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import encoder_front_common as F
 import png_common as P
 from hyperreel_amd import lib as _lib
 from hyperreel_amd import png
@@ -62,46 +63,13 @@ def test_same_frame_twice_and_two_encoders_on_two_streams():
     c, (w, h) = 3, P.shapes(3)[8]
     frames = [torch.from_numpy(P.as_float(P.image(k, w, h, c))).cuda() for k in ('disc', 'ramp')]
     expect = [P.encode_host(P.as_float(P.image(k, w, h, c)), c) for k in ('disc', 'ramp')]
-    encs = [png.PngEncoder(w, h, c), png.PngEncoder(w, h, c)]
-    assert encs[0].encode(frames[0]) == expect[0] and encs[0].encode(frames[0]) == expect[0]
-    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
-    torch.cuda.synchronize()
-    outs = []
-    for _ in range(3):
-        for e, f, s in zip(encs, frames, streams):
-            with torch.cuda.stream(s):
-                outs.append(e.encode_device(f))
-    torch.cuda.synchronize()
-    for i, (buf, length) in enumerate(outs):
-        assert buf[:int(length.item())].cpu().numpy().tobytes() == expect[i % 2]
-    for e in encs:
-        e.close()
+    F.two_encoders_on_two_streams([png.PngEncoder(w, h, c), png.PngEncoder(w, h, c)], frames, expect)
 
 
 def test_graph_capture_replays_over_a_changing_frame():
     c, (w, h) = 3, P.shapes(3)[7]
-    enc = png.PngEncoder(w, h, c)
-    frame = torch.zeros((h, w, c), dtype=torch.float32, device='cuda')
-    out = torch.empty(enc.bound, dtype=torch.uint8, device='cuda')
-    length = torch.zeros(1, dtype=torch.int64, device='cuda')
-    contents = ['disc', 'white', 'noise']
-    inputs = [torch.from_numpy(P.as_float(P.image(k, w, h, c))).cuda() for k in contents]
-    eager = [enc.encode(x) for x in inputs]
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        enc.encode_device(frame, out=out, length=length)          # warm-up outside the capture
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        enc.encode_device(frame, out=out, length=length)
-    for x, expect in zip(inputs, eager):
-        frame.copy_(x)
-        g.replay()
-        torch.cuda.synchronize()
-        assert out[:int(length.item())].cpu().numpy().tobytes() == expect
-    enc.close()
+    inputs = [torch.from_numpy(P.as_float(P.image(k, w, h, c))).cuda() for k in ('disc', 'white', 'noise')]
+    F.graph_capture_replays_over_a_changing_frame(png.PngEncoder(w, h, c), inputs)
 
 
 def test_sliced_float_frame():
@@ -159,10 +127,7 @@ def test_refusals_leave_the_output_untouched():
     torch.cuda.synchronize()
     assert out[:int(length.item())].cpu().numpy().tobytes() == P.encode_host(np.zeros((h, w, c), np.uint8), c)
     L.hr_png_encoder_destroy(handle)
-    with pytest.raises(ValueError):
-        _encoder(61, 47, 3).encode(torch.zeros((47, 61, 4), device='cuda'))
-    with pytest.raises(ValueError):
-        _encoder(61, 47, 3).encode(torch.zeros((47, 61, 3), dtype=torch.float64, device='cuda'))
+    F.front_end_refusals(_encoder(61, 47, 3))
 
 
 def test_render_then_save_png(tmp_path):
