@@ -14,8 +14,8 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_DIR = os.path.join(HERE, '_build')
 LIB_PATH = os.path.join(LIB_DIR, 'libhyperreel_hip.so')
 SOURCES = ['api.hip', 'api_model.hip', 'api_mlp.hip', 'api_render.hip', 'api_train.hip', 'api_metrics.hip', 'api_rays.hip', 'api_resize.hip', 'api_loss.hip', 'api_reg.hip', 'api_image_encode.hip', 'api_image_decode.hip', 'api_lpips.hip', 'mlp_kernel.hip', 'mlp_bf16x3_kernel.hip', 'mlp_f16x3_kernel.hip', 'mlp_f16x2_kernel.hip', 'mlp_f16f8_kernel.hip', 'fused_bf16x3_kernel.hip', 'fused_f16x3_kernel.hip', 'fused_f16x2_kernel.hip', 'fused_f16f8_kernel.hip',
-           'sample_kernel.hip', 'sample_maps_kernel.hip', 'sample_shade_kernel.hip', 'shade_kernel.hip', 'range_kernel.hip', 'band_kernel.hip', 'pack_kernels.hip', 'train_kernel.hip', 'train_det_kernel.hip', 'train_gemm_kernel.hip', 'metrics_kernel.hip', 'rays_kernel.hip', 'importance_kernel.hip', 'resize_kernel.hip', 'loss_kernel.hip', 'reg_kernel.hip', 'png_kernel.hip', 'png_decode_kernel.hip', 'jpeg_decode_kernel.hip', 'jpeg_encode_kernel.hip', 'lpips_kernel.hip']
-HEADERS = ['hr_model.h', 'hr_kernels.h', 'hr_math.h', 'hr_grid.h', 'hr_plan.h', 'hr_train.h', 'hr_mask.h', 'hr_metrics.h', 'hr_camera.h', 'hr_lightfield.h', 'hr_loss.h', 'hr_sample_rng.h', 'hr_importance.h', 'hr_resize.h', 'hr_mlp_pack.h', 'hr_shade.h', 'hr_png.h', 'hr_png_decode.h', 'hr_jpeg_decode.h', 'hr_jpeg_encode.h', 'hr_scan.h', 'hr_lpips.h', 'mlp_split_impl.inc', 'mlp_split_core.inc', 'sample_core.inc', 'sample_kernel.inc', 'sample_kernel_body.inc', 'fused_impl.inc', 'train_kernel.hip', os.path.join('..', '..', 'include', 'hyperreel_hip.h')]
+           'sample_kernel.hip', 'sample_maps_kernel.hip', 'sample_shade_kernel.hip', 'sample_time_kernel.hip', 'sample_time_density_kernel.hip', 'shade_kernel.hip', 'range_kernel.hip', 'band_kernel.hip', 'pack_kernels.hip', 'train_kernel.hip', 'train_det_kernel.hip', 'train_time_kernel.hip', 'train_time_det_kernel.hip', 'train_gemm_kernel.hip', 'metrics_kernel.hip', 'rays_kernel.hip', 'importance_kernel.hip', 'resize_kernel.hip', 'loss_kernel.hip', 'reg_kernel.hip', 'png_kernel.hip', 'png_decode_kernel.hip', 'jpeg_decode_kernel.hip', 'jpeg_encode_kernel.hip', 'lpips_kernel.hip']
+HEADERS = ['hr_model.h', 'hr_kernels.h', 'hr_math.h', 'hr_grid.h', 'hr_plan.h', 'hr_train.h', 'hr_mask.h', 'hr_metrics.h', 'hr_camera.h', 'hr_lightfield.h', 'hr_loss.h', 'hr_sample_rng.h', 'hr_importance.h', 'hr_resize.h', 'hr_mlp_pack.h', 'hr_shade.h', 'hr_time_decode.h', 'hr_png.h', 'hr_png_decode.h', 'hr_jpeg_decode.h', 'hr_jpeg_encode.h', 'hr_scan.h', 'hr_lpips.h', 'mlp_split_impl.inc', 'mlp_split_core.inc', 'sample_core.inc', 'sample_kernel.inc', 'sample_kernel_body.inc', 'sample_time_kernel.inc', 'fused_impl.inc', 'train_kernel.hip', os.path.join('..', '..', 'include', 'hyperreel_hip.h')]
 
 # -ffp-contract=off: the per-sample arithmetic follows the reference operation by
 # operation (the reference never fuses a multiply with an add across torch ops); the

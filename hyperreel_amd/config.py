@@ -253,15 +253,30 @@ DATASET_SCALARS = {
 }
 
 
-def model_config(name, z_channels=None):
+def model_config(name, z_channels=None, shading=None, density_mode=None, frames_per_keyframe=None):
     """Built-in `experiment.model` group (same keys/values as the shipped YAML).
 
     z_channels overrides `z_channels` of both ray_prediction_0 and
-    ray_intersect_0 (BASELINE config 1 uses 16)."""
+    ray_intersect_0 (BASELINE config 1 uses 16).
+    shading / density_mode / frames_per_keyframe: the toggles the shipped video YAMLs leave commented next to the live line
+    (`shadingMode: RGBtLinear | RGBtFourier | RGBIdentity`, `densityMode: DensityLinear | DensityFourier`); data_dim_color follows
+    the mode as the reference sets it (3 nb for the RGBt modes, tensorf_dynamic.py:62-65; 3 for RGBIdentity)."""
     cfg = to_cfg(_BUILDERS[name]())
     if z_channels is not None:
         cfg.embedding.embeddings.ray_prediction_0.z_channels = int(z_channels)
         cfg.embedding.embeddings.ray_intersect_0.z_channels = int(z_channels)
+    net = cfg.color.net
+    if frames_per_keyframe is not None:
+        net.frames_per_keyframe = int(frames_per_keyframe)
+    if density_mode is not None:
+        net.densityMode = density_mode
+    if shading is not None:
+        net.shadingMode = shading
+        if shading in ('RGBtLinear', 'RGBtFourier'):
+            from .plan import frames_per_keyframe as _fpk, time_basis_size
+            net.data_dim_color = 3 * time_basis_size(shading, _fpk(net, dataset_scalars(name)))
+        else:
+            net.data_dim_color = 3 if shading in ('RGB', 'RGBIdentity') else 27
     return cfg
 
 

@@ -79,6 +79,7 @@ int hr_dense_alpha(hr_model* m, const int32_t n[3], float length, int32_t num_fr
     if (m->is_coarse) return fail(HR_E_INVALID, "the coarse level of a cascade has no grids");
     if (!m->finalized) return fail(HR_E_STATE, "hr_model_finalize has not been called (or tensors changed since)");
     if (m->cfg.grid_dtype != HR_GRID_FP32) return fail(HR_E_INVALID, "hr_dense_alpha reads float32 grids");
+    if (hr_model_time_density(m)) return fail(HR_E_INVALID, "hr_dense_alpha: densityMode DensityLinear / DensityFourier is inference only (the mask update does not evaluate the density row)");
     if (n[0] < 1 || n[1] < 1 || n[2] < 1) return fail(HR_E_INVALID, "bad lattice size");
     if (m->cfg.video && num_frames < 1) return fail(HR_E_INVALID, "keyframe nets need num_frames");
     if (prev_volume_dev && (!prev_n || !prev_aabb || prev_n[0] < 1 || prev_n[1] < 1 || prev_n[2] < 1))

@@ -150,11 +150,12 @@ int build_mlp_state(hr_model* m, const float* rays_dev, int64_t n, hipStream_t s
     s.band = cur.band;
     s.vinfo.fallback = cur.vinfo.fallback;       // (calibrate_band keeps the reason while the fast path stays off)
     const bool level = m->coarse || m->is_coarse, supported = hr_mlp_range_supported(c);
-    HrMlpChoice ch = hr_mlp_choice(c, level, supported, s.act_max);
+    const bool time_density = hr_model_time_density(m);
+    HrMlpChoice ch = hr_mlp_choice(c, level, supported, s.act_max, time_density);
     if (ch.status == HR_OK && ch.needs_calibration) {
         const int rc = measure_range(m, rays_dev, n, st, s);
         if (rc != HR_OK) return rc;
-        ch = hr_mlp_choice(c, level, supported, s.act_max);
+        ch = hr_mlp_choice(c, level, supported, s.act_max, time_density);
     }
     if (ch.status == HR_E_RANGE) {
         const int want = c.mlp_precision;

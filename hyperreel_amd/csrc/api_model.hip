@@ -82,7 +82,16 @@ int validate(const hr_config& c, bool coarse = false)
     }
     for (int i = 0; i < 3; ++i)
         if (c.grid[i] < 2) return fail(HR_E_INVALID, "grid size must be >= 2 on every axis");
-    if (c.shading == HR_SHADING_RGB ? c.app_dim != 3 : c.app_dim != 27) return fail(HR_E_INVALID, "app_dim must be 3 (RGB) or 27 (SH)");
+    if (c.shading < HR_SHADING_RGB || c.shading > HR_SHADING_RGB_IDENTITY) return fail(HR_E_INVALID, "unknown shading %d", c.shading);
+    if (hr_shading_is_time(c.shading)) {              // (the descriptor checks app_dim against 3 nb: hr_model_set_time_decode)
+        if (!c.video) return fail(HR_E_INVALID, "shading RGBtLinear / RGBtFourier needs the keyframe net (a static net has no time basis)");
+        if (c.app_dim < 6 || c.app_dim > 3 * HR_TIME_MAX_NB || c.app_dim % 3) return fail(HR_E_INVALID, "app_dim %d is not 3 nb of a time basis (frames_per_keyframe 1..%d)", c.app_dim, HR_TIME_MAX_FPK);
+        if (c.casc_in_z > 0 || coarse) return fail(HR_E_INVALID, "shading RGBtLinear / RGBtFourier does not support point_prediction cascades");
+    } else if (c.shading == HR_SHADING_RGB_IDENTITY) {
+        if (c.video) return fail(HR_E_INVALID, "shading RGBIdentity on the keyframe net: the reference cannot build it");
+        if (c.app_dim != 3) return fail(HR_E_INVALID, "app_dim must be 3 (RGBIdentity)");
+        if (c.casc_in_z > 0 || coarse) return fail(HR_E_INVALID, "shading RGBIdentity does not support point_prediction cascades");
+    } else if (c.shading == HR_SHADING_RGB ? c.app_dim != 3 : c.app_dim != 27) return fail(HR_E_INVALID, "app_dim must be 3 (RGB) or 27 (SH)");
     if (hr_shading_is_mlp(c.shading) && !coarse) {     // the colour network's kernels
         if (c.casc_in_z > 0) return fail(HR_E_INVALID, "MLP shading modes do not support point_prediction cascades");
         if (c.z_channels > HR_SHADE_MAX_Z) return fail(HR_E_INVALID, "MLP shading modes support at most %d samples per ray (got %d)", HR_SHADE_MAX_Z, c.z_channels);
@@ -195,6 +204,69 @@ int hr_model_create_cascade(const hr_config* coarse, const hr_config* fine, hr_m
     return HR_OK;
 }
 
+static const char* const DENSITY_BASIS = "basis_mat_density.weight";
+
+int hr_model_set_time_decode(hr_model* m, const hr_time_decode* d)
+{
+    if (!m || !d) return fail(HR_E_INVALID, "null argument");
+    const hr_config& c = m->cfg;
+    if (m->is_coarse || m->coarse || !c.video) return fail(HR_E_INVALID, "hr_model_set_time_decode: the model is not a keyframe net (RGBt* / Density* modes on the static net)");
+    if (d->density_mode < HR_DENSITY_PLAIN || d->density_mode > HR_DENSITY_FOURIER) return fail(HR_E_INVALID, "unknown density_mode %d", d->density_mode);
+    if (!hr_shading_is_time(c.shading) && d->density_mode == HR_DENSITY_PLAIN)
+        return fail(HR_E_INVALID, "hr_model_set_time_decode: the model has neither an RGBt* shading nor a Density* mode");
+    if (hr_shading_is_mlp(c.shading) && d->density_mode != HR_DENSITY_PLAIN)
+        return fail(HR_E_INVALID, "a Density* mode together with an MLP shading mode (MLP_Fea / MLP)");
+    if (d->frames_per_keyframe < 1 || d->frames_per_keyframe > HR_TIME_MAX_FPK)
+        return fail(HR_E_INVALID, "frames_per_keyframe must be in [1,%d] (got %d)", HR_TIME_MAX_FPK, d->frames_per_keyframe);
+    if (d->num_frames < 1) return fail(HR_E_INVALID, "num_frames must be positive (got %d)", d->num_frames);
+    if (hr_shading_is_time(c.shading) && c.app_dim != hr_time_app_dim(c.shading, d->frames_per_keyframe))
+        return fail(HR_E_INVALID, "data_dim_color %d contradicts 3 nb = %d (frames_per_keyframe %d)", c.app_dim, hr_time_app_dim(c.shading, d->frames_per_keyframe),
+                    d->frames_per_keyframe);
+    if (m->finalized || !m->raw.empty()) return fail(HR_E_STATE, "hr_model_set_time_decode comes between hr_model_create and the first upload");
+    m->expect.erase(DENSITY_BASIS);
+    if (d->density_mode != HR_DENSITY_PLAIN) {
+        size_t lds = 0;
+        if (hr_time_lds_refused(c, m->p_live, &lds))
+            return fail(HR_E_INVALID, "z_channels %d x %d head columns with a density row need %zu bytes of LDS per workgroup (160 KiB available)", c.z_channels, m->p_live, lds);
+        const int nb = hr_time_nb(d->density_mode == HR_DENSITY_FOURIER, d->frames_per_keyframe);
+        m->expect[DENSITY_BASIS] = sizeof(float) * (size_t)nb * (c.n_den[0] + c.n_den[1] + c.n_den[2]);
+    }
+    m->time_desc = *d;
+    m->time_set = true;
+    return HR_OK;
+}
+
+// a density mode's basis_mat_density -> the column-major copy and the slot table of the density row (hr_plan.h: hr_time_density_slots), at finalize
+static int pack_density_basis(hr_model* m)
+{
+    const hr_config& c = m->cfg;
+    const int nb = hr_time_nb(m->time_desc.density_mode == HR_DENSITY_FOURIER, m->time_desc.frames_per_keyframe);
+    const int n_cols = c.n_den[0] + c.n_den[1] + c.n_den[2], ld = (nb + 3) & ~3;
+    std::vector<float> w((size_t)nb * n_cols), wt((size_t)(n_cols > 0 ? n_cols : 1) * ld, 0.0f);
+    if (!w.empty()) HR_HIP(hipMemcpy(w.data(), m->raw[DENSITY_BASIS].p, w.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int col = 0; col < n_cols; ++col)
+        for (int r = 0; r < nb; ++r) wt[(size_t)col * ld + r] = w[(size_t)r * n_cols + col];
+    // the plan the launches will take (hr_time_plan: the class does not depend on the ray count or on hr_render_frame's line form)
+    const HrTimePlan T = hr_time_plan(m->kcfg, m->planes, m->ca_total, hr_head_quads(c, m->p_live), rows_per_ray(c), 1, true);
+    std::vector<int> sc((size_t)T.d_slots, -1);
+    int slot = 0, col0 = 0;
+    for (int j = 0; j < 3; ++j) {       // density slot order: plane pair after plane pair, 4 cd4 each (the classes: row 0 of the matrix-shaped block)
+        for (int i = 0; i < 4 * m->planes[j].cd4; ++i) sc[slot + i] = i < c.n_den[j] ? col0 + i : -1;
+        slot += 4 * m->planes[j].cd4;
+        col0 += c.n_den[j];
+    }
+    m->dbasis_t.reset();
+    m->dslot_col.reset();
+    HR_HIP(m->dbasis_t.alloc(wt.size() * sizeof(float)));
+    HR_HIP(hipMemcpy(m->dbasis_t, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
+    HR_HIP(m->dslot_col.alloc((sc.empty() ? 1 : sc.size()) * sizeof(int)));
+    if (!sc.empty()) HR_HIP(hipMemcpy(m->dslot_col, sc.data(), sc.size() * sizeof(int), hipMemcpyHostToDevice));
+    m->d_ld = ld;
+    m->d_slots = T.d_slots;
+    m->packed_bytes += (int64_t)(wt.size() * sizeof(float) + sc.size() * sizeof(int));
+    return HR_OK;
+}
+
 static const char* const SHADE_TENSORS[6] = {"renderModule.mlp.0.weight", "renderModule.mlp.0.bias", "renderModule.mlp.2.weight",
                                              "renderModule.mlp.2.bias",   "renderModule.mlp.4.weight", "renderModule.mlp.4.bias"};
 
@@ -296,6 +368,8 @@ int hr_model_finalize(hr_model* m)
         for (const char* name : SHADE_TENSORS)
             if (m->raw.find(name) == m->raw.end()) return fail(HR_E_STATE, "MLP shading mode: tensor '%s' was never uploaded", name);
     }
+    if (hr_shading_is_time(c.shading) && !m->time_set)
+        return fail(HR_E_STATE, "shading RGBtLinear / RGBtFourier: hr_model_set_time_decode has not been called");
     for (auto& kv : m->expect)
         if (m->raw.find(kv.first) == m->raw.end())
             return fail(HR_E_MISSING, "tensor '%s%s' was never uploaded", (m->coarse && kv.first.compare(0, 4, "mlp.") == 0) ? "mlp1." : "",
@@ -380,6 +454,10 @@ int hr_model_finalize(hr_model* m)
     }
     if (hr_shading_is_mlp(c.shading)) {
         const int rc = pack_shading(m);
+        if (rc != HR_OK) return rc;
+    }
+    if (hr_model_time_density(m)) {
+        const int rc = pack_density_basis(m);
         if (rc != HR_OK) return rc;
     }
     // hr_render_frame: one line per time plane for the frame's blended keyframe rows (float32 texels)

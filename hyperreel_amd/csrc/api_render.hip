@@ -160,6 +160,7 @@ void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int
 bool launch_frame(hr_model* m, const float* rays, int64_t n, float* rgb, bool probe, hipStream_t st)
 {
     if (hr_shading_is_mlp(m->cfg.shading)) return false;      // the colour network is no part of the frame kernel: the chunked plan (launch_samples)
+    if (hr_model_time_kernel(m)) return false;                // nor are the time-dependent decode modes: their own sample kernel
     const int prec = m->mlp.active_precision, L = m->cfg.mlp_layers;
     const bool split = prec == HR_MLP_BF16X3 || prec == HR_MLP_F16X3 || prec == HR_MLP_F16X2 || prec == HR_MLP_F16F8;      // their elements: 16 bits (HrMlpTiles::wsplit)
     const HrFramePlanIn in = {n, m->opt_frame_kernel, m->opt_sample_waves, m->coarse || m->is_coarse, m->mlp.verified != 0, split, sizeof(uint16_t),
@@ -194,6 +195,26 @@ static int check_render(const hr_model* m, const float* rays, int64_t n, const f
 static bool launch_samples(const hr_model* m, const HrSampleArgs& sa, const hr_maps* maps, int64_t r0, hipStream_t st)
 {
     const bool shade = hr_shading_is_mlp(m->cfg.shading);
+    if (hr_model_time_kernel(m)) {              // time-dependent decode modes: one kernel for image, maps and diagnostics
+        hr_maps mp = hr_maps();
+        if (maps) mp = *maps;
+        if (mp.distances_dev) mp.distances_dev += r0;
+        if (mp.points_dev) mp.points_dev += r0 * 3;
+        if (mp.acc_dev) mp.acc_dev += r0;
+        HrTimeIO io = HrTimeIO();
+        const bool density = hr_model_time_density(m);
+        io.fpk = m->time_set ? m->time_desc.frames_per_keyframe : 1;
+        io.fac = m->time_set ? hr_time_scale(m->cfg.num_keyframes, m->time_desc.num_frames) : 0.0f;
+        io.c_fourier = m->cfg.shading == HR_SHADING_RGBT_FOURIER;
+        if (density) {
+            io.d_fourier = m->time_desc.density_mode == HR_DENSITY_FOURIER;
+            io.dbasis_t = m->dbasis_t;
+            io.dslot_col = m->dslot_col;
+            io.d_ld = m->d_ld;
+            io.d_slots = m->d_slots;
+        }
+        return hr_launch_samples_time(m->kcfg, sa, mp, io, density, st);
+    }
     if (!maps && !shade) {
         hr_launch_samples(m->kcfg, sa, st);
         return true;
@@ -309,7 +330,7 @@ static int render_impl(hr_model* m, const float* rays_dev, int64_t n_rays, float
     // verified fast path.  With diagnostics requested every output comes from ONE arithmetic: the f16x3 tiles throughout.
     // So does a model with an occupancy volume (hr_occupancy_test decides per cell from a head-dependent point; the band does not cover it),
     // and a render inside a stream capture whose band is out of date (hr_model_update_config since the last measurement: measuring synchronises).
-    bool verify = m->mlp.verified && !fields && !m->occ && n_rays < ((int64_t)1 << 31) && !hr_shading_is_mlp(c.shading);
+    bool verify = m->mlp.verified && !fields && !m->occ && n_rays < ((int64_t)1 << 31) && !hr_shading_is_mlp(c.shading) && !hr_model_time_kernel(m);
     if (verify && m->mlp.band_stale) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
@@ -343,7 +364,8 @@ static int render_impl(hr_model* m, const float* rays_dev, int64_t n_rays, float
                 hr_launch_head_export(m->head, fields->head_dev + r0 * (int64_t)Z * c.preds_per_z, n, Z, c.preds_per_z, m->p_live,
                                       (m->mlp.pack->n_out + 3) / 4, rows_per_ray(c), m->col_map, st);
         }
-        if (!launch_samples(m, sa, maps, r0, st)) return fail(HR_E_HIP, "the shading kernel's LDS request was refused");
+        if (!launch_samples(m, sa, maps, r0, st))
+            return fail(HR_E_HIP, hr_model_time_kernel(m) ? "the density row's table does not fit the launch's plan" : "the shading kernel's LDS request was refused");
     }
     HR_HIP(hipGetLastError());
     return HR_OK;

@@ -148,12 +148,20 @@ int hr_adam_step_dev(float* const* param_dev, const float* const* grad_dev, floa
 }
 
 // ---------------------------------------------------------------- training path
+// the sample stage's training kernels of the model: the time-dependent colour modes have a build of their own (train_time_kernel.hip)
+static void launch_train(const hr_model* m, const HrTrainArgs& a, hipStream_t st)
+{
+    if (hr_shading_is_time_family(m->cfg.shading)) hr_launch_train_time(m->cfg, &a, sizeof(a), st);
+    else hr_launch_train(m->cfg, a, st);
+}
+
 static int check_train(hr_model* m, const float* rays, int64_t n)
 {
     if (!m) return fail(HR_E_INVALID, "null model");
     if (m->is_coarse) return fail(HR_E_INVALID, "training path: pass the cascade's handle, not its coarse level");
     if (!m->finalized) return fail(HR_E_STATE, "hr_model_finalize has not been called (or tensors changed since)");
     if (const char* why = hr_train_unsupported(m->cfg)) return fail(HR_E_INVALID, "training path: %s not differentiated", why);
+    if (hr_model_time_density(m)) return fail(HR_E_INVALID, "training path: densityMode DensityLinear / DensityFourier (inference only) not differentiated");
     if (m->ca_total > HR_TRAIN_MAX_CA) return fail(HR_E_INVALID, "training path: more than %d appearance components", HR_TRAIN_MAX_CA);
     if (n < 0 || (n > 0 && !rays)) return fail(HR_E_INVALID, "bad ray buffer");
     for (hr_model* lvl : {m, m->coarse.get()}) {
@@ -342,7 +350,7 @@ static int train_forward(hr_model* m, const hr_train_tensors* params, const floa
     fill_train_args(m, a, rays_dev, head_dev, n_rays, white_bg);
     a.rgb = rgb_dev;
     if (fields) { a.f_dist = fields->distances_dev; a.f_points = fields->points_dev; a.f_weights = fields->weights_dev; }
-    hr_launch_train(m->cfg, a, st);
+    launch_train(m, a, st);
     HR_HIP(hipGetLastError());
     return HR_OK;
 }
@@ -420,7 +428,8 @@ int hr_train_backward(hr_model* m, const float* rays_dev, const float* head_dev,
         }
         ad.d_basis = reinterpret_cast<float*>(m->grad_fx + off_basis);
         ad.d_color_table = n_ct ? reinterpret_cast<float*>(m->grad_fx + off_ct) : nullptr;
-        hr_launch_train_det(m->cfg, &ad, sizeof(ad), st);
+        if (hr_shading_is_time_family(m->cfg.shading)) hr_launch_train_time_det(m->cfg, &ad, sizeof(ad), st);
+        else hr_launch_train_det(m->cfg, &ad, sizeof(ad), st);
         const float* fx_inv = &m->fx_unit->inv;
         const unsigned* fx_bad = &m->fx_unit->bad;
         for (int j = 0; j < 3; ++j) {
@@ -430,7 +439,7 @@ int hr_train_backward(hr_model* m, const float* rays_dev, const float* head_dev,
         hr_launch_fixed_to_float(m->grad_fx + off_basis, d_basis, (int64_t)n_basis, fx_inv, fx_bad, st);
         if (n_ct) hr_launch_fixed_to_float(m->grad_fx + off_ct, grads->color_table, (int64_t)n_ct, fx_inv, fx_bad, st);
     } else {
-        hr_launch_train(m->cfg, a, st);
+        launch_train(m, a, st);
     }
     HrLayoutBatch batch = {};                      // packed texel gradients -> the reference's (C, H, W) tensors, one launch
     for (int j = 0; j < 3; ++j) {

@@ -174,6 +174,22 @@ void hr_launch_samples_shade_export(const hr_config& cfg, const HrSampleArgs& ar
 // maps: ray-indexed like args.rgb; all pointers NULL when no map is asked for
 void hr_launch_samples_shade_import(const hr_config& cfg, const HrSampleArgs& args, const hr_maps& maps, float* rows, const float* rgbk, hipStream_t stream);
 
+// The time-dependent decode modes (definitions: hr_time_decode.h): an argument of sample_time_kernel.hip's kernels only
+// (HrSampleArgs stays as it is)
+struct HrTimeIO {
+    const float* dbasis_t;  // a density mode: column-major copy of basis_mat_density, column c's nb rows at dbasis_t + c * d_ld
+    const int* dslot_col;   //   slot of a ray's density row -> column of basis_mat_density (-1: the slot is zero); d_slots entries
+    int d_ld, d_slots;      //   floats of a ray's density row (class gathers: 3 x ca_total, generic gather: 4 x the planes' cd4)
+    int d_off;              //   float offset of the workgroup's density rows in its dynamic LDS
+    int d_fourier, c_fourier;    // 1: the Fourier basis (density / colour), 0: Linear
+    int fpk;                // frames_per_keyframe
+    float fac;              // hr_time_scale(num_keyframes, num_frames)
+};
+// the sample stage of a model with a time-dependent colour or density mode, or RGBIdentity: image, per-ray maps (all pointers NULL when
+// none is asked for) and diagnostics in one kernel; density: a density mode (the density row and its LDS; io.d_slots: the floats per ray
+// the caller's dslot_col was made for).  false: that table does not fit the launch's plan (nothing launched)
+bool hr_launch_samples_time(const hr_config& cfg, const HrSampleArgs& args, const hr_maps& maps, const HrTimeIO& io, bool density, hipStream_t stream);
+
 // training forward (mlp_split_impl.inc, HR_SPLIT_TRAIN_KERNEL): where the output of hidden Linear l (after its LeakyReLU) goes besides LDS --
 // act[l] + ray * ld[l] + off[l] + feature, fp32 (NULL: not kept)
 struct HrMlpTaps {
@@ -415,6 +431,9 @@ void hr_launch_train(const hr_config& cfg, const HrTrainArgs& args, hipStream_t 
 // d_basis, d_color_table) point to 64-bit fixed-point buffers of the same element counts (hr_train.h: hr_acc_t; the unit is chosen per step and
 // kept in args.fx, the model's own)
 void hr_launch_train_det(const hr_config& cfg, const void* args_flt, size_t args_bytes, hipStream_t stream);
+// the time-dependent colour modes' builds of both (train_time_kernel.hip, train_time_det_kernel.hip): `args_flt` as above
+void hr_launch_train_time(const hr_config& cfg, const void* args_flt, size_t args_bytes, hipStream_t stream);
+void hr_launch_train_time_det(const hr_config& cfg, const void* args_flt, size_t args_bytes, hipStream_t stream);
 void hr_launch_fixed_to_float(const long long* src, float* dst, int64_t n, const float* inv_dev, const unsigned* bad_dev, hipStream_t stream);   // dst[i] = src[i] * *inv_dev (NaN if *bad_dev)
 void hr_launch_features(const hr_config* cfg_dev, const float* rays, int64_t n, float* out, hipStream_t stream);
 // training GEMMs of the MLP (train_gemm_kernel.hip)

@@ -176,7 +176,17 @@ struct HR_HIDDEN hr_model {
     DevMem<float> shade_b[3];
     DevMem<float> shade_rows;            // (chunk * Z, HR_SHADE_ROW): the export form's rows
     DevMem<float> shade_rgb;             // (chunk * Z, 3): the shading kernel's colours
+    // time-dependent decode modes (hr_model_set_time_decode)
+    bool time_set = false;
+    hr_time_decode time_desc = {};
+    DevMem<float> dbasis_t;              // a density mode: column-major copy of basis_mat_density (HrTimeIO::dbasis_t)
+    DevMem<int> dslot_col;               //   density-row slot -> column (HrTimeIO::dslot_col)
+    int d_ld = 0, d_slots = 0;
 };
+
+// the model renders with sample_time_kernel.hip's kernel: a time-dependent colour mode, RGBIdentity, or a density mode
+inline bool hr_model_time_density(const hr_model* m) { return m->time_set && m->time_desc.density_mode != HR_DENSITY_PLAIN; }
+inline bool hr_model_time_kernel(const hr_model* m) { return hr_shading_is_time_family(m->cfg.shading) || hr_model_time_density(m); }
 
 // a ray with a live sample beyond it (60 degrees off a plane's normal; a sphere nearly tangent) is not what the margins of the verified fast
 // path are measured on -- its errors are the geometry's, the MLP's two-plane / Pluecker inputs included -- and is always listed

@@ -14,6 +14,7 @@
 #include "../../include/hyperreel_hip.h"
 #include "hr_grid.h"
 #include "hr_math.h"
+#include "hr_time_decode.h"
 
 // z_channels rounded up to a power of two, at least 8: the sample count the per-ray kernels are compiled for (8 ... 256)
 static inline int hr_round_zp(int z_channels)
@@ -460,7 +461,9 @@ static inline HrTrainPlan hr_train_plan(const hr_config& cfg, const HrGridPlane*
     P.atomics_rpb = zp >= groups ? 1 : groups / zp;
     // four 256-thread workgroups per CU are resident (128 registers); four rounds of them: the blocks differ in cost
     P.atomics_blocks = at_most(ceil_div(n, P.atomics_rpb), 16 * (int64_t)in.cus);
-    P.atomics_lds = sizeof(float) * (P.atomics_rpb * 3 * ca_total) + in.acc_bytes * (P.atomics_rpb * 3 * ca_total + 27 * n_basis_cols);
+    // rows of basis_mat's gradient in LDS: SH's 27 as ever (RGB's 3 fit in them), an RGBtFourier model's 3 nb when that is more
+    const int basis_rows = cfg.app_dim > 27 ? cfg.app_dim : 27;
+    P.atomics_lds = sizeof(float) * (P.atomics_rpb * 3 * ca_total) + in.acc_bytes * (P.atomics_rpb * 3 * ca_total + basis_rows * n_basis_cols);
 
     // ---- phase B, windows in LDS
     bool any = false, keyed = false;
@@ -472,7 +475,7 @@ static inline HrTrainPlan hr_train_plan(const hr_config& cfg, const HrGridPlane*
     P.lines_blocks = at_most(ceil_div(n, rpb), in.cus);
     P.bucket_lds = sizeof(int) * (size_t)(cfg.num_keyframes + 1);
     // decode matrices and their gradient, basis_mat's gradient, the rays' time taps; then the windows of plane pairs `pairs`
-    const size_t base = sizeof(float) * (2 * rpb * 3 * ca_total + 27 * n_basis_cols + 4 * rpb);
+    const size_t base = sizeof(float) * (2 * rpb * 3 * ca_total + basis_rows * n_basis_cols + 4 * rpb);
     auto request = [&](unsigned pairs) {
         size_t bytes = base;
         for (int j = 0; j < 3; ++j) {
@@ -561,7 +564,8 @@ struct HrMlpChoice {
     bool needs_calibration;
     int status;                   // HR_OK | HR_E_RANGE | HR_E_INVALID
 };
-static inline HrMlpChoice hr_mlp_choice(const hr_config& c, bool cascade_level, bool range_supported, const float* act_max)
+// time_density: the model carries a density mode of hr_model_set_time_decode (not part of hr_config)
+static inline HrMlpChoice hr_mlp_choice(const hr_config& c, bool cascade_level, bool range_supported, const float* act_max, bool time_density = false)
 {
     const int want = c.mlp_precision;
     if (c.mlp_layers == 0 || want == HR_MLP_FP32 || want == HR_MLP_BF16X3)
@@ -572,7 +576,10 @@ static inline HrMlpChoice hr_mlp_choice(const hr_config& c, bool cascade_level, 
     for (int l = 0; l < c.mlp_layers; ++l) fits = fits && isfinite(act_max[l]) && act_max[l] < HR_F16_CALIBRATION_LIMIT;
     // (an MLP shading mode: the verified path's margins are not derived for the colour network -- f16f8 / f16f8v / auto run f16x3 there)
     const bool shade_mlp = c.shading == HR_SHADING_MLP_FEA || c.shading == HR_SHADING_MLP;
-    const bool f8_ok = !shade_mlp && hr_mlp_fast_sincos_ok(c), can_verify = f8_ok && hr_mlp_can_verify(c, cascade_level);
+    // (the time-dependent decode modes and RGBIdentity, DESIGN 3m: the verified path's calibration -- its colour bar, its list passes through
+    //  the stand-alone sample kernel -- is not derived for their kernel either: the same resolution)
+    const bool time_decode = hr_shading_is_time_family(c.shading) || time_density;
+    const bool f8_ok = !shade_mlp && !time_decode && hr_mlp_fast_sincos_ok(c), can_verify = f8_ok && hr_mlp_can_verify(c, cascade_level);
     if (want == HR_MLP_AUTO) {
         if (!fits) return {HR_MLP_BF16X3, 0, true, HR_OK};
         return {can_verify ? HR_MLP_F16F8 : HR_MLP_F16X3, can_verify ? 1 : 0, true, HR_OK};
@@ -682,5 +689,44 @@ static inline int64_t hr_shade_default_chunk(int64_t head_chunk, const HrShadePl
 // shading kernel without a flagged row are skipped, and the import form masks by the flag, not by its own weight (the two forms sum
 // the density in different orders: their weights agree to rounding, not always in a comparison)
 static constexpr inline bool hr_shade_live(float weight, float thresh) { return weight > thresh; }
+
+// ---------------------------------------------------------------- time-dependent decode modes (sample_time_kernel.hip; definitions: hr_time_decode.h)
+// A model with `shadingMode: RGBtLinear | RGBtFourier | RGBIdentity` or `densityMode: DensityLinear | DensityFourier` renders every chunk
+// with its own sample kernel (hr_sample_maps_kernel's statements; never the frame kernel or the verified fast path).  Per ray it keeps in
+// LDS: the decode matrix folded with the ray's time basis (per_ray_M: the RGBt modes, as SH -- hr_sample_lds_bytes has always counted a
+// matrix per ray) and, with a density mode, the ray's density row: in the decode matrix's shape (3 x ca_total, rows 1, 2 zero) for the
+// class gathers, whose density lanes read it where they read the ones block, and one weight per density slot for the generic gather.
+static inline bool hr_time_per_ray_M(int shading) { return hr_shading_relu_half(shading); }
+static inline int hr_time_density_slots(const HrGridPlane* planes, int ca_total, int pclass)
+{
+    return pclass != 0 ? 3 * ca_total : 4 * (planes[0].cd4 + planes[1].cd4 + planes[2].cd4);
+}
+struct HrTimePlan {
+    HrSamplePlan sample;        // hr_sample_plan's with the second factor's taps decided at run time (NB = 4) and the density rows' LDS added
+    int d_slots, d_off;         // floats of a ray's density row, float offset of the workgroup's rows in its dynamic LDS (0, 0 without a density mode)
+};
+static inline HrTimePlan hr_time_plan(const hr_config& cfg, const HrGridPlane* planes, int ca_total, int nq, int rows_per_ray, int64_t n_rays, bool density)
+{
+    HrTimePlan T = HrTimePlan();
+    T.sample = hr_sample_plan(cfg, planes, ca_total, nq, rows_per_ray, n_rays, false);
+    T.sample.all_lines = 0;
+    if (density) {
+        T.d_slots = hr_time_density_slots(planes, ca_total, T.sample.pclass);
+        T.d_off = (int)(T.sample.lds / sizeof(float));
+        T.sample.lds += sizeof(float) * (size_t)(256 / T.sample.zp) * T.d_slots;
+        T.sample.big_lds = T.sample.lds > 64 * 1024;
+    }
+    return T;
+}
+// hr_sample_lds_refused for a model with a density mode (hr_model_set_time_decode: the descriptor is no part of hr_config)
+static inline bool hr_time_lds_refused(const hr_config& c, int p_live, size_t* bytes)
+{
+    HrGridPlane pl[3];
+    int ca_total = 0, n_basis_cols = 0;
+    (void)hr_plane_geometry(c, pl, &ca_total, &n_basis_cols);
+    const HrTimePlan T = hr_time_plan(c, pl, ca_total, hr_head_quads(c, p_live), rows_per_ray(c), 1, true);
+    *bytes = T.sample.lds;
+    return *bytes + 4096 + (T.sample.zp > 64 ? 0 : 256 * sizeof(float)) > HR_LDS_PER_WORKGROUP;
+}
 
 #endif  // HR_PLAN_H

@@ -384,6 +384,9 @@ const char* hr_train_unsupported(const hr_config& c)
 {
     if (c.grid_dtype != HR_GRID_FP32) return "float16 grids";
     if (c.shading == HR_SHADING_MLP_FEA || c.shading == HR_SHADING_MLP) return "the colour network of shadingMode MLP_Fea / MLP (inference only)";
+    // (shadingMode RGBtLinear / RGBtFourier / RGBIdentity: differentiated by the HR_TRAIN_TIME build of this file, train_time_kernel.hip.
+    //  densityMode DensityLinear / DensityFourier is inference only, but no part of hr_config -- hr_model_set_time_decode carries it --:
+    //  the entry points' common check (api_train.hip, check_train) names it, not this function)
     return nullptr;
 }
 
@@ -672,6 +675,47 @@ HR_FN int hr_train_slot_col(const HrTrainArgs& a, int pos)
     return col;
 }
 
+#ifdef HR_TRAIN_TIME
+// The HR_TRAIN_TIME build (train_time_kernel.hip): a ray's basis vector has nbv entries -- the time basis of an RGBt mode
+// (hr_time_decode.h; nb = app_dim / 3 functions of the ray's time and of its offset from the keyframe, the scale K (F - 1) / F is the
+// advect stage's flow_fac), SH's nine, or the single 1 of RGB / RGBIdentity -- and basis_mat 3 nbv rows, row cc * nbv + j.
+#define HR_TRAIN_NBV_MAX HR_TIME_MAX_NB
+HR_FN int hr_train_nbv(const hr_config& c) { return hr_shading_is_time(c.shading) ? c.app_dim / 3 : (c.shading == HR_SHADING_SH ? 9 : 1); }
+HR_FN void hr_train_ray_basis(const hr_config& c, const float* rr, float* b)
+{
+    if (hr_shading_is_time(c.shading)) {
+        const int nb = c.app_dim / 3, fourier = c.shading == HR_SHADING_RGBT_FOURIER;
+        const float t = rr[c.ray_dim - 1], off = c.advect ? t - hr_base_time(c, t) : 0.0f;
+        for (int j = 0; j < nb && j < HR_TRAIN_NBV_MAX; ++j) b[j] = hr_time_basis(fourier, (nb - 1) / 2, t, off, c.flow_fac, j);
+    } else if (c.shading == HR_SHADING_SH) {
+        hr_sh_deg2(rr[3], rr[4], rr[5], b);
+    } else {
+        b[0] = 1.0f;
+    }
+}
+HR_FN float hr_train_decode_coef(const hr_config& c, const HrTrainArgs& a, const float* sh, int cc, int pos)
+{
+    const int col = hr_train_slot_col(a, pos);
+    if (col < 0) return 0.0f;
+    const int nbv = hr_train_nbv(c);
+    if (nbv == 1) return a.basis[cc * a.n_basis_cols + col];
+    float v = 0.0f;
+    for (int j = 0; j < nbv; ++j) v = fmaf(sh[j], a.basis[(cc * nbv + j) * a.n_basis_cols + col], v);
+    return v;
+}
+HR_FN void hr_train_fold_basis(const hr_config& c, const HrTrainArgs& a, const float* sh, int cc, int pos, float v, hr_acc_t* acc = nullptr)
+{
+    if (v == 0.0f) return;
+    const int col = hr_train_slot_col(a, pos);
+    if (col < 0) return;
+    const int nbv = hr_train_nbv(c);
+    for (int j = 0; j < nbv; ++j) {
+        const float g = nbv == 1 ? v : sh[j] * v;
+        if (acc) HR_ATOMIC_ADD_RAY(acc + (cc * nbv + j) * a.n_basis_cols + col, g);
+        else HR_ATOMIC_ADD(a.d_basis + (cc * nbv + j) * a.n_basis_cols + col, g);
+    }
+}
+#else
 // M[cc][pos] of the ray's decode matrix (RGB: basis_mat rows; SH: basis rows folded with the view direction's SH basis)
 HR_FN float hr_train_decode_coef(const hr_config& c, const HrTrainArgs& a, const float* sh, int cc, int pos)
 {
@@ -701,6 +745,7 @@ HR_FN void hr_train_fold_basis(const hr_config& c, const HrTrainArgs& a, const f
         else HR_ATOMIC_ADD(a.d_basis + cc * a.n_basis_cols + col, v);
     }
 }
+#endif
 
 // Per-ray quantities every phase recomputes from the ray itself
 HR_FN void hr_train_ray_od(const hr_config& c, const float* r, float* ro, float* rd)
@@ -761,7 +806,11 @@ HR_FN void hr_sample_color(const hr_config& c, const float* pre, bool app, const
     for (int i = 0; i < 3; ++i) {
         raw[i] = 0.0f;
         sc[i] = 1.0f;
+#ifdef HR_TRAIN_TIME      // SH and the RGBt modes relu(x + 0.5), RGBIdentity |x + 0.5| (hr_time_color), RGB the sigmoid
+        if (app) raw[i] = (c.shading != HR_SHADING_RGB) ? hr_time_color(c.shading, pre[i]) : 1.0f / (1.0f + expf(-pre[i]));
+#else
         if (app) raw[i] = (c.shading == HR_SHADING_SH) ? fmaxf(pre[i] + 0.5f, 0.0f) : 1.0f / (1.0f + expf(-pre[i]));
+#endif
         rr[i] = raw[i];
         if (c.f_color_scale.offset >= 0) {
             sc[i] = hr_apply_act(c.f_color_scale.act, hk[c.f_color_scale.offset + i]) + 1.0f;
@@ -785,6 +834,10 @@ HR_FN void hr_sample_color_bwd(const hr_config& c, float wgt, const float* g, co
         }
         const float draw = dr * sc[i];
         if (!app) dpre[i] = 0.0f;
+#ifdef HR_TRAIN_TIME      // the activation's derivative: pre + 0.5 > 0 for relu(x + 0.5), sign(pre + 0.5) for |x + 0.5| (0 at 0, as torch.abs)
+        else if (c.shading == HR_SHADING_RGB_IDENTITY) dpre[i] = (pre[i] + 0.5f > 0.0f) ? draw : ((pre[i] + 0.5f < 0.0f) ? -draw : 0.0f);
+        else if (c.shading != HR_SHADING_RGB) dpre[i] = (pre[i] + 0.5f > 0.0f) ? draw : 0.0f;
+#endif
         else if (c.shading == HR_SHADING_SH) dpre[i] = (pre[i] + 0.5f > 0.0f) ? draw : 0.0f;
         else dpre[i] = draw * raw[i] * (1.0f - raw[i]);
     }
@@ -984,8 +1037,13 @@ HR_FN void hr_ray_train(const hr_config& c, const HrTrainArgs& a, int64_t ray)
     const HrTrainRay q = hr_train_ray(c, r);
 
     // decode matrix of the ray (RGB: basis_mat rows; SH: basis rows folded with the view direction's SH basis)
+#ifdef HR_TRAIN_TIME
+    float sh[HR_TRAIN_NBV_MAX] = {};
+    hr_train_ray_basis(c, r, sh);
+#else
     float sh[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (c.shading == HR_SHADING_SH) hr_sh_deg2(q.rd[0], q.rd[1], q.rd[2], sh);
+#endif
     float M[3 * HR_TRAIN_MAX_CA];
     for (int cc = 0; cc < 3; ++cc)
         for (int pos = 0; pos < CA; ++pos) M[cc * CA + pos] = hr_train_decode_coef(c, a, sh, cc, pos);

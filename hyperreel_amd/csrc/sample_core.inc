@@ -29,6 +29,7 @@
 #include "hr_kernels.h"
 #include "hr_math.h"
 #include "hr_mask.h"
+#include "hr_time_decode.h"
 
 #define HR_FMA(a, b, c) __builtin_fmaf((a), (b), (c))
 
@@ -163,12 +164,20 @@ __device__ __forceinline__ float4 hr_lerp4(const float4 v0, const float4 v1, flo
 
 // One float4 channel group of a sample: plane tap x (line | time-plane) tap, then density partial
 // sum (q < cd) or appearance decode through the ray's matrix M.
+// DEN (the time kernel's density modes, DESIGN 3m): the density channels are weighted by the ray's density row -- Dj: the row's slots of
+// this plane pair -- instead of summed.
+template <bool DEN = false>
 __device__ __forceinline__ void hr_consume_group(const HrGridPlane& g, int q, int cd, const float4 pa, const float4 pb, const float* M,
-                                                 int CA, float& sig_feat, float& pre0, float& pre1, float& pre2)
+                                                 int CA, float& sig_feat, float& pre0, float& pre1, float& pre2, const float* Dj = nullptr)
 {
     const float fx = pa.x * pb.x, fy = pa.y * pb.y, fz = pa.z * pb.z, fw = pa.w * pb.w;
     if (q < cd) {
-        sig_feat = sig_feat + fx; sig_feat = sig_feat + fy; sig_feat = sig_feat + fz; sig_feat = sig_feat + fw;
+        if constexpr (DEN) {
+            const float4 d = *reinterpret_cast<const float4*>(Dj + 4 * q);
+            sig_feat = HR_FMA(d.w, fw, HR_FMA(d.z, fz, HR_FMA(d.y, fy, HR_FMA(d.x, fx, sig_feat))));
+        } else {
+            sig_feat = sig_feat + fx; sig_feat = sig_feat + fy; sig_feat = sig_feat + fz; sig_feat = sig_feat + fw;
+        }
     } else {
         const int ch = g.app_off + 4 * (q - cd);
         const float4 m0 = *reinterpret_cast<const float4*>(M + ch);
@@ -259,9 +268,9 @@ __device__ __forceinline__ void hr_tap(const void* base, unsigned off, int q0, i
 //  gather with LDS hand-over, 1.66 vs 1.27 ms per frame; compile-time unrolled batches of 12-16
 //  loads in flight at 4 waves/SIMD, 1.37 ms.  The gather sits at ~1.1 vector-L1 accesses per
 //  clock per CU, i.e. it is bound by the tag-lookup rate for scattered 16-byte reads.)
-template <bool HALF, int G, int J>
+template <bool HALF, int G, int J, bool DEN = false>
 __device__ __forceinline__ void hr_gather_plane(const HrGridPlane& g, const HrAxisTaps& at, const float* M, int CA,
-                                                float& sig_feat, float& pre0, float& pre1, float& pre2)
+                                                float& sig_feat, float& pre0, float& pre1, float& pre2, const float* Dj = nullptr)
 {
     const int ng = g.cd4 + g.ca4;
     const int cd = g.cd4;
@@ -303,13 +312,13 @@ __device__ __forceinline__ void hr_gather_plane(const HrGridPlane& g, const HrAx
                 const float4 pa = hr_bilerp4(lo4(a00), lo4(a01), lo4(a10), lo4(a11), w00, w01, w10, w11);
                 const float4 pb = line ? hr_lerp4(lo4(b00), lo4(b01), bxp.w0, bxp.w1)
                                        : hr_bilerp4(lo4(b00), lo4(b01), lo4(b10), lo4(b11), v00, v01, v10, v11);
-                hr_consume_group(g, 2 * o, cd, pa, pb, M, CA, sig_feat, pre0, pre1, pre2);
+                hr_consume_group<DEN>(g, 2 * o, cd, pa, pb, M, CA, sig_feat, pre0, pre1, pre2, Dj);
             }
             if (2 * o + 1 < ng) {
                 const float4 pa = hr_bilerp4(hi4(a00), hi4(a01), hi4(a10), hi4(a11), w00, w01, w10, w11);
                 const float4 pb = line ? hr_lerp4(hi4(b00), hi4(b01), bxp.w0, bxp.w1)
                                        : hr_bilerp4(hi4(b00), hi4(b01), hi4(b10), hi4(b11), v00, v01, v10, v11);
-                hr_consume_group(g, 2 * o + 1, cd, pa, pb, M, CA, sig_feat, pre0, pre1, pre2);
+                hr_consume_group<DEN>(g, 2 * o + 1, cd, pa, pb, M, CA, sig_feat, pre0, pre1, pre2, Dj);
             }
         }
         return;
@@ -337,7 +346,7 @@ __device__ __forceinline__ void hr_gather_plane(const HrGridPlane& g, const HrAx
         }
 #pragma unroll
         for (int j = 0; j < G; ++j)
-            if (j < nb) hr_consume_group(g, q0 + j, cd, pa[j], pb[j], M, CA, sig_feat, pre0, pre1, pre2);
+            if (j < nb) hr_consume_group<DEN>(g, q0 + j, cd, pa[j], pb[j], M, CA, sig_feat, pre0, pre1, pre2, Dj);
     }
 }
 
@@ -457,9 +466,9 @@ __device__ __forceinline__ void hr_coop_issue(const HrGridPlane& g, const HrTaps
     }
 }
 
-template <int LPS, int T, int NB>
+template <int LPS, int T, int NB, bool DEN = false>
 __device__ __forceinline__ void hr_coop_consume(const HrGridPlane& g, const HrCoopLoad<NB>& L, const float* M, int CA,
-                                                float& sig_feat, float& pre0, float& pre1, float& pre2)
+                                                float& sig_feat, float& pre0, float& pre1, float& pre2, const float* Dj = nullptr)
 {
     const int j = (int)threadIdx.x & (LPS - 1);
     const bool line = (NB == 2) || (g.bw == 1);
@@ -481,8 +490,12 @@ __device__ __forceinline__ void hr_coop_consume(const HrGridPlane& g, const HrCo
         }
         const hr_f2 f_lo = pa_lo * pb_lo, f_hi = pa_hi * pb_hi;          // plane x line, 4 channels
         if (L.q < g.cd4) {                                               // density: sum over the channels
-            const hr_f2 t = f_lo + f_hi;
-            s = t.x + t.y;
+            if constexpr (DEN) {                                         // (density modes: through the ray's density row)
+                s = hr_dot4<true>(*reinterpret_cast<const hr_f4*>(Dj + 4 * L.q), f_lo, f_hi, 0.0f);
+            } else {
+                const hr_f2 t = f_lo + f_hi;
+                s = t.x + t.y;
+            }
         } else {                                                         // appearance: through the ray's decode matrix
             const int ch = g.app_off + 4 * (L.q - g.cd4);
             const hr_f4 m0 = *reinterpret_cast<const hr_f4*>(M + ch);
@@ -499,9 +512,9 @@ __device__ __forceinline__ void hr_coop_consume(const HrGridPlane& g, const HrCo
 
 // All owners of one plane pair.  PIPE 2: owner T+1's loads are issued before owner T is consumed (two HrCoopLoad sets
 // live: ~70 more VGPRs -- for kernels that run at <= 3 wavefronts per SIMD); PIPE 1: one owner at a time.
-template <int LPS, int PIPE, int NB>
+template <int LPS, int PIPE, int NB, bool DEN = false>
 __device__ __forceinline__ void hr_gather_coop_owners(const HrGridPlane& g, const HrTaps& mine, bool valid, const float* M, int CA,
-                                                      float& sig_feat, float& pre0, float& pre1, float& pre2)
+                                                      float& sig_feat, float& pre0, float& pre1, float& pre2, const float* Dj = nullptr)
 {
     const int ng = g.cd4 + g.ca4;
     for (int q0 = 0; q0 < ng; q0 += LPS) {                // one round unless the texel has more than LPS channel groups
@@ -509,47 +522,47 @@ __device__ __forceinline__ void hr_gather_coop_owners(const HrGridPlane& g, cons
             // (the scheduling fences keep the compiler from overlapping the owners on its own: at 4 wavefronts per SIMD
             //  there are no registers for a second set of texels, and the other wavefronts hide the latency)
             HrCoopLoad<NB> L;
-            hr_coop_issue<LPS, 0, NB>(g, mine, valid, q0, L); hr_coop_consume<LPS, 0, NB>(g, L, M, CA, sig_feat, pre0, pre1, pre2);
+            hr_coop_issue<LPS, 0, NB>(g, mine, valid, q0, L); hr_coop_consume<LPS, 0, NB, DEN>(g, L, M, CA, sig_feat, pre0, pre1, pre2, Dj);
             __builtin_amdgcn_sched_barrier(0);
-            hr_coop_issue<LPS, 1, NB>(g, mine, valid, q0, L); hr_coop_consume<LPS, 1, NB>(g, L, M, CA, sig_feat, pre0, pre1, pre2);
+            hr_coop_issue<LPS, 1, NB>(g, mine, valid, q0, L); hr_coop_consume<LPS, 1, NB, DEN>(g, L, M, CA, sig_feat, pre0, pre1, pre2, Dj);
             if constexpr (LPS == 4) {
                 __builtin_amdgcn_sched_barrier(0);
-                hr_coop_issue<LPS, 2, NB>(g, mine, valid, q0, L); hr_coop_consume<LPS, 2, NB>(g, L, M, CA, sig_feat, pre0, pre1, pre2);
+                hr_coop_issue<LPS, 2, NB>(g, mine, valid, q0, L); hr_coop_consume<LPS, 2, NB, DEN>(g, L, M, CA, sig_feat, pre0, pre1, pre2, Dj);
                 __builtin_amdgcn_sched_barrier(0);
-                hr_coop_issue<LPS, 3, NB>(g, mine, valid, q0, L); hr_coop_consume<LPS, 3, NB>(g, L, M, CA, sig_feat, pre0, pre1, pre2);
+                hr_coop_issue<LPS, 3, NB>(g, mine, valid, q0, L); hr_coop_consume<LPS, 3, NB, DEN>(g, L, M, CA, sig_feat, pre0, pre1, pre2, Dj);
             }
             __builtin_amdgcn_sched_barrier(0);
         } else {
             HrCoopLoad<NB> L0, L1;
             hr_coop_issue<LPS, 0, NB>(g, mine, valid, q0, L0);
             hr_coop_issue<LPS, 1, NB>(g, mine, valid, q0, L1);
-            hr_coop_consume<LPS, 0, NB>(g, L0, M, CA, sig_feat, pre0, pre1, pre2);
+            hr_coop_consume<LPS, 0, NB, DEN>(g, L0, M, CA, sig_feat, pre0, pre1, pre2, Dj);
             if constexpr (LPS == 4) {
                 hr_coop_issue<LPS, 2, NB>(g, mine, valid, q0, L0);
-                hr_coop_consume<LPS, 1, NB>(g, L1, M, CA, sig_feat, pre0, pre1, pre2);
+                hr_coop_consume<LPS, 1, NB, DEN>(g, L1, M, CA, sig_feat, pre0, pre1, pre2, Dj);
                 hr_coop_issue<LPS, 3, NB>(g, mine, valid, q0, L1);
-                hr_coop_consume<LPS, 2, NB>(g, L0, M, CA, sig_feat, pre0, pre1, pre2);
-                hr_coop_consume<LPS, 3, NB>(g, L1, M, CA, sig_feat, pre0, pre1, pre2);
+                hr_coop_consume<LPS, 2, NB, DEN>(g, L0, M, CA, sig_feat, pre0, pre1, pre2, Dj);
+                hr_coop_consume<LPS, 3, NB, DEN>(g, L1, M, CA, sig_feat, pre0, pre1, pre2, Dj);
             } else {
-                hr_coop_consume<LPS, 1, NB>(g, L1, M, CA, sig_feat, pre0, pre1, pre2);
+                hr_coop_consume<LPS, 1, NB, DEN>(g, L1, M, CA, sig_feat, pre0, pre1, pre2, Dj);
             }
         }
     }
 }
 
-template <int J, int PIPE, int NB>
+template <int J, int PIPE, int NB, bool DEN = false>
 __device__ __forceinline__ void hr_gather_plane_coop(const HrGridPlane& g, const HrAxisTaps& at, bool valid, const float* M, int CA,
-                                                     float& sig_feat, float& pre0, float& pre1, float& pre2)
+                                                     float& sig_feat, float& pre0, float& pre1, float& pre2, const float* Dj = nullptr)
 {
     const int ng = g.cd4 + g.ca4;
     if (ng == 0) return;
     if (ng == 1) {               // a single 16-byte group per texel: nothing to share
-        if (valid) hr_gather_plane<false, 1, J>(g, at, M, CA, sig_feat, pre0, pre1, pre2);
+        if (valid) hr_gather_plane<false, 1, J, DEN>(g, at, M, CA, sig_feat, pre0, pre1, pre2, Dj);
         return;
     }
     const HrTaps mine = hr_make_taps<J>(g, at);
-    if (ng == 2) hr_gather_coop_owners<2, (PIPE > 2) ? 2 : 1, NB>(g, mine, valid, M, CA, sig_feat, pre0, pre1, pre2);
-    else hr_gather_coop_owners<4, PIPE, NB>(g, mine, valid, M, CA, sig_feat, pre0, pre1, pre2);
+    if (ng == 2) hr_gather_coop_owners<2, (PIPE > 2) ? 2 : 1, NB, DEN>(g, mine, valid, M, CA, sig_feat, pre0, pre1, pre2, Dj);
+    else hr_gather_coop_owners<4, PIPE, NB, DEN>(g, mine, valid, M, CA, sig_feat, pre0, pre1, pre2, Dj);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -738,7 +751,9 @@ __device__ __forceinline__ void hr_coop_collect(const float (&x)[LPS][3], float 
 }
 
 // PC 1: [8, 4, 4]; PC 2: plane pair 0 only ([8, 0, 0], decode-matrix stride 8).  WRITES the four results.
-template <int NB, int PC>
+// DEN (the time kernel's density modes, DESIGN 3m): `ones` is the ray's density row in the decode matrix's shape -- row 0: the weight of
+// density slot 0 .. CA - 1 (the classes' density and appearance slots coincide), rows 1, 2: zeros -- and a density lane reads ITS four slots.
+template <int NB, int PC, bool DEN = false>
 __device__ __forceinline__ void hr_gather_844(const HrGridPlane* pl, const HrAxisTapsC& at, bool valid, const float* M, const float* ones,
                                               float& sig_feat, float& pre0, float& pre1, float& pre2)
 {
@@ -748,7 +763,7 @@ __device__ __forceinline__ void hr_gather_844(const HrGridPlane* pl, const HrAxi
     {   // plane pair 0: a quad per sample, lane j <-> channel group j (0, 1 density; 2, 3 appearance)
         HrTapsC<NB> mine = hr_make_taps_c<0, NB>(pl[0], at);
         mine.oa = valid ? mine.oa : HR_TAP_MASKED;
-        const float* Mj = (lane & 2) ? M + HrPc844<0>::APP_OFF + 4 * (lane & 1) : ones;
+        const float* Mj = (lane & 2) ? M + HrPc844<0>::APP_OFF + 4 * (lane & 1) : (DEN ? ones + 4 * (lane & 1) : ones);
         float x[4][3];
 #pragma unroll
         for (int t = 0; t < 4; ++t) { HR_UNDEF(x[t][0]); HR_UNDEF(x[t][1]); HR_UNDEF(x[t][2]); }
@@ -764,12 +779,12 @@ __device__ __forceinline__ void hr_gather_844(const HrGridPlane* pl, const HrAxi
         for (int t = 0; t < 2; ++t) { HR_UNDEF(x[t][0]); HR_UNDEF(x[t][1]); HR_UNDEF(x[t][2]); }
         HrTapsC<NB> m1 = hr_make_taps_c<1, NB>(pl[1], at);
         m1.oa = valid ? m1.oa : HR_TAP_MASKED;
-        const float* M1 = (lane & 1) ? M + HrPc844<1>::APP_OFF : ones;
+        const float* M1 = (lane & 1) ? M + HrPc844<1>::APP_OFF : (DEN ? ones + HrPc844<1>::APP_OFF : ones);
         hr_coop844_owner<1, 0, NB, CA>(pl[1], m1, M1, x[0]);
         hr_coop844_owner<1, 1, NB, CA>(pl[1], m1, M1, x[1]);
         HrTapsC<NB> m2 = hr_make_taps_c<2, NB>(pl[2], at);
         m2.oa = valid ? m2.oa : HR_TAP_MASKED;
-        const float* M2 = (lane & 1) ? M + HrPc844<2>::APP_OFF : ones;
+        const float* M2 = (lane & 1) ? M + HrPc844<2>::APP_OFF : (DEN ? ones + HrPc844<2>::APP_OFF : ones);
         hr_coop844_owner<2, 0, NB, CA, false>(pl[2], m2, M2, x[0]);
         hr_coop844_owner<2, 1, NB, CA, false>(pl[2], m2, M2, x[1]);
         hr_coop_collect<2>(x, r);
@@ -893,8 +908,8 @@ __device__ __forceinline__ void hr_coop844h_owner(const HrGridPlane& g, const Hr
 }
 
 // plane pairs 1, 2: the lane's own sample, one octet per texel (4 density | 4 appearance channels)
-template <int J, int NB, int CA>
-__device__ __forceinline__ void hr_own844h(const HrGridPlane& g, const HrTapsC<NB>& t, bool valid, const float* M, float (&out)[4])
+template <int J, int NB, int CA, bool DEN = false>
+__device__ __forceinline__ void hr_own844h(const HrGridPlane& g, const HrTapsC<NB>& t, bool valid, const float* M, float (&out)[4], const float* D = nullptr)
 {
     using PC = HrPc844h<J>;
     const bool line = (NB == 2) || (g.bw == 1);
@@ -914,12 +929,13 @@ __device__ __forceinline__ void hr_own844h(const HrGridPlane& g, const HrTapsC<N
         }
         hr_f2 f[4];
         hr_oct_features<NB>(a0, a1, a2, a3, b0, b1, b2, b3, t.wa, t.wb, line, f);
-        out[0] += hr_sum4(f);
+        if constexpr (DEN) out[0] = hr_dot4<false>(*reinterpret_cast<const hr_f4*>(D + PC::APP_OFF), f[0], f[1], out[0]);
+        else out[0] += hr_sum4(f);
         hr_decode_features<1, CA>(f + 2, M + PC::APP_OFF, out[1], out[2], out[3]);
     }
 }
 
-template <int NB, int PC>
+template <int NB, int PC, bool DEN = false>
 __device__ __forceinline__ void hr_gather_844h(const HrGridPlane* pl, const HrAxisTapsC& at, bool valid, const float* M, const float* ones,
                                                float& sig_feat, float& pre0, float& pre1, float& pre2)
 {
@@ -937,8 +953,8 @@ __device__ __forceinline__ void hr_gather_844h(const HrGridPlane* pl, const HrAx
         hr_coop_collect<2>(x, out);
     }
     if constexpr (PC == 1) {
-        hr_own844h<1, NB, CA>(pl[1], hr_make_taps_c<1, NB, HrPc844h<1>>(pl[1], at), valid, M, out);
-        hr_own844h<2, NB, CA>(pl[2], hr_make_taps_c<2, NB, HrPc844h<2>>(pl[2], at), valid, M, out);
+        hr_own844h<1, NB, CA, DEN>(pl[1], hr_make_taps_c<1, NB, HrPc844h<1>>(pl[1], at), valid, M, out, ones);
+        hr_own844h<2, NB, CA, DEN>(pl[2], hr_make_taps_c<2, NB, HrPc844h<2>>(pl[2], at), valid, M, out, ones);
     }
     // (a masked sample's sums were never written)
     sig_feat = valid ? out[0] : 0.0f; pre0 = valid ? out[1] : 0.0f; pre1 = valid ? out[2] : 0.0f; pre2 = valid ? out[3] : 0.0f;
@@ -1124,6 +1140,38 @@ __device__ __forceinline__ void hr_fill_decode(const hr_config& cfg, const HrSam
     }
 }
 
+// The RGBt modes' decode matrix (DESIGN 3m): M[c][ch] = sum_j basis_j(t, time_offset) * basis_mat[c nb + j][col(ch)] -- hr_fill_decode's
+// SH form with the ray's time basis (hr_time_decode.h) in the place of sh_j(d).  The nb values a slot folds per colour are contiguous in the
+// column-major copy of basis_mat; the basis is evaluated inside the fold (a lane fills at most ceil(CA / ZP) slots: no per-lane array).
+template <int ZP>
+__device__ __forceinline__ void hr_fill_decode_time(const HrSampleArgs& a, const HrTimeIO& io, float t, float time_off, int k, float* M)
+{
+    const int CA = a.ca_total;
+    const int nb = hr_time_nb(io.c_fourier, io.fpk);
+    for (int pos = k; pos < CA; pos += ZP) {
+        const int col = a.slot_col[pos];
+        float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
+        if (col >= 0) {
+            const float* b = a.basis_t + (size_t)col * a.basis_ld;
+            v0 = hr_time_fold(io.c_fourier, io.fpk, t, time_off, io.fac, b, 1);
+            v1 = hr_time_fold(io.c_fourier, io.fpk, t, time_off, io.fac, b + nb, 1);
+            v2 = hr_time_fold(io.c_fourier, io.fpk, t, time_off, io.fac, b + 2 * nb, 1);
+        }
+        M[pos] = v0; M[CA + pos] = v1; M[2 * CA + pos] = v2;
+    }
+}
+
+// The density modes' row of a ray: D[slot] = sum_j basis_j * basis_mat_density[j][col(slot)]; io.dslot_col maps the row's io.d_slots
+// floats to columns (-1: a padded channel, or rows 1, 2 of the class gathers' matrix-shaped block -- zero)
+template <int ZP>
+__device__ __forceinline__ void hr_fill_density_row(const HrTimeIO& io, float t, float time_off, int k, float* D)
+{
+    for (int pos = k; pos < io.d_slots; pos += ZP) {
+        const int col = io.dslot_col[pos];
+        D[pos] = col >= 0 ? hr_time_fold(io.d_fourier, io.fpk, t, time_off, io.fac, io.dbasis_t + (size_t)col * io.d_ld, 1) : 0.0f;
+    }
+}
+
 // Everything from the head values of sample k to the ray's colour.  PIPE: depth of the gather's load pipeline, NB: 2 = compiled for static nets only, 4 = static or keyframe, PC: plane class (hr_plane_class: 1 = [8, 4, 4], 2 = [8, 0, 0], 0 = generic).  `hrow`: this ray's head row(s) in LDS (row stride
 // HS floats; RPR rows when the head comes from a point MLP); `M`: the ray's decode matrix in LDS; `ones`: hr_gather_ones_init's block; `s_x`: 256-float
 // scratch of the block for rays that span several wavefronts (ZP > 64, stand-alone kernel only).
@@ -1133,11 +1181,15 @@ __device__ __forceinline__ void hr_fill_decode(const hr_config& cfg, const HrSam
 // sample's 27 appearance features, its view direction and its live flag go to `shade->rows` (hr_plan.h: HR_SHADE_ROW floats per sorted
 // sample) and nothing else is written; 2 = the import form -- the colour of a sample the export form found above the weight threshold
 // (the row's live flag) is read from `shade->rgbk` (the shading kernel's output) instead of being decoded, everything after it is unchanged.
-template <int ZP, bool HALF, int PIPE, int NB, int PC, bool MAPS = false, int SHADE = 0>
+// TD (sample_time_kernel.hip only; the time-dependent decode modes, DESIGN 3m): bit 0 = the colour's activation is chosen among all
+// shadings the time kernel serves (hr_time_color), bit 1 = a density mode -- `ones` is the ray's density row (class gathers: in the decode
+// matrix's shape, generic gather: one weight per density slot, plane pair after plane pair) and weights the density channels.
+template <int ZP, bool HALF, int PIPE, int NB, int PC, bool MAPS = false, int SHADE = 0, int TD = 0>
 __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSampleArgs& a, const HrRayLane& L, int64_t ray, bool ray_ok, int k,
                                                const float* hrow, int HS, const float* M, const float* ones, float* s_x,
                                                const hr_maps* maps = nullptr, const HrShadeIO* shade = nullptr)
 {
+    constexpr bool DEN = (TD & 2) != 0;
     const int tid = threadIdx.x;
     const int Z = cfg.z_channels;
     const int P = cfg.preds_per_z;
@@ -1241,8 +1293,8 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
         at.ax[2] = hr_make_tap_in(pn[2], cfg.grid[2]);
         at.t = hr_make_tap_c(pn[3], (NB == 4 && cfg.video) ? cfg.num_keyframes : 2);
         HR_SPH(3);
-        if constexpr (HALF) hr_gather_844h<NB, PC>(a.planes, at, valid, M, ones, sig_feat, pre0, pre1, pre2);
-        else hr_gather_844<NB, PC>(a.planes, at, valid, M, ones, sig_feat, pre0, pre1, pre2);
+        if constexpr (HALF) hr_gather_844h<NB, PC, DEN>(a.planes, at, valid, M, ones, sig_feat, pre0, pre1, pre2);
+        else hr_gather_844<NB, PC, DEN>(a.planes, at, valid, M, ones, sig_feat, pre0, pre1, pre2);
         HR_SPH(4);
     } else if constexpr (!HALF) {      // all lanes take part: the quad's lanes serve each other's samples
         float pn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -1258,12 +1310,19 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
         at.ax[2] = hr_make_tap(pn[2], cfg.grid[2]);
         at.t = hr_make_tap(pn[3], cfg.video ? cfg.num_keyframes : 2);
         HR_SPH(3);
+        if constexpr (DEN) {               // density row: plane pair j's slots behind those of the pairs before it
+            const float* D1 = ones + 4 * a.planes[0].cd4;
+            hr_gather_plane_coop<0, PIPE, NB, true>(a.planes[0], at, valid, M, CA, sig_feat, pre0, pre1, pre2, ones);
+            hr_gather_plane_coop<1, PIPE, NB, true>(a.planes[1], at, valid, M, CA, sig_feat, pre0, pre1, pre2, D1);
+            hr_gather_plane_coop<2, PIPE, NB, true>(a.planes[2], at, valid, M, CA, sig_feat, pre0, pre1, pre2, D1 + 4 * a.planes[1].cd4);
+        } else {
         hr_gather_plane_coop<0, PIPE, NB>(a.planes[0], at, valid, M, CA, sig_feat, pre0, pre1, pre2);
         HR_SPH(4);
         hr_gather_plane_coop<1, PIPE, NB>(a.planes[1], at, valid, M, CA, sig_feat, pre0, pre1, pre2);
         HR_SPH(5);
         hr_gather_plane_coop<2, PIPE, NB>(a.planes[2], at, valid, M, CA, sig_feat, pre0, pre1, pre2);
         HR_SPH(6);
+        }
     } else if (valid) {
         float pn[4];
         pn[0] = hr_normalize_coord(cfg, p[0], 0);
@@ -1275,9 +1334,16 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
         at.ax[1] = hr_make_tap(pn[1], cfg.grid[1]);
         at.ax[2] = hr_make_tap(pn[2], cfg.grid[2]);
         at.t = hr_make_tap(pn[3], cfg.video ? cfg.num_keyframes : 2);
+        if constexpr (DEN) {
+            const float* D1 = ones + 4 * a.planes[0].cd4;
+            hr_gather_plane<HALF, 1, 0, true>(a.planes[0], at, M, CA, sig_feat, pre0, pre1, pre2, ones);
+            hr_gather_plane<HALF, 1, 1, true>(a.planes[1], at, M, CA, sig_feat, pre0, pre1, pre2, D1);
+            hr_gather_plane<HALF, 1, 2, true>(a.planes[2], at, M, CA, sig_feat, pre0, pre1, pre2, D1 + 4 * a.planes[1].cd4);
+        } else {
         hr_gather_plane<HALF, 1, 0>(a.planes[0], at, M, CA, sig_feat, pre0, pre1, pre2);
         hr_gather_plane<HALF, 1, 1>(a.planes[1], at, M, CA, sig_feat, pre0, pre1, pre2);
         hr_gather_plane<HALF, 1, 2>(a.planes[2], at, M, CA, sig_feat, pre0, pre1, pre2);
+        }
     }
 
     // ---- density -> alpha -> transmittance -> weight (raw2alpha, tensorf_utils.py:242-253)
@@ -1337,6 +1403,13 @@ __device__ __forceinline__ void hr_sample_body(const hr_config& cfg, const HrSam
                 r0 = c[0]; r1 = c[1]; r2 = c[2];
             }
         } else if (weight > cfg.weight_thresh) {   // app_mask, tensorf_no_sample.py:201
+            if constexpr ((TD & 1) != 0) {         // the time kernel: SH and the RGBt modes relu(x + 0.5), RGBIdentity |x + 0.5| (hr_time_decode.h), RGB below
+                if (cfg.shading != HR_SHADING_RGB) {
+                    r0 = hr_time_color(cfg.shading, pre0); r1 = hr_time_color(cfg.shading, pre1); r2 = hr_time_color(cfg.shading, pre2);
+                } else {
+                    r0 = HR_RCP(1.0f + HR_EXP(-pre0)); r1 = HR_RCP(1.0f + HR_EXP(-pre1)); r2 = HR_RCP(1.0f + HR_EXP(-pre2));
+                }
+            } else
             if (cfg.shading == HR_SHADING_SH) {    // SHRender, tensorf_utils.py:334-338
                 r0 = fmaxf(pre0 + 0.5f, 0.0f); r1 = fmaxf(pre1 + 0.5f, 0.0f); r2 = fmaxf(pre2 + 0.5f, 0.0f);
             } else {                               // RGBRender, tensorf_utils.py:341-343

@@ -4,9 +4,15 @@
 // HR_SAMPLE_MAPS (false | true) and HR_SAMPLE_MAPS_PTR (nullptr | the kernel's hr_maps) select hr_sample_body's per-ray maps.
 // HR_SAMPLE_SHADE (0 unless defined; 1 export | 2 import) and HR_SAMPLE_SHADE_PTR (the kernel's HrShadeIO) select hr_sample_body's
 // forms for the MLP shading modes (sample_shade_kernel.hip).
+// HR_SAMPLE_TIME (0 unless defined; hr_sample_body's TD, a constant expression: 1 = a time-dependent colour mode or RGBIdentity, 3 = with a
+// density mode) and HR_SAMPLE_TIME_PTR (the kernel's HrTimeIO; defined by that kernel only: what the preprocessor tests) select the forms
+// of sample_time_kernel.inc (DESIGN 3m).
 #ifndef HR_SAMPLE_SHADE
 #define HR_SAMPLE_SHADE 0
 #define HR_SAMPLE_SHADE_PTR nullptr
+#endif
+#ifndef HR_SAMPLE_TIME
+#define HR_SAMPLE_TIME 0
 #endif
     constexpr int RPB = 256 / ZP;   // rays per block
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -79,9 +85,19 @@
         hr_ray_constants(cfg, R);
         hr_store_ray_record(R, s_ray + tid * HR_RAY_RECORD);
     }
+#ifdef HR_SAMPLE_TIME_PTR
+    const bool per_ray_M = hr_shading_relu_half(cfg.shading);      // SH, and the RGBt modes: folded with the ray's time basis
+#else
     const bool per_ray_M = (cfg.shading == HR_SHADING_SH);
+#endif
     float* M = s_M + (per_ray_M ? rib * 3 * CA : 0);
-    if (per_ray_M) {                               // SH: folded with the ray's view direction, which its lanes read themselves (the record is not published yet)
+#ifdef HR_SAMPLE_TIME_PTR
+    const float t_lane = ray_ok ? a.rays[ray * cfg.ray_dim + cfg.ray_dim - 1] : 0.0f;      // (the record is not published yet)
+    const float off_lane = cfg.advect ? t_lane - hr_base_time(cfg, t_lane) : 0.0f;         // hr_ray_constants' time_off
+    if (hr_shading_is_time(cfg.shading)) hr_fill_decode_time<ZP>(a, HR_SAMPLE_TIME_PTR, t_lane, off_lane, k, M);
+    else
+#endif
+    if (per_ray_M) {                          // SH: folded with the ray's view direction, which its lanes read themselves (the record is not published yet)
         HrRayLane V = hr_load_ray(cfg, a, 0, false);
         if (ray_ok) {
             const float* r = a.rays + ray * cfg.ray_dim;
@@ -100,8 +116,20 @@
 #endif
     __shared__ __attribute__((aligned(16))) float s_ones[HR_GATHER_ONES];
     hr_gather_ones_init(s_ones);
+#ifdef HR_SAMPLE_TIME_PTR                        // a density mode: the ray's density row, behind the plan's LDS, in the place of the ones
+    const float* s_row = s_ones;
+    if constexpr ((HR_SAMPLE_TIME & 2) != 0) {
+        float* const s_D = lds + HR_SAMPLE_TIME_PTR.d_off + rib * HR_SAMPLE_TIME_PTR.d_slots;
+        hr_fill_density_row<ZP>(HR_SAMPLE_TIME_PTR, t_lane, off_lane, k, s_D);
+        s_row = s_D;
+    }
+#define HR_SAMPLE_ONES s_row
+#else
+#define HR_SAMPLE_ONES s_ones
+#endif
     __syncthreads();
     const HrRayLane L = hr_read_ray_record(s_ray + rib * HR_RAY_RECORD);
 
-    hr_sample_body<ZP, HALF, 1, NB, PC, HR_SAMPLE_MAPS, HR_SAMPLE_SHADE>(cfg, a, L, ray, ray_ok, k, s_head + rib * RPR * HS, HS, M, s_ones, s_x, HR_SAMPLE_MAPS_PTR,
-                                                                         HR_SAMPLE_SHADE_PTR);
+    hr_sample_body<ZP, HALF, 1, NB, PC, HR_SAMPLE_MAPS, HR_SAMPLE_SHADE, HR_SAMPLE_TIME>(cfg, a, L, ray, ray_ok, k, s_head + rib * RPR * HS, HS, M, HR_SAMPLE_ONES, s_x,
+                                                                                         HR_SAMPLE_MAPS_PTR, HR_SAMPLE_SHADE_PTR);
+#undef HR_SAMPLE_ONES

@@ -21,13 +21,35 @@
 // The deterministic build of the sample-stage training kernels (train_det_kernel.hip: HR_TRAIN_DET, hr_acc_t = 64-bit fixed point, see
 // hr_train.h) compiles this file a second time: everything that depends on hr_acc_t lives in its own namespace there, the exports that
 // do not (rows, features, occupancy) are compiled once, in the default build.
-#ifdef HR_TRAIN_DET
+// The time-dependent colour modes (shadingMode RGBtLinear / RGBtFourier / RGBIdentity) compile this file a third and a fourth
+// time (train_time_kernel.hip, train_time_det_kernel.hip: HR_TRAIN_TIME), in namespaces of their own: there the ray's basis vector is the
+// time basis (hr_time_decode.h) where the builds above have SH's, and the activation is the mode's.  The builds above compile to the
+// instructions they always had: what differs sits behind HR_TRAIN_TIME (here and in hr_train.h).
+#if defined(HR_TRAIN_TIME) && defined(HR_TRAIN_DET)
+#define HR_TRAIN_NS hr_time_det
+#define HR_TRAIN_DET_LAUNCH hr_launch_train_time_det
+namespace hr_time_det {
+constexpr bool HR_TRAIN_DETERMINISTIC = true;
+#elif defined(HR_TRAIN_TIME)
+namespace hr_time_train {
+constexpr bool HR_TRAIN_DETERMINISTIC = false;
+#elif defined(HR_TRAIN_DET)
+#define HR_TRAIN_NS hr_det
+#define HR_TRAIN_DET_LAUNCH hr_launch_train_det
 namespace hr_det {
 constexpr bool HR_TRAIN_DETERMINISTIC = true;
 #else
 constexpr bool HR_TRAIN_DETERMINISTIC = false;
 #endif
 #include "hr_train.h"
+// the ray's basis vector: what its decode matrix folds basis_mat with (SH: sh_j(d); the time build: hr_train_ray_basis, hr_train.h)
+#ifdef HR_TRAIN_TIME
+#define HR_RAY_BASIS_DECL(sh) float sh[HR_TRAIN_NBV_MAX] = {}
+#define HR_RAY_BASIS_FILL(c, rr, sh) hr_train_ray_basis(c, rr, sh)
+#else
+#define HR_RAY_BASIS_DECL(sh) float sh[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}
+#define HR_RAY_BASIS_FILL(c, rr, sh) if (c.shading == HR_SHADING_SH) hr_sh_deg2(rr[3], rr[4], rr[5], sh)
+#endif
 
 // Phase A, one thread per ray, HR_TRAIN_RPW rays per wavefront (hr_plan.h)
 template <int ZP>
@@ -83,9 +105,9 @@ __global__ __launch_bounds__(256) void hr_train_lanes_kernel(const hr_config* __
         const int r = e / (3 * CA), i = e - r * 3 * CA;
         float v = 0.0f;
         if (ray0 + r < a.n_rays) {
-            float sh[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            HR_RAY_BASIS_DECL(sh);
             const float* rr = a.rays + (ray0 + r) * c.ray_dim;
-            if (c.shading == HR_SHADING_SH) hr_sh_deg2(rr[3], rr[4], rr[5], sh);
+            HR_RAY_BASIS_FILL(c, rr, sh);
             v = hr_train_decode_coef(c, a, sh, i / CA, i % CA);
         }
         lds[e] = v;
@@ -236,7 +258,11 @@ static void hr_launch_train_lanes(const HrTrainPlan& P, const HrTrainArgs& args,
 
 // Phase B, HR_TRAIN_LPS = 16 lanes per sample (hr_plan.h).
 // rows of basis_mat: 3 (RGB) or 27 (SH: 3 colours x 9 basis functions)
+#ifdef HR_TRAIN_TIME
+__device__ __forceinline__ int hr_train_basis_rows(const hr_config& c) { return 3 * hr_train_nbv(c); }
+#else
 __device__ __forceinline__ int hr_train_basis_rows(const hr_config& c) { return c.shading == HR_SHADING_SH ? 27 : 3; }
+#endif
 
 template <int ZP>
 __global__ __launch_bounds__(256, 4) void hr_train_gather_bwd_kernel(const hr_config* __restrict__ cfgp, const HrTrainArgs a)
@@ -259,9 +285,9 @@ __global__ __launch_bounds__(256, 4) void hr_train_gather_bwd_kernel(const hr_co
             const int r = e / (3 * CA), i = e - r * 3 * CA;
             float v = 0.0f;
             if (ray0 + r < a.n_rays) {
-                float sh[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                HR_RAY_BASIS_DECL(sh);
                 const float* rr = a.rays + (ray0 + r) * c.ray_dim;
-                if (c.shading == HR_SHADING_SH) hr_sh_deg2(rr[3], rr[4], rr[5], sh);
+                HR_RAY_BASIS_FILL(c, rr, sh);
                 v = hr_train_decode_coef(c, a, sh, i / CA, i % CA);
             }
             lds[e] = v;
@@ -278,9 +304,9 @@ __global__ __launch_bounds__(256, 4) void hr_train_gather_bwd_kernel(const hr_co
         for (int e = threadIdx.x; e < RPB * 3 * CA; e += 256) {
             const int r = e / (3 * CA), i = e - r * 3 * CA;
             if (ray0 + r >= a.n_rays) continue;
-            float sh[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            HR_RAY_BASIS_DECL(sh);
             const float* rr = a.rays + (ray0 + r) * c.ray_dim;
-            if (c.shading == HR_SHADING_SH) hr_sh_deg2(rr[3], rr[4], rr[5], sh);
+            HR_RAY_BASIS_FILL(c, rr, sh);
             hr_train_fold_basis(c, a, sh, i / CA, i % CA, HR_ACC_VALUE(dMs[e]), bacc);
         }
     }
@@ -505,9 +531,9 @@ __global__ __launch_bounds__(1024) void hr_train_gather_bwd_lines_kernel(const h
             const int r = e / (3 * CA), i = e - r * 3 * CA;
             float v = 0.0f;
             if (ray0 + r < a.n_rays) {
-                float sh[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                HR_RAY_BASIS_DECL(sh);
                 const float* rr = a.rays + (KEYED ? (int64_t)a.tape.perm[ray0 + r] : ray0 + r) * c.ray_dim;
-                if (c.shading == HR_SHADING_SH) hr_sh_deg2(rr[3], rr[4], rr[5], sh);
+                HR_RAY_BASIS_FILL(c, rr, sh);
                 v = hr_train_decode_coef(c, a, sh, i / CA, i % CA);
             }
             lds[e] = v;
@@ -530,9 +556,9 @@ __global__ __launch_bounds__(1024) void hr_train_gather_bwd_lines_kernel(const h
         for (int e = threadIdx.x; e < RPB * 3 * CA; e += 1024) {
             const int r = e / (3 * CA), i = e - r * 3 * CA;
             if (ray0 + r >= a.n_rays) continue;
-            float sh[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            HR_RAY_BASIS_DECL(sh);
             const float* rr = a.rays + (KEYED ? (int64_t)a.tape.perm[ray0 + r] : ray0 + r) * c.ray_dim;
-            if (c.shading == HR_SHADING_SH) hr_sh_deg2(rr[3], rr[4], rr[5], sh);
+            HR_RAY_BASIS_FILL(c, rr, sh);
             hr_train_fold_basis(c, a, sh, i / CA, i % CA, lds[RPB * 3 * CA + e], bacc);
         }
     }
@@ -675,16 +701,26 @@ __global__ __launch_bounds__(1024) void hr_fx_scale_kernel(const float* __restri
         fx->bad = s_bad;
     }
 }
-}   // namespace hr_det
+}   // namespace hr_det (hr_time_det)
 // the caller's HrTrainArgs is the default build's (float pointers); the structs differ in pointee types only
-void hr_launch_train_det(const hr_config& cfg, const void* args_flt, size_t args_bytes, hipStream_t stream)
+void HR_TRAIN_DET_LAUNCH(const hr_config& cfg, const void* args_flt, size_t args_bytes, hipStream_t stream)
 {
-    hr_det::HrTrainArgs a;
-    if (args_bytes != sizeof(a) || !reinterpret_cast<const hr_det::HrTrainArgs*>(args_flt)->fx) return;
+    HR_TRAIN_NS::HrTrainArgs a;
+    if (args_bytes != sizeof(a) || !reinterpret_cast<const HR_TRAIN_NS::HrTrainArgs*>(args_flt)->fx) return;
     memcpy(&a, args_flt, sizeof(a));
     const bool have = a.d_rgb && a.n_rays > 0;
-    hipLaunchKernelGGL(hr_det::hr_fx_scale_kernel, dim3(1), dim3(1024), 0, stream, have ? a.d_rgb : nullptr, have ? a.n_rays * 3 : 0, a.fx);
-    hr_det::hr_launch_train_impl(cfg, a, stream);
+    hipLaunchKernelGGL(HR_TRAIN_NS::hr_fx_scale_kernel, dim3(1), dim3(1024), 0, stream, have ? a.d_rgb : nullptr, have ? a.n_rays * 3 : 0, a.fx);
+    HR_TRAIN_NS::hr_launch_train_impl(cfg, a, stream);
+}
+#elif defined(HR_TRAIN_TIME)
+}   // namespace hr_time_train
+// (the caller's HrTrainArgs is the default build's: the same struct in another namespace)
+void hr_launch_train_time(const hr_config& cfg, const void* args_flt, size_t args_bytes, hipStream_t stream)
+{
+    hr_time_train::HrTrainArgs a;
+    if (args_bytes != sizeof(a)) return;
+    memcpy(&a, args_flt, sizeof(a));
+    hr_time_train::hr_launch_train_impl(cfg, a, stream);
 }
 #else
 void hr_launch_train(const hr_config& cfg, const HrTrainArgs& args, hipStream_t stream) { hr_launch_train_impl(cfg, args, stream); }

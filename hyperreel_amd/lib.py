@@ -6,7 +6,7 @@ raises.  The product never routes through PyTorch ops or the CPU oracle.
 import ctypes as C
 import os
 
-from .plan import hr_camera, hr_config, hr_fields, hr_fisheye, hr_lightfield, hr_maps, hr_ndc, hr_shading_mlp
+from .plan import hr_camera, hr_config, hr_fields, hr_fisheye, hr_lightfield, hr_maps, hr_ndc, hr_shading_mlp, hr_time_decode
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, '_build', 'libhyperreel_hip.so')
@@ -211,6 +211,7 @@ SYMBOLS = [
     ('hr_stage_mlp', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ('hr_stage_samples', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ('hr_model_set_shading_mlp', C.c_int, [C.c_void_p, C.POINTER(hr_shading_mlp)]),
+    ('hr_model_set_time_decode', C.c_int, [C.c_void_p, C.POINTER(hr_time_decode)]),
     ('hr_stage_shade', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ('hr_debug_trace_mlp', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ('hr_model_device_bytes', C.c_int64, [C.c_void_p]),

@@ -19,7 +19,8 @@ from torch import nn
 from . import lib as _lib
 from .config import n_to_reso, to_plain
 from .data import make_camera, make_fisheye, make_ndc
-from .plan import MLP_PRECISION, compile_model, fast_sincos_ok, hr_fields, hr_lightfield, hr_maps, shading_mlp, shading_width, upload_names
+from .plan import (MLP_PRECISION, compile_model, fast_sincos_ok, frames_per_keyframe, hr_fields, hr_lightfield, hr_maps, shading_mlp, shading_width,
+                   time_basis_size, upload_names)
 
 _MLP_PRECISION_NAME = {code: name for name, code in MLP_PRECISION.items()}      # HR_OPT_MLP_PRECISION_ACTIVE -> 'f16x3' ...
 
@@ -123,7 +124,7 @@ class HostTensorVM(nn.Module):
     """Parameter container shaped like TensorVMSplit (nlf/nets/tensorf_base.py:895-991) or
     TensorVMKeyframeTime (nlf/nets/tensorf_dynamic.py:108-244)."""
 
-    def __init__(self, net_cfg, grid_size, num_keyframes):
+    def __init__(self, net_cfg, grid_size, num_keyframes, num_frames=None):
         super().__init__()
         self.video = net_cfg['type'] == 'tensor_vm_split_time'
         self.n_den = list(net_cfg.get('n_lamb_sigma', [8, 8, 8]))
@@ -153,7 +154,12 @@ class HostTensorVM(nn.Module):
         if shade is not None:                    # MLP_Fea / MLP: the reference's renderModule (tensorf_base.py:38-69, 106-135, 252-262)
             self.renderModule = HostRenderModule(shading_width(net_cfg['shadingMode'], shade), shade.feature_c)
         if self.video:
-            self.basis_mat_density = nn.Linear(sum(self.n_den), 1, bias=False)
+            # densityMode DensityLinear / DensityFourier: one row per function of the time basis (tensorf_dynamic.py:69-74, 122-124)
+            self.density_mode = net_cfg.get('densityMode', 'Density')
+            rows = 1
+            if self.density_mode != 'Density':
+                rows = time_basis_size(self.density_mode, frames_per_keyframe(net_cfg, {'num_frames': num_frames or 1, 'num_keyframes': num_keyframes}))
+            self.basis_mat_density = nn.Linear(sum(self.n_den), rows, bias=False)
         self.init_svd_volume(grid_size)
 
     def _dens(self, shape):
@@ -212,6 +218,8 @@ class HostTensorVM(nn.Module):
         owner = self._owner() if self._owner is not None else None
         if owner is None:
             raise RuntimeError('getDenseAlpha needs the owning HipLightfieldModel (its native handle)')
+        if getattr(self, 'density_mode', 'Density') != 'Density':
+            raise NotImplementedError(f'getDenseAlpha / updateAlphaMask with densityMode {self.density_mode}: the density modes are inference only')
         h = owner.native()
         n = [int(v) for v in grid_size]
         dev = self.aabb.device
@@ -357,9 +365,9 @@ class HostTensorVM(nn.Module):
 
 
 class HostColorModel(nn.Module):
-    def __init__(self, net_cfg, grid_size, num_keyframes):
+    def __init__(self, net_cfg, grid_size, num_keyframes, num_frames=None):
         super().__init__()
-        self.net = HostTensorVM(net_cfg, grid_size, num_keyframes)
+        self.net = HostTensorVM(net_cfg, grid_size, num_keyframes, num_frames)
 
     def set_iter(self, i):
         self.net.set_iter(i)
@@ -440,7 +448,7 @@ class HipLightfieldModel(nn.Module):
             grid = n_to_reso(net['N_voxel_init'], to_plain(net['aabb']))
         self.param = _Dummy()
         self.embedding_model = HostEmbedding(cfg, mlp_layer_shapes(cfg), self.dataset)
-        self.color_model = HostColorModel(net, grid, self.dataset['num_keyframes'])
+        self.color_model = HostColorModel(net, grid, self.dataset['num_keyframes'], self.dataset.get('num_frames'))
         self.color_model.net._owner = weakref.ref(self)
         self.cur_iter = None           # training iteration of the activation / PE schedules; None = converged (see set_iter)
         self._n = _Native()
@@ -628,6 +636,8 @@ class HipLightfieldModel(nn.Module):
         n.occ_key = None                       # a fresh handle holds no occupancy volume
         if getattr(hc, 'shade_mlp', None) is not None:         # MLP shading modes: the colour network's descriptor, before any upload
             _lib.call('hr_model_set_shading_mlp', h, C.byref(hc.shade_mlp))
+        if getattr(hc, 'time_decode', None) is not None:       # RGBt* / Density* modes: the time basis' descriptor, before any upload
+            _lib.call('hr_model_set_time_decode', h, C.byref(hc.time_decode))
         self._apply_options()
         if self._reserve:
             _lib.call('hr_model_reserve', h, self._reserve)
@@ -1032,6 +1042,8 @@ class HipLightfieldModel(nn.Module):
         mode = self.cfg['color']['net'].get('shadingMode', 'MLP_PE')
         if shading_mlp(self.cfg['color']['net']) is not None:
             raise NotImplementedError(f'training with shadingMode {mode}: the colour network is inference only')
+        if self.cfg['color']['net'].get('densityMode', 'Density') != 'Density':
+            raise NotImplementedError(f"training with densityMode {self.cfg['color']['net']['densityMode']}: the density modes are inference only")
         h, hc = self.native(values_travel=True), self._hc
         rays = self._check_rays(rays)
         net_cfg = self.cfg['color']['net']

@@ -38,7 +38,10 @@ ISECT = {'z_plane': 0, 'sphere': 1, 'cylinder': 2, 'sphere_new': 3, 'cylinder_ne
 ISECT_Z_CHANNELS = {0: 1, 1: 4, 2: 4, 3: 8, 4: 8, 5: 1, 6: 1, 7: 4}     # z_vals channels each type reads per sample
 CONTRACT = {'identity': 0, 'mipnerf': 1, 'bbox': 2, 'z_depth': 2, 'donerf': 3}   # bbox and z_depth share the affine kernel path
 DENSITY = {'relu': 0, 'softplus': 1, 'relu_abs': 2}
-SHADING = {'RGB': 0, 'SH': 1, 'MLP_Fea': 2, 'MLP': 3}
+SHADING = {'RGB': 0, 'SH': 1, 'MLP_Fea': 2, 'MLP': 3, 'RGBtLinear': 4, 'RGBtFourier': 5, 'RGBIdentity': 6}
+TIME_SHADING = ('RGBtLinear', 'RGBtFourier')          # the keyframe net's time-dependent colour (utils/tensorf_utils.py:351-400)
+DENSITY_MODE = {'Density': 0, 'DensityLinear': 1, 'DensityFourier': 2}      # HR_DENSITY_* (tensorf_utils.py:403-456)
+TIME_MAX_FPK = 8                          # include/hyperreel_hip.h: HR_TIME_MAX_FPK -- frames_per_keyframe the time kernel accepts
 MLP_SHADING = ('MLP_Fea', 'MLP')          # TensoRF's per-sample colour networks (tensorf_base.py:38-69, 106-135): inference only
 SHADE_MAX_PE, SHADE_MAX_C, SHADE_MAX_Z = 6, 256, 64        # csrc/hr_plan.h: HR_SHADE_MAX_*
 
@@ -65,6 +68,55 @@ def shading_mlp(net):
     if not 1 <= d.feature_c <= SHADE_MAX_C:
         raise NotImplementedError(f"shadingMode '{mode}': featureC {d.feature_c} outside 1..{SHADE_MAX_C}")
     return d
+
+
+class hr_time_decode(C.Structure):
+    """The time basis of an RGBt* / Density* model (include/hyperreel_hip.h); compile_config hands it on as hc.time_decode."""
+    _fields_ = [('density_mode', C.c_int32), ('frames_per_keyframe', C.c_int32), ('num_frames', C.c_int32)]
+
+
+def frames_per_keyframe(net, dataset):
+    """tensorf_dynamic.py:51-55: the net's own `frames_per_keyframe`, else num_frames // num_keyframes."""
+    if 'frames_per_keyframe' in net:
+        return int(net['frames_per_keyframe'])
+    return int(dataset['num_frames']) // max(int(dataset['num_keyframes']), 1)
+
+
+def time_basis_size(mode, fpk):
+    """nb of a Linear / Fourier mode: [1, t] or [t, cos x fpk, sin x fpk]."""
+    return 2 * fpk + 1 if mode.endswith('Fourier') else 2
+
+
+def time_decode(net, dataset):
+    """-> hr_time_decode of a colour net's YAML group, or None (no RGBt* shading and densityMode Density).  Refuses by name what the
+    reference cannot build and what the kernels do not cover."""
+    mode = net.get('shadingMode', 'MLP_PE')
+    dmode = net.get('densityMode', 'Density')
+    video = net['type'] == 'tensor_vm_split_time'
+    if dmode not in DENSITY_MODE:
+        raise NotImplementedError(f"densityMode '{dmode}' (Density, DensityLinear, DensityFourier)")
+    if mode == 'RGBIdentity':
+        if video:
+            raise NotImplementedError("shadingMode 'RGBIdentity' on tensor_vm_split_time: the reference cannot build it (init_one_svd's assertion)")
+        if int(net.get('data_dim_color', 27)) != 3:
+            raise NotImplementedError(f"shadingMode 'RGBIdentity' with data_dim_color {net.get('data_dim_color', 27)}: the three rows are the colour (3)")
+    if not video:
+        if mode in TIME_SHADING or dmode != 'Density':
+            raise NotImplementedError(f"shadingMode '{mode}' / densityMode '{dmode}' on the static net '{net['type']}': the time basis is the keyframe net's")
+        return None
+    if mode not in TIME_SHADING and dmode == 'Density':
+        return None
+    if dmode != 'Density' and mode in MLP_SHADING:
+        raise NotImplementedError(f"densityMode '{dmode}' together with the MLP shading mode '{mode}'")
+    fpk = frames_per_keyframe(net, dataset)
+    if not 1 <= fpk <= TIME_MAX_FPK:
+        raise NotImplementedError(f"frames_per_keyframe {fpk} outside 1..{TIME_MAX_FPK} (shadingMode '{mode}', densityMode '{dmode}')")
+    if mode in TIME_SHADING:
+        want, dim = 3 * time_basis_size(mode, fpk), int(net.get('data_dim_color', 27))
+        if dim != want:
+            raise NotImplementedError(f"shadingMode '{mode}' with data_dim_color {dim}: the reference builds basis_mat with 3 nb = {want} rows "
+                                      f"(frames_per_keyframe {fpk})")
+    return hr_time_decode(DENSITY_MODE[dmode], fpk, int(dataset['num_frames']))
 
 
 def shading_width(mode, d):
@@ -793,9 +845,14 @@ def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp
         raise NotImplementedError("shadingMode 'MLP_PE': the reference cannot run it (MLPRender_PE's first Linear expects more inputs than its "
                                   "forward concatenates)")
     if shading not in SHADING:
-        raise NotImplementedError(f"shadingMode '{shading}' is outside the hot-path scope (RGB, SH, MLP_Fea, MLP)")
+        raise NotImplementedError(f"shadingMode '{shading}' is outside the hot-path scope ({', '.join(SHADING)})")
     hc.shading = SHADING[shading]
     hc.shade_mlp = shading_mlp(n)             # None for RGB / SH; not part of hr_config: hr_model_set_shading_mlp takes it
+    hc.time_decode = time_decode(n, dataset)  # None without an RGBt* / Density* mode; hr_model_set_time_decode takes it
+    if (hc.time_decode is not None or shading == 'RGBIdentity') and not _coarse:
+        if is_cascade(cfg):
+            raise NotImplementedError(f"shadingMode '{shading}' / densityMode '{n.get('densityMode', 'Density')}' with a point_prediction cascade")
+        # ('auto', 'f16f8' and 'f16f8v' run f16x3 for the ray MLP of these models: hr_mlp_choice, csrc/hr_plan.h, decides that in one place)
     if hc.shade_mlp is not None and not _coarse:
         if hc.z_channels > SHADE_MAX_Z:
             raise NotImplementedError(f"shadingMode '{shading}' with z_channels {hc.z_channels} > {SHADE_MAX_Z}")
@@ -812,8 +869,6 @@ def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp
     hc.white_bg = int(bool(n.get('white_bg', 0)) and not bool(n.get('black_bg', 0)))
     hc.ray_dim = 8 if (hc.video or max_col > 6 or hc.advect or hc.color_table_views > 0) else 6   # camera id = rays[..., -2]
     if hc.video:
-        if n.get('densityMode', 'Density') != 'Density':
-            raise NotImplementedError(f"densityMode {n.get('densityMode')}")
         K, Fr = int(dataset['num_keyframes']), int(dataset['num_frames'])
         hc.num_keyframes = K
         hc.time_scale = float((Fr - 1) / Fr)  # tensorf_dynamic.py:58-59
@@ -855,6 +910,8 @@ def compile_cascade(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='f
     mode = cfg['color']['net'].get('shadingMode', 'MLP_PE')
     if mode in MLP_SHADING:
         raise NotImplementedError(f"shadingMode '{mode}' with a point_prediction cascade")
+    if mode in TIME_SHADING or mode == 'RGBIdentity' or cfg['color']['net'].get('densityMode', 'Density') != 'Density':
+        raise NotImplementedError(f"shadingMode '{mode}' / densityMode '{cfg['color']['net'].get('densityMode', 'Density')}' with a point_prediction cascade")
     items = list(cfg['embedding']['embeddings'].items())
     types = [e['type'] for _, e in items]
     ip = types.index('point_prediction')
@@ -945,6 +1002,9 @@ def upload_names(hc, coarse=None):
             for j in range(3):
                 names.append((f'{what}_{kind}.{j}', f'color_model.net.{what}_{kind}.{j}'))
     names.append(('basis_mat.weight', 'color_model.net.basis_mat.weight'))
+    td = getattr(hc, 'time_decode', None)
+    if td is not None and td.density_mode != 0:             # DensityLinear / DensityFourier: (nb, sum n_lamb_sigma)
+        names.append(('basis_mat_density.weight', 'color_model.net.basis_mat_density.weight'))
     if getattr(hc, 'shade_mlp', None) is not None:          # MLPRender_Fea / MLPRender: Sequential indices 0, 2, 4
         for i in (0, 2, 4):
             for what in ('weight', 'bias'):

@@ -217,6 +217,14 @@ def make_state_dict(cfg, dataset, grid_size=None, seed=0, density='dense', app_s
             b = 1.0 / math.sqrt(n_in)
             sd[f'{NET}renderModule.mlp.{i}.weight'] = _uniform(rng, (o, n_in), b * (4.0 if i == 4 else 1.0))
             sd[f'{NET}renderModule.mlp.{i}.bias'] = _uniform(rng, (o,), b) if i != 4 else np.zeros((o,), np.float32)
+    # densityMode DensityLinear / DensityFourier: basis_mat_density has one row per function of the time basis (tensorf_dynamic.py:69-74,
+    # 122-124).  Drawn LAST, over the one-row tensor every keyframe scene carries, so that every other tensor of a seed is what it was.
+    # (The RGBt* colour modes need nothing here: basis_mat is drawn above with data_dim_color = 3 nb rows.)
+    dmode = net.get('densityMode', 'Density')
+    if video and dmode != 'Density':
+        from .plan import frames_per_keyframe, time_basis_size
+        rows = time_basis_size(dmode, frames_per_keyframe(net, dataset))
+        sd[NET + 'basis_mat_density.weight'] = _uniform(rng, (rows, sum(nd)), 1.0 / math.sqrt(max(sum(nd), 1)))
     return sd
 
 

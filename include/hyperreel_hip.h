@@ -107,7 +107,10 @@ enum { HR_DENSITY_RELU = 0, HR_DENSITY_SOFTPLUS = 1, HR_DENSITY_RELU_ABS = 2 };
 enum { HR_SHADING_RGB = 0, HR_SHADING_SH = 1,
        /* TensoRF's per-sample colour networks (nlf/nets/tensorf_base.py:38-69 MLPRender_Fea, :106-135 MLPRender): inference only; the
         * network is described by hr_model_set_shading_mlp (below), app_dim is 27 */
-       HR_SHADING_MLP_FEA = 2, HR_SHADING_MLP = 3 };
+       HR_SHADING_MLP_FEA = 2, HR_SHADING_MLP = 3,
+       /* the keyframe net's time-dependent colour (utils/tensorf_utils.py:346-400): the appearance features are coefficients of a
+        * per-ray time basis, described by hr_model_set_time_decode (below); app_dim is 3 nb (RGBT_*) or 3 (RGB_IDENTITY: |x + 0.5|) */
+       HR_SHADING_RGBT_LINEAR = 4, HR_SHADING_RGBT_FOURIER = 5, HR_SHADING_RGB_IDENTITY = 6 };
 /* arithmetic of the MLP GEMMs: exact fp32 MFMA, or three 16-bit MFMA products of the hi/lo split operands with fp32
  * accumulation (needs mlp_hidden 256): bf16 halves (~2^-17 relative per product, fp32 range) or fp16 halves (~2^-22,
  * i.e. fp32-grade, but activations must stay below 65504); F16X2 additionally takes the weights as single halfs (two
@@ -216,7 +219,7 @@ typedef struct hr_config {
     int32_t grid[3];                     /* gridSize [Nx,Ny,Nz] */
     int32_t num_keyframes;               /* K (video) */
     int32_t n_den[3], n_app[3];          /* n_lamb_sigma, n_lamb_sh */
-    int32_t app_dim;                     /* 3 (RGB) or 27 (SH degree 2) */
+    int32_t app_dim;                     /* 3 (RGB, RGB_IDENTITY), 27 (SH degree 2, MLP_*) or 3 nb (RGBT_*) */
     int32_t shading;                     /* HR_SHADING_* */
     float distance_scale;
     float weight_thresh;                 /* rm_weight_mask_thre */
@@ -1108,6 +1111,32 @@ typedef struct hr_shading_mlp {
 } hr_shading_mlp;
 int hr_model_set_shading_mlp(hr_model* m, const hr_shading_mlp* desc);
 int hr_stage_shade(hr_model* m, const float* feat_dev, const float* viewdirs_dev, int64_t n, float* rgb_dev, void* stream);
+
+/* Time-dependent colour of a keyframe net (`shadingMode: RGBtLinear | RGBtFourier`, utils/tensorf_utils.py:351-400) and `RGBIdentity`
+ * (:346-348) of a static net.  The appearance features after basis_mat are the coefficients of a per-ray basis of nb functions,
+ *   RGBT_LINEAR   [1, t]                                              nb = 2
+ *   RGBT_FOURIER  [t, cos(2 pi f s) f = 0 .. fpk-1, sin(2 pi f s) ..]   nb = 2 fpk + 1,  s = time_offset * num_keyframes * (num_frames - 1) / num_frames
+ * with t the ray's time (its last column) and time_offset its distance to the keyframe before it; colour c = relu(sum_j basis_j *
+ * feature[c * nb + j] + 0.5), app_dim = 3 nb.  RGB_IDENTITY: colour c = |feature[c] + 0.5|, app_dim = 3, no descriptor.
+ * `densityMode: DensityLinear | DensityFourier` (:407-456): the density before its activation is sum_j basis_j * feature_d[j], with
+ * feature_d = basis_mat_density . (the density components) and the same bases; any of HR_SHADING_RGB / SH / RGBT_* beside it.
+ * hr_model_set_time_decode: between hr_model_create and the first upload (HR_E_STATE later) of a keyframe model with an
+ * HR_SHADING_RGBT_* shading or a density mode.  HR_E_INVALID, naming it: a static net or a cascade, neither an RGBT shading nor a
+ * density mode, frames_per_keyframe outside 1..HR_TIME_MAX_FPK, an app_dim that is not 3 nb, a density mode beside an MLP shading
+ * mode, or a density row that does not fit the workgroup's LDS.  With a density mode hr_model_upload then takes
+ * `basis_mat_density.weight` (nb, sum n_den).  hr_model_finalize returns HR_E_STATE, naming the call, for an RGBT model without it.
+ * Such a model renders through every hr_render* entry point (its own sample kernel; never the frame kernel or the
+ * verified fast path: HR_MLP_AUTO / F16F8 / F16F8V run f16x3).  The hr_train_* entry points differentiate the three colour modes
+ * (their own build of the training kernels, the deterministic one included); with a density mode they, and hr_dense_alpha, return
+ * HR_E_INVALID naming it.  Additive: no existing struct or signature moved. */
+#define HR_TIME_MAX_FPK 8
+enum { HR_DENSITY_PLAIN = 0, HR_DENSITY_LINEAR = 1, HR_DENSITY_FOURIER = 2 };
+typedef struct hr_time_decode {
+    int32_t density_mode;                /* HR_DENSITY_* */
+    int32_t frames_per_keyframe;         /* net.frames_per_keyframe, else num_frames // num_keyframes (tensorf_dynamic.py:51-55) */
+    int32_t num_frames;                  /* dataset.num_frames */
+} hr_time_decode;
+int hr_model_set_time_decode(hr_model* m, const hr_time_decode* desc);
 
 /* Profiling aid: runs the MLP stage with a per-wave phase timeline.  trace_dev receives 64
  * s_memtime stamps per wave (4 waves per workgroup, workgroups of 64 or 128 rays); only the
