@@ -150,12 +150,12 @@ int build_mlp_state(hr_model* m, const float* rays_dev, int64_t n, hipStream_t s
     s.band = cur.band;
     s.vinfo.fallback = cur.vinfo.fallback;       // (calibrate_band keeps the reason while the fast path stays off)
     const bool level = m->coarse || m->is_coarse, supported = hr_mlp_range_supported(c);
-    const bool time_density = hr_model_time_density(m);
-    HrMlpChoice ch = hr_mlp_choice(c, level, supported, s.act_max, time_density);
+    const HrSampleKind kind = hr_model_sample_kind(m);
+    HrMlpChoice ch = hr_mlp_choice(c, kind, level, supported, s.act_max);
     if (ch.status == HR_OK && ch.needs_calibration) {
         const int rc = measure_range(m, rays_dev, n, st, s);
         if (rc != HR_OK) return rc;
-        ch = hr_mlp_choice(c, level, supported, s.act_max, time_density);
+        ch = hr_mlp_choice(c, kind, level, supported, s.act_max);
     }
     if (ch.status == HR_E_RANGE) {
         const int want = c.mlp_precision;
@@ -324,7 +324,7 @@ int calibrate_band(hr_model* m, hipStream_t st)
             for (int64_t r0 = 0; r0 < nu; r0 += m->chunk) {
                 const int64_t n = (nu - r0 < m->chunk) ? (nu - r0) : m->chunk;
                 const float* rays = sel + r0 * c.ray_dim;
-                launch_front(m, rays, n, st, -1, 1);
+                launch_front(m, rays, n, st, 1);
                 HrSampleArgs sa;
                 fill_sample_args(m, sa, rays, n, rgb2 + r0 * 3);
                 hr_launch_samples(m->kcfg, sa, st);

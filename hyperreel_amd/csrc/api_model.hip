@@ -226,7 +226,7 @@ int hr_model_set_time_decode(hr_model* m, const hr_time_decode* d)
     m->expect.erase(DENSITY_BASIS);
     if (d->density_mode != HR_DENSITY_PLAIN) {
         size_t lds = 0;
-        if (hr_time_lds_refused(c, m->p_live, &lds))
+        if (hr_sample_lds_refused(c, m->p_live, HR_SAMPLE_TIME_DENSITY, &lds))
             return fail(HR_E_INVALID, "z_channels %d x %d head columns with a density row need %zu bytes of LDS per workgroup (160 KiB available)", c.z_channels, m->p_live, lds);
         const int nb = hr_time_nb(d->density_mode == HR_DENSITY_FOURIER, d->frames_per_keyframe);
         m->expect[DENSITY_BASIS] = sizeof(float) * (size_t)nb * (c.n_den[0] + c.n_den[1] + c.n_den[2]);
@@ -246,8 +246,8 @@ static int pack_density_basis(hr_model* m)
     if (!w.empty()) HR_HIP(hipMemcpy(w.data(), m->raw[DENSITY_BASIS].p, w.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (int col = 0; col < n_cols; ++col)
         for (int r = 0; r < nb; ++r) wt[(size_t)col * ld + r] = w[(size_t)r * n_cols + col];
-    // the plan the launches will take (hr_time_plan: the class does not depend on the ray count or on hr_render_frame's line form)
-    const HrTimePlan T = hr_time_plan(m->kcfg, m->planes, m->ca_total, hr_head_quads(c, m->p_live), rows_per_ray(c), 1, true);
+    // the plan the launches will take (the class does not depend on the ray count or on hr_render_frame's line form)
+    const HrSampleFormPlan T = hr_sample_form_plan(m->kcfg, m->planes, m->ca_total, hr_head_quads(c, m->p_live), rows_per_ray(c), 1, false, {HR_SAMPLE_TIME_DENSITY, true, false});
     std::vector<int> sc((size_t)T.d_slots, -1);
     int slot = 0, col0 = 0;
     for (int j = 0; j < 3; ++j) {       // density slot order: plane pair after plane pair, 4 cd4 each (the classes: row 0 of the matrix-shaped block)
@@ -642,7 +642,7 @@ int hr_model_get_option(hr_model* m, int32_t option, int32_t* value)
         }
     } else if (option == HR_OPT_FRAME_KERNEL_ACTIVE) {
         if (!m->finalized) return fail(HR_E_STATE, "hr_model_finalize has not been called");
-        *value = launch_frame(m, nullptr, 64, nullptr, true, nullptr) ? 1 : 0;
+        *value = hr_render_route(render_route_facts(m, 64, false, false)).route == HR_ROUTE_FRAME ? 1 : 0;
     } else return fail(HR_E_INVALID, "unknown option %d", option);
     return HR_OK;
 }

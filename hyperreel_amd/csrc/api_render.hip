@@ -115,6 +115,28 @@ static void fill_shade_args(const hr_model* m, HrShadeArgs& a, const float* feat
     for (int l = 0; l < 3; ++l) { a.wpack[l] = m->shade_w[l]; a.bias[l] = m->shade_b[l]; }
 }
 
+static void fill_time_io(const hr_model* m, HrTimeIO& io, bool density)
+{
+    io = HrTimeIO();
+    io.fpk = m->time_set ? m->time_desc.frames_per_keyframe : 1;
+    io.fac = m->time_set ? hr_time_scale(m->cfg.num_keyframes, m->time_desc.num_frames) : 0.0f;
+    io.c_fourier = m->cfg.shading == HR_SHADING_RGBT_FOURIER;
+    if (!density) return;
+    io.d_fourier = m->time_desc.density_mode == HR_DENSITY_FOURIER;
+    io.dbasis_t = m->dbasis_t, io.dslot_col = m->dslot_col;
+    io.d_ld = m->d_ld, io.d_slots = m->d_slots;
+}
+
+// the caller's maps (NULL: none) from the launch's first ray r0 on
+static hr_maps maps_from(const hr_maps* maps, int64_t r0)
+{
+    hr_maps mp = maps ? *maps : hr_maps();
+    if (mp.distances_dev) mp.distances_dev += r0;
+    if (mp.points_dev) mp.points_dev += r0 * 3;
+    if (mp.acc_dev) mp.acc_dev += r0;
+    return mp;
+}
+
 // Cascade, everything before the final sample kernel: coarse MLP -> coarse intersect (emits the point MLP's input
 // rows, one per coarse sample) -> point MLP over n * casc_in_z rows.  Leaves the fine head in m->head.
 static void launch_cascade_front(hr_model* m, const float* rays, int64_t n, hipStream_t st)
@@ -137,9 +159,8 @@ static void launch_cascade_front(hr_model* m, const float* rays, int64_t n, hipS
     launch_mlp(m, kc, mb, st);
 }
 
-// redo0 >= 0: first pass of the verified fast path -- tiles that raise a range bit list their rays (indices start at redo0);
-// safe: the whole launch with the f16x3 tiles (hr_render_fields with diagnostics: one arithmetic for every output)
-void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int64_t redo0, int tier)
+// The MLP stage of a chunked launch (tier 1: the whole launch with the f16x3 tiles -- one arithmetic for every output)
+void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int tier)
 {
     if (m->coarse) {
         launch_cascade_front(m, rays, n, st);
@@ -147,28 +168,26 @@ void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int
     }
     HrMlpArgs ma;
     fill_mlp_args(m, ma, rays, n, tier);
-    if (redo0 >= 0) {
-        ma.ray0 = redo0;
-        ma.redo_list = m->redo_list;
-        ma.redo_count = m->redo_count;
-        ma.redo_cap = m->redo_cap;
-    }
     launch_mlp(m, m->kcfg, ma, st, tier);
 }
 
-// The frame kernel (fused_impl.inc) for the whole ray list; false: hr_frame_plan says the call does not fit it (nothing launched)
-bool launch_frame(hr_model* m, const float* rays, int64_t n, float* rgb, bool probe, hipStream_t st)
+// What hr_render_route decides a call of n rays by, as the model stands (`capturing` is the caller's to ask); *frame: the frame kernel's plan
+HrRouteIn render_route_facts(const hr_model* m, int64_t n, bool fields, bool maps, HrFramePlan* frame)
 {
-    if (hr_shading_is_mlp(m->cfg.shading)) return false;      // the colour network is no part of the frame kernel: the chunked plan (launch_samples)
-    if (hr_model_time_kernel(m)) return false;                // nor are the time-dependent decode modes: their own sample kernel
     const int prec = m->mlp.active_precision, L = m->cfg.mlp_layers;
     const bool split = prec == HR_MLP_BF16X3 || prec == HR_MLP_F16X3 || prec == HR_MLP_F16X2 || prec == HR_MLP_F16F8;      // their elements: 16 bits (HrMlpTiles::wsplit)
     const HrFramePlanIn in = {n, m->opt_frame_kernel, m->opt_sample_waves, m->coarse || m->is_coarse, m->mlp.verified != 0, split, sizeof(uint16_t),
                               (m->mlp.pack->n_out + 3) / 4, m->mlp.pack->k0p, L > 0 ? m->mlp.pack->tiles[0].n_tiles[L - 1] : 0, m->n_cus};
     const HrGridPlane planes[3] = {render_plane(m, 0), render_plane(m, 1), render_plane(m, 2)};
     const HrFramePlan P = hr_frame_plan(m->kcfg, planes, m->ca_total, in);
-    if (!P.fits) return false;
-    if (probe || n <= 0) return true;
+    if (frame) *frame = P;
+    return {n, fields, maps, hr_model_sample_kind(m), m->mlp.verified != 0, (bool)m->occ, m->mlp.band_stale, false, P.fits != 0};
+}
+
+// The frame kernel (fused_impl.inc) of plan P for the whole ray list; false: the runtime refused the kernel's LDS request (nothing launched)
+static bool launch_frame(hr_model* m, const HrFramePlan& P, const float* rays, int64_t n, float* rgb, hipStream_t st)
+{
+    const int prec = m->mlp.active_precision;
     HrMlpArgs ma;
     fill_mlp_args(m, ma, rays, n);
     ma.head = nullptr;
@@ -188,56 +207,35 @@ static int check_render(const hr_model* m, const float* rays, int64_t n, const f
     return HR_OK;
 }
 
-// The sample stage of one launch: the plain kernel, or with `maps` (hr_render_maps: non-NULL, some pointer set) the kernel that also
-// writes the per-ray maps.  r0: the launch's first ray in the caller's buffers, as args.rgb is offset (0 for the list-driven passes,
-// whose rays are indices into the whole call)
-// false: the runtime refused a kernel's LDS request (an MLP shading mode's shading kernel; the launch's pixels are not written)
+// The sample stage of one launch, by the model's kind (hr_plan.h: the launchers plan their form with hr_sample_form_plan).  maps: hr_render_maps' (non-NULL:
+// some pointer set).  r0: the launch's first ray in the caller's buffers, as args.rgb is offset (0 for the list-driven passes, whose rays are indices into the call)
+// false: the launch's pixels are not written (SHADE: the shading kernel's LDS request was refused; TIME_DENSITY: the density row's table was made for another plan)
 static bool launch_samples(const hr_model* m, const HrSampleArgs& sa, const hr_maps* maps, int64_t r0, hipStream_t st)
 {
-    const bool shade = hr_shading_is_mlp(m->cfg.shading);
-    if (hr_model_time_kernel(m)) {              // time-dependent decode modes: one kernel for image, maps and diagnostics
-        hr_maps mp = hr_maps();
-        if (maps) mp = *maps;
-        if (mp.distances_dev) mp.distances_dev += r0;
-        if (mp.points_dev) mp.points_dev += r0 * 3;
-        if (mp.acc_dev) mp.acc_dev += r0;
-        HrTimeIO io = HrTimeIO();
-        const bool density = hr_model_time_density(m);
-        io.fpk = m->time_set ? m->time_desc.frames_per_keyframe : 1;
-        io.fac = m->time_set ? hr_time_scale(m->cfg.num_keyframes, m->time_desc.num_frames) : 0.0f;
-        io.c_fourier = m->cfg.shading == HR_SHADING_RGBT_FOURIER;
-        if (density) {
-            io.d_fourier = m->time_desc.density_mode == HR_DENSITY_FOURIER;
-            io.dbasis_t = m->dbasis_t;
-            io.dslot_col = m->dslot_col;
-            io.d_ld = m->d_ld;
-            io.d_slots = m->d_slots;
+    const hr_maps mp = maps_from(maps, r0);
+    switch (const HrSampleKind kind = hr_model_sample_kind(m)) {
+        case HR_SAMPLE_DECODE:
+            if (maps) hr_launch_samples_maps(m->kcfg, sa, mp, st);
+            else hr_launch_samples(m->kcfg, sa, st);
+            return true;
+        case HR_SAMPLE_SHADE: {     // the chunk's samples exported, shaded by the colour network, composited by the import form
+            HrSampleArgs ex = sa;
+            ex.fields = hr_fields();                    // diagnostics are the import form's
+            hr_launch_samples_shade_export(m->kcfg, ex, m->shade_rows, st);
+            HrShadeArgs ha;
+            fill_shade_args(m, ha, m->shade_rows, HR_SHADE_ROW, m->shade_rows + HR_SHADE_FEAT, HR_SHADE_ROW, sa.n_rays * m->cfg.z_channels, m->shade_rgb);
+            ha.live_col = HR_SHADE_FEAT + 3;
+            if (!hr_launch_shade(ha, st)) return false;
+            hr_launch_samples_shade_import(m->kcfg, sa, mp, m->shade_rows, m->shade_rgb, st);
+            return true;
         }
-        return hr_launch_samples_time(m->kcfg, sa, mp, io, density, st);
+        case HR_SAMPLE_TIME:
+        case HR_SAMPLE_TIME_DENSITY:        // one kernel for image, maps and diagnostics
+            HrTimeIO io;
+            fill_time_io(m, io, kind == HR_SAMPLE_TIME_DENSITY);
+            return (kind == HR_SAMPLE_TIME_DENSITY ? hr_launch_samples_time_density : hr_launch_samples_time)(m->kcfg, sa, mp, io, st);
     }
-    if (!maps && !shade) {
-        hr_launch_samples(m->kcfg, sa, st);
-        return true;
-    }
-    hr_maps mp = hr_maps();
-    if (maps) mp = *maps;
-    if (mp.distances_dev) mp.distances_dev += r0;
-    if (mp.points_dev) mp.points_dev += r0 * 3;
-    if (mp.acc_dev) mp.acc_dev += r0;
-    if (!shade) {
-        hr_launch_samples_maps(m->kcfg, sa, mp, st);
-        return true;
-    }
-    // MLP shading modes: the chunk's samples exported, shaded by the colour network, composited by the import form
-    HrSampleArgs ex = sa;
-    ex.fields = hr_fields();                    // diagnostics are the import form's
-    hr_launch_samples_shade_export(m->kcfg, ex, m->shade_rows, st);
-    HrShadeArgs ha;
-    fill_shade_args(m, ha, m->shade_rows, HR_SHADE_ROW, m->shade_rows + HR_SHADE_FEAT, HR_SHADE_ROW, sa.n_rays * m->cfg.z_channels, m->shade_rgb);
-    ha.live_col = HR_SHADE_FEAT + 3;
-    if (!hr_launch_shade(ha, st)) return false;
-    hr_launch_samples_shade_import(m->kcfg, sa, mp, m->shade_rows, m->shade_rgb, st);
-    return true;
+    return false;
 }
 
 // The verified fast path over one call's rays: first pass in f16f8 with the rays at risk listed on the device, then the list
@@ -319,53 +317,52 @@ static int render_impl(hr_model* m, const float* rays_dev, int64_t n_rays, float
     if (maps && !maps->distances_dev && !maps->points_dev && !maps->acc_dev) maps = nullptr;
     const hr_config& c = m->cfg;
     const int Z = c.z_channels;
-    if (!fields && !maps && launch_frame(m, rays_dev, n_rays, rgb_dev, false, st)) {
-        HR_HIP(hipGetLastError());
-        return HR_OK;
-    }
-    // (Running the sample stage of chunk i on a second stream under the MLP of chunk i+1 was
-    //  measured twice -- plain, and with the MLP limited to one workgroup per CU so that sample
-    //  blocks could co-reside -- and is slower than back-to-back launches: 3.0-3.9 vs 2.79 ms per
-    //  800x800 frame; the two kernels do not interleave on the CUs.)
-    // verified fast path.  With diagnostics requested every output comes from ONE arithmetic: the f16x3 tiles throughout.
-    // So does a model with an occupancy volume (hr_occupancy_test decides per cell from a head-dependent point; the band does not cover it),
-    // and a render inside a stream capture whose band is out of date (hr_model_update_config since the last measurement: measuring synchronises).
-    bool verify = m->mlp.verified && !fields && !m->occ && n_rays < ((int64_t)1 << 31) && !hr_shading_is_mlp(c.shading) && !hr_model_time_kernel(m);
-    if (verify && m->mlp.band_stale) {
+    // the plan the call takes: hr_render_route (whether the stream is being captured matters to a verified model with a stale band alone)
+    HrFramePlan frame;
+    HrRouteIn in = render_route_facts(m, n_rays, fields != nullptr, maps != nullptr, &frame);
+    if (in.mlp_verified && in.band_stale) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-        if (cs == hipStreamCaptureStatusNone) {
-            rc = calibrate_band(m, st);
-            if (rc != HR_OK) return rc;
-            verify = verify && m->mlp.verified;            // HR_MLP_AUTO may just have given the fast path up
-        } else {
-            verify = false;
-        }
+        in.capturing = cs != hipStreamCaptureStatusNone;
     }
-    if (verify && n_rays > 0) {
-        render_verified(m, m->mlp.band, rays_dev, n_rays, rgb_dev, hr_redo_list_cap(n_rays, m->redo_cap), st, maps);
-        HR_HIP(hipGetLastError());
-        return HR_OK;
+    HrRenderRoute route = hr_render_route(in);
+    if (route.calibrate_first) {
+        rc = calibrate_band(m, st);
+        if (rc != HR_OK) return rc;
+        in.mlp_verified = m->mlp.verified != 0, in.band_stale = m->mlp.band_stale;      // HR_MLP_AUTO may just have given the fast path up
+        route = hr_render_route(in);
     }
-    const bool safe_all = m->mlp.verified != 0;
-    const int64_t per = hr_even_chunk(m->chunk, n_rays);
-    for (int64_t r0 = 0; r0 < n_rays; r0 += per) {
-        const int64_t n = (n_rays - r0 < per) ? (n_rays - r0) : per;
-        const float* rays = rays_dev + r0 * c.ray_dim;
-        launch_front(m, rays, n, st, -1, safe_all ? 1 : 0);
-        HrSampleArgs sa;
-        fill_sample_args(m, sa, rays, n, rgb_dev + r0 * 3);
-        if (fields) {
-            if (fields->distances_dev) sa.fields.distances_dev = fields->distances_dev + r0 * Z;
-            if (fields->points_dev) sa.fields.points_dev = fields->points_dev + r0 * Z * 3;
-            if (fields->sigma_dev) sa.fields.sigma_dev = fields->sigma_dev + r0 * Z;
-            if (fields->weights_dev) sa.fields.weights_dev = fields->weights_dev + r0 * Z;
-            if (fields->head_dev)
-                hr_launch_head_export(m->head, fields->head_dev + r0 * (int64_t)Z * c.preds_per_z, n, Z, c.preds_per_z, m->p_live,
-                                      (m->mlp.pack->n_out + 3) / 4, rows_per_ray(c), m->col_map, st);
+    switch (route.route) {
+        case HR_ROUTE_VERIFIED:
+            render_verified(m, m->mlp.band, rays_dev, n_rays, rgb_dev, hr_redo_list_cap(n_rays, m->redo_cap), st, maps);
+            break;
+        case HR_ROUTE_FRAME:
+            if (n_rays <= 0 || launch_frame(m, frame, rays_dev, n_rays, rgb_dev, st)) break;
+            [[fallthrough]];                               // the runtime refused the frame kernel's LDS request: launch by launch
+        case HR_ROUTE_CHUNKED: {
+            // (the sample stage of chunk i on a second stream under the MLP of chunk i + 1 is slower than back-to-back launches, 3.0-3.9
+            //  vs 2.79 ms per 800x800 frame: the two kernels do not interleave on the CUs -- DESIGN 10)
+            const int64_t per = hr_even_chunk(m->chunk, n_rays);
+            for (int64_t r0 = 0; r0 < n_rays; r0 += per) {
+                const int64_t n = (n_rays - r0 < per) ? (n_rays - r0) : per;
+                const float* rays = rays_dev + r0 * c.ray_dim;
+                launch_front(m, rays, n, st, route.tier);
+                HrSampleArgs sa;
+                fill_sample_args(m, sa, rays, n, rgb_dev + r0 * 3);
+                if (fields) {
+                    if (fields->distances_dev) sa.fields.distances_dev = fields->distances_dev + r0 * Z;
+                    if (fields->points_dev) sa.fields.points_dev = fields->points_dev + r0 * Z * 3;
+                    if (fields->sigma_dev) sa.fields.sigma_dev = fields->sigma_dev + r0 * Z;
+                    if (fields->weights_dev) sa.fields.weights_dev = fields->weights_dev + r0 * Z;
+                    if (fields->head_dev)
+                        hr_launch_head_export(m->head, fields->head_dev + r0 * (int64_t)Z * c.preds_per_z, n, Z, c.preds_per_z, m->p_live,
+                                              (m->mlp.pack->n_out + 3) / 4, rows_per_ray(c), m->col_map, st);
+                }
+                if (!launch_samples(m, sa, maps, r0, st))
+                    return fail(HR_E_HIP, hr_model_time_kernel(m) ? "the density row's table does not fit the launch's plan" : "the shading kernel's LDS request was refused");
+            }
+            break;
         }
-        if (!launch_samples(m, sa, maps, r0, st))
-            return fail(HR_E_HIP, hr_model_time_kernel(m) ? "the density row's table does not fit the launch's plan" : "the shading kernel's LDS request was refused");
     }
     HR_HIP(hipGetLastError());
     return HR_OK;

@@ -185,10 +185,10 @@ struct HrTimeIO {
     int fpk;                // frames_per_keyframe
     float fac;              // hr_time_scale(num_keyframes, num_frames)
 };
-// the sample stage of a model with a time-dependent colour or density mode, or RGBIdentity: image, per-ray maps (all pointers NULL when
-// none is asked for) and diagnostics in one kernel; density: a density mode (the density row and its LDS; io.d_slots: the floats per ray
-// the caller's dslot_col was made for).  false: that table does not fit the launch's plan (nothing launched)
-bool hr_launch_samples_time(const hr_config& cfg, const HrSampleArgs& args, const hr_maps& maps, const HrTimeIO& io, bool density, hipStream_t stream);
+// the sample stage of a model with a time-dependent colour or density mode, or RGBIdentity: image, per-ray maps (all pointers NULL when none is asked for) and diagnostics in
+// one kernel; _density: with a density mode (io.d_slots: the floats per ray the caller's dslot_col was made for).  false: that table does not fit the launch's plan (nothing launched)
+bool hr_launch_samples_time(const hr_config& cfg, const HrSampleArgs& args, const hr_maps& maps, const HrTimeIO& io, hipStream_t stream);
+bool hr_launch_samples_time_density(const hr_config& cfg, const HrSampleArgs& args, const hr_maps& maps, const HrTimeIO& io, hipStream_t stream);
 
 // training forward (mlp_split_impl.inc, HR_SPLIT_TRAIN_KERNEL): where the output of hidden Linear l (after its LeakyReLU) goes besides LDS --
 // act[l] + ray * ld[l] + off[l] + feature, fp32 (NULL: not kept)

@@ -184,9 +184,10 @@ struct HR_HIDDEN hr_model {
     int d_ld = 0, d_slots = 0;
 };
 
-// the model renders with sample_time_kernel.hip's kernel: a time-dependent colour mode, RGBIdentity, or a density mode
-inline bool hr_model_time_density(const hr_model* m) { return m->time_set && m->time_desc.density_mode != HR_DENSITY_PLAIN; }
-inline bool hr_model_time_kernel(const hr_model* m) { return hr_shading_is_time_family(m->cfg.shading) || hr_model_time_density(m); }
+// the model's sample stage (hr_plan.h); time kernel: sample_time_kernel.hip's -- a time-dependent colour mode, RGBIdentity, or a density mode
+inline HrSampleKind hr_model_sample_kind(const hr_model* m) { return hr_sample_kind(m->cfg.shading, m->time_set && m->time_desc.density_mode != HR_DENSITY_PLAIN); }
+inline bool hr_model_time_density(const hr_model* m) { return hr_model_sample_kind(m) == HR_SAMPLE_TIME_DENSITY; }
+inline bool hr_model_time_kernel(const hr_model* m) { return hr_model_sample_kind(m) == HR_SAMPLE_TIME || hr_model_time_density(m); }
 
 // a ray with a live sample beyond it (60 degrees off a plane's normal; a sphere nearly tangent) is not what the margins of the verified fast
 // path are measured on -- its errors are the geometry's, the MLP's two-plane / Pluecker inputs included -- and is always listed
@@ -201,8 +202,8 @@ HR_HIDDEN int calibrate_band(hr_model* m, hipStream_t st);
 HR_HIDDEN void launch_mlp(const hr_model* m, const hr_config& c, const HrMlpArgs& a, hipStream_t st, int tier = 0);
 HR_HIDDEN void fill_mlp_args(const hr_model* m, HrMlpArgs& a, const float* rays, int64_t n, int tier = 0);
 HR_HIDDEN void fill_sample_args(const hr_model* m, HrSampleArgs& a, const float* rays, int64_t n, float* rgb);
-HR_HIDDEN void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int64_t redo0 = -1, int tier = 0);
-HR_HIDDEN bool launch_frame(hr_model* m, const float* rays, int64_t n, float* rgb, bool probe, hipStream_t st);
+HR_HIDDEN void launch_front(hr_model* m, const float* rays, int64_t n, hipStream_t st, int tier = 0);
+HR_HIDDEN HrRouteIn render_route_facts(const hr_model* m, int64_t n, bool fields, bool maps, HrFramePlan* frame = nullptr);
 HR_HIDDEN void render_verified(hr_model* m, const HrBand& band, const float* rays_dev, int64_t n_rays, float* rgb_dev, int list_cap, hipStream_t st,
                                const hr_maps* maps = nullptr);
 

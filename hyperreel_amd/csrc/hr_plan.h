@@ -1,5 +1,5 @@
 // Host-side decisions shared by hr_model_create / finalize, the render launchers and the training launcher: plane-pair geometry, plane
-// class, the render call's launch plans (live head columns, launch sizing, the sample kernel, the frame kernel, a frame's time tap),
+// class, the render call's launch plans (live head columns, launch sizing, the sample stage in every form, the frame kernel, the route, a frame's time tap),
 // the training step's launch plan, the MLP's arithmetic (which one, whether verified, the margins' rules).  Plain C++ (no HIP types, no
 // hr_model, no getenv); the CPU suite compiles it as it is (tests/host_math/hr_plan_host.cpp).
 #ifndef HR_PLAN_H
@@ -216,20 +216,17 @@ static inline size_t hr_sample_lds_bytes(int nq, int ca_total, int ZP, int rows_
 }
 
 #define HR_LDS_PER_WORKGROUP ((size_t)160 * 1024)
-// true: hr_model_create refuses a level of configuration c with p_live live head columns; *bytes: the sample kernel's request.
-// The margin set aside next to it: 4096 bytes for the kernel's static words (the ray records, hr_gather_ones) and the 256-float
-// cross-wave scratch, reserved for every sample count although hr_sample_lds_bytes asks for it only above 64 samples -- the bound has
-// always counted it, and the set of accepted configurations stays what it was.
-static inline bool hr_sample_lds_refused(const hr_config& c, int p_live, size_t* bytes)
+// The kind of a model's sample stage: its kernels (hr_sample_form_plan, below); the frame kernel and verification are DECODE's alone (hr_render_route, hr_mlp_choice)
+enum HrSampleKind {
+    HR_SAMPLE_DECODE = 0,        // RGB / SH through basis_mat: hr_sample_kernel, hr_sample_maps_kernel
+    HR_SAMPLE_SHADE,             // MLP_Fea / MLP: export form, colour network, import form
+    HR_SAMPLE_TIME,              // RGBtLinear / RGBtFourier / RGBIdentity with the plain density: hr_sample_time_kernel, TD 1
+    HR_SAMPLE_TIME_DENSITY       // a density mode under any shading hr_model_set_time_decode admits it with: TD 3
+};
+static inline bool hr_shading_is_mlp(int shading) { return shading == HR_SHADING_MLP_FEA || shading == HR_SHADING_MLP; }
+static inline HrSampleKind hr_sample_kind(int shading, bool time_density)      // time_density: a density mode of hr_model_set_time_decode (no part of hr_config)
 {
-    HrGridPlane pl[3];
-    int ca_total = 0, n_basis_cols = 0;
-    (void)hr_plane_geometry(c, pl, &ca_total, &n_basis_cols);      // (an inconsistent geometry is refused by hr_model_finalize)
-    const int zp = hr_round_zp(c.z_channels);
-    *bytes = hr_sample_lds_bytes(hr_head_quads(c, p_live), ca_total, zp, rows_per_ray(c));
-    // an MLP shading mode: the export form of the sample stage keeps all 27 rows of basis_mat behind it (sample_shade_kernel.hip)
-    if (c.shading == HR_SHADING_MLP_FEA || c.shading == HR_SHADING_MLP) *bytes += sizeof(float) * (size_t)27 * ca_total;
-    return *bytes + 4096 + (zp > 64 ? 0 : 256 * sizeof(float)) > HR_LDS_PER_WORKGROUP;
+    return time_density ? HR_SAMPLE_TIME_DENSITY : hr_shading_is_time_family(shading) ? HR_SAMPLE_TIME : hr_shading_is_mlp(shading) ? HR_SAMPLE_SHADE : HR_SAMPLE_DECODE;
 }
 
 // What hr_launch_samples chooses for a launch: samples per ray rounded up (ZP), plane class, line form, grid and LDS
@@ -355,6 +352,31 @@ static inline HrFramePlan hr_frame_plan(const hr_config& cfg, const HrGridPlane*
     if (in.frame_mode < 2 || (ZP != 32 && ZP != 64)) return P;
     (void)fit(32, ZP == 32 ? 2 : 1, 8, 4, ZP == 32 ? 32 : 8 * RPW);
     return P;
+}
+
+// ---- which plan a render call takes (render_impl, api_render.hip; HR_OPT_FRAME_KERNEL_ACTIVE asks with 64 rays and nothing else)
+enum HrRoute { HR_ROUTE_FRAME = 0, HR_ROUTE_VERIFIED, HR_ROUTE_CHUNKED };
+struct HrRouteIn {
+    int64_t n_rays;
+    bool fields, maps;                  // diagnostics / per-ray maps requested (maps: some pointer set)
+    HrSampleKind kind;
+    bool mlp_verified, occupancy;       // HrMlpState::verified; an occupancy volume is set
+    bool band_stale, capturing;         // the margins are out of date; the stream is being captured (asked of a verified model with a stale band only)
+    bool frame_fits;                    // hr_frame_plan(...).fits
+};
+// tier of a chunked route: 0 = the model's primary arithmetic, 1 = the f16x3 tiles.  calibrate_first: measure the band (calibrate_band),
+// refresh mlp_verified and band_stale, ask again (route and tier are then those of a call that cannot measure)
+struct HrRenderRoute { int route, tier, calibrate_first; };
+// The frame kernel: the image alone of a DECODE model, where it fits.  The verified fast path: not with diagnostics (ONE arithmetic for every
+// output), an occupancy volume (a head-dependent decision the band does not cover) or a stale band inside a stream capture (measuring synchronises)
+static inline HrRenderRoute hr_render_route(const HrRouteIn& in)
+{
+    const bool decode = in.kind == HR_SAMPLE_DECODE;
+    if (!in.fields && !in.maps && decode && in.frame_fits) return {HR_ROUTE_FRAME, 0, 0};
+    const bool eligible = in.mlp_verified && !in.fields && !in.occupancy && in.n_rays < ((int64_t)1 << 31) && decode;
+    const HrRenderRoute chunked = {HR_ROUTE_CHUNKED, in.mlp_verified ? 1 : 0, 0};
+    if (eligible && in.band_stale) return {chunked.route, chunked.tier, in.capturing ? 0 : 1};
+    return (eligible && in.n_rays > 0) ? HrRenderRoute{HR_ROUTE_VERIFIED, 0, 0} : chunked;
 }
 
 // ---------------------------------------------------------------- the training step (train_kernel.hip)
@@ -564,8 +586,7 @@ struct HrMlpChoice {
     bool needs_calibration;
     int status;                   // HR_OK | HR_E_RANGE | HR_E_INVALID
 };
-// time_density: the model carries a density mode of hr_model_set_time_decode (not part of hr_config)
-static inline HrMlpChoice hr_mlp_choice(const hr_config& c, bool cascade_level, bool range_supported, const float* act_max, bool time_density = false)
+static inline HrMlpChoice hr_mlp_choice(const hr_config& c, HrSampleKind kind, bool cascade_level, bool range_supported, const float* act_max)
 {
     const int want = c.mlp_precision;
     if (c.mlp_layers == 0 || want == HR_MLP_FP32 || want == HR_MLP_BF16X3)
@@ -574,12 +595,9 @@ static inline HrMlpChoice hr_mlp_choice(const hr_config& c, bool cascade_level, 
     if (!range_supported) return {want, 0, true, HR_E_INVALID};
     bool fits = true;
     for (int l = 0; l < c.mlp_layers; ++l) fits = fits && isfinite(act_max[l]) && act_max[l] < HR_F16_CALIBRATION_LIMIT;
-    // (an MLP shading mode: the verified path's margins are not derived for the colour network -- f16f8 / f16f8v / auto run f16x3 there)
-    const bool shade_mlp = c.shading == HR_SHADING_MLP_FEA || c.shading == HR_SHADING_MLP;
-    // (the time-dependent decode modes and RGBIdentity, DESIGN 3m: the verified path's calibration -- its colour bar, its list passes through
-    //  the stand-alone sample kernel -- is not derived for their kernel either: the same resolution)
-    const bool time_decode = hr_shading_is_time_family(c.shading) || time_density;
-    const bool f8_ok = !shade_mlp && !time_decode && hr_mlp_fast_sincos_ok(c), can_verify = f8_ok && hr_mlp_can_verify(c, cascade_level);
+    // f16f8, and so verification, only for the DECODE kind (the verified path's margins are not derived for the colour network, DESIGN 3l, nor
+    // its calibration -- its colour bar, its list passes through the stand-alone sample kernel -- for the time kernel, 3m): f16x3 there
+    const bool f8_ok = kind == HR_SAMPLE_DECODE && hr_mlp_fast_sincos_ok(c), can_verify = f8_ok && hr_mlp_can_verify(c, cascade_level);
     if (want == HR_MLP_AUTO) {
         if (!fits) return {HR_MLP_BF16X3, 0, true, HR_OK};
         return {can_verify ? HR_MLP_F16F8 : HR_MLP_F16X3, can_verify ? 1 : 0, true, HR_OK};
@@ -589,6 +607,8 @@ static inline HrMlpChoice hr_mlp_choice(const hr_config& c, bool cascade_level, 
     if (!fits) return {want, 0, true, HR_E_RANGE};
     return {want == HR_MLP_F16F8V ? HR_MLP_F16F8 : want, want == HR_MLP_F16F8V ? 1 : 0, true, HR_OK};
 }
+// ... of a model without a density mode: the kind the shading alone gives
+static inline HrMlpChoice hr_mlp_choice(const hr_config& c, bool cascade_level, bool range_supported, const float* act_max) { return hr_mlp_choice(c, hr_sample_kind(c.shading, false), cascade_level, range_supported, act_max); }
 
 // The caller's calibration rays that stay with the model (the band of the verified fast path is measured on them, again after
 // hr_model_update_config): every stride-th of the n, at most 65 536
@@ -643,7 +663,6 @@ static inline int hr_verify_fallback(float listed_frac, float max_d_rgb)
 #define HR_SHADE_TILE_M 64        // rows of one MFMA tile of the shading kernel
 #define HR_SHADE_SPAN 512         // consecutive rows a workgroup of the shading kernel owns: their live rows, compacted, fill its tiles
 
-static inline bool hr_shading_is_mlp(int shading) { return shading == HR_SHADING_MLP_FEA || shading == HR_SHADING_MLP; }
 // width of the network's input: tensorf_base.py:43 (MLPRender_Fea), :111 (MLPRender)
 static inline int hr_shade_width(int shading, int view_pe, int fea_pe)
 {
@@ -701,32 +720,41 @@ static inline int hr_time_density_slots(const HrGridPlane* planes, int ca_total,
 {
     return pclass != 0 ? 3 * ca_total : 4 * (planes[0].cd4 + planes[1].cd4 + planes[2].cd4);
 }
-struct HrTimePlan {
-    HrSamplePlan sample;        // hr_sample_plan's with the second factor's taps decided at run time (NB = 4) and the density rows' LDS added
-    int d_slots, d_off;         // floats of a ray's density row, float offset of the workgroup's rows in its dynamic LDS (0, 0 without a density mode)
-};
-static inline HrTimePlan hr_time_plan(const hr_config& cfg, const HrGridPlane* planes, int ca_total, int nq, int rows_per_ray, int64_t n_rays, bool density)
+
+// ---------------------------------------------------------------- the sample stage of one launch, in every form (launch_samples, api_render.hip)
+// A launch's form: the model's kind and which of its kernels -- DECODE: with the per-ray maps or without; SHADE: the export or the import form
+struct HrSampleForm { HrSampleKind kind; bool maps, exported; };
+// hr_sample_plan extended by the form's own block behind the plan's LDS: its float offset, and the floats of a ray's density row
+struct HrSampleFormPlan : HrSamplePlan { int x_off, d_slots; };
+// The one planner: hr_sample_plan for DECODE (rows_emitted is that kind's alone).  SHADE: the generic gather; its export form keeps all rows of basis_mat.
+// The time kernel decides the second factor's taps at run time (no line form; the class is kept); with a density mode it keeps the workgroup's density rows
+static inline HrSampleFormPlan hr_sample_form_plan(const hr_config& cfg, const HrGridPlane* planes, int ca_total, int nq, int rows_per_ray, int64_t n_rays,
+                                                   bool rows_emitted, const HrSampleForm& form)
 {
-    HrTimePlan T = HrTimePlan();
-    T.sample = hr_sample_plan(cfg, planes, ca_total, nq, rows_per_ray, n_rays, false);
-    T.sample.all_lines = 0;
-    if (density) {
-        T.d_slots = hr_time_density_slots(planes, ca_total, T.sample.pclass);
-        T.d_off = (int)(T.sample.lds / sizeof(float));
-        T.sample.lds += sizeof(float) * (size_t)(256 / T.sample.zp) * T.d_slots;
-        T.sample.big_lds = T.sample.lds > 64 * 1024;
-    }
-    return T;
+    HrSampleFormPlan P = {hr_sample_plan(cfg, planes, ca_total, nq, rows_per_ray, n_rays, rows_emitted && form.kind == HR_SAMPLE_DECODE), 0, 0};
+    if (form.kind == HR_SAMPLE_SHADE) P.pclass = 0;
+    if (form.kind != HR_SAMPLE_DECODE) P.all_lines = 0;
+    if (form.kind == HR_SAMPLE_TIME_DENSITY) P.d_slots = hr_time_density_slots(planes, ca_total, P.pclass);
+    const int block = form.kind == HR_SAMPLE_TIME_DENSITY ? (256 / P.zp) * P.d_slots : (form.kind == HR_SAMPLE_SHADE && form.exported) ? HR_SHADE_FEAT * ca_total : -1;
+    if (block >= 0) P.x_off = (int)(P.lds / sizeof(float)), P.lds += sizeof(float) * (size_t)block;
+    P.big_lds = P.lds > 64 * 1024;
+    return P;
 }
-// hr_sample_lds_refused for a model with a density mode (hr_model_set_time_decode: the descriptor is no part of hr_config)
-static inline bool hr_time_lds_refused(const hr_config& c, int p_live, size_t* bytes)
+
+// true: a level of configuration c with p_live live head columns is refused for a sample stage of `kind`; *bytes: the request of the kind's largest
+// form.  The margin set aside next to it: 4096 bytes for the kernel's static words (the ray records, hr_gather_ones) and the 256-float cross-wave
+// scratch, reserved for every sample count although hr_sample_lds_bytes asks for it only above 64 samples -- the bound has always counted it.
+static inline bool hr_sample_lds_refused(const hr_config& c, int p_live, HrSampleKind kind, size_t* bytes)
 {
     HrGridPlane pl[3];
     int ca_total = 0, n_basis_cols = 0;
-    (void)hr_plane_geometry(c, pl, &ca_total, &n_basis_cols);
-    const HrTimePlan T = hr_time_plan(c, pl, ca_total, hr_head_quads(c, p_live), rows_per_ray(c), 1, true);
-    *bytes = T.sample.lds;
-    return *bytes + 4096 + (T.sample.zp > 64 ? 0 : 256 * sizeof(float)) > HR_LDS_PER_WORKGROUP;
+    (void)hr_plane_geometry(c, pl, &ca_total, &n_basis_cols);      // (an inconsistent geometry is refused by hr_model_finalize)
+    const HrSamplePlan P = hr_sample_form_plan(c, pl, ca_total, hr_head_quads(c, p_live), rows_per_ray(c), 1, false, HrSampleForm{kind, false, true});
+    *bytes = P.lds;
+    return *bytes + 4096 + (P.zp > 64 ? 0 : 256 * sizeof(float)) > HR_LDS_PER_WORKGROUP;
+}
+static inline bool hr_sample_lds_refused(const hr_config& c, int p_live, size_t* bytes) {      // hr_model_create: the kind the shading alone gives
+    return hr_sample_lds_refused(c, p_live, hr_sample_kind(c.shading, false), bytes);
 }
 
 #endif  // HR_PLAN_H

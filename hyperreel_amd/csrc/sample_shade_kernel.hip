@@ -6,7 +6,7 @@
 //                                  diagnostics are the statements every other model runs
 // Their own templates and translation unit (the precedent of sample_maps_kernel.hip): hr_sample_kernel's and hr_sample_maps_kernel's code
 // objects and kernel arguments stay as they are -- the workspace pointers are an argument of these kernels only.  Compiled for the
-// generic gather (PC 0, NB 4) and at most 64 samples per ray, which is what hr_model_set_shading_mlp accepts.
+// generic gather (PC 0, NB 4: what hr_sample_form_plan names for both forms) and at most 64 samples per ray (hr_model_set_shading_mlp).
 #include "sample_kernel.inc"
 
 // (the export form at 2 workgroups per SIMD-quad: the float16 gather inside the rolled loop over basis_mat's row triples spills 16
@@ -45,50 +45,28 @@ __global__ __launch_bounds__(256, (HrGatherTune<ZP, HALF>::MIN_BLOCKS)) void hr_
 #undef HR_SAMPLE_MAPS
 }
 
-template <class F>
-static void hr_shade_dispatch(int zp, bool half, F&& f)
-{
-    auto tex = [&](auto z) { if (half) f(z, std::true_type()); else f(z, std::false_type()); };
-    switch (zp) {
-        case 8: tex(std::integral_constant<int, 8>()); break;
-        case 16: tex(std::integral_constant<int, 16>()); break;
-        case 32: tex(std::integral_constant<int, 32>()); break;
-        case 64: tex(std::integral_constant<int, 64>()); break;
-        default: break;              // more than HR_SHADE_MAX_Z samples: refused by hr_model_set_shading_mlp
-    }
-}
-
-// the plan of both forms: hr_sample_plan's workgroups and LDS with the generic gather; the export form's 27 x ca_total matrix sits behind it
-static HrSamplePlan hr_sample_shade_plan(const hr_config& cfg, const HrSampleArgs& args, bool exported)
-{
-    HrSamplePlan P = hr_sample_plan(cfg, args.planes, args.ca_total, args.nq, args.rows_per_ray, args.n_rays, false);
-    P.pclass = 0;
-    P.all_lines = 0;
-    if (exported) P.lds += sizeof(float) * (size_t)HR_SHADE_FEAT * args.ca_total;
-    P.big_lds = P.lds > 64 * 1024;
-    return P;
-}
-
 void hr_launch_samples_shade_export(const hr_config& cfg, const HrSampleArgs& args, float* rows, hipStream_t stream)
 {
     if (args.n_rays <= 0) return;
-    const HrSamplePlan P = hr_sample_shade_plan(cfg, args, true);
+    const HrSampleFormPlan P = hr_sample_form_plan(cfg, args.planes, args.ca_total, args.nq, args.rows_per_ray, args.n_rays, false, HrSampleForm{HR_SAMPLE_SHADE, false, true});
     HrShadeIO io = {};
     io.rows = rows;
-    io.m_off = (int)((P.lds - sizeof(float) * (size_t)HR_SHADE_FEAT * args.ca_total) / sizeof(float));
-    hr_shade_dispatch(P.zp, cfg.grid_dtype == HR_GRID_FP16, [&](auto zp, auto half) {
-        hr_launch_sample_kernel(P, &hr_sample_shade_export_kernel<zp(), half()>, stream, args.cfg_dev, args, io);
+    io.m_off = P.x_off;
+    hr_sample_dispatch(P, cfg.grid_dtype == HR_GRID_FP16, [&](auto zp, auto half, auto pc, auto nb) {
+        if constexpr (pc() == 0 && nb() == 4 && zp() <= HR_SHADE_MAX_Z)
+            hr_launch_sample_kernel(P, &hr_sample_shade_export_kernel<zp(), half()>, stream, args.cfg_dev, args, io);
     });
 }
 
 void hr_launch_samples_shade_import(const hr_config& cfg, const HrSampleArgs& args, const hr_maps& maps, float* rows, const float* rgbk, hipStream_t stream)
 {
     if (args.n_rays <= 0) return;
-    const HrSamplePlan P = hr_sample_shade_plan(cfg, args, false);
+    const HrSampleFormPlan P = hr_sample_form_plan(cfg, args.planes, args.ca_total, args.nq, args.rows_per_ray, args.n_rays, false, HrSampleForm{HR_SAMPLE_SHADE, true, false});
     HrShadeIO io = {};
     io.rows = rows;
     io.rgbk = rgbk;
-    hr_shade_dispatch(P.zp, cfg.grid_dtype == HR_GRID_FP16, [&](auto zp, auto half) {
-        hr_launch_sample_kernel(P, &hr_sample_shade_import_kernel<zp(), half()>, stream, args.cfg_dev, args, maps, io);
+    hr_sample_dispatch(P, cfg.grid_dtype == HR_GRID_FP16, [&](auto zp, auto half, auto pc, auto nb) {
+        if constexpr (pc() == 0 && nb() == 4 && zp() <= HR_SHADE_MAX_Z)
+            hr_launch_sample_kernel(P, &hr_sample_shade_import_kernel<zp(), half()>, stream, args.cfg_dev, args, maps, io);
     });
 }

@@ -33,14 +33,14 @@ template <int TD>
 static bool hr_launch_samples_time_td(const hr_config& cfg, const HrSampleArgs& args, const hr_maps& maps, const HrTimeIO& io_in, hipStream_t stream)
 {
     if (args.n_rays <= 0) return true;
-    const HrTimePlan T = hr_time_plan(cfg, args.planes, args.ca_total, args.nq, args.rows_per_ray, args.n_rays, (TD & 2) != 0);
-    if ((TD & 2) != 0 && io_in.d_slots != T.d_slots) return false;
+    const HrSampleFormPlan P = hr_sample_form_plan(cfg, args.planes, args.ca_total, args.nq, args.rows_per_ray, args.n_rays, false, {(TD & 2) != 0 ? HR_SAMPLE_TIME_DENSITY : HR_SAMPLE_TIME, true, false});
+    if ((TD & 2) != 0 && io_in.d_slots != P.d_slots) return false;
     HrTimeIO io = io_in;
-    io.d_slots = T.d_slots;
-    io.d_off = T.d_off;
-    hr_sample_dispatch(T.sample, cfg.grid_dtype == HR_GRID_FP16, [&](auto zp, auto half, auto pc, auto nb) {
+    io.d_slots = P.d_slots;
+    io.d_off = P.x_off;
+    hr_sample_dispatch(P, cfg.grid_dtype == HR_GRID_FP16, [&](auto zp, auto half, auto pc, auto nb) {
         if constexpr (decltype(nb)::value == 4)      // (the plan never asks for the line form)
-            hr_launch_sample_kernel(T.sample, &hr_sample_time_kernel<zp(), half(), pc(), TD>, stream, args.cfg_dev, args, maps, io);
+            hr_launch_sample_kernel(P, &hr_sample_time_kernel<zp(), half(), pc(), TD>, stream, args.cfg_dev, args, maps, io);
     });
     return true;
 }

@@ -167,6 +167,10 @@ class SamplePlan(ctypes.Structure):         # mirrors HrSamplePlan (hyperreel_am
     _fields_ = [(k, ctypes.c_int) for k in ('zp', 'pclass', 'all_lines', 'big_lds')] + [('blocks', ctypes.c_uint), ('lds', ctypes.c_size_t)]
 
 
+class SampleFormPlan(ctypes.Structure):     # mirrors HrSampleFormPlan: HrSamplePlan and the form's own block
+    _fields_ = SamplePlan._fields_ + [('x_off', ctypes.c_int), ('d_slots', ctypes.c_int)]
+
+
 class FramePlan(ctypes.Structure):          # mirrors HrFramePlan (hyperreel_amd/csrc/hr_plan.h)
     _fields_ = [(k, ctypes.c_int) for k in ('fits', 'zp', 'pclass', 'tile_rays', 'ns', 'nb', 'nbuf', 'm_copies', 'head_stride', 'n_tiles', 'grid')] + \
                [('lds', ctypes.c_size_t)]
@@ -264,6 +268,28 @@ def sample_plan(hc, n_rays=4096, rows_emitted=False, frame_lines=False):
     out, inst = SamplePlan(), (ctypes.c_int * 4)()
     plan_lib().hp_sample_plan(ctypes.byref(hc), ctypes.c_longlong(n_rays), int(bool(rows_emitted)), int(bool(frame_lines)), ctypes.byref(out), inst)
     return out, tuple(inst)
+
+
+SAMPLE_KIND = {'decode': 0, 'shade': 1, 'time': 2, 'time_density': 3}        # HrSampleKind
+ROUTE = {'frame': 0, 'verified': 1, 'chunked': 2}                             # HrRoute
+
+
+def sample_form_plan(hc, kind, n_rays=4096, maps=False, exported=False, frame_lines=False):
+    """hr_sample_form_plan for a launch of form (kind, maps, exported) on a model of `hc`, and the instantiation hr_sample_dispatch names."""
+    out, inst = SampleFormPlan(), (ctypes.c_int * 4)()
+    assert plan_lib().hp_sizeof_sample_form_plan() == ctypes.sizeof(SampleFormPlan)
+    plan_lib().hp_sample_form_plan(ctypes.byref(hc), ctypes.c_longlong(n_rays), int(bool(frame_lines)), SAMPLE_KIND[kind], int(bool(maps)),
+                                   int(bool(exported)), ctypes.byref(out), inst)
+    return out, tuple(inst)
+
+
+def render_route(n_rays=640000, fields=False, maps=False, kind='decode', mlp_verified=False, occupancy=False, band_stale=False, capturing=False,
+                 frame_fits=False):
+    """hr_render_route of the facts given: (route name, tier, calibrate_first)."""
+    out = (ctypes.c_int * 3)()
+    plan_lib().hp_render_route(ctypes.c_longlong(n_rays), int(fields), int(maps), SAMPLE_KIND[kind], int(mlp_verified), int(occupancy), int(band_stale),
+                               int(capturing), int(frame_fits), out)
+    return {v: k for k, v in ROUTE.items()}[out[0]], out[1], out[2]
 
 
 def frame_plan(hc, n_rays=640000, frame_mode=1, sample_waves=0, cascade=False, verified=False, split_mlp=True, frame_lines=False):

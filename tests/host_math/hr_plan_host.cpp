@@ -8,6 +8,7 @@ extern "C" {
 int hp_sizeof_plane() { return (int)sizeof(HrGridPlane); }
 int hp_sizeof_plan() { return (int)sizeof(HrTrainPlan); }
 int hp_sizeof_sample_plan() { return (int)sizeof(HrSamplePlan); }
+int hp_sizeof_sample_form_plan() { return (int)sizeof(HrSampleFormPlan); }
 int hp_sizeof_frame_plan() { return (int)sizeof(HrFramePlan); }
 int hp_sizeof_time_tap() { return (int)sizeof(HrTimeTap); }
 int hp_round_zp(int z_channels) { return hr_round_zp(z_channels); }
@@ -86,10 +87,30 @@ static Level level_of(const hr_config& c, int frame_lines)
     return v;
 }
 
+int hp_sample_kind(int shading, int time_density) { return hr_sample_kind(shading, time_density != 0); }
+
 // 1: hr_model_create refuses the level for the sample kernel's LDS; *bytes: the kernel's request
 int hp_sample_lds_refused(const hr_config* c, size_t* bytes)
 {
     return hr_sample_lds_refused(*c, level_of(*c, 0).p_live, bytes) ? 1 : 0;
+}
+
+// the plan of a launch of form (kind, maps, exported) and the instantiation <ZP, HALF, PC, NB> hr_sample_dispatch names for it
+void hp_sample_form_plan(const hr_config* c, long long n_rays, int frame_lines, int kind, int maps, int exported, HrSampleFormPlan* out, int* inst)
+{
+    const Level v = level_of(*c, frame_lines);
+    *out = hr_sample_form_plan(*c, v.planes, v.ca_total, v.nq, rows_per_ray(*c), n_rays, false, HrSampleForm{(HrSampleKind)kind, maps != 0, exported != 0});
+    hr_sample_dispatch(*out, c->grid_dtype == HR_GRID_FP16, [&](auto zp, auto half, auto pc, auto nb) {
+        inst[0] = decltype(zp)::value; inst[1] = decltype(half)::value; inst[2] = decltype(pc)::value; inst[3] = decltype(nb)::value;
+    });
+}
+
+// hr_render_route: out = {route, tier, calibrate_first}
+void hp_render_route(long long n_rays, int fields, int maps, int kind, int mlp_verified, int occupancy, int band_stale, int capturing, int frame_fits, int* out)
+{
+    const HrRenderRoute r = hr_render_route(HrRouteIn{n_rays, fields != 0, maps != 0, (HrSampleKind)kind, mlp_verified != 0, occupancy != 0, band_stale != 0,
+                                                      capturing != 0, frame_fits != 0});
+    out[0] = r.route; out[1] = r.tier; out[2] = r.calibrate_first;
 }
 
 // hr_sample_plan as the launcher calls it

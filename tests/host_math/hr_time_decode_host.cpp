@@ -42,11 +42,12 @@ void td_plan(const hr_config* c, int p_live, long long n_rays, int density, long
     HrGridPlane pl[3];
     int ca_total = 0, n_cols = 0;
     (void)hr_plane_geometry(*c, pl, &ca_total, &n_cols);
-    const HrTimePlan T = hr_time_plan(*c, pl, ca_total, hr_head_quads(*c, p_live), rows_per_ray(*c), n_rays, density != 0);
+    const HrSampleForm form = {density ? HR_SAMPLE_TIME_DENSITY : HR_SAMPLE_TIME, true, false};
+    const HrSampleFormPlan T = hr_sample_form_plan(*c, pl, ca_total, hr_head_quads(*c, p_live), rows_per_ray(*c), n_rays, false, form);
     size_t bytes = 0;
-    const bool refused = hr_time_lds_refused(*c, p_live, &bytes);
-    const long long v[11] = {T.sample.zp, T.sample.pclass, T.sample.all_lines, T.sample.big_lds, T.sample.blocks, (long long)T.sample.lds,
-                             T.d_slots, T.d_off, hr_time_per_ray_M(c->shading) ? 1 : 0, refused ? 1 : 0, (long long)bytes};
+    const bool refused = hr_sample_lds_refused(*c, p_live, HR_SAMPLE_TIME_DENSITY, &bytes);
+    const long long v[11] = {T.zp, T.pclass, T.all_lines, T.big_lds, T.blocks, (long long)T.lds,
+                             T.d_slots, T.x_off, hr_time_per_ray_M(c->shading) ? 1 : 0, refused ? 1 : 0, (long long)bytes};
     for (int i = 0; i < 11; ++i) out[i] = v[i];
 }
 // hr_sample_lds_bytes of the same level: what the plan had before the density rows
@@ -62,7 +63,7 @@ void td_choice(const hr_config* c, int time_density, int* out)
 {
     float act[HR_MAX_LAYERS];
     for (int l = 0; l < HR_MAX_LAYERS; ++l) act[l] = 1.0f;
-    const HrMlpChoice ch = hr_mlp_choice(*c, false, true, act, time_density != 0);
+    const HrMlpChoice ch = hr_mlp_choice(*c, hr_sample_kind(c->shading, time_density != 0), false, true, act);
     out[0] = ch.active_precision; out[1] = ch.verified; out[2] = ch.status;
 }
 

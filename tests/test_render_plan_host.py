@@ -1,13 +1,13 @@
 """CPU check of the render call's decisions in hyperreel_amd/csrc/hr_plan.h, compiled for the host (tests/host_math/hr_plan_host.cpp):
-launch sizing, the sample kernel's LDS and instantiation, the create-time LDS bound, live head columns, a frame's time tap, the frame
-kernel's plan.  The expectations are worked out by hand in the docstrings, not taken from the code."""
+launch sizing, the sample kernel's LDS and instantiation, the create-time LDS bound, the sample stage's kinds and forms, the call's route,
+live head columns, a frame's time tap, the frame kernel's plan.  The expectations are worked out by hand in the docstrings, not taken from the code."""
 import ctypes
 
 import numpy as np
 import pytest
 
-from helpers import (Golden, SamplePlan, even_chunk, frame_plan, frame_time_tap, live_columns, math_lib, plan_lib, plane_geometry, redo_list_cap,
-                     sample_lds_refused, sample_plan, sweep_cases)
+from helpers import (SAMPLE_KIND, Golden, SamplePlan, even_chunk, frame_plan, frame_time_tap, live_columns, math_lib, plan_lib, plane_geometry,
+                     redo_list_cap, render_route, sample_form_plan, sample_lds_refused, sample_plan, sweep_cases)
 from hyperreel_amd import config as C
 from hyperreel_amd import plan
 
@@ -122,6 +122,24 @@ def test_create_time_lds_bound(z, inside, outside):
         assert request == bound - (0 if zp > 64 else 1024)
 
 
+@pytest.mark.parametrize('n_app,request_bytes,refused', [((100, 100, 96), 157408, False), ((100, 100, 100), 159376, True)])
+def test_create_time_lds_bound_of_an_mlp_shaded_model(n_app, request_bytes, refused):
+    """The same bound, evaluated on the SHADE kind's largest form: the export form keeps all 27 rows of basis_mat (27 x ca floats) behind
+    the plan's LDS.  DoNeRF's head at 8 samples (11 live columns, nq = 22, 32 rays per workgroup, no cross-wave scratch), shading set by
+    hand to MLP_Fea: 4 x (32 x 92 + 96 ca) + 108 ca = 11 776 + 384 ca + 108 ca bytes, refused when that + 4 096 + 1 024 > 163 840, i.e.
+    ca > 298.67.  ca = 296 (100 + 100 + 96): 11 776 + 492 x 296 = 157 408, + 5 120 = 162 528: accepted.  ca = 300: 11 776 + 147 600 =
+    159 376, + 5 120 = 164 496: refused.  (The same components under RGB shading ask for 108 ca less and are both accepted.)"""
+    hc = _donerf_with_app(8, n_app)
+    ca = sum(n_app)
+    assert live_columns(hc)[1] == 11 and all(a % 4 == 0 for a in n_app)
+    assert sample_lds_refused(hc) == (False, 11776 + 384 * ca)
+    hc.shading = plan.SHADING['MLP_Fea']
+    assert 11776 + 384 * ca + 108 * ca == request_bytes and (request_bytes + 4096 + 1024 > 160 * KIB) == refused
+    assert sample_lds_refused(hc) == (refused, request_bytes)
+    # the request is the export form's plan
+    assert sample_form_plan(hc, 'shade', exported=True)[0].lds == request_bytes
+
+
 # ---------------------------------------------------------------- hr_sample_plan
 def _want_class(hc, rows_emitted):
     """[8, 4, 4] on all three pairs -> 1, [8, 0, 0] -> 2, anything else -> 0 (float16 texels alike); never for a kernel that emits
@@ -177,6 +195,103 @@ def test_sample_plan_special_cases():
     coarse = [hc0 for _, hc0, is_coarse in _levels('sweep/shiny_z_plane_cascaded') if is_coarse][0]
     assert tuple(coarse.n_den) == (8, 4, 4) and sample_plan(coarse)[1] == (8, 0, 1, 2)         # its planes alone would be class 1
     assert sample_plan(coarse, rows_emitted=True)[1] == (8, 0, 0, 4)
+
+
+# ---------------------------------------------------------------- hr_sample_kind, hr_sample_form_plan
+def test_sample_kind():
+    """A density mode (whatever the shading) -> TIME_DENSITY; else RGBtLinear, RGBtFourier and RGBIdentity -> TIME, MLP_Fea and MLP ->
+    SHADE, RGB and SH -> DECODE."""
+    want = {'RGB': 'decode', 'SH': 'decode', 'MLP_Fea': 'shade', 'MLP': 'shade', 'RGBtLinear': 'time', 'RGBtFourier': 'time', 'RGBIdentity': 'time'}
+    assert set(want) == set(plan.SHADING)
+    for name, kind in want.items():
+        assert plan_lib().hp_sample_kind(plan.SHADING[name], 0) == SAMPLE_KIND[kind], name
+        assert plan_lib().hp_sample_kind(plan.SHADING[name], 1) == SAMPLE_KIND['time_density'], name
+
+
+def test_form_plan_of_an_mlp_shaded_model():
+    """DoNeRF ([8, 4, 4] static: its planes alone are class 1 with line taps) with the shading set to MLP_Fea.  The DECODE plan: 32 samples,
+    8 rays per workgroup, nq = 32 x 11 / 4 = 88: 8 x (352 + 4) + 8 x 3 x 16 = 3 232 floats = 12 928 bytes.  Both SHADE forms take the
+    generic gather, (32, float32, 0, 4); the import form asks for the same LDS, the export form for 27 x 16 x 4 = 1 728 bytes more, its
+    block starting where the DECODE plan ends, at float 3 232."""
+    hc = _config('donerf_sphere')
+    hc.shading = plan.SHADING['MLP_Fea']
+    for frame_lines in (False, True):
+        dec, inst = sample_form_plan(hc, 'decode', n_rays=130, frame_lines=frame_lines)
+        assert (dec.pclass, dec.all_lines, inst) == (1, 1, (32, 0, 1, 2))
+        assert (dec.lds, dec.big_lds, dec.blocks, dec.x_off, dec.d_slots) == (12928, 0, 17, 0, 0)
+        for exported in (False, True):
+            p, inst = sample_form_plan(hc, 'shade', n_rays=130, maps=not exported, exported=exported, frame_lines=frame_lines)
+            assert (p.zp, p.pclass, p.all_lines, inst) == (32, 0, 0, (32, 0, 0, 4))
+            assert (p.lds, p.x_off) == ((12928 + 1728, 3232) if exported else (12928, 0))
+            assert (p.big_lds, p.blocks, p.d_slots) == (0, 17, 0)
+    # the DECODE forms are hr_sample_plan, with the maps or without
+    for maps in (False, True):
+        dec, inst = sample_form_plan(hc, 'decode', maps=maps)
+        ref, ref_inst = sample_plan(hc)
+        assert all(getattr(dec, k) == getattr(ref, k) for k, _ in SamplePlan._fields_) and inst == ref_inst
+
+
+def test_form_plan_of_a_time_colour_model():
+    """technicolor ([8, 0, 0] keyframe net) with RGBtFourier: the TIME form keeps class 2 and never takes the line form -- not inside
+    hr_render_frame either, where the DECODE plan of the same planes does; (32, float32, 2, 4).  No block of its own: the LDS is the
+    DECODE plan's (a decode matrix per ray was always counted)."""
+    cfg = C.model_config('technicolor_z_plane', shading='RGBtFourier')
+    hc = plan.compile_model(cfg, C.dataset_scalars('technicolor_z_plane'), [28, 24, 20])[1]
+    assert hc.shading == plan.SHADING['RGBtFourier']
+    for frame_lines in (False, True):
+        dec, dec_inst = sample_form_plan(hc, 'decode', frame_lines=frame_lines)
+        assert (dec.pclass, dec.all_lines, dec_inst) == (2, int(frame_lines), (32, 0, 2, 2 if frame_lines else 4))
+        p, inst = sample_form_plan(hc, 'time', maps=True, frame_lines=frame_lines)
+        assert (p.pclass, p.all_lines, inst) == (2, 0, (32, 0, 2, 4))
+        assert (p.lds, p.big_lds, p.blocks, p.x_off, p.d_slots) == (dec.lds, dec.big_lds, dec.blocks, 0, 0)
+        # with a density mode: class 2 keeps the row in the decode matrix's shape, 3 x 8 floats per ray behind the plan's LDS
+        d, inst = sample_form_plan(hc, 'time_density', maps=True, frame_lines=frame_lines)
+        assert (d.pclass, d.all_lines, inst) == (2, 0, (32, 0, 2, 4))
+        assert (d.d_slots, d.x_off, d.lds) == (24, dec.lds // 4, dec.lds + 4 * 8 * 24)
+
+
+# ---------------------------------------------------------------- hr_render_route
+def test_render_route_table():
+    """Which plan a call takes, from the facts alone.
+      * the frame kernel: the image alone (no diagnostics, no maps) of a DECODE model where hr_frame_plan fits -- DoNeRF under
+        HR_OPT_FRAME_KERNEL = 1; a call without rays takes the route too (and launches nothing).
+      * the verified fast path: a verified model's image, with or without maps; not with diagnostics, not with an occupancy volume, not
+        for 2^31 rays or more, not for no rays: those render launch by launch with the f16x3 tiles (tier 1).
+      * a stale band: measured first (calibrate_first) unless the stream is being captured -- then tier 1 launches, nothing measured.
+        After the measurement the caller asks again with what it left: still verified -> the fast path; given up -> tier 0.
+      * an unverified model: launch by launch in its own arithmetic (tier 0), stale band or not.
+      * SHADE, TIME, TIME_DENSITY: never the frame kernel, never the fast path, never a measurement -- whatever the other facts say."""
+    hc = _config('donerf_sphere')
+    fits = bool(frame_plan(hc, frame_mode=1).fits)
+    assert fits and not frame_plan(hc, frame_mode=1, verified=True).fits
+    R = render_route
+    assert R(frame_fits=fits) == ('frame', 0, 0) and R(frame_fits=fits, n_rays=0) == ('frame', 0, 0)
+    assert R(frame_fits=fits, maps=True) == ('chunked', 0, 0) and R(frame_fits=fits, fields=True) == ('chunked', 0, 0)
+    assert R(frame_fits=False) == ('chunked', 0, 0)
+    for kind in ('shade', 'time', 'time_density'):
+        assert R(frame_fits=True, kind=kind) == ('chunked', 0, 0)
+    V = dict(mlp_verified=True)
+    assert R(**V) == ('verified', 0, 0) and R(**V, maps=True) == ('verified', 0, 0)
+    assert R(**V, n_rays=1) == ('verified', 0, 0) and R(**V, n_rays=(1 << 31) - 1) == ('verified', 0, 0)
+    assert R(**V, fields=True) == ('chunked', 1, 0) and R(**V, fields=True, maps=True) == ('chunked', 1, 0)
+    assert R(**V, occupancy=True) == ('chunked', 1, 0)
+    assert R(**V, n_rays=1 << 31) == ('chunked', 1, 0)
+    assert R(**V, n_rays=0) == ('chunked', 1, 0)
+    # a stale band
+    assert R(**V, band_stale=True)[2] == 1 and R(**V, band_stale=True, maps=True)[2] == 1 and R(**V, band_stale=True, n_rays=0)[2] == 1
+    assert R(**V, band_stale=True)[:2] == ('chunked', 1)               # (what the call would take without the measurement)
+    assert R(mlp_verified=True, band_stale=False) == ('verified', 0, 0)
+    assert R(mlp_verified=False, band_stale=False) == ('chunked', 0, 0)
+    assert R(**V, band_stale=True, capturing=True) == ('chunked', 1, 0)
+    for ineligible in (dict(fields=True), dict(occupancy=True), dict(n_rays=1 << 31)):          # nothing to measure for
+        assert R(**V, band_stale=True, **ineligible) == ('chunked', 1, 0)
+    assert R() == ('chunked', 0, 0) and R(band_stale=True) == ('chunked', 0, 0) and R(occupancy=True, maps=True) == ('chunked', 0, 0)
+    for kind in ('shade', 'time', 'time_density'):
+        for bits in range(64):
+            fields, maps, occ, stale, cap, ff = ((bits >> i) & 1 for i in range(6))
+            for n in (0, 130, 1 << 31):
+                assert R(n_rays=n, fields=fields, maps=maps, kind=kind, mlp_verified=True, occupancy=occ, band_stale=stale, capturing=cap,
+                         frame_fits=ff) == ('chunked', 1, 0)
 
 
 # ---------------------------------------------------------------- hr_live_columns
