@@ -3,21 +3,29 @@ that libhyperreel_hip.so consumes (include/hyperreel_hip.h).
 
 This is the host-side half of the drop-in boundary: everything the reference's module
 constructors derive at build time is derived here, in the reference's own precision and
-order, so the kernels only see numbers:
+order, so the kernels only see numbers.  compile_config is the list of these stages, one function per reference constructor:
 
-  RayPredictionEmbedding.__init__   nlf/embedding/ray.py:213-315   (param groups, PE, head layout, depth-2)
-  Intersect.__init__                nlf/intersect/base.py:52-126   (near/far, sort, contract, activation)
-  IntersectZPlane.__init__          nlf/intersect/z.py:16-75       (anchor samples, z_scale)
-  IntersectSphereOld/CylinderOld    nlf/intersect/primitive.py:181-233, 366-418
-  MIPNeRFContract.__init__          nlf/contract.py:113-141
-  AdvectPointsEmbedding.__init__    nlf/embedding/point.py:741-778
-  PointOffsetEmbedding.__init__     nlf/embedding/point.py:338-369
-  TensorBase.__init__               nlf/nets/tensorf_base.py:137-248
-  TensorVMKeyframeTime.__init__     nlf/nets/tensorf_dynamic.py:45-77
+  RayPointEmbedding.__init__        nlf/embedding/embedding.py:59-98    _embedding_stages
+  RayPredictionEmbedding.__init__   nlf/embedding/ray.py:213-315        _ray_prediction: _param_group, _ray_mlp, _head_layout
+  TensorVMNoSample's colour heads   nlf/nets/tensorf_no_sample.py:222-243   _color_fields
+  ColorTransformEmbedding.__init__  nlf/embedding/point.py:558-602      _color_table
+  Intersect.__init__                nlf/intersect/base.py:52-126        _intersect: _intersect_base (near/far, sort, mask, activation)
+  the contracts                     nlf/contract.py:65-240              _contract: _Affine, _MipNerf, _DoNeRF
+  IntersectZPlane.__init__          nlf/intersect/z.py:16-75            _anchors: _anchor_range, _anchor_line, _z_scale
+  the sphere / cylinder / distance primitives   nlf/intersect/primitive.py:126-488   the same three
+  IntersectVoxelGrid, IntersectDeformableVoxelGrid   nlf/intersect/voxel.py:19-70, 115-182   _voxel_anchors, _deformable_anchors
+  AdvectPointsEmbedding.__init__    nlf/embedding/point.py:741-778      _advect
+  PointOffsetEmbedding.__init__     nlf/embedding/point.py:338-369      _point_offset
+  TensorBase.__init__               nlf/nets/tensorf_base.py:137-248    _colour_net, _shading (shading_mlp, time_decode)
+  TensorVMKeyframeTime.__init__     nlf/nets/tensorf_dynamic.py:45-77   _colour_net
+  PointPredictionEmbedding.__init__ nlf/embedding/point.py:39-218       compile_cascade
+and _mlp_arithmetic, the library's own arithmetic word.  What a stage reads is in its signature: the YAML group, `hc`, the heads, and a
+_Ctx (training iteration, aabb buffer, dataset scalars, coarse level); `at_iteration` only supplies compile_config's defaults.
 
 Anything outside the hot-path scope raises NotImplementedError with
 the offending key -- never a silent fallback.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -204,7 +212,8 @@ class hr_maps(C.Structure):
 
 
 # --------------------------------------------------------------------------- small helpers
-# Training iteration the schedules are evaluated at while compile_config runs (None: converged, every weight 1)
+# The defaults `at_iteration` supplies; compile_config reads the two once, into its _Ctx, and nothing below it looks at them.
+# Training iteration the schedules are evaluated at (None: converged, every weight 1)
 _ITERATION = None
 # Bounding box of the feature grids when it is not the YAML's: TensorBase keeps `aabb` as a buffer that `shrink`
 # replaces during training (nlf/nets/tensorf_base.py:1191-1232) and that checkpoints therefore carry
@@ -276,16 +285,16 @@ class at_iteration:
         return False
 
 
-def _act(cfg):
+def _act(cfg, iteration=None):
     """get_activation (nlf/activations.py:566-570).  EaseValue (:462-496), w * act(x) + (1 - w) * start_value, is folded
-    into the inner activation's `outer` (times w) and `add`; with _ITERATION None (inference) w == 1."""
+    into the inner activation's `outer` (times w) and `add`; with `iteration` None (inference) w == 1."""
     if cfg is None:
         cfg = 'identity'
     if isinstance(cfg, str):
         cfg = {'type': cfg}
     scale, add = 1.0, 0.0                      # y_final = scale * inner(x) + add
     while cfg['type'] == 'ease_value':
-        w = ease_weight(cfg, _ITERATION)
+        w = ease_weight(cfg, iteration)
         add += scale * (1.0 - w) * float(cfg.get('start_value', 0.0))
         scale *= w
         cfg = cfg['activation']
@@ -419,10 +428,7 @@ class _Affine:
 
 # --------------------------------------------------------------------------- the compiler
 MLP_PRECISION = {'fp32': 0, 'bf16x3': 1, 'f16x3': 2, 'f16x2': 3, 'auto': 4, 'f16f8': 5, 'f16f8v': 6}
-
-
 GRID_DTYPE = {'fp32': 0, 'fp16': 1}
-
 FAST_SINCOS_MAX_FREQ = 16.0     # HR_FAST_SINCOS_MAX_FREQ (csrc/hr_plan.h)
 
 
@@ -442,99 +448,84 @@ def fast_sincos_ok(hc):
     return True
 
 
-def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp32', _coarse=False, iteration='inherit'):
-    """cfg: `experiment.model` group (dict/Cfg); dataset: {near, far, depth_range,
-    num_keyframes, num_frames}; grid_size: [Nx, Ny, Nz] of the uploaded planes.
-    iteration: training iteration of the EaseValue / WindowedPE schedules (None: converged; default: whatever an
-    enclosing `at_iteration` set, else converged)."""
-    if iteration != 'inherit':
-        with at_iteration(iteration):
-            return compile_config(cfg, dataset, grid_size, mlp_precision, grid_dtype, _coarse)
-    if cfg.get('param', {}).get('fn', 'identity') != 'identity':
-        raise NotImplementedError("model.param.fn other than 'identity'")
-    if cfg['embedding']['type'] != 'ray_point':
-        raise NotImplementedError(f"embedding type {cfg['embedding']['type']}")
-    hc = hr_config()
-    for name in ('f_z_vals', 'f_isect_sigma', 'f_offset_sigma', 'f_point_offset', 'f_color_scale',
-                 'f_color_shift', 'f_spatial_flow', 'f_color_scale_global', 'f_color_shift_global'):
-        setattr(hc, name, _absent_field())
+# What a stage may depend on besides the YAML: the training iteration of the schedules (None: converged), the colour net's `aabb` buffer
+# when it is not the YAML's (None: the YAML's), the dataset scalars, and whether this is the coarse level of a cascade
+_Ctx = collections.namedtuple('_Ctx', 'iteration aabb dataset coarse')
+_HEAD_FIELDS = [name for name, kind in hr_config._fields_ if kind is hr_head_field]      # f_z_vals ... f_color_shift_global
+_STAGES = {'ray_prediction', 'ray_intersect', 'advect_points', 'point_offset', 'add_point_outputs', 'extract_fields', 'color_transform'}
+
+
+def _set(arr, values, n=None):
+    """arr[k] = values[k] for the first n slots (default: all) of a ctypes float / int32 array"""
+    conv = int if arr._type_ is C.c_int32 else float
+    for k in range(len(arr) if n is None else n):
+        arr[k] = conv(values[k])
+
+
+def _embedding_stages(cfg):
+    """RayPointEmbedding.__init__'s stage list (nlf/embedding/embedding.py:59-98), checked for types and order.  -> {type: its first stage}"""
     stages = list(cfg['embedding']['embeddings'].values())
     types = [s['type'] for s in stages]
-    allowed = {'ray_prediction', 'ray_intersect', 'advect_points', 'point_offset', 'add_point_outputs', 'extract_fields',
-               'color_transform'}
     for t in types:
-        if t not in allowed:
+        if t not in _STAGES:
             raise NotImplementedError(f"embedding '{t}' is outside the hot-path scope")
     order = [t for t in types if t in ('ray_prediction', 'ray_intersect', 'advect_points', 'point_offset')]
     if order[:2] != ['ray_prediction', 'ray_intersect'] or order[2:] not in ([], ['point_offset'], ['advect_points'],
                                                                              ['advect_points', 'point_offset']):
         raise NotImplementedError(f'embedding order {order} (expected prediction, intersect[, advect][, offset])')
+    return {t: stages[types.index(t)] for t in types}
 
-    # ---- ray_prediction ------------------------------------------------------------
-    pred = stages[types.index('ray_prediction')]
-    if pred.get('ray_outputs'):
-        raise NotImplementedError('ray_outputs')
-    if pred.get('rays_name', 'rays') != 'rays':
-        raise NotImplementedError('rays_name')
-    groups = list(pred['params'].values())
-    if len(groups) > HR_MAX_GROUPS:
-        raise NotImplementedError(f'more than {HR_MAX_GROUPS} parameter groups')
-    hc.n_groups = len(groups)
-    mlp_in = 0
-    max_col = 0
-    for i, g in enumerate(groups):
-        pg = hc.groups[i]
-        pg.start, pg.end = int(g['start']), int(g['end'])
-        max_col = max(max_col, pg.end)
-        p = g['param']
-        fn = p['fn']
-        if fn not in PARAM:
-            raise NotImplementedError(f"ray param '{fn}' is outside the hot-path scope")
-        if p.get('use_local_param', False):
-            raise NotImplementedError('use_local_param')
-        pg.fn = PARAM[fn]
-        org = p.get('origin', [0.0, 0.0, 0.0])
-        for k in range(3):
-            pg.origin[k] = float(org[k])
-        if fn == 'pluecker':
-            if pg.end - pg.start < 6:
-                raise ValueError('pluecker needs 6 ray columns')
-            pg.a, pg.b = float(p.get('direction_multiplier', 1.0)), float(p.get('moment_multiplier', 1.0))
-            n = 6
-        elif fn == 'two_plane':
-            if pg.end - pg.start < 6:
-                raise ValueError('two_plane needs 6 ray columns')
-            pg.a, pg.b = float(p.get('near', -1.0)), float(p.get('far', 0.0))
-            n = 4
-        else:
-            n = pg.end - pg.start
-            if n > 8:
-                raise NotImplementedError('identity param with more than 8 columns')
-        pe = g.get('pe')
-        if pe is None:
-            pg.pe_type = 0
-        else:
-            if pe['type'] not in ('windowed', 'basic'):
-                raise NotImplementedError(f"pe '{pe['type']}' is outside the hot-path scope")
-            if 'window_iters' in pe or pe.get('ceil', False):
-                raise NotImplementedError('windowed PE with explicit window_iters / ceil is outside the hot-path scope')
-            pg.pe_type = PE[pe['type']]
-            pg.pe_n_freqs = int(pe['n_freqs'])
-            pg.pe_exclude_identity = int(bool(pe.get('exclude_identity', False))) if pe['type'] == 'windowed' else 0
-            pg.pe_freq_mult = float(pe.get('freq_multiplier', 2.0))
-            pg.pe_base_mult = float(pe.get('base_multiplier', 1.0)) if pe['type'] == 'windowed' else 1.0
-            if pe['type'] == 'windowed':
-                if pg.pe_n_freqs > 8:
-                    raise NotImplementedError('windowed PE with more than 8 frequencies')
-                for j, w in enumerate(windowed_pe_weights(pe, _ITERATION)):
-                    pg.pe_weight[j] = w
-            k = 2 * pg.pe_n_freqs
-            n = n * (k if pg.pe_exclude_identity else k + 1)
-        mlp_in += n
-    hc.mlp_in = mlp_in
-    if mlp_in > HR_MAX_MLP_IN:
-        raise NotImplementedError(f'MLP input of {mlp_in} features (max {HR_MAX_MLP_IN})')
-    net = pred['net']
+
+def _param_group(pg, g, iteration):
+    """One `params` group of RayPredictionEmbedding (nlf/embedding/ray.py:213-260): ray columns, parameterisation (nlf/param.py) and PE
+    (nlf/pe.py) into `pg`, the windowed weights at `iteration`.  -> the number of features the group hands the MLP"""
+    pg.start, pg.end = int(g['start']), int(g['end'])
+    p = g['param']
+    fn = p['fn']
+    if fn not in PARAM:
+        raise NotImplementedError(f"ray param '{fn}' is outside the hot-path scope")
+    if p.get('use_local_param', False):
+        raise NotImplementedError('use_local_param')
+    pg.fn = PARAM[fn]
+    _set(pg.origin, p.get('origin', [0.0, 0.0, 0.0]))
+    if fn == 'pluecker':
+        if pg.end - pg.start < 6:
+            raise ValueError('pluecker needs 6 ray columns')
+        pg.a, pg.b = float(p.get('direction_multiplier', 1.0)), float(p.get('moment_multiplier', 1.0))
+        n = 6
+    elif fn == 'two_plane':
+        if pg.end - pg.start < 6:
+            raise ValueError('two_plane needs 6 ray columns')
+        pg.a, pg.b = float(p.get('near', -1.0)), float(p.get('far', 0.0))
+        n = 4
+    else:
+        n = pg.end - pg.start
+        if n > 8:
+            raise NotImplementedError('identity param with more than 8 columns')
+    pe = g.get('pe')
+    if pe is None:
+        pg.pe_type = 0
+        return n
+    if pe['type'] not in ('windowed', 'basic'):
+        raise NotImplementedError(f"pe '{pe['type']}' is outside the hot-path scope")
+    if 'window_iters' in pe or pe.get('ceil', False):
+        raise NotImplementedError('windowed PE with explicit window_iters / ceil is outside the hot-path scope')
+    pg.pe_type = PE[pe['type']]
+    pg.pe_n_freqs = int(pe['n_freqs'])
+    pg.pe_exclude_identity = int(bool(pe.get('exclude_identity', False))) if pe['type'] == 'windowed' else 0
+    pg.pe_freq_mult = float(pe.get('freq_multiplier', 2.0))
+    pg.pe_base_mult = float(pe.get('base_multiplier', 1.0)) if pe['type'] == 'windowed' else 1.0
+    if pe['type'] == 'windowed':
+        if pg.pe_n_freqs > 8:
+            raise NotImplementedError('windowed PE with more than 8 frequencies')
+        for j, w in enumerate(windowed_pe_weights(pe, iteration)):
+            pg.pe_weight[j] = w
+    k = 2 * pg.pe_n_freqs
+    return n * (k if pg.pe_exclude_identity else k + 1)
+
+
+def _ray_mlp(hc, net):
+    """The ray MLP as RayPredictionEmbedding builds it (ray.py:262-285; BaseMLP nlf/nets/mlp.py:127-172): layers, hidden width, skip mask"""
     if net['type'] not in ('base', 'zero'):
         raise NotImplementedError(f"net '{net['type']}' is outside the hot-path scope (BaseMLP, ZeroMLP)")
     zero_net = net['type'] == 'zero'               # nlf/nets/mlp.py:14-33: all-zero head, the other keys are ignored
@@ -558,6 +549,11 @@ def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp
             raise NotImplementedError('skip connection into layer 0')
     hc.mlp_skip_mask = mask
     hc.leaky_slope = 0.01
+
+
+def _head_layout(hc, pred, iteration):
+    """z_channels and the `outputs` of RayPredictionEmbedding (ray.py:286-315): each head's offset, width and activation at `iteration`.
+    -> {head name: hr_head_field}"""
     Z = int(pred['z_channels'])
     if Z > HR_KERNEL_MAX_Z:
         raise NotImplementedError(f'z_channels {Z} > {HR_KERNEL_MAX_Z}')
@@ -566,15 +562,42 @@ def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp
     off = 0
     for name, o in pred['outputs'].items():
         f = hr_head_field()
-        f.offset, f.channels, f.act = off, int(o['channels']), _act(o.get('activation'))
+        f.offset, f.channels, f.act = off, int(o['channels']), _act(o.get('activation'), iteration)
         heads[name] = f
         off += f.channels
     hc.preds_per_z = off
     if 'z_vals' not in heads:
         raise NotImplementedError('model without a z_vals head')
     hc.f_z_vals = heads['z_vals']
-    # ExtractFieldsEmbedding (embedding/point.py:236-244): the colour net only sees the listed fields
-    seen = set(stages[types.index('extract_fields')]['fields']) if 'extract_fields' in types else None
+    return heads
+
+
+def _ray_prediction(hc, pred, ctx):
+    """RayPredictionEmbedding.__init__ (nlf/embedding/ray.py:213-315): parameter groups and their PE, the MLP's shape, the head layout.
+    -> ({head name: hr_head_field}, the largest ray column a group reads)"""
+    if pred.get('ray_outputs'):
+        raise NotImplementedError('ray_outputs')
+    if pred.get('rays_name', 'rays') != 'rays':
+        raise NotImplementedError('rays_name')
+    groups = list(pred['params'].values())
+    if len(groups) > HR_MAX_GROUPS:
+        raise NotImplementedError(f'more than {HR_MAX_GROUPS} parameter groups')
+    hc.n_groups = len(groups)
+    mlp_in = 0
+    max_col = 0
+    for i, g in enumerate(groups):
+        mlp_in += _param_group(hc.groups[i], g, ctx.iteration)
+        max_col = max(max_col, hc.groups[i].end)
+    hc.mlp_in = mlp_in
+    if mlp_in > HR_MAX_MLP_IN:
+        raise NotImplementedError(f'MLP input of {mlp_in} features (max {HR_MAX_MLP_IN})')
+    _ray_mlp(hc, pred['net'])
+    return _head_layout(hc, pred, ctx.iteration), max_col
+
+
+def _color_fields(hc, heads, seen):
+    """The colour heads TensorVMNoSample.forward reads (nlf/nets/tensorf_no_sample.py:222-243).  seen: the fields an
+    ExtractFieldsEmbedding lets through (embedding/point.py:236-244: the colour net only sees the listed fields; None: all)"""
     has = lambda k: k in heads and (seen is None or k in seen)
     if has('color_scale'):                           # tensorf_no_sample.py:222-225 (color_shift is read unguarded)
         if not has('color_shift'):
@@ -599,27 +622,195 @@ def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp
             raise ValueError(f'{k[2:]} needs 3 channels')
     if has('weights_shift'):
         raise NotImplementedError("head 'weights_shift' is outside the hot-path scope")
-    # ColorTransformEmbedding (embedding/point.py:558-602): a no-op unless dataset.val_all
-    hc.color_table_t_act, hc.color_table_s_act = _act(None), _act(None)
-    if 'color_transform' in types and dataset.get('val_all', False):
-        ct = stages[types.index('color_transform')]
-        tf, sf = ct.get('out_transform_field', 'color_transform_global'), ct.get('out_shift_field', 'color_shift_global')
-        if (tf, sf) != ('color_transform_global', 'color_shift_global'):
-            raise NotImplementedError('color_transform with renamed output fields')
-        if 'color_shift_global' in heads:
-            raise NotImplementedError('color_transform next to a color_shift_global head')
-        vis = lambda k: seen is None or k in seen
-        # tensorf_no_sample.py:240-243: a color_scale_global head takes precedence over the transform
-        if vis(tf) and vis(sf) and hc.f_color_scale_global.offset < 0:
-            hc.color_table_views = int(dataset['total_images_per_frame'])
-            hc.color_table_t_act = _act(ct.get('transform_activation'))
-            hc.color_table_s_act = _act(ct.get('shift_activation'))
 
-    # ---- ray_intersect --------------------------------------------------------------
-    st = stages[types.index('ray_intersect')]
-    if int(st['z_channels']) != Z:
+
+def _color_table(hc, stage, heads, seen, ctx):
+    """ColorTransformEmbedding (embedding/point.py:558-602): a per-view table of transforms; a no-op unless dataset.val_all.
+    stage: the `color_transform` stage or None"""
+    hc.color_table_t_act, hc.color_table_s_act = _act(None), _act(None)
+    if stage is None or not ctx.dataset.get('val_all', False):
+        return
+    tf, sf = stage.get('out_transform_field', 'color_transform_global'), stage.get('out_shift_field', 'color_shift_global')
+    if (tf, sf) != ('color_transform_global', 'color_shift_global'):
+        raise NotImplementedError('color_transform with renamed output fields')
+    if 'color_shift_global' in heads:
+        raise NotImplementedError('color_transform next to a color_shift_global head')
+    vis = lambda k: seen is None or k in seen
+    # tensorf_no_sample.py:240-243: a color_scale_global head takes precedence over the transform
+    if vis(tf) and vis(sf) and hc.f_color_scale_global.offset < 0:
+        hc.color_table_views = int(ctx.dataset['total_images_per_frame'])
+        hc.color_table_t_act = _act(stage.get('transform_activation'), ctx.iteration)
+        hc.color_table_s_act = _act(stage.get('shift_activation'), ctx.iteration)
+
+
+def _intersect_base(hc, ic, heads, ctx):
+    """Intersect.__init__ (nlf/intersect/base.py:52-126): what every intersect type shares -- mask, origin, near / far, the z_vals
+    activation, sort, the density field"""
+    for k in ('weight_fn', 'sort_outputs', 'dropout', 'normalize', 'residual_z', 'residual_distance', 'clamp',
+              'use_local_prediction', 'flip_axes', 'use_disparity', 'max_axis'):
+        if ic.get(k):
+            raise NotImplementedError(f'intersect.{k}')
+    if ic.get('num_repeat', 1) != 1:
+        raise NotImplementedError('intersect.num_repeat')
+    if 'mask' in ic:                              # base.py:104-108,197-198; inference runs at iter 1e7
+        hc.isect_mask_off = int((10_000_000 if ctx.iteration is None else ctx.iteration) > ic['mask'].get('stop_iters', float('inf')))
+    _set(hc.isect_origin, ic.get('origin', [0.0, 0.0, 0.0]))
+    udb = ic.get('use_dataset_bounds', False)
+    hc.near = float(ic['near']) if 'near' in ic else (float(ctx.dataset['near']) if udb else 0.0)   # base.py:88-94
+    hc.far = float(ic.get('far', float('inf')))
+    hc.z_act = _act(ic.get('activation'), ctx.iteration)
+    hc.sort = int(bool(ic.get('sort', False)))
+    if ic.get('use_sigma', False):
+        fld = ic.get('in_density_field', 'sigma')
+        if fld in heads:
+            if heads[fld].channels != 1:
+                raise NotImplementedError('intersect density field with more than one channel')
+            hc.f_isect_sigma = heads[fld]
+
+
+def _contract(hc, ic, dataset):
+    """The intersect's contract (nlf/contract.py: IdentityContract, BBoxContract :65-87, ZDepthContract :90-111, MIPNeRFContract
+    :113-176, DoNeRFContract :195-240) as the kernels' constants.  -> the map from a distance to the anchors' space: the contract's
+    contract_distance with `contract_samples`, else the float32 cast"""
+    contract = None
+    if 'contract' in ic:
+        c = ic['contract']
+        kind = c['type']
+        if kind not in CONTRACT:
+            raise NotImplementedError(f"contract '{kind}' is outside the hot-path scope")
+        if 'stop_iters' in c:
+            raise NotImplementedError('contract.stop_iters')
+        hc.contract_type = CONTRACT[kind]
+        hc.contract_samples = int(bool(c.get('contract_samples', False)))
+        if kind in ('bbox', 'z_depth'):
+            contract = _Affine(c, dataset)
+            _set(hc.c_aff_min, contract.lo)
+            _set(hc.c_aff_size, contract.size)
+            hc.c_aff_fac = float(contract.fac)
+        elif kind == 'mipnerf':
+            contract = _MipNerf(c, dataset)
+            hc.c_r0, hc.c_r_inv_end, hc.c_r_scale = float(contract.r0), float(inv := contract.r0 / contract.r1), float(1.0 / (1.0 - inv))
+            hc.c_d0, hc.c_d_inv_end, hc.c_d_scale = float(contract.d0), float(inv := contract.d0 / contract.d1), float(1.0 / (1.0 - inv))
+        elif kind == 'donerf':
+            contract = _DoNeRF(c, dataset)
+            hc.c_pow_fac, hc.c_pow_power, hc.c_pow_inv_power = float(contract.fac), float(contract.power), float(contract.inv_power)
+        elif hc.contract_samples:
+            hc.contract_samples = 0          # IdentityContract.inverse_contract_distance is the identity
+    return contract.contract_distance if (hc.contract_samples and contract is not None) else (lambda v: F32(v))
+
+
+def _anchor_range(t, ic, ds):
+    """(initial, end) of the anchors of the intersect types with one distance per sample.  Without `use_dataset_bounds` every type reads
+    the YAML's `initial` / `end` (0, 1); with it the YAML's values stand where given -- z_plane does not look -- and the defaults are:
+      z_plane (z.py:25-39)                                          -near             -far
+      sphere, cylinder (primitive.py:185-215 / 370-400)             1.5 near          1.5 far
+      sphere_new, cylinder_new (primitive.py:256-303 / 441-488)     1.5 near facing outward, else -1.5 far       1.5 far
+      euclidean_distance_unified (primitive.py:131-160)             -far              far"""
+    if not ic.get('use_dataset_bounds', False):
+        return F32(ic.get('initial', 0.0)), F32(ic.get('end', 1.0))
+    if t == 'z_plane':
+        return F32(-ds['near']), F32(-ds['far'])
+    if t in ('sphere', 'cylinder'):
+        initial, end = (lambda: ds['near'] * 1.5), (lambda: ds['far'] * 1.5)
+    elif t in ('sphere_new', 'cylinder_new'):
+        initial, end = (lambda: ds['near'] * 1.5) if ic['outward_facing'] else (lambda: -ds['far'] * 1.5), (lambda: ds['far'] * 1.5)
+    else:
+        initial, end = (lambda: -ds['far']), (lambda: ds['far'])
+    return F32(ic['initial']) if 'initial' in ic else F32(initial()), F32(ic['end']) if 'end' in ic else F32(end())
+
+
+def _anchor_line(cdist, initial, end, n):
+    """n anchors from `initial` to `end` in the contracted space: torch.linspace(contract(initial), contract(end), n), all float32"""
+    return torch_linspace_f32(cdist(F32(initial)), cdist(F32(end)), n)
+
+
+def _z_scale(t, ic, Z, samples):
+    """The scale of a predicted z offset: a given `z_scale`; else the anchors' spacing, which z_plane's `num_samples_for_scale`
+    (z.py:63-65) stretches by Z / num_samples_for_scale; 1 where a single anchor has no spacing"""
+    if Z <= 1:
+        return F32(ic.get('z_scale', 1.0))
+    if 'z_scale' in ic:
+        return F32(ic['z_scale'])
+    if 'num_samples_for_scale' in ic and t == 'z_plane':
+        return np.abs(samples[1] - samples[0]) * F32(Z / float(ic['num_samples_for_scale']))
+    return np.abs(samples[1] - samples[0])
+
+
+def _grid_z_scale(ic, axis, samples, nz):
+    """The voxel grids' scale along one axis (voxel.py:57-64, 175-182): a given `z_scale`, else |samples[1] - samples[0]| (1 for a
+    single plane); a zero scale becomes 1"""
+    zs = F32(ic['z_scale'][axis]) if 'z_scale' in ic else (np.abs(samples[1] - samples[0]) if nz > 1 else F32(1.0))
+    return float(zs) if zs != 0 else 1.0
+
+
+def _voxel_anchors(hc, ic, Z, cdist, ds):
+    """IntersectVoxelGrid.__init__ (nlf/intersect/voxel.py:19-70): Z/3 axis planes per axis, sample k -> axis k % 3"""
+    if Z % 3:
+        raise ValueError('voxel_grid needs z_channels divisible by 3')
+    nz = Z // 3
+    fac = ic.get('fac', 1.0)
+    if ic.get('use_dataset_bounds', False):
+        if 'bbox_min' not in ds and not ('initial' in ic and 'end' in ic):
+            raise ValueError('voxel_grid with use_dataset_bounds reads dataset.bbox_min / bbox_max')
+        initial = ic['initial'] if 'initial' in ic else (np.asarray(ds['bbox_min'], F32) * F32(fac))
+        end = ic['end'] if 'end' in ic else (np.asarray(ds['bbox_max'], F32) * F32(fac))
+    else:
+        initial, end = ic.get('initial', [0.0, 0.0, 0.0]), ic.get('end', [1.0, 1.0, 1.0])
+    cols = [_anchor_line(cdist, initial[d], end[d], nz) for d in range(3)]
+    _set(hc.samples, np.stack(cols, -1).reshape(-1), 3 * nz)
+    _set(hc.voxel_scale, [_grid_z_scale(ic, d, cols[d], nz) for d in range(3)])
+    hc.z_scale = 1.0
+    hc.isect_outward = int(bool(ic.get('outward_facing', False)))
+
+
+def _deformable_anchors(hc, ic, Z, cdist):
+    """IntersectDeformableVoxelGrid.__init__ (nlf/intersect/voxel.py:115-176): one plane family per start normal"""
+    if ic.get('use_dataset_bounds', False):
+        raise NotImplementedError('deformable_voxel_grid with use_dataset_bounds (reads the dataset point cloud)')
+    normals = ic.get('start_normal', [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]])
+    na = len(normals)
+    if not 1 <= na <= 3 or Z % na:
+        raise ValueError('deformable_voxel_grid needs 1..3 start normals dividing z_channels')
+    hc.dvg_axes = na
+    _set(hc.dvg_normals, [normals[a][i] for a in range(na) for i in range(3)], 3 * na)
+    hc.dvg_normal_scale = float(ic.get('normal_scale_factor', 0.1))
+    nz = Z // na
+    initial, end = ic.get('initial', [0.0, 0.0, 0.0]), ic.get('end', [1.0, 1.0, 1.0])
+    flat = np.stack([_anchor_line(cdist, initial[d], end[d], nz) for d in range(na)], -1).reshape(-1).astype(F32)   # torch.stack(samples, -1).view(-1, 1)
+    _set(hc.samples, flat, Z)
+    if 'z_scale' in ic and na != 1:
+        raise NotImplementedError('deformable_voxel_grid.z_scale with more than one axis (the reference cannot broadcast it)')
+    # voxel.py:171-172 takes |samples[1] - samples[0]| of the FLATTENED (Z, 1) samples
+    hc.z_scale = _grid_z_scale(ic, 0, flat, nz)
+
+
+def _anchors(hc, t, ic, cdist, ds):
+    """The anchor samples and z_scale of the intersect's subclass: IntersectZPlane (nlf/intersect/z.py:16-75), the primitives
+    (nlf/intersect/primitive.py:131-160, 181-233, 256-303, 366-418, 441-488) and the voxel grids"""
+    Z = hc.z_channels
+    if t == 'voxel_grid':
+        return _voxel_anchors(hc, ic, Z, cdist, ds)
+    if t == 'deformable_voxel_grid':
+        return _deformable_anchors(hc, ic, Z, cdist)
+    initial, end = _anchor_range(t, ic, ds)
+    if t in ('sphere', 'cylinder', 'sphere_new', 'cylinder_new'):
+        hc.origin_scale = float(ic.get('origin_scale_factor', 0.0))
+    if t in ('sphere', 'cylinder'):
+        _set(hc.origin_initial, ic.get('origin_initial', [1.0, 1.0, 1.0]))
+    elif t in ('sphere_new', 'cylinder_new'):
+        hc.resize_scale = float(ic.get('resize_scale_factor', 0.0))
+        _set(hc.resize_initial, ic.get('resize_initial', [1.0, 1.0, 1.0]))
+    samples = _anchor_line(cdist, initial, end, Z)
+    _set(hc.samples, samples, Z)
+    hc.z_scale = float(_z_scale(t, ic, Z, samples))
+
+
+def _intersect(hc, stage, heads, ctx):
+    """RayIntersectEmbedding's intersect: the base (Intersect.__init__, nlf/intersect/base.py:52-126), its contract, and the
+    subclass' anchors"""
+    if int(stage['z_channels']) != hc.z_channels:
         raise ValueError('ray_prediction and ray_intersect disagree on z_channels')
-    ic = st['intersect']
+    ic = stage['intersect']
     t = ic['type']
     if t not in ISECT:
         raise NotImplementedError(f"intersect '{t}' is outside the hot-path scope (SURVEY 8f-1)")
@@ -628,199 +819,56 @@ def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp
         # the reference reshapes z_vals to (B, Z, n) and fails (or silently mis-strides) otherwise
         raise ValueError(f"intersect '{t}' needs {ISECT_Z_CHANNELS[hc.isect_type]} z_vals channels, "
                          f"the head has {hc.f_z_vals.channels}")
-    for k in ('weight_fn', 'sort_outputs', 'dropout', 'normalize', 'residual_z', 'residual_distance', 'clamp',
-              'use_local_prediction', 'flip_axes', 'use_disparity', 'max_axis'):
-        if ic.get(k):
-            raise NotImplementedError(f'intersect.{k}')
-    if ic.get('num_repeat', 1) != 1:
-        raise NotImplementedError('intersect.num_repeat')
-    if 'mask' in ic:                              # base.py:104-108,197-198; inference runs at iter 1e7
-        hc.isect_mask_off = int((10_000_000 if _ITERATION is None else _ITERATION) > ic['mask'].get('stop_iters', float('inf')))
-    udb = ic.get('use_dataset_bounds', False)
-    org = ic.get('origin', [0.0, 0.0, 0.0])
-    for k in range(3):
-        hc.isect_origin[k] = float(org[k])
-    hc.near = float(ic['near']) if 'near' in ic else (float(dataset['near']) if udb else 0.0)   # base.py:88-94
-    hc.far = float(ic.get('far', float('inf')))
-    hc.z_act = _act(ic.get('activation'))
-    hc.sort = int(bool(ic.get('sort', False)))
-    if ic.get('use_sigma', False):
-        fld = ic.get('in_density_field', 'sigma')
-        if fld in heads:
-            if heads[fld].channels != 1:
-                raise NotImplementedError('intersect density field with more than one channel')
-            hc.f_isect_sigma = heads[fld]
-    contract = None
-    if 'contract' in ic:
-        ct = ic['contract']['type']
-        if ct not in CONTRACT:
-            raise NotImplementedError(f"contract '{ct}' is outside the hot-path scope")
-        if 'stop_iters' in ic['contract']:
-            raise NotImplementedError('contract.stop_iters')
-        hc.contract_type = CONTRACT[ct]
-        hc.contract_samples = int(bool(ic['contract'].get('contract_samples', False)))
-        if ct in ('bbox', 'z_depth'):
-            contract = _Affine(ic['contract'], dataset)
-            for k in range(3):
-                hc.c_aff_min[k], hc.c_aff_size[k] = float(contract.lo[k]), float(contract.size[k])
-            hc.c_aff_fac = float(contract.fac)
-        elif ct == 'mipnerf':
-            contract = _MipNerf(ic['contract'], dataset)
-            hc.c_r0 = float(contract.r0)
-            inv_end = contract.r0 / contract.r1
-            hc.c_r_inv_end = float(inv_end)
-            hc.c_r_scale = float(1.0 / (1.0 - inv_end))
-            hc.c_d0 = float(contract.d0)
-            inv_end = contract.d0 / contract.d1
-            hc.c_d_inv_end = float(inv_end)
-            hc.c_d_scale = float(1.0 / (1.0 - inv_end))
-        elif ct == 'donerf':
-            contract = _DoNeRF(ic['contract'], dataset)
-            hc.c_pow_fac, hc.c_pow_power, hc.c_pow_inv_power = float(contract.fac), float(contract.power), float(contract.inv_power)
-        elif hc.contract_samples:
-            hc.contract_samples = 0          # IdentityContract.inverse_contract_distance is the identity
-    cdist = contract.contract_distance if (hc.contract_samples and contract is not None) else (lambda v: F32(v))
-    if t == 'voxel_grid':                     # voxel.py:19-70: Z/3 axis planes per axis, sample k -> axis k % 3
-        if Z % 3:
-            raise ValueError('voxel_grid needs z_channels divisible by 3')
-        nz = Z // 3
-        fac = ic.get('fac', 1.0)
-        if udb:
-            if 'bbox_min' not in dataset and not ('initial' in ic and 'end' in ic):
-                raise ValueError('voxel_grid with use_dataset_bounds reads dataset.bbox_min / bbox_max')
-            initial = ic['initial'] if 'initial' in ic else (np.asarray(dataset['bbox_min'], F32) * F32(fac))
-            end = ic['end'] if 'end' in ic else (np.asarray(dataset['bbox_max'], F32) * F32(fac))
-        else:
-            initial, end = ic.get('initial', [0.0, 0.0, 0.0]), ic.get('end', [1.0, 1.0, 1.0])
-        cols = [torch_linspace_f32(cdist(F32(initial[d])), cdist(F32(end[d])), nz) for d in range(3)]
-        for j in range(nz):
-            for d in range(3):
-                hc.samples[3 * j + d] = float(cols[d][j])
-        for d in range(3):
-            if 'z_scale' in ic:
-                zs = F32(ic['z_scale'][d])
-            else:
-                zs = np.abs(cols[d][1] - cols[d][0]) if nz > 1 else F32(1.0)
-            hc.voxel_scale[d] = float(zs) if zs != 0 else 1.0
-        hc.z_scale = 1.0
-        hc.isect_outward = int(bool(ic.get('outward_facing', False)))
-        samples = None
-    elif t == 'deformable_voxel_grid':        # voxel.py:115-176: one plane family per start normal
-        if udb:
-            raise NotImplementedError('deformable_voxel_grid with use_dataset_bounds (reads the dataset point cloud)')
-        normals = ic.get('start_normal', [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]])
-        na = len(normals)
-        if not 1 <= na <= 3 or Z % na:
-            raise ValueError('deformable_voxel_grid needs 1..3 start normals dividing z_channels')
-        hc.dvg_axes = na
-        for a_ in range(na):
-            for i in range(3):
-                hc.dvg_normals[3 * a_ + i] = float(normals[a_][i])
-        hc.dvg_normal_scale = float(ic.get('normal_scale_factor', 0.1))
-        nz = Z // na
-        ini, en = ic.get('initial', [0.0, 0.0, 0.0]), ic.get('end', [1.0, 1.0, 1.0])
-        cols = [torch_linspace_f32(cdist(F32(ini[d])), cdist(F32(en[d])), nz) for d in range(na)]
-        flat = np.stack(cols, -1).reshape(-1).astype(F32)       # torch.stack(samples, -1).view(-1, 1)
-        for k in range(Z):
-            hc.samples[k] = float(flat[k])
-        if 'z_scale' in ic:
-            if na != 1:
-                raise NotImplementedError('deformable_voxel_grid.z_scale with more than one axis (the reference cannot broadcast it)')
-            zs = F32(ic['z_scale'][0])
-        else:
-            # voxel.py:171-172 takes |samples[1] - samples[0]| of the FLATTENED (Z, 1) samples
-            zs = np.abs(flat[1] - flat[0]) if nz > 1 else F32(1.0)
-        hc.z_scale = float(zs) if zs != 0 else 1.0
-        samples = None
-    elif t == 'z_plane':                      # z.py:25-39
-        if udb:
-            initial, end = F32(-dataset['near']), F32(-dataset['far'])
-        else:
-            initial, end = F32(ic.get('initial', 0.0)), F32(ic.get('end', 1.0))
-    elif t in ('sphere', 'cylinder'):         # primitive.py:185-215 / 370-400
-        if udb:
-            initial = F32(ic['initial']) if 'initial' in ic else F32(dataset['near'] * 1.5)
-            end = F32(ic['end']) if 'end' in ic else F32(dataset['far'] * 1.5)
-        else:
-            initial, end = F32(ic.get('initial', 0.0)), F32(ic.get('end', 1.0))
-        hc.origin_scale = float(ic.get('origin_scale_factor', 0.0))
-        oi = ic.get('origin_initial', [1.0, 1.0, 1.0])
-        for k in range(3):
-            hc.origin_initial[k] = float(oi[k])
-    elif t in ('sphere_new', 'cylinder_new'):   # primitive.py:256-303 / 441-488
-        if udb:
-            if ic['outward_facing']:
-                initial = F32(ic['initial']) if 'initial' in ic else F32(dataset['near'] * 1.5)
-            else:
-                initial = F32(ic['initial']) if 'initial' in ic else F32(-dataset['far'] * 1.5)
-            end = F32(ic['end']) if 'end' in ic else F32(dataset['far'] * 1.5)
-        else:
-            initial, end = F32(ic.get('initial', 0.0)), F32(ic.get('end', 1.0))
-        hc.origin_scale = float(ic.get('origin_scale_factor', 0.0))
-        hc.resize_scale = float(ic.get('resize_scale_factor', 0.0))
-        ri = ic.get('resize_initial', [1.0, 1.0, 1.0])
-        for k in range(3):
-            hc.resize_initial[k] = float(ri[k])
-    else:                                     # euclidean_distance_unified, primitive.py:131-160
-        if udb:
-            initial = F32(ic['initial']) if 'initial' in ic else F32(-dataset['far'])
-            end = F32(ic['end']) if 'end' in ic else F32(dataset['far'])
-        else:
-            initial, end = F32(ic.get('initial', 0.0)), F32(ic.get('end', 1.0))
-    if t not in ('voxel_grid', 'deformable_voxel_grid'):
-        samples = torch_linspace_f32(cdist(initial), cdist(end), Z)
-        for k in range(Z):
-            hc.samples[k] = float(samples[k])
-        if Z > 1:
-            if 'z_scale' in ic:
-                zs = F32(ic['z_scale'])
-            elif 'num_samples_for_scale' in ic and t == 'z_plane':       # z.py:63-65
-                zs = np.abs(samples[1] - samples[0]) * F32(Z / float(ic['num_samples_for_scale']))
-            else:
-                zs = np.abs(samples[1] - samples[0])
-        else:
-            zs = F32(ic.get('z_scale', 1.0))
-        hc.z_scale = float(zs)
+    _intersect_base(hc, ic, heads, ctx)
+    _anchors(hc, t, ic, _contract(hc, ic, ctx.dataset), ctx.dataset)
 
-    # ---- advect / offset --------------------------------------------------------------
-    if 'advect_points' in types:
-        ad = stages[types.index('advect_points')]
-        if ad.get('use_angular_flow', False):
-            raise NotImplementedError('angular flow')
-        hc.advect = 1
-        hc.use_spatial_flow = int(bool(ad.get('use_spatial_flow', False)))
-        K, Fr = int(dataset['num_keyframes']), int(dataset['num_frames'])
-        if K > 0:
-            fac = K * (Fr - 1) / Fr           # flow_utils.py:18-19
-            hc.flow_fac = float(fac)
-            hc.flow_inv_fac = float(1.0 / fac)
-            hc.flow_kmax = float(K - 1.0)
-        hc.flow_act = _act(ad.get('spatial_flow_activation'))
-        if hc.use_spatial_flow:
-            if 'spatial_flow' not in heads:
-                raise ValueError('advect_points needs a spatial_flow head')
-            hc.f_spatial_flow = heads['spatial_flow']
-    else:
-        hc.flow_act = _act(None)
-    if 'point_offset' in types:
-        po = stages[types.index('point_offset')]
-        for k in ('dropout', 'in_points_field', 'out_points_field', 'in_offset_field'):
-            if k in po and po[k] not in (None, 'points', 'point_offset'):
-                raise NotImplementedError(f'point_offset.{k}')
-        hc.point_offset = 1
-        hc.offset_act = _act(po.get('activation'))
-        if 'point_offset' not in heads:
-            raise ValueError('point_offset needs a point_offset head')
-        hc.f_point_offset = heads['point_offset']
-        fld = po.get('in_density_field', 'sigma')
-        if po.get('use_sigma', True) and fld in heads:
-            if heads[fld].channels != 1:
-                raise NotImplementedError('offset density field with more than one channel')
-            hc.f_offset_sigma = heads[fld]
-    else:
-        hc.offset_act = _act(None)
 
-    # ---- colour net ---------------------------------------------------------------------
+def _advect(hc, stage, heads, ctx):
+    """AdvectPointsEmbedding.__init__ (nlf/embedding/point.py:741-778).  stage: the `advect_points` stage or None"""
+    hc.flow_act = _act(None)
+    if stage is None:
+        return
+    if stage.get('use_angular_flow', False):
+        raise NotImplementedError('angular flow')
+    hc.advect = 1
+    hc.use_spatial_flow = int(bool(stage.get('use_spatial_flow', False)))
+    K, Fr = int(ctx.dataset['num_keyframes']), int(ctx.dataset['num_frames'])
+    if K > 0:
+        fac = K * (Fr - 1) / Fr           # flow_utils.py:18-19
+        hc.flow_fac = float(fac)
+        hc.flow_inv_fac = float(1.0 / fac)
+        hc.flow_kmax = float(K - 1.0)
+    hc.flow_act = _act(stage.get('spatial_flow_activation'), ctx.iteration)
+    if hc.use_spatial_flow:
+        if 'spatial_flow' not in heads:
+            raise ValueError('advect_points needs a spatial_flow head')
+        hc.f_spatial_flow = heads['spatial_flow']
+
+
+def _point_offset(hc, stage, heads, ctx):
+    """PointOffsetEmbedding.__init__ (nlf/embedding/point.py:338-369).  stage: the `point_offset` stage or None"""
+    hc.offset_act = _act(None)
+    if stage is None:
+        return
+    for k in ('dropout', 'in_points_field', 'out_points_field', 'in_offset_field'):
+        if k in stage and stage[k] not in (None, 'points', 'point_offset'):
+            raise NotImplementedError(f'point_offset.{k}')
+    hc.point_offset = 1
+    hc.offset_act = _act(stage.get('activation'), ctx.iteration)
+    if 'point_offset' not in heads:
+        raise ValueError('point_offset needs a point_offset head')
+    hc.f_point_offset = heads['point_offset']
+    fld = stage.get('in_density_field', 'sigma')
+    if stage.get('use_sigma', True) and fld in heads:
+        if heads[fld].channels != 1:
+            raise NotImplementedError('offset density field with more than one channel')
+        hc.f_offset_sigma = heads[fld]
+
+
+def _colour_net(hc, cfg, grid_size, mlp_precision, max_col, ctx):
+    """TensorBase.__init__ (nlf/nets/tensorf_base.py:137-248) -- aabb, grid, component counts, shading, density activation, background --,
+    the ray row's width (max_col: the largest ray column a parameter group reads) and TensorVMKeyframeTime.__init__'s time constants
+    (nlf/nets/tensorf_dynamic.py:45-77).  -> the MLP arithmetic to ask for (_shading)"""
     if cfg['color']['type'] != 'base':
         raise NotImplementedError(f"color model {cfg['color']['type']}")
     n = cfg['color']['net']
@@ -829,35 +877,13 @@ def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp
     hc.video = int(n['type'] == 'tensor_vm_split_time')
     if 'filter' in n:
         raise NotImplementedError('net.filter (apply_filter_weights)')
-    aabb = np.asarray(n['aabb'] if _AABB is None else _AABB, F32).reshape(2, 3)
-    for k in range(3):
-        hc.aabb[k], hc.aabb[3 + k] = float(aabb[0][k]), float(aabb[1][k])
-    inv = F32(2.0) / (aabb[1] - aabb[0])      # tensorf_base.py:296-297
-    for k in range(3):
-        hc.inv_size[k] = float(inv[k])
-        hc.grid[k] = int(grid_size[k])
-    nd, na = list(n.get('n_lamb_sigma', [8, 8, 8])), list(n.get('n_lamb_sh', [24, 24, 24]))
-    for k in range(3):
-        hc.n_den[k], hc.n_app[k] = int(nd[k]), int(na[k])
-    shading = n.get('shadingMode', 'MLP_PE')
-    if shading == 'MLP_PE':
-        # in_mlpC counts 3 + 6 pos_pe position inputs that forward never concatenates for these nets (tensorf_base.py:77 vs 93-99)
-        raise NotImplementedError("shadingMode 'MLP_PE': the reference cannot run it (MLPRender_PE's first Linear expects more inputs than its "
-                                  "forward concatenates)")
-    if shading not in SHADING:
-        raise NotImplementedError(f"shadingMode '{shading}' is outside the hot-path scope ({', '.join(SHADING)})")
-    hc.shading = SHADING[shading]
-    hc.shade_mlp = shading_mlp(n)             # None for RGB / SH; not part of hr_config: hr_model_set_shading_mlp takes it
-    hc.time_decode = time_decode(n, dataset)  # None without an RGBt* / Density* mode; hr_model_set_time_decode takes it
-    if (hc.time_decode is not None or shading == 'RGBIdentity') and not _coarse:
-        if is_cascade(cfg):
-            raise NotImplementedError(f"shadingMode '{shading}' / densityMode '{n.get('densityMode', 'Density')}' with a point_prediction cascade")
-        # ('auto', 'f16f8' and 'f16f8v' run f16x3 for the ray MLP of these models: hr_mlp_choice, csrc/hr_plan.h, decides that in one place)
-    if hc.shade_mlp is not None and not _coarse:
-        if hc.z_channels > SHADE_MAX_Z:
-            raise NotImplementedError(f"shadingMode '{shading}' with z_channels {hc.z_channels} > {SHADE_MAX_Z}")
-        if mlp_precision in ('f16f8', 'f16f8v') and hc.mlp_hidden == 256:
-            mlp_precision = 'f16x3'           # the verified path's margins are not derived for this decoder ('auto': hr_mlp_choice decides the same)
+    aabb = np.asarray(n['aabb'] if ctx.aabb is None else ctx.aabb, F32).reshape(2, 3)
+    _set(hc.aabb, aabb.reshape(-1))
+    _set(hc.inv_size, F32(2.0) / (aabb[1] - aabb[0]))      # tensorf_base.py:296-297
+    _set(hc.grid, grid_size)
+    _set(hc.n_den, list(n.get('n_lamb_sigma', [8, 8, 8])))
+    _set(hc.n_app, list(n.get('n_lamb_sh', [24, 24, 24])))
+    mlp_precision = _shading(hc, cfg, n, mlp_precision, ctx)
     hc.app_dim = int(n.get('data_dim_color', 27))
     hc.distance_scale = float(n.get('distance_scale', 25))
     hc.weight_thresh = float(n.get('rm_weight_mask_thre', 0.0001))
@@ -869,21 +895,44 @@ def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp
     hc.white_bg = int(bool(n.get('white_bg', 0)) and not bool(n.get('black_bg', 0)))
     hc.ray_dim = 8 if (hc.video or max_col > 6 or hc.advect or hc.color_table_views > 0) else 6   # camera id = rays[..., -2]
     if hc.video:
-        K, Fr = int(dataset['num_keyframes']), int(dataset['num_frames'])
+        K, Fr = int(ctx.dataset['num_keyframes']), int(ctx.dataset['num_frames'])
         hc.num_keyframes = K
         hc.time_scale = float((Fr - 1) / Fr)  # tensorf_dynamic.py:58-59
         hc.time_offset = float(0.5 / K)
-        if not hc.advect and not _coarse:
+        if not hc.advect and not ctx.coarse:
             raise NotImplementedError('video net without an advect_points stage (base_times)')
-    # GEMM arithmetic of the MLP.  'auto' (HR_MLP_AUTO) lets the library choose when the kernel supports the width: 'f16x3' -- three
-    # fp16 MFMA products of hi/lo split operands (11 + 11 mantissa bits, weights pre-scaled by an exact power of two), fp32 accumulate,
-    # raw head within 1e-6 of the exact fp32 chain (bf16x3: 7e-6, same cost), which is what keeps the reference's threshold decisions
-    # (`dist <= near`, intersect/base.py:194-203) from flipping -- wherever hr_model_finalize's activation-range calibration shows the
-    # MLP's activations to stay below 65504 / 8 (fp16 halves saturate at 65504; the reference's BaseMLP is fp32, nlf/nets/mlp.py:127-172),
-    # and 'bf16x3' (fp32 exponent range) otherwise.  Round 5: where the model allows it (a plain ray MLP, <= 64 samples per ray) 'auto' is 'f16f8v' --
-    # the f16 + fp8 arithmetic (two thirds of f16x3's matrix-pipe time) with every ray that has a comparison within 2.5e-6 of the scene's extent of
-    # flipping rendered again with the f16x3 tiles by a second, list-driven pass on the device (include/hyperreel_hip.h, HR_MLP_F16F8V).  A forced 'f16x3' / 'f16x2' that fails the same test is refused by name
-    # (HR_E_RANGE).  'fp32' is the exact fp32 MFMA; other hidden widths only have that.
+    return mlp_precision
+
+
+def _shading(hc, cfg, n, mlp_precision, ctx):
+    """The colour net's shadingMode / densityMode (tensorf_base.py:238-241; tensorf_dynamic.py:45-77) and the descriptors that go with
+    them.  -> the MLP arithmetic to ask for, which an MLP shading mode turns from f16f8 / f16f8v into f16x3"""
+    shading = n.get('shadingMode', 'MLP_PE')
+    if shading == 'MLP_PE':
+        # in_mlpC counts 3 + 6 pos_pe position inputs that forward never concatenates for these nets (tensorf_base.py:77 vs 93-99)
+        raise NotImplementedError("shadingMode 'MLP_PE': the reference cannot run it (MLPRender_PE's first Linear expects more inputs than its "
+                                  "forward concatenates)")
+    if shading not in SHADING:
+        raise NotImplementedError(f"shadingMode '{shading}' is outside the hot-path scope ({', '.join(SHADING)})")
+    hc.shading = SHADING[shading]
+    hc.shade_mlp = shading_mlp(n)             # None for RGB / SH; not part of hr_config: hr_model_set_shading_mlp takes it
+    hc.time_decode = time_decode(n, ctx.dataset)  # None without an RGBt* / Density* mode; hr_model_set_time_decode takes it
+    if (hc.time_decode is not None or shading == 'RGBIdentity') and not ctx.coarse:
+        if is_cascade(cfg):
+            raise NotImplementedError(f"shadingMode '{shading}' / densityMode '{n.get('densityMode', 'Density')}' with a point_prediction cascade")
+        # ('auto', 'f16f8' and 'f16f8v' run f16x3 for the ray MLP of these models: hr_mlp_choice, csrc/hr_plan.h, decides that in one place)
+    if hc.shade_mlp is not None and not ctx.coarse:
+        if hc.z_channels > SHADE_MAX_Z:
+            raise NotImplementedError(f"shadingMode '{shading}' with z_channels {hc.z_channels} > {SHADE_MAX_Z}")
+        if mlp_precision in ('f16f8', 'f16f8v') and hc.mlp_hidden == 256:
+            return 'f16x3'                    # the verified path's margins are not derived for this decoder ('auto': hr_mlp_choice decides the same)
+    return mlp_precision
+
+
+def _mlp_arithmetic(hc, mlp_precision, grid_dtype):
+    """The caller's words for the ray MLP's GEMM arithmetic and the grids' storage as HR_MLP_* / HR_GRID_*.  'auto' stays the library's
+    choice (hr_mlp_choice, csrc/hr_plan.h; DESIGN 3 "Arithmetic" and 3c) for a 256-wide MLP; any other width, and a ZeroMLP, has the
+    exact fp32 kernel only"""
     if mlp_precision == 'auto' or hc.mlp_layers == 0:
         mlp_precision = 'auto' if hc.mlp_hidden == 256 else 'fp32'
     if mlp_precision in ('bf16x3', 'f16x3', 'f16x2', 'f16f8', 'f16f8v') and hc.mlp_hidden != 256:
@@ -892,6 +941,31 @@ def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp
     if grid_dtype not in GRID_DTYPE:
         raise ValueError(f"grid_dtype must be one of {sorted(GRID_DTYPE)} (got {grid_dtype!r})")
     hc.grid_dtype = GRID_DTYPE[grid_dtype]
+
+
+def compile_config(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='fp32', _coarse=False, iteration='inherit'):
+    """cfg: `experiment.model` group (dict/Cfg); dataset: {near, far, depth_range,
+    num_keyframes, num_frames}; grid_size: [Nx, Ny, Nz] of the uploaded planes.
+    iteration: training iteration of the EaseValue / WindowedPE schedules (None: converged; default: whatever an
+    enclosing `at_iteration` set, else converged)."""
+    ctx = _Ctx(iteration if iteration != 'inherit' else _ITERATION, _AABB, dataset, _coarse)     # the only read of the two globals
+    if cfg.get('param', {}).get('fn', 'identity') != 'identity':
+        raise NotImplementedError("model.param.fn other than 'identity'")
+    if cfg['embedding']['type'] != 'ray_point':
+        raise NotImplementedError(f"embedding type {cfg['embedding']['type']}")
+    hc = hr_config()
+    for name in _HEAD_FIELDS:
+        setattr(hc, name, _absent_field())
+    stages = _embedding_stages(cfg)
+    heads, max_col = _ray_prediction(hc, stages['ray_prediction'], ctx)
+    seen = set(stages['extract_fields']['fields']) if 'extract_fields' in stages else None
+    _color_fields(hc, heads, seen)
+    _color_table(hc, stages.get('color_transform'), heads, seen, ctx)
+    _intersect(hc, stages['ray_intersect'], heads, ctx)
+    _advect(hc, stages.get('advect_points'), heads, ctx)
+    _point_offset(hc, stages.get('point_offset'), heads, ctx)
+    mlp_precision = _colour_net(hc, cfg, grid_size, mlp_precision, max_col, ctx)
+    _mlp_arithmetic(hc, mlp_precision, grid_dtype)
     return hc
 
 
@@ -964,8 +1038,8 @@ def compile_cascade(cfg, dataset, grid_size, mlp_precision='auto', grid_dtype='f
     hc1 = compile_config(c1, dataset, grid_size, mlp_precision, grid_dtype)
     hc1.ray_dim = hc0.ray_dim = max(hc0.ray_dim, 8 if (hc1.video or hc1.advect or hc1.color_table_views > 0) else 6)
     hc1.casc_in_z, hc1.casc_row_dim, hc1.casc_n_inputs = in_z, row_dim, len(kinds)
-    for i, (k, d) in enumerate(zip(kinds, dims)):
-        hc1.casc_input_kind[i], hc1.casc_input_dim[i] = k, d
+    _set(hc1.casc_input_kind, kinds, len(kinds))
+    _set(hc1.casc_input_dim, dims, len(dims))
     return hc0, hc1
 
 

@@ -199,8 +199,7 @@ def test_ease_value_and_windowed_pe_weights():
     assert plan.ease_weight(ev, 10000) == 0.5 and plan.ease_weight(ev, 16000) == 1.0 and plan.ease_weight(ev, 10**7) == 1.0
     zero = dict(ev, window_iters=0)
     assert plan.ease_weight(zero, 3999) == 0.0 and plan.ease_weight(zero, 4000) == 1.0
-    with plan.at_iteration(10000):
-        a = plan._act(ev)
+    a = plan._act(ev, 10000)
     assert a.type == 1 and a.outer == 0.5 and a.add == 0.5
     a = plan._act(ev)
     assert a.outer == 1.0 and a.add == 0.0
@@ -214,6 +213,11 @@ def test_ease_value_and_windowed_pe_weights():
     cfg, ds = C.epoch_to_iter(C.model_config('donerf_sphere'), 4000), C.dataset_scalars('donerf_sphere')
     a = bytes(plan.compile_config(cfg, ds, [8, 8, 8]))
     assert a == bytes(plan.compile_config(cfg, ds, [8, 8, 8], iteration=10**7)) != bytes(plan.compile_config(cfg, ds, [8, 8, 8], iteration=2000))
+    # at_iteration supplies the default of `iteration`, for every compile_* call it wraps, and takes it back
+    with plan.at_iteration(2000):
+        inside = [bytes(plan.compile_config(cfg, ds, [8, 8, 8])) for _ in range(2)]
+        assert bytes(plan.compile_config(cfg, ds, [8, 8, 8], iteration=None)) == a
+    assert inside == [bytes(plan.compile_config(cfg, ds, [8, 8, 8], iteration=2000))] * 2 and bytes(plan.compile_config(cfg, ds, [8, 8, 8])) == a
 
 
 def test_the_models_aabb_buffer_not_the_yaml_drives_the_compiled_box():
