@@ -41,3 +41,21 @@ def unit_descriptor(recipe):
     kw = recipe['kwargs']
     mode = 'MLP_Fea' if recipe['module'] == 'MLPRender_Fea' else 'MLP'
     return mode, int(kw['viewpe']), int(kw.get('feape', 0)), int(kw['featureC'])
+
+
+def shade_port(cfg, dataset, state_dict):
+    """time_decode_oracle.composite_port for a model with shadingMode MLP_Fea / MLP: TorchPort (built as the SH model the 27-row basis_mat
+    fits) up to the weights and the 27 appearance features of a live sample, then shade() above on them and the ray's direction."""
+    import copy
+    from time_decode_oracle import composite_port
+    net = cfg['color']['net']
+    mode, view_pe, fea_pe = net['shadingMode'], int(net.get('view_pe', 6)), int(net.get('fea_pe', 6))
+    pre = 'model.color_model.net.renderModule.'
+    weights = {k[len(pre):]: v for k, v in state_dict.items() if k.startswith(pre)}
+    as_sh = copy.deepcopy(cfg)
+    as_sh['color']['net']['shadingMode'] = 'SH'
+
+    def colour(port, feat, t, off, viewdirs):
+        return torch.from_numpy(shade(mode, view_pe, fea_pe, weights, feat.detach().numpy(), viewdirs.detach().numpy()))
+
+    return composite_port(as_sh, dataset, state_dict, colour=colour)
